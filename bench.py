@@ -8,11 +8,14 @@
 One "step" = one pass of the hot path over one batch: ccn_sample of 8 images (256x256, base=128,
 ch_mult=(1,2,2)) through 50 DDIM steps, replayed as one hipGraph, inputs resident in HBM.  Consecutive steps are
 independent batches (like consecutive batches of cli.eval); they are timed one after the other.  `--inflight 2` keeps two
-in flight per GPU, each on its own stream with its own workspace and graph (every launch still works on a batch of 8);
-with the default that figure is measured after the timed region and reported as config.value_with_two_steps_in_flight.  Ranks hold
-independent batches (weak scaling, no data-path collective).  Rank 0 prints ONE JSON line with the
-contract fields plus `roofline` (dominant kernel, HIP-event timed in a launch-by-launch pass of the same
-workload) and, at N=1, `cpu_baseline` (the oracle timed on the host cores on a bounded sample).
+in flight per GPU, each on its own stream with its own workspace and graph (every launch still works on a batch of 8).  Ranks hold
+independent batches (weak scaling, no data-path collective).  Rank 0 prints ONE JSON line with the contract fields.
+
+A plain run only sets up, warms up, times the steps and prints that line.  `--full` adds, after the timed region:
+config.value_with_two_steps_in_flight (value_with_one_step_in_flight under `--inflight 2`), `roofline` (dominant kernel, HIP-event
+timed in a launch-by-launch pass of the same workload), `parity` / `parity_mode` (the fp32 mode and the reference's golden
+record) and, at N=1, `cpu_baseline` (the oracle timed on the host cores on a bounded sample); `--no-*` drops one of them.
+`--dump-outputs DIR` writes the last timed step's result (the images a caller of ccn_sample receives) as DIR/x_final.npy.
 """
 from __future__ import annotations
 
@@ -62,7 +65,14 @@ def main() -> None:
     ap.add_argument("--weight-rounding", choices=["phases", "diffused", "nearest"], default="phases",
                     help="bf16 mode: how ccn_commit_params rounds the conv weights (A/B runs; the default is the library's)")
     ap.add_argument("--no-parity", action="store_true", help="skip the parity block (bf16 vs the reference's golden / fp32 mode, PSNR delta)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the other number of steps in flight, the roofline pass, the parity block "
+                         "and the CPU baseline (each unless its --no-* is given); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as DIR/x_final.npy (float32; per rank x_final_rank<r>.npy when --gpus > 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # --gpus N without a launcher: start the N ranks ourselves (child processes, before this process touches the GPU)
     from clip_feature_codec.utils.launch import ensure_ranks, init_process_group, rank_env, collective_device, single_rank_env
@@ -107,8 +117,8 @@ def main() -> None:
 
     # The timed steps run one after the other by default.  Consecutive steps are independent batches (as consecutive batches of cli.eval
     # are), so they can also be kept in flight two at a time, step i on stream i % 2 with its own workspace and captured graph: one
-    # batch's kernel tails and launch gaps then fill with the other's work.  `--inflight 2` times that; with the default the figure is
-    # measured after the timed region and reported as config.value_with_two_steps_in_flight.
+    # batch's kernel tails and launch gaps then fill with the other's work.  `--inflight 2` times that; `--full` with the default measures the
+    # figure after the timed region and reports it as config.value_with_two_steps_in_flight.
     nfl = args.inflight
     streams = [torch.cuda.Stream(device=dev) for _ in range(2)]
 
@@ -119,8 +129,9 @@ def main() -> None:
         with torch.cuda.stream(st):
             return sampler.sample(net, z, (B, 3, S, S), steps=T, x_T=x_T, slot=i % lanes)
 
-    for i in range(2):                                               # plan + graph capture of both slots, outside warm-up and timing
-        step(i, 2)
+    slots = 2 if (nfl == 2 or args.full) else 1                      # --full also times the other number of steps in flight
+    for i in range(slots):                                           # plan + graph capture of every slot used, outside warm-up and timing
+        step(i, slots)
 
     def fence():
         torch.cuda.synchronize()
@@ -147,6 +158,14 @@ def main() -> None:
         per_rank = [B * args.steps / float(v[1].item()) for v in every]
     assert torch.isfinite(x).all()
     value = world * B * args.steps / dt
+    if args.dump_outputs:
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        a = x.float().cpu().numpy()
+        cap = (64 << 20) // 4 // world                               # at most 64 MB of float32 over all ranks
+        if a.size > cap:
+            a = a.reshape(-1)[::-(-a.size // cap)]                   # a fixed strided sample of a larger output
+        np.save(out_dir / ("x_final.npy" if world == 1 else f"x_final_rank{rank}.npy"), a)
     # the other way of running the same steps (see above): a short second measurement, outside the timed region
     def timed(lanes, n):
         fence()
@@ -161,10 +180,10 @@ def main() -> None:
         del keep
         return round(world * B * n / d, 3)
     other_lanes = 1 if nfl == 2 else 2
-    other_value = timed(other_lanes, min(4, max(2, args.steps - args.steps % 2)))
+    other_value = timed(other_lanes, min(4, max(2, args.steps - args.steps % 2))) if args.full else None
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         nat = net.native()
         nat.profile(True)
         sampler.sample(net, z, (B, 3, S, S), steps=T, x_T=x_T)       # launch by launch, HIP events around every kernel
@@ -210,7 +229,7 @@ def main() -> None:
     # (b) this library's fp32 parity mode on all rows, (c) PSNR against synthetic originals in both modes (north_star: 0.1 %)
     parity = parity_mode = None
     headline = (S, args.base, ch_mult, T) == (256, 128, (1, 2, 2), 50)
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         from clip_feature_codec.eval.metrics import psnr
         x16 = sampler.sample(net, z, (B, 3, S, S), steps=T, x_T=x_T) if args.dtype == "bf16" else None
         net32 = CLIPCondUNet(512, args.base, ch_mult, dtype="fp32").to(dev).eval()
@@ -264,7 +283,7 @@ def main() -> None:
             quality_gate_met = bool(parity["fp32_mode_row0_vs_reference_cpu"]["pass"])
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import ref_unet, ref_diffusion
         # the box's CPU share, not the host's core count: oversubscribed torch threads crawl under a cgroup quota
         ncpu = min(len(os.sched_getaffinity(0)), int(os.environ.get("CCN_CPU_THREADS", "16")))

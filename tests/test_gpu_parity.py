@@ -426,7 +426,7 @@ def test_c2_bench_workload_bf16_parity_numbers(golden, synth, c2_sd, tmp_path):
     """The exact bench.py workload (C2: batch 8, 256 px, 50 steps, bf16, fused graph on the persistent kernel) against
     (a) the reference's device='cpu' run of record 0 (golden), (b) this library's fp32 parity mode on all 8 rows, and
     (c) PSNR against the synthetic originals in both modes -- north_star asks for PSNR within 0.1 % (eval/metrics.py:22-29).
-    Measured on MI355X (the same numbers are printed in bench.py's `parity` block on every run):
+    Measured on MI355X (the same numbers are printed in the `parity` block of every `bench.py --full` run):
       fp32 mode row 0 vs reference: max-abs 2.9e-4 (gate 1e-3: met);
       bf16 row 0 vs reference: max-abs 0.21, mean-abs 0.032; bf16 vs fp32 mode, all rows: max-abs 0.32, mean-abs 0.032
       (the reference's own bf16-autocast run deviates 0.30 / 0.037 from its fp32 run on these weights);

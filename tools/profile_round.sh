@@ -4,12 +4,12 @@
 set -u
 R=${1:-rXX}; O=gpurun_out/prof_$R; mkdir -p $O
 export TMPDIR=/tmp
-python bench.py --steps 5 --warmup 1 > $O/${R}_bench_bf16.json 2> $O/bench.err
-if [ -d .cmp_r02 ]; then (cd .cmp_r02 && python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-roofline > ../$O/${R}_bench_bf16_round2_build_same_box.json 2>> ../$O/bench.err); fi
-python bench.py --steps 2 --warmup 1 --dtype fp32 --no-cpu-baseline --no-parity > $O/${R}_bench_fp32.json 2>> $O/bench.err
+python bench.py --steps 5 --warmup 1 --full > $O/${R}_bench_bf16.json 2> $O/bench.err
+if [ -d .cmp_r02 ]; then (cd .cmp_r02 && python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-roofline $(grep -qe '"--full"' bench.py && echo --full) > ../$O/${R}_bench_bf16_round2_build_same_box.json 2>> ../$O/bench.err); fi
+python bench.py --steps 2 --warmup 1 --dtype fp32 --no-cpu-baseline --no-parity --full > $O/${R}_bench_fp32.json 2>> $O/bench.err
 python bench_train.py > $O/${R}_bench_train_bf16.json 2>> $O/bench.err
 python tools/eval_e2e.py --n 256 > $O/${R}_eval_e2e.txt 2>&1
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$O/stats -- python3 $OLDPWD/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-parity > /dev/null 2>&1)
+(cd "$TMPDIR" && rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$O/stats -- python3 $OLDPWD/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-parity --full > /dev/null 2>&1)
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/${R}_bench_bf16_kernel_stats.csv
 (cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $OLDPWD/$O/trace -- python3 $OLDPWD/tools/prof_sample.py --steps 3 > /dev/null 2>&1)
 python tools/trace_forward.py $O/trace > $O/${R}_forward_launch_by_launch.txt
