@@ -374,12 +374,10 @@ namespace {
 template <typename F>
 int pack_and_upload(ccn_handle_s* h, ConvW& cw, int taps, F&& at)
 {
-    const int cke = h->cfg.dtype == CCN_DTYPE_BF16 ? 64 : 32;
     cw.BN = conv_bn_for(cw.Cout, cw.kind);
     cw.Cout_pad = (int)align_up(cw.Cout, cw.BN);
     cw.ntaps_w = taps;
     const size_t n = (size_t)taps * cw.Cout_pad * cw.Cin_pad;
-    (void)cke;
     if (h->cfg.dtype == CCN_DTYPE_BF16) {
         std::vector<uint16_t> buf(n, 0);
         for (int t = 0; t < taps; ++t)
@@ -397,7 +395,7 @@ int pack_and_upload(ccn_handle_s* h, ConvW& cw, int taps, F&& at)
 int pack_conv3(ccn_handle_s* h, ConvW& cw, const std::string& name)     // Conv2d weight (O, I, 3, 3)
 {
     const float* w = h->host.at(name + ".weight").data();
-    const int cke = h->cfg.dtype == CCN_DTYPE_BF16 ? 64 : 32;
+    const int cke = conv_cin_chunk(h->cfg.dtype);
     cw.Cin_pad = (int)align_up(cw.Cin, cke);
     const int I = cw.Cin;
     int rc = pack_and_upload(h, cw, 9, [&](int t, int o, int i) { return i < I ? w[((size_t)o * I + i) * 9 + t] : 0.f; });
@@ -429,7 +427,7 @@ int pack_conv3(ccn_handle_s* h, ConvW& cw, const std::string& name)     // Conv2
 int pack_convT(ccn_handle_s* h, ConvW& cw, const std::string& name)     // ConvTranspose2d weight (I, O, 4, 4)
 {
     const float* w = h->host.at(name + ".weight").data();
-    const int cke = h->cfg.dtype == CCN_DTYPE_BF16 ? 64 : 32;
+    const int cke = conv_cin_chunk(h->cfg.dtype);
     cw.Cin_pad = (int)align_up(cw.Cin, cke);
     const int I = cw.Cin, O = cw.Cout;
     int rc = pack_and_upload(h, cw, 16, [&](int t, int o, int i) { return i < I ? w[((size_t)i * O + o) * 16 + t] : 0.f; });
@@ -451,7 +449,7 @@ int pack_convT(ccn_handle_s* h, ConvW& cw, const std::string& name)     // ConvT
 int pack_stem(ccn_handle_s* h, ConvW& cw, const std::string& name)      // Conv2d weight (O, img_ch, 3, 3) as K = I*9
 {
     const float* w = h->host.at(name + ".weight").data();
-    const int cke = h->cfg.dtype == CCN_DTYPE_BF16 ? 64 : 32;
+    const int cke = conv_cin_chunk(h->cfg.dtype);
     cw.Cin_pad = cke;
     const int K = cw.Cin * 9;
     int rc = pack_and_upload(h, cw, 1, [&](int, int o, int k) { return k < K ? w[(size_t)o * K + k] : 0.f; });
@@ -476,41 +474,6 @@ int pack_stem(ccn_handle_s* h, ConvW& cw, const std::string& name)      // Conv2
 }
 
 // ---- plan -------------------------------------------------------------------------------------------------
-struct ConvGeom { int Hout, Wout, MH, MW, OS, npar, ntaps, n_ty, n_tx, n_nt, th; };
-
-ConvGeom conv_geom(const ConvW& cw, int B, int Hin, int Win)
-{
-    ConvGeom g{};
-    switch (cw.kind) {
-        case KIND_C3S2: g.Hout = (Hin - 1) / 2 + 1; g.Wout = (Win - 1) / 2 + 1; g.MH = g.Hout; g.MW = g.Wout; g.OS = 1; g.npar = 1; g.ntaps = 9; break;
-        case KIND_CT4: g.Hout = Hin * 2; g.Wout = Win * 2; g.MH = Hin; g.MW = Win; g.OS = 2; g.npar = 4; g.ntaps = 4; break;
-        case KIND_STEM: g.Hout = Hin; g.Wout = Win; g.MH = Hin; g.MW = Win; g.OS = 1; g.npar = 1; g.ntaps = 1; break;
-        default: g.Hout = Hin; g.Wout = Win; g.MH = Hin; g.MW = Win; g.OS = 1; g.npar = 1; g.ntaps = 9; break;
-    }
-    g.n_nt = cw.Cout_pad / cw.BN;
-    g.th = conv_tile_rows(cw.kind, cw.BN, B, g.MH, g.MW, g.npar, g.n_nt);
-    g.n_ty = ceil_div(g.MH, g.th); g.n_tx = ceil_div(g.MW, 32);
-    return g;
-}
-
-void fill_taps(ConvArgs& a, int kind)
-{
-    std::memset(a.tapinfo, 0, sizeof(a.tapinfo));
-    if (kind == KIND_STEM) { a.tapinfo[0] = ConvArgs::make_tap(0, 0, 0); return; }
-    if (kind == KIND_CT4) {
-        // out = 2*in - 1 + k  (ConvTranspose2d k=4, s=2, p=1): even out <- k in {1 (d=0), 3 (d=-1)}; odd out <- k in {0 (d=+1), 2 (d=0)}
-        static const int kk[2][2] = {{1, 3}, {0, 2}}, dd[2][2] = {{0, -1}, {1, 0}};
-        for (int py = 0; py < 2; ++py)
-            for (int px = 0; px < 2; ++px)
-                for (int i = 0; i < 2; ++i)
-                    for (int j = 0; j < 2; ++j)
-                        a.tapinfo[(py * 2 + px) * 4 + i * 2 + j] = ConvArgs::make_tap(dd[py][i], dd[px][j], kk[py][i] * 4 + kk[px][j]);
-        return;
-    }
-    for (int ky = 0; ky < 3; ++ky)
-        for (int kx = 0; kx < 3; ++kx) a.tapinfo[ky * 3 + kx] = ConvArgs::make_tap(ky - 1, kx - 1, ky * 3 + kx);
-}
-
 struct PlanBuilder {
     ccn_handle_s* h;
     Plan* plan;
@@ -528,96 +491,54 @@ struct PlanBuilder {
     float2* new_ab(int C) { return (float2*)bump.take((size_t)B * C * sizeof(float2)); }
     int groups_for(int C) const { return C < h->G ? C : h->G; }
 
-    // 2 when the layer should run split-K on the persistent kernel (see conv()), else 1
-    int split_k_for(const ConvW& cw, const ConvGeom& g, bool has_gn, bool s2pr) const
+    // the inference plan's policy for conv_route: the stride-2 conv on the persistent kernel from 128 eight-row tiles (half the CUs),
+    // the ConvTranspose only where conv_tile_rows gives 8 rows; split-K on the stride-2 layers (CCN_SPLITK_S1=1: the 3x3 s1 layers too)
+    ConvRoute route(const ConvW& cw, int Hin, int Win, bool gn_ab, bool res, bool film) const
     {
-        static const bool off = diag_env("CCN_NO_SPLITK") != nullptr;
-        if (off || h->cfg.dtype != CCN_DTYPE_BF16 || !cw.wfrag || cw.BN != 128) return 1;
-        // Measured at C2: a single-tile-per-workgroup launch of the persistent kernel carries ~25 us of fixed cost (cold first
-        // chunk, serial last epilogue, hand-off), so halving the K loop of the 32-pixel 3x3 s1 layers (56 us) does not beat the
-        // 4-row kernel (53 us); it does help the stride-2 conv into that level (63 -> 56 us), whose alternative is 128 tiles.
-        // CCN_SPLITK_S1=1 enables it for the stride-1 layers too.
-        static const bool s1_too = diag_env("CCN_SPLITK_S1") != nullptr;
-        if (!((cw.kind == KIND_C3S1 && s1_too) || (cw.kind == KIND_C3S2 && s2pr))) return 1;
-        if (!conv_pr_selected(h->cfg.dtype, cw.kind, cw.BN, 8)) return 1;
-        const int cke = 64;
-        const long tiles8 = (long)B * ceil_div(g.MH, 8) * g.n_tx * g.npar * g.n_nt;
-        int nchunk = cw.Cin_pad / cke;
-        if (cw.kind == KIND_C3S2) { if ((nchunk & 1)) return 1; nchunk *= 5; }
-        (void)has_gn;
-        return (tiles8 >= 32 && tiles8 <= 128 && nchunk >= 4 && (nchunk & 1) == 0) ? 2 : 1;
+        static const ConvPolicy policy{true, 128, false, !diag_env("CCN_NO_SPLITK"), diag_env("CCN_SPLITK_S1") != nullptr, true};
+        return conv_route({h->cfg.dtype, cw.kind, false, cw.BN, cw.Cin, cw.Cin_pad, cw.Cout, cw.Cout_pad, B, Hin, Win, h->G, cw.wfrag != nullptr,
+                           gn_ab, res, film}, policy);
     }
 
     // conv launch; `want_part`: also emit the partial sums of the output's GroupNorm
     // `in_norm` (instead of gn_ab): the input goes through this GroupNorm (+ SiLU) first; its finalize either becomes part of
-    // the conv launch itself (persistent kernel, see in_kernel_stats) or a gn_finalize launch in front of it
+    // the conv launch itself (persistent kernel, conv_in_kernel_stats) or a gn_finalize launch in front of it
     void conv(const ConvW& cw, int family, const TensorRef& in, TensorRef& out, const float2* gn_ab, int film_off,
               const TensorRef* res, bool want_part, bool is_stem = false, bool is_head = false, const NormW* in_norm = nullptr)
     {
-        ConvGeom g = conv_geom(cw, B, in.H, in.W);
-        // stride-2 convs: the 4-wave kernel works on 4-row tiles; the persistent kernel (bf16) takes them on 8-row tiles as soon
-        // as half the CUs get a tile (it is ~2.5x more efficient per tile)
-        const int cke = h->cfg.dtype == CCN_DTYPE_BF16 ? 64 : 32;
-        const bool s2pr = cw.kind == KIND_C3S2 && cw.wfrag && conv_pr_selected(h->cfg.dtype, cw.kind, cw.BN, 8) && !gn_ab &&
-                          cw.Cin_pad / cke >= 2 && (double)B * g.Hout * g.Wout * cw.Cout * h->elem < 2.0e9 &&
-                          (long)B * ceil_div(g.MH, 8) * g.n_tx * g.n_nt >= 128;
-        if (s2pr) { g.th = 8; g.n_ty = ceil_div(g.MH, 8); }
-        // small layers (at most #CUs/2 tiles of 8 rows: the 32-pixel level at C2): 8-row tiles on the persistent kernel with the
-        // Cin chunks split over two workgroups per tile instead of 4-row tiles on the LDS-bound kernel
-        const int ksplit = res ? 1 : split_k_for(cw, g, gn_ab != nullptr, s2pr);      // (the split-K instantiation has no residual path of its own)
-        if (ksplit == 2 && g.th != 8) { g.th = 8; g.n_ty = ceil_div(g.MH, 8); }
+        const ConvRoute r = route(cw, in.H, in.W, gn_ab != nullptr, res != nullptr, film_off >= 0);
+        const ConvGeom& g = r.g;
         std::shared_ptr<ConvArgs> ap(new ConvArgs());
         ConvArgs& a = *ap;
-        a.in = in.p; a.w = cw.w; a.wfrag = cw.wfrag; a.bias = cw.bias; a.out = out.p;
+        r.fill(a);
+        a.in = in.p; a.w = cw.w; a.wfrag = r.uses_frag() ? cw.wfrag : nullptr; a.bias = cw.bias; a.out = out.p;
         a.film = nullptr; a.res = res ? res->p : nullptr;
-        a.B = B; a.Hin = in.H; a.Win = in.W; a.Cin = cw.Cin; a.Cin_pad = cw.Cin_pad;
-        a.Hout = g.Hout; a.Wout = g.Wout; a.Cout = cw.Cout; a.Cout_pad = cw.Cout_pad;
-        a.MH = g.MH; a.MW = g.MW; a.OS = g.OS; a.npar = g.npar; a.ntaps = g.ntaps;
-        a.n_ty = g.n_ty; a.n_tx = g.n_tx; a.n_nt = g.n_nt; a.th = g.th;
-        a.nchunk = cw.Cin_pad / cke;
-        a.silu = 1;
-        a.G = groups_for(cw.Cout); a.cpg = cw.Cout / a.G;
-        a.nslot = g.n_ty * g.n_tx * g.npar * g.n_nt;
-        if (s2pr) { a.nchunk = 5 * (cw.Cin_pad / cke); a.ntaps = 2; }   // plane passes (ccn_conv_pr.hip)
-        const bool pr = cw.wfrag && conv_pr_selected(h->cfg.dtype, cw.kind, cw.BN, g.th) && cw.Cin_pad / cke >= 2 && (cw.kind != KIND_C3S2 || s2pr) &&
-                        (double)B * g.Hout * g.Wout * cw.Cout * h->elem < 2.0e9;
-        if (!pr) a.wfrag = nullptr;
-        a.use_pr = pr ? 1 : 0;
+        static const bool no_instat = diag_env("CCN_NO_INSTAT") != nullptr;       // diagnostics build only
         if (in_norm) {
-            if (pr && ksplit != 2 && cw.kind == KIND_C3S1 && in_kernel_stats(in, cw.Cin)) {
-                const int cpg_in = cw.Cin / groups_for(cw.Cin);
+            const int G_in = groups_for(cw.Cin), cpg_in = cw.Cin / G_in;
+            if (r.gs_ok && !no_instat && in.C == cw.Cin && conv_in_kernel_stats(h->cfg.dtype, in.C, G_in, in.n_sp, in.bn)) {
                 a.gs_part = in.part; a.gs_gamma = in_norm->gamma; a.gs_beta = in_norm->beta;
                 a.gs_inv_count = 1.0 / ((double)cpg_in * in.H * in.W);
                 a.gs_nsp = in.n_sp; a.gs_nnt = in.n_nt; a.gs_bn = in.bn; a.gs_cpg = cpg_in;
             } else gn_ab = gn(in, *in_norm);                     // (pushes the finalize launch in front of this conv)
         }
         a.gn_ab = gn_ab;
-        a.ksplit = 1;
-        if (pr && ksplit == 2) {
-            a.ksplit = 2;
+        if (r.ksplit == 2) {
             a.kpart = bump.take((size_t)B * g.Hout * g.Wout * cw.Cout * h->elem);
-            const size_t fbytes = (size_t)B * g.n_ty * g.n_tx * g.npar * g.n_nt * 4 * sizeof(unsigned);
+            const size_t fbytes = (size_t)B * r.fin_blocks * 4 * sizeof(unsigned);
             a.kflag = (unsigned*)bump.take(fbytes);
             if (a.kflag) plan->zero_once.push_back({a.kflag, fbytes});
         }
-        // (the persistent kernel publishes ONE partial per tile: its four producer waves' sums are combined in LDS first)
-        const bool stem2 = is_stem && cw.wfrag && stem2_supported(h->cfg.dtype, cw.Cin, cw.Cout, h->G);
-        a.use_stem2 = stem2 ? 1 : 0;
-        if (stem2) { a.wfrag = cw.wfrag; a.nslot = 4 * stem2_blocks(in.H, in.W, nullptr); }   // one slot per wave
         a.film_bstride = film_stride;
         a.err = h->err_dev;
-        fill_taps(a, cw.kind);
         if (want_part) {
             out.part = (float2*)bump.take((size_t)B * a.G * a.nslot * sizeof(float2));
-            out.n_sp = g.n_ty * g.n_tx * g.npar; out.n_nt = g.n_nt; out.bn = cw.BN;
-            if (pr) out.pr = true;
-            if (stem2) { out.n_sp = a.nslot; out.n_nt = 1; out.bn = 1 << 30; out.pr = true; }
+            out.n_sp = r.part_nsp; out.n_nt = r.part_nnt; out.bn = r.part_bn;
+            if (r.pr || r.stem2) out.pr = true;
+            out.prod = ap;
         }
         a.part = out.part;
-        a.bn = cw.BN;
-        a.fin_blocks = g.n_ty * g.n_tx * g.npar * g.n_nt;
-        if (want_part) out.prod = ap;
-        const double macs = (double)B * g.Hout * g.Wout * cw.Cout * (double)(cw.kind == KIND_CT4 ? 4 : (cw.kind == KIND_STEM ? 9 : 9)) * cw.Cin;
+        const double macs = (double)B * g.Hout * g.Wout * cw.Cout * (double)(cw.kind == KIND_CT4 ? 4 : 9) * cw.Cin;
         double bytes = ((double)B * in.H * in.W * cw.Cin + (double)B * g.Hout * g.Wout * cw.Cout + (res ? (double)B * g.Hout * g.Wout * cw.Cout : 0.0)
                         + (double)(cw.kind == KIND_CT4 ? 16 : 9) * cw.Cin * cw.Cout) * h->elem;
         if (is_stem) bytes = (double)B * in.H * in.W * cw.Cin * 4 + ((double)B * g.Hout * g.Wout * cw.Cout + 9.0 * cw.Cin * cw.Cout) * h->elem;
@@ -646,21 +567,6 @@ struct PlanBuilder {
             return launch_conv(dtype, kind, bn, k, s);
         };
         plan->ops.push_back(std::move(L));
-    }
-
-    // The persistent kernel can form the scale/shift of its input's GroupNorm itself from the producer's partial sums (every
-    // producer wave reduces 8 groups x 8 lanes): 8 groups, a thread's 8-channel slice inside one group, and few enough slots
-    // per group that the reduction (slots / 8 loads per lane, redone whenever a workgroup moves to another sample) stays
-    // cheaper than the ~6.5 us of a finalize launch + kernel boundary -- true below the 256-pixel level at C2.
-    bool in_kernel_stats(const TensorRef& t, int C) const
-    {
-        static const bool off = diag_env("CCN_NO_INSTAT") != nullptr;       // diagnostics build only
-        if (off || h->cfg.dtype != CCN_DTYPE_BF16 || t.n_sp <= 0 || t.C != C) return false;
-        const int G = groups_for(C), cpg = C / G;
-        if (G != 8 || (cpg % 8) != 0) return false;
-        int nj = 1;
-        for (int g = 0; g < G; ++g) { const int n = ((g + 1) * cpg - 1) / t.bn - (g * cpg) / t.bn + 1; if (n > nj) nj = n; }
-        return (long)t.n_sp * nj <= 64;                            // 8 slots per lane: one round of loads
     }
 
     // GroupNorm finalize of tensor `t` for the norm (gamma, beta): returns the scale/shift table
@@ -720,16 +626,6 @@ struct PlanBuilder {
         return o;
     }
 
-    // the 3x3 s1 conv `cw` on an H x W input will run on the persistent kernel (same conditions as conv())
-    bool will_use_pr(const ConvW& cw, int H, int W) const
-    {
-        ConvGeom g = conv_geom(cw, B, H, W);
-        const int cke = h->cfg.dtype == CCN_DTYPE_BF16 ? 64 : 32;
-        if (split_k_for(cw, g, true, false) == 2) g.th = 8;
-        return cw.wfrag && conv_pr_selected(h->cfg.dtype, cw.kind, cw.BN, g.th) && cw.Cin_pad / cke >= 2 &&
-               (double)B * g.Hout * g.Wout * cw.Cout * h->elem < 2.0e9;
-    }
-
     // x + conv2(SiLU(GN2(FiLM(conv1(SiLU(GN1(x))))))) -- models/blocks.py:40-44
     TensorRef resblock(const ResW& r, const TensorRef& x, bool out_feeds_gn, int film_off = -2)
     {
@@ -738,7 +634,7 @@ struct PlanBuilder {
         // images/s against pre-pass + finalize-free conv; CCN_PREACT_PR=1 restores the pre-pass in front of it for A/B runs)
         static const bool preact_pr = diag_env("CCN_PREACT_PR") != nullptr;
         const bool pre = conv_wants_preact(r.c1.kind, r.c1.BN, r.c1.Cout_pad / r.c1.BN) && r.C / (h->elem == 2 ? 8 : 4) <= 256 &&
-                         (preact_pr || r.c1.Cout_pad / r.c1.BN >= 6 || !will_use_pr(r.c1, x.H, x.W));
+                         (preact_pr || r.c1.Cout_pad / r.c1.BN >= 6 || !route(r.c1, x.H, x.W, false, false, false).pr);
         static const bool fuse_act = !diag_env("CCN_NO_FUSED_GNACT");       // finalize folded into the pre-pass (A/B switch)
         const bool f1 = pre && fuse_act && x.n_sp > 0, f2 = pre && fuse_act;     // (n_sp, not the pointer: null while measuring)
         TensorRef y = new_tensor(r.C, x.H, x.W);

@@ -430,7 +430,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
         const int g = lane >> 3, sub = lane & 7;
         const int cpg = a.gs_cpg, pnt = a.gs_nnt, nsp = a.gs_nsp;
         const int jlo = CCN_FDIV(g * cpg, a.fd_gsbn, a.gs_bn), jhi = CCN_FDIV((g + 1) * cpg - 1, a.fd_gsbn, a.gs_bn), nj = jhi - jlo + 1;
-        const float2* const base = a.gs_part + (size_t)(b * 8 + g) * ((size_t)nsp * pnt) + jlo;   // nsp * nj <= 64 (host: in_kernel_stats)
+        const float2* const base = a.gs_part + (size_t)(b * 8 + g) * ((size_t)nsp * pnt) + jlo;   // nsp * nj <= 64 (host: conv_in_kernel_stats)
         int off[8];
         svmask = 0u;
 #pragma unroll

@@ -178,6 +178,50 @@ bool stem2_supported(int dtype, int cin, int cout, int G);
 int stem2_blocks(int H, int W, int* upw_out);
 hipError_t launch_stem2(const ConvArgs& a, hipStream_t s);
 
+// ---- one conv launch, described once for the inference plan (ccn_api.hip) and the training step (ccn_train.hip) --------------
+// Cin chunk of the kernels' K loop: one 128-byte LDS row (64 bf16 / 32 fp32); the operands' Cin_pad is a multiple of it
+inline int conv_cin_chunk(int dtype) { return dtype == 1 ? 64 : 32; }
+
+// pixel geometry: output size, the M grid a tile walks, output stride, parities and weight taps per parity, tiles of th x 32 pixels.
+// `four`: the 4x4 s2 p1 form of KIND_C3S2 (the training step's data gradient of the ConvTranspose)
+struct ConvGeom { int Hout, Wout, MH, MW, OS, npar, ntaps, n_ty, n_tx; };
+ConvGeom conv_geom(int kind, bool four, int Hin, int Win, int th);
+// tapinfo[16] of ConvArgs (and of the weight-gradient kernel's arguments)
+void fill_taps(int* tapinfo, int kind, bool four);
+
+// What the caller's build of the library does differently (one constant per caller, the diagnostics build's switches folded in)
+struct ConvPolicy {
+    bool pr;               // the persistent kernel at all
+    long s2_min_tiles8;    // stride-2 conv on the persistent kernel from this many 8-row tiles
+    bool ct_like_s2;       // ConvTranspose: decided like the stride-2 conv (8-row tiles forced), else only where conv_tile_rows gives 8 rows
+    bool split_k;          // split-K on the persistent kernel (stride-2 layers)
+    bool split_k_s1;       // ... and on the 3x3 s1 layers
+    bool stem2;            // the dedicated stem kernel
+};
+// What the caller knows about the launch
+struct ConvQuery {
+    int dtype, kind;
+    bool four;
+    int BN, Cin, Cin_pad, Cout, Cout_pad, B, Hin, Win;
+    int G;                 // GroupNorm groups of the model (a layer uses min(C, G))
+    bool frag;             // a fragment-ordered weight operand exists
+    bool gn_ab, res, film; // prologue scale/shift table, residual, FiLM present
+};
+// Everything derived from those: kernel, tiles, K loop, GroupNorm slots
+struct ConvRoute {
+    ConvQuery q;
+    ConvGeom g;            // at the chosen tile rows
+    int th, n_nt, nchunk, ntaps, ksplit, nslot, fin_blocks;
+    bool pr, stem2;
+    bool gs_ok;            // may form its input GroupNorm's statistics in-kernel (conv_in_kernel_stats on the input's partial sums)
+    int part_nsp, part_nnt, part_bn;   // layout of the output's GroupNorm partial sums, as gn_finalize and the consumers take it
+    bool uses_frag() const { return pr || stem2; }
+    void fill(ConvArgs& a) const;      // every field of `a` but the pointers, film_bstride and err
+};
+ConvRoute conv_route(const ConvQuery& q, const ConvPolicy& p);
+// the persistent kernel can finalize its input's GroupNorm (C channels, G groups) from the producer's n_sp x bn partial sums
+bool conv_in_kernel_stats(int dtype, int C, int G, int n_sp, int bn);
+
 // dedicated head (ccn_head.hip): bf16 mode, out_norm folded into per-sample weights, the nine taps in the MFMA N dimension
 bool head2_supported(int dtype, int cin, int cout, int G);
 size_t head2_scratch_bytes(int B, int C);

@@ -442,6 +442,114 @@ bool conv_pr_selected(int dtype, int kind, int bn, int th)
     return dtype == 1 && conv_ws_enabled() && conv_variant() == 4 && conv_pr_supported(kind, bn, th);
 }
 
+ConvGeom conv_geom(int kind, bool four, int Hin, int Win, int th)
+{
+    ConvGeom g{};
+    switch (kind) {
+        case KIND_C3S2: g.Hout = (Hin - 1) / 2 + 1; g.Wout = (Win - 1) / 2 + 1; g.MH = g.Hout; g.MW = g.Wout; g.OS = 1; g.npar = 1; g.ntaps = four ? 16 : 9; break;
+        case KIND_CT4: g.Hout = Hin * 2; g.Wout = Win * 2; g.MH = Hin; g.MW = Win; g.OS = 2; g.npar = 4; g.ntaps = 4; break;
+        case KIND_STEM: g.Hout = Hin; g.Wout = Win; g.MH = Hin; g.MW = Win; g.OS = 1; g.npar = 1; g.ntaps = 1; break;
+        default: g.Hout = Hin; g.Wout = Win; g.MH = Hin; g.MW = Win; g.OS = 1; g.npar = 1; g.ntaps = 9; break;
+    }
+    g.n_ty = (g.MH + th - 1) / th; g.n_tx = (g.MW + 31) / 32;
+    return g;
+}
+
+void fill_taps(int* tapinfo, int kind, bool four)
+{
+    for (int i = 0; i < 16; ++i) tapinfo[i] = 0;
+    if (kind == KIND_STEM) { tapinfo[0] = ConvArgs::make_tap(0, 0, 0); return; }
+    if (kind == KIND_CT4) {
+        // out = 2*in - 1 + k (ConvTranspose2d k=4, s=2, p=1): even out <- k in {1 (d=0), 3 (d=-1)}; odd out <- k in {0 (d=+1), 2 (d=0)}
+        static const int kk[2][2] = {{1, 3}, {0, 2}}, dd[2][2] = {{0, -1}, {1, 0}};
+        for (int py = 0; py < 2; ++py)
+            for (int px = 0; px < 2; ++px)
+                for (int i = 0; i < 2; ++i)
+                    for (int j = 0; j < 2; ++j)
+                        tapinfo[(py * 2 + px) * 4 + i * 2 + j] = ConvArgs::make_tap(dd[py][i], dd[px][j], kk[py][i] * 4 + kk[px][j]);
+        return;
+    }
+    const int k = four ? 4 : 3;                              // 4x4 s2 p1: in = 2 m + (k - 1), k = 0..3
+    for (int ky = 0; ky < k; ++ky)
+        for (int kx = 0; kx < k; ++kx) tapinfo[ky * k + kx] = ConvArgs::make_tap(ky - 1, kx - 1, ky * k + kx);
+}
+
+ConvRoute conv_route(const ConvQuery& q, const ConvPolicy& p)
+{
+    ConvRoute r{};
+    r.q = q;
+    r.n_nt = q.Cout_pad / q.BN;
+    const ConvGeom g8 = conv_geom(q.kind, q.four, q.Hin, q.Win, 8);
+    const long tiles8 = (long)q.B * g8.n_ty * g8.n_tx * g8.npar * r.n_nt;
+    r.th = conv_tile_rows(q.kind, q.BN, q.B, g8.MH, g8.MW, g8.npar, r.n_nt);
+    const int nch = q.Cin_pad / conv_cin_chunk(q.dtype);
+    // The persistent register-weight kernel (ccn_conv_pr.hip): bf16, fragment-ordered weights, >= 2 Cin chunks, outputs below 2 GB.
+    // 3x3 s1 on 8- or 4-row tiles; the stride-2 conv (plane passes) on 8-row tiles as soon as enough of the CUs get one (it is ~2.5x
+    // more efficient per tile than the 4-wave kernel on 4-row tiles), the ConvTranspose (parities) likewise or where conv_tile_rows
+    // gives 8 rows.  Neither of those forms has an input GroupNorm, nor a ConvTranspose in the 4x4 form.
+    const double out_bytes = (double)q.B * g8.Hout * g8.Wout * q.Cout * (q.dtype == 1 ? 2 : 4);
+    if (p.pr && q.frag && nch >= 2 && !(q.res && q.film) && out_bytes < 2.0e9) {
+        if (q.kind == KIND_C3S1) r.pr = conv_pr_selected(q.dtype, q.kind, q.BN, r.th);
+        else if (!q.gn_ab && (q.kind == KIND_C3S2 || (q.kind == KIND_CT4 && !q.four))) {
+            if (q.kind == KIND_CT4 && !p.ct_like_s2) r.pr = conv_pr_selected(q.dtype, q.kind, q.BN, r.th);
+            else if (conv_pr_selected(q.dtype, q.kind, q.BN, 8) && tiles8 >= p.s2_min_tiles8) { r.pr = true; r.th = 8; }
+        }
+    }
+    // Split-K: small layers (at most #CUs/2 tiles of 8 rows: the 32-pixel level at C2) on 8-row tiles with the Cin chunks split over
+    // two workgroups per tile.  Measured at C2: a single-tile-per-workgroup launch of the persistent kernel carries ~25 us of fixed cost
+    // (cold first chunk, serial last epilogue, hand-off), so halving the K loop of the 32-pixel 3x3 s1 layers (56 us) does not beat the
+    // 4-row kernel (53 us); it does help the stride-2 conv into that level (63 -> 56 us), whose alternative is 128 tiles.  The split-K
+    // instantiation has no residual path.
+    r.ksplit = 1;
+    if (r.pr && p.split_k && !q.res && (q.kind == KIND_C3S2 || (q.kind == KIND_C3S1 && p.split_k_s1))) {
+        const int nk = q.kind == KIND_C3S2 ? 5 * nch : nch;              // K steps (stride 2: five plane passes per chunk)
+        if (tiles8 >= 32 && tiles8 <= 128 && nk >= 4 && (nch & 1) == 0) { r.ksplit = 2; r.th = 8; }
+    }
+    r.g = conv_geom(q.kind, q.four, q.Hin, q.Win, r.th);
+    r.nchunk = nch; r.ntaps = r.g.ntaps;
+    if (r.pr && q.kind == KIND_C3S2) {                                   // plane passes (ccn_conv_pr.hip)
+        if (q.four) r.nchunk *= 4;                                       // 4x4: four passes of 2x2 taps (ntaps stays 16)
+        else { r.nchunk *= 5; r.ntaps = 2; }                             // 3x3: five passes of two tap slots
+    }
+    r.gs_ok = r.pr && r.ksplit == 1 && q.kind == KIND_C3S1;
+    // (the persistent kernel publishes ONE partial per tile: its four producer waves' sums are combined in LDS first)
+    r.fin_blocks = r.g.n_ty * r.g.n_tx * r.g.npar * r.n_nt;
+    r.nslot = r.fin_blocks;
+    r.part_nsp = r.g.n_ty * r.g.n_tx * r.g.npar; r.part_nnt = r.n_nt; r.part_bn = q.BN;
+    r.stem2 = p.stem2 && q.kind == KIND_STEM && q.frag && stem2_supported(q.dtype, q.Cin, q.Cout, q.G) && !q.gn_ab && !q.film && !q.res;
+    if (r.stem2) {                                                       // one slot per wave
+        r.nslot = 4 * stem2_blocks(q.Hin, q.Win, nullptr);
+        r.part_nsp = r.nslot; r.part_nnt = 1; r.part_bn = 1 << 30;
+    }
+    return r;
+}
+
+void ConvRoute::fill(ConvArgs& a) const
+{
+    a.B = q.B; a.Hin = q.Hin; a.Win = q.Win; a.Cin = q.Cin; a.Cin_pad = q.Cin_pad;
+    a.Hout = g.Hout; a.Wout = g.Wout; a.Cout = q.Cout; a.Cout_pad = q.Cout_pad;
+    a.MH = g.MH; a.MW = g.MW; a.OS = g.OS; a.npar = g.npar; a.ntaps = ntaps;
+    a.th = th; a.n_ty = g.n_ty; a.n_tx = g.n_tx; a.n_nt = n_nt; a.nchunk = nchunk;
+    a.use_pr = pr ? 1 : 0; a.use_stem2 = stem2 ? 1 : 0; a.ksplit = ksplit;
+    a.silu = 1;
+    a.G = q.Cout < q.G ? q.Cout : q.G; a.cpg = q.Cout / a.G;
+    a.nslot = nslot; a.fin_blocks = fin_blocks; a.bn = q.BN;
+    fill_taps(a.tapinfo, q.kind, q.four);
+}
+
+// The persistent kernel can form the scale/shift of its input's GroupNorm itself from the producer's partial sums (every producer
+// wave reduces 8 groups x 8 lanes): 8 groups, a thread's 8-channel slice inside one group, and few enough slots per group that the
+// reduction (slots / 8 loads per lane, redone whenever a workgroup moves to another sample) stays cheaper than the ~6.5 us of a
+// finalize launch + kernel boundary -- true below the 256-pixel level at C2.
+bool conv_in_kernel_stats(int dtype, int C, int G, int n_sp, int bn)
+{
+    if (dtype != 1 || n_sp <= 0 || G != 8 || (C / G) % 8 != 0) return false;
+    const int cpg = C / G;
+    int nj = 1;
+    for (int g = 0; g < G; ++g) { const int n = ((g + 1) * cpg - 1) / bn - (g * cpg) / bn + 1; if (n > nj) nj = n; }
+    return (long)n_sp * nj <= 64;                                       // 8 slots per lane: one round of loads
+}
+
 hipError_t launch_conv(int dtype, int kind, int bn, const ConvArgs& a, hipStream_t s)
 {
     if (a.use_stem2) return launch_stem2(a, s);

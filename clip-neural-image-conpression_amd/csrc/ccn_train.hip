@@ -15,6 +15,7 @@
 #include "../../include/ccn_hip.h"
 #include "ccn_train.h"
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -37,7 +38,6 @@ int tfail(int code, const std::string& msg) { ccn_internal_set_error(msg.c_str()
     } while (0)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 struct PInfo { std::string name; std::vector<int64_t> shape; size_t off = 0; size_t numel() const { size_t n = 1; for (auto d : shape) n *= (size_t)d; return n; } };
 
@@ -179,7 +179,7 @@ bool alloc_dev(ccn_trainer_s* tr, size_t bytes, void** out, std::string& err)
 // operand geometry and device buffers of one convolution (forward and data-gradient operands)
 bool setup_conv(ccn_trainer_s* tr, TConvW& w, std::string& err)
 {
-    const int cke = tr->elem == 2 ? 64 : 32;
+    const int cke = conv_cin_chunk(tr->cfg.dtype);
     const int fkind = w.kind;
     w.BN = conv_bn_for(w.Cout, fkind);
     w.Cout_pad = (int)align_up(w.Cout, w.BN);
@@ -245,42 +245,6 @@ bool setup_conv(ccn_trainer_s* tr, TConvW& w, std::string& err)
         w.pf_d = {src, w.wd_frag, fkind == KIND_C3S2 ? PK_FRAG_CT_DG : PK_FRAG_P4_DG, w.Cout, w.Cin, 16, w.dCout_pad, w.dCin_pad};
     }
     return true;
-}
-
-void fill_taps(int* tapinfo, int kind, bool four_by_four)
-{
-    std::memset(tapinfo, 0, 16 * sizeof(int));
-    if (kind == KIND_STEM) { tapinfo[0] = ConvArgs::make_tap(0, 0, 0); return; }
-    if (kind == KIND_CT4) {
-        // out = 2*in - 1 + k (ConvTranspose2d k=4, s=2, p=1): even out <- k in {1 (d=0), 3 (d=-1)}; odd out <- k in {0 (d=+1), 2 (d=0)}
-        static const int kk[2][2] = {{1, 3}, {0, 2}}, dd[2][2] = {{0, -1}, {1, 0}};
-        for (int py = 0; py < 2; ++py)
-            for (int px = 0; px < 2; ++px)
-                for (int i = 0; i < 2; ++i)
-                    for (int j = 0; j < 2; ++j)
-                        tapinfo[(py * 2 + px) * 4 + i * 2 + j] = ConvArgs::make_tap(dd[py][i], dd[px][j], kk[py][i] * 4 + kk[px][j]);
-        return;
-    }
-    if (four_by_four) {                                      // 4x4 s2 p1 convolution: in = 2 m + (k - 1), k = 0..3
-        for (int ky = 0; ky < 4; ++ky)
-            for (int kx = 0; kx < 4; ++kx) tapinfo[ky * 4 + kx] = ConvArgs::make_tap(ky - 1, kx - 1, ky * 4 + kx);
-        return;
-    }
-    for (int ky = 0; ky < 3; ++ky)
-        for (int kx = 0; kx < 3; ++kx) tapinfo[ky * 3 + kx] = ConvArgs::make_tap(ky - 1, kx - 1, ky * 3 + kx);
-}
-
-struct Geom { int Hout, Wout, MH, MW, OS, npar, ntaps; };
-Geom geom_of(int kind, int Hin, int Win, bool four_by_four)
-{
-    Geom g{};
-    switch (kind) {
-        case KIND_C3S2: g.Hout = (Hin - 1) / 2 + 1; g.Wout = (Win - 1) / 2 + 1; g.MH = g.Hout; g.MW = g.Wout; g.OS = 1; g.npar = 1; g.ntaps = four_by_four ? 16 : 9; break;
-        case KIND_CT4: g.Hout = Hin * 2; g.Wout = Win * 2; g.MH = Hin; g.MW = Win; g.OS = 2; g.npar = 4; g.ntaps = 4; break;
-        case KIND_STEM: g.Hout = Hin; g.Wout = Win; g.MH = Hin; g.MW = Win; g.OS = 1; g.npar = 1; g.ntaps = 1; break;
-        default: g.Hout = Hin; g.Wout = Win; g.MH = Hin; g.MW = Win; g.OS = 1; g.npar = 1; g.ntaps = 9; break;
-    }
-    return g;
 }
 
 // One walk over the layer list.  `launch` off: only the allocation sequence (and the scratch maxima) are reproduced.
@@ -370,76 +334,53 @@ struct Walk {
     }
 
     // ---- forward pieces --------------------------------------------------------------------------------------------------
-    // generic launch of the forward conv kernels.  `kind`: kernel family; N = output channels of this launch, K = input channels
-    // input GroupNorm formed inside the persistent kernel from the producer's partial sums (its GS = 1; the inference plan's in_kernel_stats)
-    struct GsIn { const float2* part; int n_sp, n_nt, bn, cpg; const float* gamma; const float* beta; double inv_count; };
-    bool run_conv(int fam, int kind, bool four, const PackDesc& plain, const PackDesc& frag, int BN, int K, int Kpad, int N, int Npad, const float* bias,
-                  const void* in, int Hin, int Win, TT* out, void* out_p, const float2* gn_ab, const float* film, const void* res, bool want_part, float* eps_out,
-                  const GsIn* gs = nullptr, bool* gs_used = nullptr)
+    // The training step's policy for conv_route: the stride-2 conv, the ConvTranspose and the 4x4 data-gradient form on the persistent
+    // kernel from CCN_TRAIN_PR2_MIN (64) eight-row tiles, no split-K.  `four`: the 4x4 form of KIND_C3S2.
+    ConvRoute route(int kind, bool four, const PackDesc& frag, int BN, int K, int Kpad, int N, int Npad, int Hin, int Win, bool gn_ab, bool film, bool res) const
     {
-        const Geom g = geom_of(kind, Hin, Win, four);
-        const int cke = tr->elem == 2 ? 64 : 32;
-        const int n_nt = Npad / BN;
-        int th = conv_tile_rows(kind, BN, B, g.MH, g.MW, g.npar, n_nt);
-        // the persistent register-weight kernel (ccn_conv_pr.hip) where the inference plan would use it: bf16, 3x3 s1 on 8- or 4-row tiles;
-        // stride-2 conv (plane passes) and ConvTranspose (parities) on 8-row tiles as soon as half the CUs get one
-        static const bool no_pr = diag_env("CCN_TRAIN_NO_PR") != nullptr;     // A/B switches
-        static const bool no_pr2 = diag_env("CCN_TRAIN_NO_PR_S2CT") != nullptr;
-        static const long pr2_min = diag_env("CCN_TRAIN_PR2_MIN") ? atol(diag_env("CCN_TRAIN_PR2_MIN")) : 64;
-        bool pr = false;
-        if (!no_pr && frag.dst && Kpad / cke >= 2 && !(res && film) && (double)B * g.Hout * g.Wout * N * tr->elem < 2.0e9) {
-            if (kind == KIND_C3S1) pr = conv_pr_selected(tr->cfg.dtype, kind, BN, th);
-            else if (!no_pr2 && !gn_ab && (kind == KIND_C3S2 || (kind == KIND_CT4 && !four)) && conv_pr_selected(tr->cfg.dtype, kind, BN, 8) &&
-                     (long)B * ceil_div(g.MH, 8) * ceil_div(g.MW, 32) * g.npar * n_nt >= pr2_min) { pr = true; th = 8; }
-        }
-        static const bool no_stem2 = diag_env("CCN_TRAIN_NO_STEM2") != nullptr;
-        const bool stem2 = !no_stem2 && kind == KIND_STEM && frag.dst && stem2_supported(tr->cfg.dtype, K, N, tr->G) && !gn_ab && !film && !res;
-        if (!base) pack_list.push_back((pr || stem2) ? frag : plain);      // measuring walk: this shape's repack list
+        static const char* pr2_min = diag_env("CCN_TRAIN_PR2_MIN");         // A/B switches
+        static const ConvPolicy policy{!diag_env("CCN_TRAIN_NO_PR"), diag_env("CCN_TRAIN_NO_PR_S2CT") ? LONG_MAX : (pr2_min ? atol(pr2_min) : 64), true,
+                                       false, false, !diag_env("CCN_TRAIN_NO_STEM2")};
+        return conv_route({tr->cfg.dtype, kind, four, BN, K, Kpad, N, Npad, B, Hin, Win, tr->G, frag.dst != nullptr, gn_ab, res, film}, policy);
+    }
+    ConvRoute fwd_route(const TConvW& w, int Hin, int Win, bool gn_ab, bool film, bool res) const
+    {
+        return route(w.kind, false, w.pf_f, w.BN, w.Cin, w.Cin_pad, w.Cout, w.Cout_pad, Hin, Win, gn_ab, film, res);
+    }
+    // launch of the conv kernels on route `r`
+    // input GroupNorm formed inside the persistent kernel from the producer's partial sums (its GS = 1; only where r.gs_ok)
+    struct GsIn { const float2* part; int n_sp, n_nt, bn, cpg; const float* gamma; const float* beta; double inv_count; };
+    bool run_conv(int fam, const ConvRoute& r, const PackDesc& plain, const PackDesc& frag, const float* bias, const void* in, TT* out, void* out_p,
+                  const float2* gn_ab, const float* film, const void* res, bool want_part, float* eps_out, const GsIn* gs = nullptr)
+    {
+        if (!base) pack_list.push_back(r.uses_frag() ? frag : plain);   // measuring walk: this shape's repack list
         ConvArgs a{};
-        a.in = in; a.w = plain.dst; a.wfrag = pr ? frag.dst : nullptr; a.use_pr = pr ? 1 : 0; a.bias = bias; a.out = out_p;
+        r.fill(a);
+        a.in = in; a.w = plain.dst; a.wfrag = r.uses_frag() ? frag.dst : nullptr; a.bias = bias; a.out = out_p;
         a.gn_ab = gn_ab; a.film = film; a.res = res;
-        if (gs_used) *gs_used = false;
-        if (gs && pr && kind == KIND_C3S1) {                    // (no split-K in the training step)
+        if (gs) {
             a.gn_ab = nullptr;
             a.gs_part = gs->part; a.gs_gamma = gs->gamma; a.gs_beta = gs->beta; a.gs_inv_count = gs->inv_count;
             a.gs_nsp = gs->n_sp; a.gs_nnt = gs->n_nt; a.gs_bn = gs->bn; a.gs_cpg = gs->cpg;
-            if (gs_used) *gs_used = true;
         }
-        a.B = B; a.Hin = Hin; a.Win = Win; a.Cin = K; a.Cin_pad = Kpad;
-        a.Hout = g.Hout; a.Wout = g.Wout; a.Cout = N; a.Cout_pad = Npad;
-        a.MH = g.MH; a.MW = g.MW; a.OS = g.OS; a.npar = g.npar; a.ntaps = g.ntaps;
-        a.th = th; a.n_ty = ceil_div(g.MH, th); a.n_tx = ceil_div(g.MW, 32); a.n_nt = n_nt;
-        a.nchunk = Kpad / cke;
-        if (pr && kind == KIND_C3S2) {                                     // plane passes (ccn_conv_pr.hip)
-            if (four) a.nchunk *= 4;                                       // 4x4: four passes of 2x2 taps (a.ntaps stays 16)
-            else { a.nchunk *= 5; a.ntaps = 2; }                           // 3x3: five passes of two tap slots
-        }
-        a.silu = 1; a.ksplit = 1;
-        a.G = groups_for(N); a.cpg = N / a.G;
-        a.nslot = a.n_ty * a.n_tx * g.npar * n_nt;                        // (the persistent kernel too: one partial per tile)
-        if (stem2) { a.use_stem2 = 1; a.wfrag = frag.dst; a.nslot = 4 * stem2_blocks(Hin, Win, nullptr); }   // one slot per wave
         a.film_bstride = tr->F;
-        a.bn = BN;
-        a.fin_blocks = a.n_ty * a.n_tx * g.npar * n_nt;
         a.eps_out = eps_out;
         // (measured and dropped: capping the data-gradient convs' persistent grid to the CUs the side stream's weight-gradient kernel
         // leaves free -- 192 / 160 / 128 workgroups: 652-658 vs 663 images/s uncapped; docs/EXPERIMENTS.md R3.12)
-        fill_taps(a.tapinfo, kind, four);
         if (want_part && out) {
             out->part = (float2*)take((size_t)B * a.G * a.nslot * sizeof(float2));
-            out->n_sp = a.n_ty * a.n_tx * g.npar; out->n_nt = n_nt; out->bn = BN;
-            if (stem2) { out->n_sp = a.nslot; out->n_nt = 1; out->bn = 1 << 30; }
+            out->n_sp = r.part_nsp; out->n_nt = r.part_nnt; out->bn = r.part_bn;
             a.part = out->part;
         }
         if (!launch) return true;
-        mark(fam, 2.0 * B * g.Hout * g.Wout * (double)N * (kind == KIND_CT4 ? 4 : (kind == KIND_STEM ? 1 : g.ntaps)) * (kind == KIND_STEM ? 9.0 * K : (double)K));
-        return ok(launch_conv(tr->cfg.dtype, kind, BN, a, st), "conv");
+        const int kind = r.q.kind, K = r.q.Cin, N = r.q.Cout;
+        mark(fam, 2.0 * B * r.g.Hout * r.g.Wout * (double)N * (kind == KIND_CT4 ? 4 : (kind == KIND_STEM ? 1 : r.g.ntaps)) * (kind == KIND_STEM ? 9.0 * K : (double)K));
+        return ok(launch_conv(tr->cfg.dtype, kind, r.q.BN, a, st), "conv");
     }
-    bool conv_fwd(const TConvW& w, const TT& in, TT& out, const float2* gn_ab, const float* film, const TT* res, bool want_part, const void* in_override = nullptr,
-                  float* eps_out = nullptr, const GsIn* gs = nullptr, bool* gs_used = nullptr)
+    bool conv_fwd(const TConvW& w, const TT& in, TT& out, const float2* gn_ab, const float* film, const TT* res, bool want_part, const void* in_override = nullptr)
     {
-        return run_conv(TF_CONV_FWD, w.kind, false, w.pd_f, w.pf_f, w.BN, w.Cin, w.Cin_pad, w.Cout, w.Cout_pad, launch ? par(w.pb) : nullptr, in_override ? in_override : in.p, in.H, in.W,
-                        &out, out.p, gn_ab, film, res ? res->p : nullptr, want_part, eps_out, gs, gs_used);
+        return run_conv(TF_CONV_FWD, fwd_route(w, in.H, in.W, gn_ab != nullptr, film != nullptr, res != nullptr), w.pd_f, w.pf_f, launch ? par(w.pb) : nullptr,
+                        in_override ? in_override : in.p, &out, out.p, gn_ab, film, res ? res->p : nullptr, want_part, nullptr);
     }
     // ---- forward ResBlock conv with its GroupNorm + SiLU, side-stream form (bf16, plain stream launches) --------------------------------
     // The conv transforms its raw input in its producer waves (the inference kernels' prologue: statistics formed in-kernel from the
@@ -452,17 +393,10 @@ struct Walk {
         static const bool off_ = diag_env("CCN_TRAIN_NO_SIDE_PRE") != nullptr;       // A/B switch
         return launch && !off_ && side_active() && !tr->use_graph && tr->pack_dg_done && tr->elem == 2;
     }
-    bool in_kernel_stats_ok(const TT& t, int C) const
-    {
-        const int G = groups_for(C), cpg = C / G;
-        if (tr->elem != 2 || t.n_sp <= 0 || G != 8 || (cpg % 8) != 0) return false;
-        int nj = 1;
-        for (int g = 0; g < G; ++g) { const int n = ((g + 1) * cpg - 1) / t.bn - (g * cpg) / t.bn + 1; if (n > nj) nj = n; }
-        return (long)t.n_sp * nj <= 64;
-    }
-    // (allocation order of the pre-pass form, which the never-launching measuring / replay walks go through: activated tensor -- by the
-    // caller --, tables, conv output, the output's partial sums)
-    bool norm_conv_fwd_side(const TT& x, const TNorm& n, const TConvW& w, float2*& ab, float2*& stats, const TT& xa, TT& y, const float* film_r, const TT* res)
+    // `r`: the conv's route, decided before anything is enqueued.  Launching walks only (side_pre_ok); allocation order of the pre-pass form,
+    // which the never-launching measuring / replay walks go through: activated tensor -- by the caller --, tables, conv output, partial sums
+    bool norm_conv_fwd_side(const TT& x, const TNorm& n, const TConvW& w, const ConvRoute& r, float2*& ab, float2*& stats, const TT& xa, TT& y,
+                            const float* film_r, const TT* res)
     {
         const int G = groups_for(x.C), cpg = x.C / G;
         ab = (float2*)take((size_t)B * x.C * sizeof(float2));
@@ -476,34 +410,27 @@ struct Walk {
             return true;
         };
         const int dt = tr->cfg.dtype;
-        // (the second condition is run_conv's own size limit for the persistent kernel: past it the conv takes the table route below)
-        if (launch && in_kernel_stats_ok(x, x.C) && (double)B * x.H * x.W * w.Cout * tr->elem < 2.0e9) {
+        const void* res_p = res ? res->p : nullptr;
+        if (r.gs_ok && conv_in_kernel_stats(dt, x.C, G, x.n_sp, x.bn)) {
             // statistics in the conv itself; the side stream's pass writes the activated tensor AND the tables the backward pass reads
             const GsIn gs{x.part, x.n_sp, x.n_nt, x.bn, cpg, par(n.pg), par(n.pb), 1.0 / count};
-            bool used = false;
             if (!fork()) return false;
             if (!ok(launch_gn_act_fused(dt, x.p, xa.p, B, x.H * x.W, x.C, x.part, G, x.n_sp, x.n_nt, x.bn, cpg, count, par(n.pg), par(n.pb), 1e-5f, tr->side, ab, stats),
                     "gn_act_fused")) return false;
-            if (!conv_fwd(w, x, y, nullptr, film_r, res, true, nullptr, nullptr, &gs, &used)) return false;
-            if (used) return true;
-            // (the conv did not land on the persistent kernel: it ran WITHOUT its GroupNorm -- cannot happen for the shapes side_pre_ok()
-            // admits, checked here rather than assumed)
-            err = "internal: in-kernel statistics requested for a conv outside the persistent kernel";
-            return false;
+            return run_conv(TF_CONV_FWD, r, w.pd_f, w.pf_f, par(w.pb), x.p, &y, y.p, nullptr, film_r, res_p, true, nullptr, &gs);
         }
-        if (launch) {
-            if (!ok(launch_gn_stats(x.part, B, G, x.n_sp, x.n_nt, x.bn, cpg, x.C, count, par(n.pg), par(n.pb), 1e-5f, ab, stats, st), "gn_stats")) return false;
-            if (!fork()) return false;
-            if (!ok(launch_gn_act(dt, x.p, ab, xa.p, B, x.H * x.W, x.C, tr->side), "gn_act")) return false;
-        }
-        return conv_fwd(w, x, y, ab, film_r, res, true);
+        if (!ok(launch_gn_stats(x.part, B, G, x.n_sp, x.n_nt, x.bn, cpg, x.C, count, par(n.pg), par(n.pb), 1e-5f, ab, stats, st), "gn_stats")) return false;
+        if (!fork()) return false;
+        if (!ok(launch_gn_act(dt, x.p, ab, xa.p, B, x.H * x.W, x.C, tr->side), "gn_act")) return false;
+        return run_conv(TF_CONV_FWD, r, w.pd_f, w.pf_f, par(w.pb), x.p, &y, y.p, ab, film_r, res_p, true, nullptr);
     }
     // dX = conv'(dY): N = the forward conv's Cin
     bool conv_dgrad(const TConvW& w, const void* dy, int Hdy, int Wdy, void* dx, const void* res)
     {
         g_sum_rows = 0;                                         // the gradient tensor that follows comes out of a conv: no channel sums
-        return run_conv(TF_CONV_DGRAD, w.dkind, w.kind == KIND_CT4, w.pd_d, w.pf_d, w.dBN, w.kind == KIND_HEAD ? tr->cfg.img_ch : w.Cout, w.dCin_pad, w.Cin, w.dCout_pad, tr->zero_bias, dy, Hdy, Wdy,
-                        nullptr, dx, nullptr, nullptr, res, false, nullptr);
+        const ConvRoute r = route(w.dkind, w.kind == KIND_CT4, w.pf_d, w.dBN, w.kind == KIND_HEAD ? tr->cfg.img_ch : w.Cout, w.dCin_pad, w.Cin, w.dCout_pad,
+                                  Hdy, Wdy, false, false, res != nullptr);
+        return run_conv(TF_CONV_DGRAD, r, w.pd_d, w.pf_d, tr->zero_bias, dy, nullptr, dx, nullptr, nullptr, res, false, nullptr);
     }
     bool preact(const TT& t, const float2* ab, const TT& out)
     {
@@ -598,19 +525,21 @@ struct Walk {
                     static const bool no_pre = diag_env("CCN_TRAIN_NO_PREACT") != nullptr;       // A/B switch
                     ResSave s; s.x = x;
                     s.pre = !no_pre && r.C / (tr->elem == 2 ? 8 : 4) <= 256;
-                    // (side form: same allocation sequence as the pre-pass form -- activated tensor, tables, conv output -- so the
-                    // measuring and replay walks, which never launch, need not know which one ran)
-                    const bool sidef = s.pre && side_pre_ok() && conv_pr_selected(tr->cfg.dtype, KIND_C3S1, r.c1.BN, 8) && r.c1.pf_f.dst && r.c1.Cin_pad / 64 >= 2;
-                    if (sidef) {
+                    // Side form where both convs run on the persistent kernel (their input GroupNorm in the prologue either way).  Same
+                    // allocation sequence as the pre-pass form -- activated tensor, tables, conv output -- so the measuring and replay walks,
+                    // which never launch, need not know which one ran.
+                    const float* film_r = film ? film + r.film_off : nullptr;
+                    const ConvRoute r1 = fwd_route(r.c1, x.H, x.W, true, film_r != nullptr, false), r2 = fwd_route(r.c2, x.H, x.W, true, false, true);
+                    if (s.pre && side_pre_ok() && r1.pr && r2.pr) {
                         s.xa = new_tensor(r.C, x.H, x.W);
-                        if (!norm_conv_fwd_side(x, r.n1, r.c1, s.ab1, s.st1, s.xa, s.y, film ? film + r.film_off : nullptr, nullptr)) return false;
+                        if (!norm_conv_fwd_side(x, r.n1, r.c1, r1, s.ab1, s.st1, s.xa, s.y, film_r, nullptr)) return false;
                         s.ya = new_tensor(r.C, x.H, x.W);
-                        if (!norm_conv_fwd_side(s.y, r.n2, r.c2, s.ab2, s.st2, s.ya, s.o, nullptr, &x)) return false;
+                        if (!norm_conv_fwd_side(s.y, r.n2, r.c2, r2, s.ab2, s.st2, s.ya, s.o, nullptr, &x)) return false;
                     } else {
                     if (s.pre) { s.xa = new_tensor(r.C, x.H, x.W); if (!gn_fwd_preact(x, r.n1, s.ab1, s.st1, s.xa)) return false; }
                     else if (!gn_fwd(x, r.n1, s.ab1, s.st1)) return false;
                     s.y = new_tensor(r.C, x.H, x.W);
-                    if (!conv_fwd(r.c1, s.pre ? s.xa : x, s.y, s.pre ? nullptr : s.ab1, film ? film + r.film_off : nullptr, nullptr, true)) return false;
+                    if (!conv_fwd(r.c1, s.pre ? s.xa : x, s.y, s.pre ? nullptr : s.ab1, film_r, nullptr, true)) return false;
                     if (s.pre) { s.ya = new_tensor(r.C, x.H, x.W); if (!gn_fwd_preact(s.y, r.n2, s.ab2, s.st2, s.ya)) return false; }
                     else if (!gn_fwd(s.y, r.n2, s.ab2, s.st2)) return false;
                     s.o = new_tensor(r.C, x.H, x.W);
@@ -656,8 +585,8 @@ struct Walk {
                         break;
                     }
                     TT none;
-                    if (!run_conv(TF_CONV_FWD, KIND_HEAD, false, tr->head.pd_f, tr->head.pf_f, tr->head.BN, tr->head.Cin, tr->head.Cin_pad, tr->head.Cout, tr->head.Cout_pad,
-                                  launch ? par(tr->head.pb) : nullptr, x.p, x.H, x.W, &none, nullptr, ab_o, nullptr, nullptr, false, eps)) return false;
+                    if (!run_conv(TF_CONV_FWD, fwd_route(tr->head, x.H, x.W, ab_o != nullptr, false, false), tr->head.pd_f, tr->head.pf_f,
+                                  launch ? par(tr->head.pb) : nullptr, x.p, &none, nullptr, ab_o, nullptr, nullptr, false, eps)) return false;
                     break;
                 }
             }
@@ -692,12 +621,12 @@ struct Walk {
     // channels that exist in the parameter
     bool wgrad_generic(int kind, const void* x, int Hin, int Win, int Cin, int Civ, const float2* gn_ab, int silu, const void* dy, int Cout, int Cov, float* gdst)
     {
-        const Geom g = geom_of(kind, Hin, Win, false);
+        const ConvGeom g = conv_geom(kind, false, Hin, Win, 4);
         WgArgs a{};
         a.x = x; a.gn_ab = gn_ab; a.silu = silu; a.dy = dy; a.part = scr_wg;
         a.B = B; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = g.Hout; a.Wout = g.Wout; a.Cout = Cout;
         a.MH = g.MH; a.MW = g.MW; a.OS = g.OS; a.npar = g.npar; a.ntaps = g.ntaps; a.taps_w = kind == KIND_CT4 ? 16 : (kind == KIND_STEM ? 1 : 9);
-        a.n_ty = ceil_div(g.MH, 4); a.n_tx = ceil_div(g.MW, 32);
+        a.n_ty = g.n_ty; a.n_tx = g.n_tx;
         const int ns_alone = wgrad_nsplit(tr->cfg.dtype, kind, B, g.MH, g.MW, Cin, Cout, false), ns_conc = wgrad_nsplit(tr->cfg.dtype, kind, B, g.MH, g.MW, Cin, Cout, true);
         a.nsplit = side_active() ? ns_conc : ns_alone;
         fill_taps(a.tapinfo, kind, false);
