@@ -127,6 +127,17 @@ struct GraphEntry {
     hipGraphExec_t exec = nullptr;
 };
 
+// one conv-family launch of a plan as decided at plan build (ccn_internal_plan_routes)
+struct RouteRec {
+    std::string name;          // the activation it writes: <block>.film (conv1), <block> (conv2), down.N, up.N, in_conv; out = head
+    int kind = 0;
+    const char* kernel = "";   // conv_kernel_name(conv_kernel_for(...)), or head2
+    int th = 0, ksplit = 1, n_nt = 1;
+    const char* gn = "none";   // input GroupNorm: none, prologue (finalize launch + conv prologue), instat (in-kernel statistics),
+                               // preact / preact_fused (GroupNorm + SiLU pass in front), weights (head2: folded into the weights)
+    bool film = false, res = false;
+};
+
 constexpr size_t kMaxGraphsPerPlan = 4;
 struct Plan {
     int B = 0, H = 0, W = 0, steps = 0;
@@ -142,6 +153,7 @@ struct Plan {
     std::vector<int32_t> ts_keep;        // the timestep table currently in ts_dev (uploaded synchronously, only when it changes)
     std::vector<Launch> ops;             // one UNet evaluation (+ DDIM update in the head)
     std::map<std::string, TensorRef> named;
+    std::vector<RouteRec> routes;        // every conv-family launch of `ops`, in order
     std::vector<GraphEntry> graphs;
     ~Plan() {
         for (auto& g : graphs) {
@@ -513,6 +525,9 @@ struct PlanBuilder {
         r.fill(a);
         a.in = in.p; a.w = cw.w; a.wfrag = r.uses_frag() ? cw.wfrag : nullptr; a.bias = cw.bias; a.out = out.p;
         a.film = nullptr; a.res = res ? res->p : nullptr;
+        RouteRec rec;
+        rec.kind = cw.kind; rec.th = r.th; rec.ksplit = r.ksplit; rec.n_nt = r.n_nt; rec.film = film_off >= 0; rec.res = res != nullptr;
+        rec.gn = gn_ab ? "prologue" : "none";
         static const bool no_instat = diag_env("CCN_NO_INSTAT") != nullptr;       // diagnostics build only
         if (in_norm) {
             const int G_in = groups_for(cw.Cin), cpg_in = cw.Cin / G_in;
@@ -520,9 +535,12 @@ struct PlanBuilder {
                 a.gs_part = in.part; a.gs_gamma = in_norm->gamma; a.gs_beta = in_norm->beta;
                 a.gs_inv_count = 1.0 / ((double)cpg_in * in.H * in.W);
                 a.gs_nsp = in.n_sp; a.gs_nnt = in.n_nt; a.gs_bn = in.bn; a.gs_cpg = cpg_in;
-            } else gn_ab = gn(in, *in_norm);                     // (pushes the finalize launch in front of this conv)
+                rec.gn = "instat";
+            } else { gn_ab = gn(in, *in_norm); rec.gn = "prologue"; }     // (pushes the finalize launch in front of this conv)
         }
         a.gn_ab = gn_ab;
+        rec.kernel = conv_kernel_name(conv_kernel_for(cw.kind, cw.BN, a));
+        plan->routes.push_back(rec);
         if (r.ksplit == 2) {
             a.kpart = bump.take((size_t)B * g.Hout * g.Wout * cw.Cout * h->elem);
             const size_t fbytes = (size_t)B * r.fin_blocks * 4 * sizeof(unsigned);
@@ -567,6 +585,12 @@ struct PlanBuilder {
             return launch_conv(dtype, kind, bn, k, s);
         };
         plan->ops.push_back(std::move(L));
+    }
+    // the route record of the conv just added: the activation it writes and, for an operand made by a pre-pass, how
+    void label(const std::string& name, const char* gn_form = nullptr)
+    {
+        plan->routes.back().name = name;
+        if (gn_form) plan->routes.back().gn = gn_form;
     }
 
     // GroupNorm finalize of tensor `t` for the norm (gamma, beta): returns the scale/shift table
@@ -643,6 +667,7 @@ struct PlanBuilder {
             const float2* ab1 = gn(x, r.n1);
             TensorRef xa = preact(x, ab1); conv(r.c1, F_C3S1, xa, y, nullptr, film_off == -2 ? r.film_off : film_off, nullptr, true);
         } else conv(r.c1, F_C3S1, x, y, nullptr, film_off == -2 ? r.film_off : film_off, nullptr, true, false, false, &r.n1);
+        label(r.prefix + ".film", f1 ? "preact_fused" : (pre ? "preact" : nullptr));
         plan->named[r.prefix + ".film"] = y;
         TensorRef o = new_tensor(r.C, x.H, x.W);
         if (f2) { TensorRef ya = preact_fused(y, r.n2); conv(r.c2, F_C3S1, ya, o, nullptr, -1, &x, out_feeds_gn); }
@@ -650,6 +675,7 @@ struct PlanBuilder {
             const float2* ab2 = gn(y, r.n2);
             TensorRef ya = preact(y, ab2); conv(r.c2, F_C3S1, ya, o, nullptr, -1, &x, out_feeds_gn);
         } else conv(r.c2, F_C3S1, y, o, nullptr, -1, &x, out_feeds_gn, false, false, &r.n2);
+        label(r.prefix, f2 ? "preact_fused" : (pre ? "preact" : nullptr));
         plan->named[r.prefix] = o;
         return o;
     }
@@ -672,7 +698,7 @@ int build_plan(ccn_handle_s* h, Plan* plan, void* ws, bool measure)
     plan->counters = (unsigned*)pb.bump.take((size_t)kMaxNorms * B * 4);
     plan->n_counters = 0;
 
-    plan->ops.clear(); plan->named.clear();
+    plan->ops.clear(); plan->named.clear(); plan->routes.clear();
     TensorRef img; img.C = c.img_ch; img.H = H; img.W = W;     // NCHW fp32, pointer supplied per call
     TensorRef x;
     std::vector<TensorRef> skips;
@@ -684,6 +710,7 @@ int build_plan(ccn_handle_s* h, Plan* plan, void* ws, bool measure)
             case L_STEM: {
                 x = pb.new_tensor(h->stem.Cout, H, W);
                 pb.conv(h->stem, F_STEM, img, x, nullptr, -1, nullptr, next_is_gn, true, false);
+                pb.label(L.name);
                 plan->named[L.name] = x;
                 break;
             }
@@ -697,6 +724,7 @@ int build_plan(ccn_handle_s* h, Plan* plan, void* ws, bool measure)
                 if ((x.H % 2) || (x.W % 2)) return fail(CCN_EINVAL, "H and W must be divisible by 2^len(ch_mult)");
                 TensorRef o = pb.new_tensor(cw.Cout, x.H / 2, x.W / 2);
                 pb.conv(cw, F_C3S2, x, o, nullptr, -1, nullptr, next_is_gn);
+                pb.label(L.name);
                 plan->named[L.name] = o;
                 x = o;
                 break;
@@ -707,6 +735,7 @@ int build_plan(ccn_handle_s* h, Plan* plan, void* ws, bool measure)
                 TensorRef sk = skips.back(); skips.pop_back();
                 if (sk.C != cw.Cout || sk.H != o.H || sk.W != o.W) return fail(CCN_EINVAL, "skip shape mismatch");
                 pb.conv(cw, F_CT4, x, o, nullptr, -1, &sk, next_is_gn);
+                pb.label(L.name);
                 plan->named[L.name] = o;
                 x = o;
                 break;
@@ -732,11 +761,15 @@ int build_plan(ccn_handle_s* h, Plan* plan, void* ws, bool measure)
                         return launch_head2(k, ab, wf, scratch, sc.step, s);
                     };
                     plan->ops.push_back(std::move(Lh));
+                    RouteRec rec;
+                    rec.name = L.name; rec.kind = KIND_HEAD; rec.kernel = "head2"; rec.th = 8; rec.gn = "weights";
+                    plan->routes.push_back(rec);
                     break;
                 }
                 const float2* ab = pb.gn(x, h->out_norm);
                 TensorRef none;
                 pb.conv(h->head, F_HEAD, x, none, ab, -1, nullptr, false, false, true);
+                pb.label(L.name);
                 break;
             }
         }
@@ -1305,6 +1338,28 @@ int ccn_read_activation(ccn_handle_t h, const char* name, float* out_dev, size_t
     HIPCHK(launch_nhwc_to_nchw(h->cfg.dtype, t.p, out_dev, p->B, t.C, t.H, t.W, s));
     HIPCHK(hipStreamSynchronize(s));
     return CCN_OK;
+}
+
+// Test hook, not part of include/ccn_hip.h: one line per conv-family launch of the plan that ccn_read_activation reads (the one the
+// last ccn_forward / ccn_sample used), "<activation> <kind> <kernel> th=.. ksplit=.. n_nt=.. gn=.. film=0|1 res=0|1", as decided when
+// that plan was built.  snprintf-like: writes at most cap bytes (NUL-terminated) and returns the length of the whole report, or -1.
+extern "C" int ccn_internal_plan_routes(ccn_handle_t h, char* buf, size_t cap)
+{
+    if (!h || h->plans.empty()) return -1;
+    static const char* kinds[] = {"C3S1", "C3S2", "CT4", "STEM", "HEAD"};
+    std::string text;
+    for (const RouteRec& r : h->plans.back()->routes) {
+        char line[256];
+        std::snprintf(line, sizeof(line), "%s %s %s th=%d ksplit=%d n_nt=%d gn=%s film=%d res=%d\n", r.name.c_str(), kinds[r.kind], r.kernel,
+                      r.th, r.ksplit, r.n_nt, r.gn, r.film ? 1 : 0, r.res ? 1 : 0);
+        text += line;
+    }
+    if (buf && cap) {
+        const size_t n = std::min(text.size(), cap - 1);
+        std::memcpy(buf, text.data(), n);
+        buf[n] = 0;
+    }
+    return (int)text.size();
 }
 
 int ccn_poll_errors(ccn_handle_t h)

@@ -155,6 +155,10 @@ int conv_bn_for(int cout, int kind);                       // N-tile width used 
 size_t conv_lds_bytes(int dtype, int kind, int bn);
 hipError_t conv_prepare();                                 // raise dynamic-LDS limits once
 hipError_t launch_conv(int dtype, int kind, int bn, const ConvArgs& a, hipStream_t s);
+// the kernel launch_conv runs for these arguments (the route report of the inference plan asks the same function)
+enum ConvKernel { CK_IGEMM = 0, CK_WS, CK_FR, CK_PR, CK_STEM2 };
+ConvKernel conv_kernel_for(int kind, int bn, const ConvArgs& a);
+const char* conv_kernel_name(ConvKernel k);
 // rows of 32 pixels per workgroup tile for this layer (decided once, at plan time)
 int conv_tile_rows(int kind, int bn, int B, int MH, int MW, int npar, int n_nt);
 // warp-specialised kernel (ccn_conv_ws.hip): 3x3 s1 and ConvTranspose parities, BN 64/128

@@ -550,18 +550,42 @@ bool conv_in_kernel_stats(int dtype, int C, int G, int n_sp, int bn)
     return (long)n_sp * nj <= 64;                                       // 8 slots per lane: one round of loads
 }
 
-hipError_t launch_conv(int dtype, int kind, int bn, const ConvArgs& a, hipStream_t s)
+ConvKernel conv_kernel_for(int kind, int bn, const ConvArgs& a)
 {
-    if (a.use_stem2) return launch_stem2(a, s);
-    if (a.use_pr && kind == KIND_C3S2) return launch_conv_pr(dtype, a, s);
+    if (a.use_stem2) return CK_STEM2;
+    if (a.use_pr && kind == KIND_C3S2) return CK_PR;
     if (conv_ws_enabled() && conv_ws_supported(kind, bn)) {
-        static const int dbg = diag_env("CCN_DBG") ? atoi(diag_env("CCN_DBG")) : 0;
-        ConvArgs d = a; d.dbg = dbg;
-        if (a.use_pr) return launch_conv_pr(dtype, d, s);        // decided at plan time (variant 4, bf16, 8-row tiles)
+        if (a.use_pr) return CK_PR;                              // decided at plan time (variant 4, bf16, 8-row tiles)
         // free-running kernel on 8-row tiles only: on 4-row tiles a consumer wave would issue 8 DMA pieces per 16 MFMAs and
         // the private weight copies double the L2 traffic of the already weight-heavy 128-pixel tile
         const int variant = conv_variant();
-        if (variant == 2 || (variant >= 3 && a.th == 8)) return launch_conv_fr(dtype, bn, d, s);
+        if (variant == 2 || (variant >= 3 && a.th == 8)) return CK_FR;
+        return CK_WS;
+    }
+    return CK_IGEMM;
+}
+
+const char* conv_kernel_name(ConvKernel k)
+{
+    switch (k) {
+        case CK_WS: return "ws";
+        case CK_FR: return "fr";
+        case CK_PR: return "pr";
+        case CK_STEM2: return "stem2";
+        default: return "igemm";
+    }
+}
+
+hipError_t launch_conv(int dtype, int kind, int bn, const ConvArgs& a, hipStream_t s)
+{
+    const ConvKernel k = conv_kernel_for(kind, bn, a);
+    if (k == CK_STEM2) return launch_stem2(a, s);
+    if (k == CK_PR && kind == KIND_C3S2) return launch_conv_pr(dtype, a, s);
+    if (k != CK_IGEMM) {
+        static const int dbg = diag_env("CCN_DBG") ? atoi(diag_env("CCN_DBG")) : 0;
+        ConvArgs d = a; d.dbg = dbg;
+        if (k == CK_PR) return launch_conv_pr(dtype, d, s);
+        if (k == CK_FR) return launch_conv_fr(dtype, bn, d, s);
         return launch_conv_ws(dtype, bn, d, s);
     }
     if (a.th != 4) return hipErrorInvalidValue;
