@@ -15,31 +15,22 @@
 // into registers before the pass barrier.
 //
 // Tile: TH x 32 output-space pixels (TH = 4*MF/2: 4 or 8 rows of 32) x BN = 64*NF output channels.
-#include "ccn_device.h"
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+//
+// The workgroup decode, the operands' buffer descriptors, the chunk-0 input prologue, the epilogue and the GroupNorm partial-sum
+// tail are the same in ccn_conv_fr.hip and are included from tile/*.inc (ccn_conv_tile.h says why as text).  Here: the LDS ring
+// layout, the three roles with their stamps, and their loops.
+#include "ccn_conv_tile.h"
 
 namespace ccn {
 
 namespace {
 
-template <int TH> struct WsGeom {
-    static constexpr int HROWS = TH + 2, HPITCH = 34;
-    static constexpr int A_BYTES = HROWS * HPITCH * 128;
-    static constexpr int AU = HROWS * HPITCH * 8;            // 16-byte units per chunk
-};
 template <int TH, int BN, int TPS> struct WsLds {
-    static constexpr int A_BYTES = WsGeom<TH>::A_BYTES;
+    static constexpr int A_BYTES = TileGeom<TH>::A_BYTES;
     static constexpr int BT_BYTES = BN * 128;                // one tap of one stage
     static constexpr int B_BYTES = TPS * BT_BYTES;           // one stage
     static constexpr int LOOP = 2 * A_BYTES + 2 * B_BYTES;
-    static constexpr int CP = BN + 4;
-    static constexpr int CS1_BYTES = 128 * CP * 4;           // fp32 epilogue tile of one 128-pixel pass
-    static constexpr int CS_BYTES = (TH / 4) * CS1_BYTES;    // all passes at once: one barrier for the whole epilogue
-    static constexpr int RED_BYTES = 8 * BN * 2 * 4 + BN * 2 * 4;
-    static constexpr int TOTAL = LOOP > CS_BYTES + RED_BYTES ? LOOP : CS_BYTES + RED_BYTES;
+    static constexpr int TOTAL = EpiLds<TH, BN, 8>::total(LOOP);
 };
 
 }  // namespace
@@ -58,8 +49,10 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(const ConvArgs a)
     constexpr int NB = MF == 4 ? 1 : 2, NA = 4 - NB;
     constexpr int A0 = 4 + NB;                  // first A-producer wave
     static_assert(NSPC * TPS == NTAPS && NSPC >= 2, "taps must split evenly into >= 2 stages per chunk");
-    using G = WsGeom<TH>;
+    constexpr int NWAVES = 8;
+    using G = TileGeom<TH>;
     using L = WsLds<TH, BN, TPS>;
+    using E = EpiLds<TH, BN, NWAVES>;
     constexpr int HPITCH = G::HPITCH;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const As = smem;                         // 2 chunk buffers
@@ -68,74 +61,15 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(const ConvArgs a)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
 
-    int bid = blockIdx.x;
-    const int nt = bid % a.n_nt; bid /= a.n_nt;
-    const int par = bid % a.npar; bid /= a.npar;
-    const int tx = bid % a.n_tx; bid /= a.n_tx;
-    const int ty = bid % a.n_ty;
-    const int b = bid / a.n_ty;
-    const int my0 = ty * TH, mx0 = tx * 32, n0 = nt * BN;
-    const int py = par >> 1, px_ = par & 1;
-    const int par_off = par * 4;
-
-    const unsigned char* const wbase = (const unsigned char*)a.w;
-    const unsigned char* const inb = (const unsigned char*)a.in;
-    const bool gn = a.gn_ab != nullptr;
-    const int iy0 = my0 - 1, ix0 = mx0 - 1;
-    // diagnostic stamps (CCN_STAMPS_PTR(a) is null outside profiling runs): slot 0 entry, 1 prologue done, 2 loop done, 3 exit, per role
-    auto stamp = [&](int slot) __attribute__((always_inline)) {
-        if (CCN_STAMPS_PTR(a) && lane == 0 && (wave == 0 || wave == 4 || wave == A0)) {
-            unsigned long long* st = CCN_STAMPS_PTR(a) + ((size_t)blockIdx.x * 3 + (wave == 0 ? 0 : (wave == 4 ? 1 : 2))) * 8;
-            st[slot] = __builtin_amdgcn_s_memrealtime();
-            if (slot == 1) st[5] = __builtin_amdgcn_s_memtime();       // shader-clock stamps around the loop -> in-kernel clock
-            if (slot == 2) st[6] = __builtin_amdgcn_s_memtime();
-        }
-    };
-    unsigned long long bar_wait = 0;      // diagnostic: shader cycles spent inside the loop's barriers
-    auto loop_barrier = [&]() __attribute__((always_inline)) {
-        if (CCN_STAMPS_PTR(a)) { const unsigned long long t0 = __builtin_amdgcn_s_memtime(); __syncthreads(); bar_wait += __builtin_amdgcn_s_memtime() - t0; }
-        else __syncthreads();
-    };
-    auto stamp_wait = [&]() __attribute__((always_inline)) {
-        if (CCN_STAMPS_PTR(a) && lane == 0 && (wave == 0 || wave == 4 || wave == A0))
-            CCN_STAMPS_PTR(a)[((size_t)blockIdx.x * 3 + (wave == 0 ? 0 : (wave == 4 ? 1 : 2))) * 8 + 4] = bar_wait;
-    };
-    stamp(0);
-    const size_t wtap_bytes = (size_t)a.Cout_pad * a.Cin_pad * sizeof(T);      // one tap of the packed weights
-    // Buffer descriptors: a wave-uniform base in SGPRs + a 32-bit per-lane byte offset, and hardware range checking --
-    // an offset past num_records returns zeros without touching memory, which implements the conv zero padding, the
-    // tile overhang and the Cin tail with no branch around any load (loads issue back to back).
-    constexpr unsigned OOB = 0x7FFFFFF0u;
-    const unsigned in_bytes = (unsigned)((size_t)a.B * a.Hin * a.Win * a.Cin * sizeof(T));
-    auto in_srd = [&](int chunk) __attribute__((always_inline)) {
-        const unsigned off = (unsigned)((size_t)chunk * CKE * sizeof(T));
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(inb + off), 0, in_bytes - off, 0x00020000);
-    };
-    auto w_srd = [&](int tap, int chunk) __attribute__((always_inline)) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(wbase + (size_t)a.tapinfo_w(par_off + tap) * wtap_bytes + (size_t)chunk * CKE * sizeof(T)),
-                                                 0, (unsigned)wtap_bytes, 0x00020000);
-    };
+#include "tile/decode.inc"              // -> b, ty, tx, par, nt; my0, mx0, n0; py, px_, par_off
+    constexpr int STAMP_B0 = 4;                 // stamp rows: consumers, B producers (first wave 4), A producers
+    constexpr bool LOOP_BARRIER_RAW = false;    // the stage barrier also publishes the producers' ds_writes: full __syncthreads()
+#include "tile/stamps.inc"              // -> stamp(slot), raw_barrier(), loop_barrier(), stamp_wait(); stamps slot 0
+#include "tile/operands.inc"            // -> gn, iy0, ix0, OOB, in_srd(chunk), w_srd(tap, chunk)
 
     // ------------------------------------------------------------------ prologue: chunk 0 and stage 0 by all 512 threads
     {
-        const int ck = tid & 7;
-        GnCoef<T> gk;
-        const bool cv = ck * EPC < a.Cin;
-        gk.load(a.gn_ab + (size_t)b * a.Cin + (cv ? ck * EPC : 0), gn && cv);
-        constexpr int PIT = (G::AU + 511) / 512;
-        u32x4 raw[PIT];
-        unsigned okm = 0;
-        const auto srd0 = in_srd(0);
-#pragma unroll
-        for (int i = 0; i < PIT; ++i) {
-            const int px = (tid >> 3) + 64 * i;
-            const int hy = px / HPITCH, hx = px - hy * HPITCH;
-            const int iy = iy0 + hy, ix = ix0 + hx;
-            const bool ok = px < G::HROWS * HPITCH && cv && iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win;
-            const unsigned off = ok ? (unsigned)((((size_t)(b * a.Hin + iy) * a.Win + ix) * a.Cin + ck * EPC) * sizeof(T)) : OOB;
-            raw[i] = __builtin_amdgcn_raw_buffer_load_b128(srd0, off, 0, 0);
-            if (ok) okm |= 1u << i;
-        }
+#include "tile/prologue_a_load.inc"     // Cin chunk 0 of the input halo requested -> raw[], okm, gk
         constexpr int BU0 = TPS * BN * 8 / 512;
         u32x4 b0[BU0];
 #pragma unroll
@@ -143,15 +77,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(const ConvArgs a)
             const int idx = tid + 512 * u, tt = idx / (BN * 8), rem = idx - tt * (BN * 8), n = rem >> 3, ckb = rem & 7;
             b0[u] = __builtin_amdgcn_raw_buffer_load_b128(w_srd(__builtin_amdgcn_readfirstlane(tt), 0), (unsigned)(((size_t)(n0 + n) * a.Cin_pad) * sizeof(T) + ckb * 16), 0, 0);
         }
-#pragma unroll
-        for (int i = 0; i < PIT; ++i) {
-            const int px = (tid >> 3) + 64 * i;
-            if (px < G::HROWS * HPITCH) {
-                u32x4 o = raw[i];
-                if (((okm >> i) & 1u) && gn) o = gk.template apply<true>(raw[i]);
-                *(u32x4*)(As + px * 128 + (((ck ^ (px >> 1)) & 7) << 4)) = o;
-            }
-        }
+#include "tile/prologue_a_write.inc"    // ... GroupNorm + SiLU, swizzled write into As
 #pragma unroll
         for (int u = 0; u < BU0; ++u) {
             const int idx = tid + 512 * u, tt = idx / (BN * 8), rem = idx - tt * (BN * 8), n = rem >> 3, ckb = rem & 7;
@@ -160,77 +86,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(const ConvArgs a)
     }
 
     // ------------------------------------------------------------------ epilogue pieces (used by every role after its loop)
-    float* const Cs = (float*)smem;
-    constexpr int CP = L::CP;
-    constexpr int NOCT = BN / 8, PSL = 512 / NOCT, NIT = 128 / PSL;
-    constexpr int NPASS = TH / 4;
-    const int o = tid % NOCT, ps = tid / NOCT;
-    const int nb = n0 + o * 8;
-    const bool nvalid = nb < a.Cout;
-    float f1[8], f2[8], s1[8], s2[8];           // v = acc * f1 + f2 with f2 = bias * f1 + shift; running sum / sum of squares
-    unsigned char* const outb = (unsigned char*)a.out;
-    const unsigned char* const resb = (const unsigned char*)a.res;
-    auto epi_init = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { f1[e] = 1.f; f2[e] = 0.f; s1[e] = 0.f; s2[e] = 0.f; }
-        if (nvalid) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) f2[e] = a.bias[nb + e];
-            if (a.film) {
-                const float* fp = a.film + (size_t)b * a.film_bstride;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { f1[e] = 1.0f + fp[nb + e]; f2[e] = fmaf(f2[e], f1[e], fp[a.Cout + nb + e]); }
-            }
-        }
-    };
-    // Whole tile at once: every residual / skip row is requested before the single barrier that publishes the fp32
-    // tiles (one 128-pixel tile per 4 tile rows), so the HBM latency of the residual overlaps the accumulator hand-off.
-    auto epi_all = [&]() __attribute__((always_inline)) {
-        u32x4 rres[NPASS * NIT][EPC == 8 ? 1 : 2];
-        size_t eoff[NPASS * NIT];
-        unsigned vmask = 0;
-#pragma unroll
-        for (int q = 0; q < NPASS * NIT; ++q) {
-            const int pass = q / NIT, itp = q - pass * NIT;
-            const int m = itp * PSL + ps;
-            const int my = my0 + pass * 4 + (m >> 5), mx = mx0 + (m & 31);
-            const bool v = nvalid && my < a.MH && mx < a.MW;
-            const int oy = my * a.OS + py, ox = mx * a.OS + px_;
-            eoff[q] = (((size_t)(b * a.Hout + oy) * a.Wout + ox) * a.Cout + nb) * sizeof(T);
-            if (v) vmask |= 1u << q;
-#pragma unroll
-            for (int w = 0; w < (EPC == 8 ? 1 : 2); ++w) {
-                rres[q][w] = u32x4{0u, 0u, 0u, 0u};
-                if (v && resb) rres[q][w] = *(const u32x4*)(resb + eoff[q] + 16 * w);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < NPASS * NIT; ++q) {
-            if ((vmask >> q) & 1u) {
-                const int pass = q / NIT, itp = q - pass * NIT;
-                const int m = itp * PSL + ps;
-                const float* cs = Cs + pass * (L::CS1_BYTES / 4) + m * CP + o * 8;
-                float v[8];
-                const f32x4 c0 = *(const f32x4*)cs, c1 = *(const f32x4*)(cs + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v[e] = c0[e]; v[4 + e] = c1[e]; }
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = fmaf(v[e], f1[e], f2[e]);
-                if (resb) {
-                    float rv[8];
-                    Vec16<T>::unpack(rres[q][0], rv);
-                    if constexpr (EPC == 4) Vec16<T>::unpack(rres[q][1], rv + 4);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += rv[e];
-                }
-                *(u32x4*)(outb + eoff[q]) = Vec16<T>::pack(v);
-                if constexpr (EPC == 4) *(u32x4*)(outb + eoff[q] + 16) = Vec16<T>::pack(v + 4);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { s1[e] += v[e]; s2[e] = fmaf(v[e], v[e], s2[e]); }
-            }
-        }
-    };
+#include "tile/epilogue.inc"            // -> Cs, epi_init(), epi_all(); f1, f2, s1, s2
     const bool do_epi = !CCN_DBG_BIT(a, 8);
 
     if (wave >= A0) {
@@ -426,66 +282,20 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(const ConvArgs a)
         stamp(2); stamp_wait();
         if (do_epi) {
             epi_init();
-#pragma unroll
-            for (int i = 0; i < MF; ++i) {
-                const int row = wm * MF + i;                        // tile row of this fragment -> pass row/4, rows (row&3)*32..
-                float* const cst = Cs + (row / 4) * (L::CS1_BYTES / 4);
-#pragma unroll
-                for (int j = 0; j < NF; ++j)
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) {
-                        const int m = (row & 3) * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-                        cst[m * CP + (wn * NF + j) * 32 + r] = acc[i][j][q];
-                    }
-            }
+#include "tile/acc_to_lds.inc"          // acc[][] -> fp32 tile Cs
             epi_all();
         }
         stamp(3);
     }
     if (!do_epi) return;
     if (a.part) {
-        // fixed-order reduction: lanes sharing an octet, then the 8 waves, then the channels of each group
-#pragma unroll
-        for (int s = NOCT; s < 64; s <<= 1)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { s1[e] += __shfl_xor(s1[e], s); s2[e] += __shfl_xor(s2[e], s); }
-        float* const red = (float*)(smem + L::CS_BYTES);        // [8][BN][2]
-        float* const chs = red + 8 * BN * 2;                    // [BN][2]
-        if (lane < NOCT) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                red[(wave * BN + lane * 8 + e) * 2 + 0] = s1[e];
-                red[(wave * BN + lane * 8 + e) * 2 + 1] = s2[e];
-            }
-        }
-        __syncthreads();
-        if (tid < BN) {
-            float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) { t1 += red[(w * BN + tid) * 2]; t2 += red[(w * BN + tid) * 2 + 1]; }
-            chs[tid * 2] = t1; chs[tid * 2 + 1] = t2;
-        }
-        __syncthreads();
-        if (n0 < a.Cout) {
-            const int nend = min(n0 + BN, a.Cout);
-            const int g = n0 / a.cpg + tid;
-            if (g <= (nend - 1) / a.cpg) {
-                const int clo = max(g * a.cpg, n0), chi = min((g + 1) * a.cpg, nend);
-                float t1 = 0.f, t2 = 0.f;
-                for (int c = clo; c < chi; ++c) { t1 += chs[(c - n0) * 2]; t2 += chs[(c - n0) * 2 + 1]; }
-                const int slot = (((ty * a.n_tx + tx) * a.npar + par) * a.n_nt) + nt;
-                part_store(a.part + (size_t)(b * a.G + g) * a.nslot + slot, t1, t2);
-            }
-        }
-        if (a.fin_counter) gn_fused_finalize<512>(a, b, (unsigned*)red, tid);
+#include "tile/gn_part_tail.inc"        // s1, s2 -> GroupNorm partials (-> in-kernel finalize)
     }
 }
 
 // ---- dispatch -------------------------------------------------------------------------------------------------
 // 3x3 s1: 4-row tiles stage 3 taps per barrier, 8-row tiles 1 tap (LDS); ConvTranspose parities (4 taps): 2 / 1.
-typedef void (*ws_fn_t)(const ConvArgs);
-
-template <typename T> static ws_fn_t pick_ws_t(int ntaps, int th, int bn)
+template <typename T> static tile_fn_t pick_ws_t(int ntaps, int th, int bn)
 {
     if (ntaps == 9) {
         if (th == 8) return bn == 128 ? conv_ws_kernel<T, 4, 2, 9, 1> : conv_ws_kernel<T, 4, 1, 9, 1>;
@@ -494,7 +304,7 @@ template <typename T> static ws_fn_t pick_ws_t(int ntaps, int th, int bn)
     if (th == 8) return bn == 128 ? conv_ws_kernel<T, 4, 2, 4, 1> : conv_ws_kernel<T, 4, 1, 4, 1>;
     return bn == 128 ? conv_ws_kernel<T, 2, 2, 4, 2> : conv_ws_kernel<T, 2, 1, 4, 2>;
 }
-static ws_fn_t pick_ws(int dtype, int ntaps, int th, int bn)
+static tile_fn_t pick_ws(int dtype, int ntaps, int th, int bn)
 {
     return dtype == 0 ? pick_ws_t<float>(ntaps, th, bn) : pick_ws_t<__bf16>(ntaps, th, bn);
 }
@@ -507,55 +317,15 @@ static size_t ws_lds(int ntaps, int th, int bn)
 
 bool conv_ws_supported(int kind, int bn) { return (kind == KIND_C3S1 || kind == KIND_CT4) && (bn == 128 || bn == 64); }
 
-hipError_t conv_ws_prepare()
-{
-    for (int dt = 0; dt < 2; ++dt)
-        for (int ntaps = 4; ntaps <= 9; ntaps += 5)
-            for (int th = 4; th <= 8; th += 4)
-                for (int bn = 64; bn <= 128; bn += 64) {
-                    hipError_t e = hipFuncSetAttribute((const void*)pick_ws(dt, ntaps, th, bn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)ws_lds(ntaps, th, bn));
-                    if (e != hipSuccess) return e;
-                }
-    return hipSuccess;
-}
+hipError_t conv_ws_prepare() { return tiled_prepare(pick_ws, ws_lds); }
 
-// Diagnostic: CCN_STAMPS=<grid>[:<ntaps>] records s_memrealtime stamps of every launch with that grid (last one wins);
-// ccn_internal_dump_stamps writes them out.  Never set in timed runs.
-static unsigned long long* g_stamps = nullptr;
-static unsigned g_stamp_grid = 0;
-extern "C" int ccn_internal_dump_stamps(const char* path)
-{
-    if (!g_stamps || !g_stamp_grid) return 1;
-    std::vector<unsigned long long> h((size_t)g_stamp_grid * 24);
-    if (hipMemcpy(h.data(), g_stamps, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return 2;
-    FILE* f = fopen(path, "w");
-    if (!f) return 3;
-    for (unsigned b = 0; b < g_stamp_grid; ++b) {
-        for (int k = 0; k < 24; ++k) fprintf(f, "%llu%c", h[(size_t)b * 24 + k], k == 23 ? '\n' : ' ');
-    }
-    fclose(f);
-    return 0;
-}
+static StampBuf g_stamps;
+extern "C" int ccn_internal_dump_stamps(const char* path) { return g_stamps.dump(path); }
 
 hipError_t launch_conv_ws(int dtype, int bn, const ConvArgs& a, hipStream_t s)
 {
     const unsigned grid = (unsigned)(a.B * a.n_ty * a.n_tx * a.npar * a.n_nt);
-    static const char* env = diag_env("CCN_STAMPS");
-    if (env) {
-        unsigned want = (unsigned)atoi(env), want_taps = strchr(env, ':') ? (unsigned)atoi(strchr(env, ':') + 1) : 9u;
-        if (grid == want && (unsigned)a.ntaps == want_taps) {
-            if (!g_stamps) { if (hipMalloc((void**)&g_stamps, (size_t)8192 * 24 * 8) != hipSuccess) return hipErrorOutOfMemory; }
-            if (grid <= 8192) {
-                g_stamp_grid = grid;
-                ConvArgs d = a; d.stamps = g_stamps;
-                hipLaunchKernelGGL(pick_ws(dtype, a.ntaps, a.th, bn), dim3(grid), dim3(512), ws_lds(a.ntaps, a.th, bn), s, d);
-                return hipGetLastError();
-            }
-        }
-    }
-    hipLaunchKernelGGL(pick_ws(dtype, a.ntaps, a.th, bn), dim3(grid), dim3(512), ws_lds(a.ntaps, a.th, bn), s, a);
-    return hipGetLastError();
+    return launch_tiled(pick_ws(dtype, a.ntaps, a.th, bn), grid, ws_lds(a.ntaps, a.th, bn), a, s, g_stamps);
 }
 
 }  // namespace ccn

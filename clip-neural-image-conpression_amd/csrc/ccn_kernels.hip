@@ -17,8 +17,7 @@
 // half h reads chunk 2*kk+h of its A row (a pixel) and of its B row (an output channel), so the K order seen by
 // the two operands is identical by construction.  LDS rows are XOR-swizzled by ((row>>1)&7) at 16-B granularity:
 // 32 consecutive rows read at one chunk index hit 16 distinct 16-B slots per ds_read_b128 lane group.
-#include "ccn_device.h"
-#include <cstdlib>
+#include "ccn_conv_tile.h"
 
 namespace ccn {
 
@@ -35,10 +34,7 @@ template <int AK, int IS> struct HaloGeom {
 template <int AK, int IS, int BN> struct LdsGeom {
     static constexpr int A_BYTES = HaloGeom<AK, IS>::BYTES;
     static constexpr int B_BYTES = BN * 128;
-    static constexpr int CP = BN + 4;                       // fp32 epilogue tile pitch (floats)
-    static constexpr int CS_BYTES = 128 * CP * 4;
-    static constexpr int RED_BYTES = 4 * BN * 2 * 4 + BN * 2 * 4;
-    static constexpr int TOTAL = cmax(A_BYTES + 2 * B_BYTES, CS_BYTES + RED_BYTES);
+    static constexpr int TOTAL = EpiLds<4, BN, 4>::total(A_BYTES + 2 * B_BYTES);
 };
 
 template <typename T, int AK, int IS, int EPI, int WM, int WN, int MF, int NF>
@@ -50,6 +46,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a)
     constexpr int CKE = 8 * EPC;
     using HG = HaloGeom<AK, IS>;
     using LG = LdsGeom<AK, IS, BN>;
+    constexpr int TH = 4, NWAVES = 4;
+    using E = EpiLds<TH, BN, NWAVES>;               // the epilogue's fp32 tile and reduction scratch, over the loop's buffers
     constexpr int HPITCH = HG::PITCH;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const As = smem;
@@ -59,15 +57,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a)
     const int r = lane & 31, h = lane >> 5;
     const int wm = wave / WN, wn = wave % WN;
 
-    int bid = blockIdx.x;
-    const int nt = bid % a.n_nt; bid /= a.n_nt;
-    const int par = bid % a.npar; bid /= a.npar;
-    const int tx = bid % a.n_tx; bid /= a.n_tx;
-    const int ty = bid % a.n_ty;
-    const int b = bid / a.n_ty;
-    const int my0 = ty * 4, mx0 = tx * 32, n0 = nt * BN;
-    const int py = par >> 1, px_ = par & 1;
-    const int par_off = par * 4;
+#include "tile/decode.inc"              // -> b, ty, tx, par, nt; my0, mx0, n0; py, px_, par_off
 
     const unsigned char* const wbase = (const unsigned char*)a.w;
     const unsigned char* const inb = (const unsigned char*)a.in;
@@ -215,7 +205,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a)
     // ---- epilogue: accumulators -> LDS fp32 tile -> coalesced 16-B rows ----------------------------
     __syncthreads();
     float* const Cs = (float*)smem;
-    constexpr int CP = LG::CP;
+    constexpr int CP = E::CP;
 #pragma unroll
     for (int i = 0; i < MF; ++i)
 #pragma unroll
@@ -304,40 +294,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a)
             }
         }
         if (a.part) {
-            // fixed-order reduction: lanes sharing an octet (xor strides >= NOCT), then waves, then channels of a group
-#pragma unroll
-            for (int s = NOCT; s < 64; s <<= 1)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { s1[e] += __shfl_xor(s1[e], s); s2[e] += __shfl_xor(s2[e], s); }
-            float* const red = (float*)(smem + LG::CS_BYTES);       // [4][BN][2]
-            float* const chs = red + 4 * BN * 2;                    // [BN][2]
-            if (lane < NOCT) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    red[(wave * BN + lane * 8 + e) * 2 + 0] = s1[e];
-                    red[(wave * BN + lane * 8 + e) * 2 + 1] = s2[e];
-                }
-            }
-            __syncthreads();
-            if (tid < BN) {
-                float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) { t1 += red[(w * BN + tid) * 2]; t2 += red[(w * BN + tid) * 2 + 1]; }
-                chs[tid * 2] = t1; chs[tid * 2 + 1] = t2;
-            }
-            __syncthreads();
-            if (n0 < a.Cout) {
-                const int nend = min(n0 + BN, a.Cout);
-                const int g = n0 / a.cpg + tid;
-                if (g <= (nend - 1) / a.cpg) {
-                    const int clo = max(g * a.cpg, n0), chi = min((g + 1) * a.cpg, nend);
-                    float t1 = 0.f, t2 = 0.f;
-                    for (int c = clo; c < chi; ++c) { t1 += chs[(c - n0) * 2]; t2 += chs[(c - n0) * 2 + 1]; }
-                    const int slot = (((ty * a.n_tx + tx) * a.npar + par) * a.n_nt) + nt;
-                    part_store(a.part + (size_t)(b * a.G + g) * a.nslot + slot, t1, t2);
-                }
-            }
-            if (a.fin_counter) gn_fused_finalize<256>(a, b, (unsigned*)red, tid);
+#include "tile/gn_part_tail.inc"        // s1, s2 -> GroupNorm partials (-> in-kernel finalize)
         }
     }
 }
