@@ -10,6 +10,8 @@ batch resident in HBM: draw t and noise, q_sample, UNet forward, MSE loss, backw
 gradient buffer over RCCL), AdamW.  Data-parallel: every rank holds its own batch of 4 (weak scaling; global batch 4 N).
 Rank 0 prints ONE JSON line with `roofline` for the dominant kernel family (HIP events inside the library, on the stream the
 kernels run on) and, at N = 1, `cpu_baseline` (the oracle's step -- torch-CPU autograd + AdamW -- on the host cores).
+`--recon-w W --tv-w W` (default 0: the line above, unchanged) add the reference's L1 and TV terms on the clamped x0 prediction
+(train/diffusion_train.py:125-128; its defaults are 0.05 and 1e-4) through the fused loss kernel; the config block then names them.
 """
 from __future__ import annotations
 
@@ -46,6 +48,8 @@ def main() -> None:
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--base", type=int, default=128)
     ap.add_argument("--ch-mult", type=str, default="1,2,2")
+    ap.add_argument("--recon-w", type=float, default=0.0, help="weight of l1(x0_pred, x0) (the reference's train_diffusion default: 0.05)")
+    ap.add_argument("--tv-w", type=float, default=0.0, help="weight of total_variation(x0_pred) (the reference's default: 1e-4)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     args = ap.parse_args()
@@ -91,7 +95,8 @@ def main() -> None:
     z = torch.from_numpy(synth.synth_z(world * B)[rank * B:rank * B + B]).to(dev)
 
     def step():
-        return train_step(net, sch, opt, x0, z, ddp=world > 1, graph=os.environ.get("CCN_TRAIN_GRAPH", "0") == "1")
+        return train_step(net, sch, opt, x0, z, ddp=world > 1, graph=os.environ.get("CCN_TRAIN_GRAPH", "0") == "1",
+                          recon_w=args.recon_w, tv_w=args.tv_w)
 
     def fence():
         torch.cuda.synchronize()
@@ -188,6 +193,11 @@ def main() -> None:
             "rccl_ranks": ranks_seen, "backend": (dist.get_backend() if world > 1 else None),
             "final_loss": round(float(loss), 5), "roofline": roofline, "cpu_baseline": cpu,
         }
+        if args.recon_w > 0 or args.tv_w > 0:
+            # the reference's default objective in the fused loss kernel (ccn_diffusion_loss_grad); the CPU baseline stays the eps-MSE step
+            line["config"]["objective"] = {"recon_w": args.recon_w, "tv_w": args.tv_w,
+                                           "loss": "mse + recon_w * l1(x0_pred, x0) + tv_w * tv(x0_pred), x0_pred clamped to [-1, 1]"}
+            line["final_loss_terms"] = {k: round(float(v), 6) for k, v in zip(("total", "mse", "l1", "tv"), net.train_state().last_loss_terms)}
         print(json.dumps(line))
     if world > 1:
         dist.barrier()

@@ -67,6 +67,7 @@ SIGNATURES = {
     "ccn_train_profile_read": (c_i32, [c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_f32), ctypes.POINTER(c_i32),
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_i32, ctypes.POINTER(c_i32)]),
     "ccn_mse_loss_grad": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "ccn_diffusion_loss_grad": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "ccn_adamw_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp]),
     "ccn_adamw_step_zero_grad": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp]),
     "ccn_last_error": (ctypes.c_char_p, []),
@@ -424,6 +425,35 @@ def mse_loss_grad(eps: torch.Tensor, target: torch.Tensor, want_grad: bool = Tru
         check(lib.ccn_mse_loss_grad(eps.data_ptr(), target.data_ptr(), eps.numel(), loss.data_ptr(), ptr(d), scratch.data_ptr(),
                                     current_stream(eps.device)))
     return loss, d
+
+
+OBJECTIVE_SCRATCH_FLOATS = 8192
+
+
+def diffusion_loss_grad(eps: torch.Tensor, noise: torch.Tensor, x_t: torch.Tensor, x0: torch.Tensor, a: torch.Tensor, s: torch.Tensor,
+                        recon_w: float, tv_w: float, want_grad: bool = True, bufs=None):
+    """mse(eps, noise) + recon_w * l1(x0_pred, x0) + tv_w * TV(x0_pred), x0_pred = clamp((x_t - s eps) / a, -1, 1), and its gradient
+    with respect to ``eps`` in one pass (train/diffusion_train.py:124-129).  ``a`` / ``s``: (B,) gathered schedule coefficients.
+    Returns ``(terms, d_eps)``: ``terms`` is a (4,) tensor -- total, mse, l1, tv (l1 and tv unweighted).
+    ``bufs``: optional preallocated ``(terms, d_eps, scratch)``, scratch of ``OBJECTIVE_SCRATCH_FLOATS`` floats."""
+    lib = load_library()
+    eps = require_dev(eps, "eps"); noise = require_dev(noise, "noise"); x_t = require_dev(x_t, "x_t"); x0 = require_dev(x0, "x0")
+    a = require_dev(a, "a"); s = require_dev(s, "s")
+    if eps.dim() != 4 or not (eps.shape == noise.shape == x_t.shape == x0.shape):
+        raise ValueError("eps, noise, x_t and x0 must be (B, C, H, W) tensors of one shape")
+    B, C, H, W = eps.shape
+    if a.numel() != B or s.numel() != B:
+        raise ValueError("a and s must hold one coefficient per sample")
+    terms, d, scratch = (bufs if bufs is not None else (None, None, None))
+    if terms is None:
+        terms = torch.empty(4, dtype=torch.float32, device=eps.device)
+        d = torch.empty_like(eps) if want_grad else None
+        scratch = torch.empty(OBJECTIVE_SCRATCH_FLOATS, dtype=torch.float32, device=eps.device)
+    with torch.cuda.device(eps.device):
+        check(lib.ccn_diffusion_loss_grad(eps.data_ptr(), noise.data_ptr(), x_t.data_ptr(), x0.data_ptr(), a.data_ptr(), s.data_ptr(),
+                                          B, C, H, W, float(recon_w), float(tv_w), terms.data_ptr(), ptr(d), scratch.data_ptr(),
+                                          current_stream(eps.device)))
+    return terms, d
 
 
 def adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float, beta1: float, beta2: float,

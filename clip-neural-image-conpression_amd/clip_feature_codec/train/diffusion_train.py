@@ -1,4 +1,4 @@
-"""The epsilon-MSE training step of ``CLIPCondUNet`` on libccn_hip.so.
+"""The training step of ``CLIPCondUNet`` on libccn_hip.so: epsilon-MSE, optionally with the reference's L1 and TV terms.
 
 Reference: ``train/diffusion_train.py:119-124,137-140`` -- per batch::
 
@@ -10,8 +10,14 @@ Here ``net(x_t, z, t)`` of a ``CLIPCondUNet`` in training mode returns an ``eps_
 (``UNetFunction``) whose backward is the library's hand-written backward pass, so the three reference lines run
 unchanged with any torch optimiser.  The parameters are re-homed as views into ONE flat fp32 buffer (what the C ABI
 reads); ``FusedAdamW`` is the matching one-launch optimiser, and ``train_step`` is the loop body above with the
-fused loss kernel.  The optional extras of the reference loop (L1 / TV / CLIP-alignment terms, :125-136) need models
-that are not part of this path and are not provided.
+fused loss kernel.
+
+The reference's default objective adds two terms on ``x0_pred = predict_x0_from_eps(x_t, t, eps_hat).clamp(-1, 1)`` (:125-128):
+``recon_w * l1(x0_pred, x0) + tv_w * total_variation(x0_pred)``.  ``train_step(..., recon_w=, tv_w=)`` evaluates them and their
+gradient in the same single pass as the MSE (``ccn_diffusion_loss_grad``), and ``train_diffusion`` runs its batches through it.
+Still not provided: the CLIP-alignment term (``clip_w``, :129-136), which needs ``open_clip`` with downloaded weights
+(SURVEY.md section 8, row a18), and ``GradScaler`` (:137-139), which under bf16 changes nothing but the skipped step on
+non-finite gradients.
 
 With ``torch.distributed`` initialised, ``train_step(..., ddp=True)`` averages the flat gradient buffer over the ranks
 with one all-reduce (RCCL over xGMI on a GPU node): the data-parallel step of BASELINE.json configs[4].
@@ -141,6 +147,9 @@ class TrainState:
         self.dtype = dtype
         self.ddp_bucketed = False          # UNetFunction.backward all-reduces finished gradient ranges while it still runs
         self.sync_grads = True             # False inside no_sync(): gradient accumulation over micro-batches without communication
+        # (4,) total, mse, l1, tv (l1, tv unweighted) of the last train_step with recon_w / tv_w: a view of a static buffer, read it
+        # before the next step; None after an MSE-only step
+        self.last_loss_terms: Optional[torch.Tensor] = None
         self._works: list = []
 
     def no_sync(self):
@@ -187,6 +196,16 @@ class TrainState:
             self._static = bufs
         return bufs
 
+    def objective_buffers(self, sb: dict) -> dict:
+        """What the L1 / TV objective adds to ``static_buffers``: the gathered schedule coefficients, the four loss terms and the
+        reduction scratch, at fixed addresses like the rest."""
+        if "terms" not in sb:
+            dev, b = sb["x0"].device, sb["x0"].shape[0]
+            sb.update(a=torch.empty(b, dtype=torch.float32, device=dev), s=torch.empty(b, dtype=torch.float32, device=dev),
+                      terms=torch.zeros(4, dtype=torch.float32, device=dev),
+                      scratch_obj=torch.empty(_native.OBJECTIVE_SCRATCH_FLOATS, dtype=torch.float32, device=dev))
+        return sb
+
 
 class FusedAdamW:
     """``torch.optim.AdamW`` semantics over the flat buffers, one kernel launch per step (train/diffusion_train.py:105,138)."""
@@ -225,8 +244,14 @@ def average_gradients(flat_grad: torch.Tensor) -> torch.Tensor:
 
 
 def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[torch.Tensor] = None,
-               noise: Optional[torch.Tensor] = None, ddp=False, graph: bool = False) -> torch.Tensor:
+               noise: Optional[torch.Tensor] = None, ddp=False, graph: bool = False, recon_w: float = 0.0,
+               tv_w: float = 0.0) -> torch.Tensor:
     """One optimisation step; returns the (detached) loss.  ``t`` / ``noise`` default to the reference's draws.
+
+    ``recon_w`` / ``tv_w`` (the reference's ``train_diffusion`` defaults are 0.05 and 1e-4): the loss becomes
+    ``mse + recon_w * l1(x0_pred, x0) + tv_w * total_variation(x0_pred)`` with ``x0_pred = predict_x0_from_eps(...).clamp(-1, 1)``
+    (train/diffusion_train.py:124-128), evaluated with its gradient by one kernel on the static buffers; the four terms are then
+    in ``net.train_state().last_loss_terms``.  With both 0 (the default) the step is the epsilon-MSE step, launch for launch.
 
     All tensors the library touches live at fixed addresses (``TrainState.static_buffers``), so with ``graph=True`` the forward and
     the backward are replayed as captured hipGraphs after the first step of a shape -- measured SLOWER than plain stream launches
@@ -246,9 +271,24 @@ def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[tor
     else:
         sb["noise"].copy_(noise)
     state.trainer.set_graph(graph)
-    sch.q_sample(sb["x0"], sb["t"], sb["noise"], out=sb["x_t"])
-    state.trainer.forward(fp.flat, sb["x_t"], sb["z"], sb["t"], out=sb["eps"])
-    loss, d_eps = _native.mse_loss_grad(sb["eps"], sb["noise"], bufs=(sb["loss"], sb["d_eps"], sb["scratch"]))
+    if recon_w < 0 or tv_w < 0:
+        raise ValueError("recon_w and tv_w must be non-negative")
+    if recon_w > 0 or tv_w > 0:
+        state.objective_buffers(sb)
+        dev = sb["x0"].device
+        torch.index_select(sch.sqrt_alphas_cumprod.to(dev), 0, sb["t"], out=sb["a"])
+        torch.index_select(sch.sqrt_one_minus_alphas_cumprod.to(dev), 0, sb["t"], out=sb["s"])
+        _native.q_sample(sb["x0"], sb["noise"], sb["a"], sb["s"], sb["x_t"])
+        state.trainer.forward(fp.flat, sb["x_t"], sb["z"], sb["t"], out=sb["eps"])
+        terms, d_eps = _native.diffusion_loss_grad(sb["eps"], sb["noise"], sb["x_t"], sb["x0"], sb["a"], sb["s"], recon_w, tv_w,
+                                                   bufs=(sb["terms"], sb["d_eps"], sb["scratch_obj"]))
+        loss = terms[0]
+        state.last_loss_terms = terms
+    else:
+        sch.q_sample(sb["x0"], sb["t"], sb["noise"], out=sb["x_t"])
+        state.trainer.forward(fp.flat, sb["x_t"], sb["z"], sb["t"], out=sb["eps"])
+        loss, d_eps = _native.mse_loss_grad(sb["eps"], sb["noise"], bufs=(sb["loss"], sb["d_eps"], sb["scratch"]))
+        state.last_loss_terms = None
     import torch.distributed as dist
     have_pg = bool(ddp) and dist.is_available() and dist.is_initialized()
     world = dist.get_world_size() if have_pg else 1
@@ -307,22 +347,50 @@ def total_variation(x: torch.Tensor) -> torch.Tensor:
     return (x[:, :, 1:, :] - x[:, :, :-1, :]).abs().mean() + (x[:, :, :, 1:] - x[:, :, :, :-1]).abs().mean()
 
 
+def autograd_objective_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: torch.Tensor, noise: torch.Tensor,
+                            recon_w: float = 0.0, tv_w: float = 0.0) -> torch.Tensor:
+    """The loop body of train/diffusion_train.py:119-128,137-140 through autograd: the objective from torch ops on (B, 3, S, S), the
+    library's forward and backward behind ``UNetFunction``, ``opt.step()`` and ``opt.zero_grad()`` as two passes.  What
+    ``train_step(recon_w=, tv_w=)`` fuses; kept as ``train_diffusion(fused_objective=False)`` and for A/B (tools/objective_ab.py)."""
+    import torch.nn.functional as F
+    state: TrainState = net.train_state()
+    state.fp.rebind_grads()
+    x_t = sch.q_sample(x0, t, noise)
+    eps_hat = net(x_t, z, t)
+    loss = F.mse_loss(eps_hat, noise)
+    if recon_w > 0 or tv_w > 0:
+        # predict_x0_from_eps (diffusion/scheduler.py:51-55) written with torch ops: its gradient must reach eps_hat
+        sg = sch.sqrt_one_minus_alphas_cumprod[t].view(-1, 1, 1, 1); ac = sch.sqrt_alphas_cumprod[t].view(-1, 1, 1, 1)
+        x0_pred = ((x_t - sg * eps_hat) / ac).clamp(-1, 1)
+        if recon_w > 0:
+            loss = loss + recon_w * F.l1_loss(x0_pred, x0)
+        if tv_w > 0:
+            loss = loss + tv_w * total_variation(x0_pred)
+    loss.backward()
+    state.wait_grad_sync()
+    opt.step()
+    opt.zero_grad()
+    return loss.detach()
+
+
 def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size: int = 8, lr: float = 2e-4, timesteps: int = 1000,
                     schedule: str = "cosine", recon_w: float = 0.05, clip_w: float = 0.1, tv_w: float = 1e-4, device: str = "cuda",
-                    save_dir=None, base: int = 128, ch_mult=(1, 2, 2), dtype: str = "bf16", num_workers: int = 2, log=print):
+                    save_dir=None, base: int = 128, ch_mult=(1, 2, 2), dtype: str = "bf16", num_workers: int = 2, log=print,
+                    fused_objective: bool = True):
     """The reference's ``train_diffusion`` (same arguments, defaults, checkpoint names and log line) on the MI355X kernels.
 
-    Per batch (train/diffusion_train.py:115-140): t ~ U{0..T-1}, noise ~ N, x_t = q_sample, eps_hat = net(x_t, z, t) through the
-    library's forward, loss = mse(eps_hat, noise) [+ recon_w * L1(x0_pred, x0) + tv_w * TV(x0_pred): a few elementwise torch ops on
-    (B, 3, S, S) whose gradient reaches eps_hat], ``loss.backward()`` runs the library's backward, AdamW step.  The CLIP-alignment
-    term (clip_w, :129-136) needs ``open_clip`` with downloaded weights: when that import fails the term is skipped with a note
-    (SURVEY.md section 8c).  Additions that default to the reference's behaviour: ``base`` / ``ch_mult`` / ``dtype``.  With
-    ``torch.distributed`` initialised the records are sharded over the ranks and the flat gradient buffer is averaged with one
-    all-reduce per step.
+    Per batch (train/diffusion_train.py:115-140): t ~ U{0..T-1}, noise ~ N, then ``train_step`` with the ``t`` / ``noise`` drawn here:
+    x_t = q_sample, eps_hat = net(x_t, z, t), loss = mse(eps_hat, noise) + recon_w * L1(x0_pred, x0) + tv_w * TV(x0_pred) and its
+    gradient from one kernel, the library's backward, the fused AdamW step.  The running loss is accumulated on the device and read
+    once per epoch.  ``fused_objective=False`` keeps the earlier route for A/B: the same objective from torch ops on (B, 3, S, S)
+    through autograd (``UNetFunction``), the loss read back every batch.  The CLIP-alignment term (clip_w, :129-136) needs
+    ``open_clip`` with downloaded weights: it is skipped with a note; ``GradScaler`` (:137-139) is not
+    reproduced.  Additions that default to the reference's behaviour: ``base`` / ``ch_mult`` / ``dtype``.  With
+    ``torch.distributed`` initialised the records are sharded over the ranks and the flat gradient buffer is all-reduced bucket
+    by bucket while the backward runs.
     """
     from pathlib import Path
     import torch.distributed as dist
-    import torch.nn.functional as F
     from ..models.unet import CLIPCondUNet
     from ..diffusion.scheduler import NoiseScheduler
     save_dir = Path(save_dir or store_dir)
@@ -355,29 +423,20 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
         if sampler is not None:
             sampler.set_epoch(ep)
         running, seen = 0.0, 0
+        running_dev = torch.zeros((), dtype=torch.float64, device=device)
         for x0, z in dl:
             x0 = x0.to(device); z = z.to(device)
             b = x0.size(0)
             t = torch.randint(0, timesteps, (b,), device=device, dtype=torch.long)
             noise = torch.randn_like(x0)
-            state.fp.rebind_grads()
-            x_t = sch.q_sample(x0, t, noise)
-            eps_hat = net(x_t, z, t)
-            loss = F.mse_loss(eps_hat, noise)
-            if recon_w > 0 or tv_w > 0:
-                # predict_x0_from_eps (diffusion/scheduler.py:51-55) written with torch ops: its gradient must reach eps_hat
-                sg = sch.sqrt_one_minus_alphas_cumprod[t].view(-1, 1, 1, 1); ac = sch.sqrt_alphas_cumprod[t].view(-1, 1, 1, 1)
-                x0_pred = ((x_t - sg * eps_hat) / ac).clamp(-1, 1)
-                if recon_w > 0:
-                    loss = loss + recon_w * F.l1_loss(x0_pred, x0)
-                if tv_w > 0:
-                    loss = loss + tv_w * total_variation(x0_pred)
-            loss.backward()
-            state.wait_grad_sync()
-            opt.step()
-            opt.zero_grad()
-            running += float(loss.detach()) * b
+            if fused_objective:
+                loss = train_step(net, sch, opt, x0, z, t=t, noise=noise, ddp=ddp, recon_w=max(recon_w, 0.0), tv_w=max(tv_w, 0.0))
+                running_dev += loss.double() * b          # the loss is a view of a static buffer: consumed here, in stream order
+            else:
+                running += float(autograd_objective_step(net, sch, opt, x0, z, t, noise, recon_w, tv_w)) * b
             seen += b
+        if fused_objective:
+            running = float(running_dev)                  # the one host read of the epoch
         if rank0:
             torch.save(net.state_dict(), save_dir / f"diffusion_unet_ep{ep + 1}.pt")
             log(f"[train] epoch {ep + 1}/{epochs} loss={running / max(seen, 1):.4f}")

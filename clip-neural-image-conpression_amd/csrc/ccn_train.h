@@ -100,6 +100,12 @@ hipError_t launch_add2(float* y, const float* a, const float* b, int64_t n, hipS
 // ---- loss and optimiser ---------------------------------------------------------------------------------------------------
 // loss = mean((eps - target)^2) (F.mse_loss, train/diffusion_train.py:124); d_eps = 2 (eps - target) / n; scratch >= 1024 floats
 hipError_t launch_mse_loss_grad(const float* eps, const float* target, int64_t n, float* loss, float* d_eps, float* scratch, hipStream_t s);
+// the reference's default objective (train/diffusion_train.py:124-129): mse + recon_w L1(x0_pred, x0) + tv_w TV(x0_pred) with
+// x0_pred = clamp((x_t - s eps) / a, -1, 1) recomputed per tile; loss[4] = total, mse, l1, tv; scratch >= 8192 floats, 8-byte aligned.
+// recon_w == tv_w == 0 runs launch_mse_loss_grad itself.
+hipError_t launch_diffusion_loss_grad(const float* eps, const float* noise, const float* xt, const float* x0, const float* a, const float* sg,
+                                      int B, int C, int H, int W, float recon_w, float tv_w, float* loss, float* d_eps, float* scratch,
+                                      hipStream_t s);
 // torch.optim.AdamW step (train/diffusion_train.py:105,138): decoupled weight decay, bias-corrected moments
 hipError_t launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
                         int step, hipStream_t s, bool zero_grad = false);

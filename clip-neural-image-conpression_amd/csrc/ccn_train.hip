@@ -1086,6 +1086,22 @@ int ccn_mse_loss_grad(const float* eps_dev, const float* target_dev, int64_t n, 
     return CCN_OK;
 }
 
+int ccn_diffusion_loss_grad(const float* eps_dev, const float* noise_dev, const float* x_t_dev, const float* x0_dev, const float* a_dev,
+                            const float* s_dev, int32_t B, int32_t C, int32_t H, int32_t W, float recon_w, float tv_w, float* loss_dev,
+                            float* d_eps_dev, float* scratch_dev, void* stream)
+{
+    if (!eps_dev || !noise_dev || !x_t_dev || !x0_dev || !a_dev || !s_dev || !loss_dev || !scratch_dev || B <= 0 || C <= 0)
+        return tfail(CCN_EINVAL, "bad argument");
+    if (H < 2 || W < 2) return tfail(CCN_EINVAL, "H and W must be at least 2 (the total variation of a one-pixel-wide image is a mean over nothing)");
+    if (!(recon_w >= 0.f) || !(tv_w >= 0.f)) return tfail(CCN_EINVAL, "recon_w and tv_w must be non-negative");
+    if (((uintptr_t)scratch_dev & 7) != 0) return tfail(CCN_EINVAL, "scratch_dev must be 8-byte aligned");
+    if ((int64_t)B * C * H * W > (int64_t)1 << 40) return tfail(CCN_EINVAL, "tensor too large");
+    if (launch_diffusion_loss_grad(eps_dev, noise_dev, x_t_dev, x0_dev, a_dev, s_dev, B, C, H, W, recon_w, tv_w, loss_dev, d_eps_dev, scratch_dev,
+                                   (hipStream_t)stream) != hipSuccess)
+        return tfail(CCN_EHIP, "objective launch failed");
+    return CCN_OK;
+}
+
 int ccn_adamw_step(float* params_dev, const float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n, float lr, float beta1, float beta2,
                    float eps, float weight_decay, int32_t step, void* stream)
 {

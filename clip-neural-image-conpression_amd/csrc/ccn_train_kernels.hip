@@ -12,7 +12,7 @@
 //                        the residual-gradient add and the FiLM backward (scale by 1+s, sums for d scale / d shift).
 //   im2col27 / nchw_to_nhwc_pad   layout changes that let the stem / head weights use the same weight-gradient kernel.
 //   tlinear_*            conditioning MLP / FiLM linears, fp32.
-//   adamw_kernel, mse_loss_grad
+//   adamw_kernel, mse_loss_grad, objective_* (MSE + L1 + TV of the reference's default objective, one pass)
 #include "ccn_device.h"
 #include "ccn_train.h"
 #include <cstdlib>
@@ -1435,6 +1435,199 @@ hipError_t launch_mse_loss_grad(const float* eps, const float* target, int64_t n
     const int nb = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
     hipLaunchKernelGGL(mse_partial_kernel, dim3(nb), dim3(256), 0, s, eps, target, n, (float)(1.0 / (double)n), d_eps, scratch);
     hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(64), 0, s, scratch, nb, 1.0 / (double)n, loss);
+    return hipGetLastError();
+}
+
+// ---- the reference's default objective: MSE + recon_w L1(x0_pred, x0) + tv_w TV(x0_pred) (train/diffusion_train.py:124-129) ------
+// x0_pred = clamp((x_t - s eps) / a, -1, 1) is never stored: a workgroup takes OBJ_TY rows x OBJ_TX columns of one (b, c) plane,
+// recomputes p = x0_pred for that tile plus a one-pixel halo into LDS (the same expression and op order as predict_x0_kernel, so the
+// clamp mask is the one ccn_predict_x0 + torch.clamp would give) and differentiates the 4-neighbour stencil from LDS:
+//   dL/dp = recon_w sgn(p - x0) / n + tv_w [ (sgn(p - p_up) - sgn(p_down - p)) / n_h + (sgn(p - p_left) - sgn(p_right - p)) / n_w ]
+//   d_eps = 2 (eps - noise) / n + [-1 <= raw <= 1] dL/dp (-s / a)
+// with sgn(0) = 0 (torch's abs backward), the clamp bounds inclusive (torch's clamp backward) and neighbours outside the image
+// absent.  Each pixel owns its down and right difference in the TV sums.  The LDS row is laid out so that the tile's interior
+// starts on a 16-byte boundary (columns 3 and OBJ_TX + 4 are the left / right halo): every interior access is a ds_*_b128.
+// Sums: fp64 per thread -> wave shuffle tree -> 4 doubles per workgroup in scratch -> objective_final_kernel adds them in a fixed
+// order: bit-reproducible from run to run, no atomics.
+constexpr int OBJ_TX = 128, OBJ_TY = 16, OBJ_LD = OBJ_TX + 8, OBJ_MAX_WG = 1024;
+
+__device__ __forceinline__ float sgnf(float v) { return (float)((v > 0.f) - (v < 0.f)); }
+
+// VEC: W % 4 == 0 and every tensor 16-byte aligned, so that a quad of columns is inside the image as a whole and is one 16-byte access
+template <bool VEC> __device__ __forceinline__ void obj_load4(const float* __restrict__ p, int cnt, float v[4])
+{
+    if (VEC) {
+        const f32x4 t = *(const f32x4*)p;
+        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = j < cnt ? p[j] : 0.f;
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void objective_partial_kernel(const float* __restrict__ eps, const float* __restrict__ noise,
+                                                                 const float* __restrict__ xt, const float* __restrict__ x0,
+                                                                 const float* __restrict__ a, const float* __restrict__ sg, int C, int H, int W,
+                                                                 int nby, int nbx, int ntiles, float inv_n, float c_l1, float c_tvh, float c_tvw,
+                                                                 float* __restrict__ d_eps, double* __restrict__ scratch)
+{
+    __shared__ __attribute__((aligned(16))) float tile[OBJ_TY + 2][OBJ_LD];
+    __shared__ double red[4][4];
+    const int tid = threadIdx.x, q = tid & 31, rr = tid >> 5;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};                      // sum (eps-noise)^2, sum |p-x0|, sum |p_down-p|, sum |p_right-p|
+    for (int tix = blockIdx.x; tix < ntiles; tix += gridDim.x) {
+        const int bx = tix % nbx, by = (tix / nbx) % nby, plane = tix / (nbx * nby);
+        const int xs = bx * OBJ_TX, ys = by * OBJ_TY;
+        const float ca = a[plane / C], cs = sg[plane / C];
+        const size_t pbase = (size_t)plane * H * W;
+        const int gx = xs + 4 * q;
+        const int cw = gx >= W ? 0 : (W - gx < 4 ? W - gx : 4);                 // columns of this thread's quad inside the image
+        float e[2][4];
+        unsigned inside[2] = {0u, 0u};                                           // bit j: -1 <= raw <= 1 at column gx + j
+        // ---- p of the tile's own rows (eps stays in registers for the second phase), then the halo rows and columns ---------
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int r = rr + 8 * k, gy = ys + r;
+            if (gy < H && cw > 0) {
+                const size_t o = pbase + (size_t)gy * W + gx;
+                float v[4];
+                obj_load4<VEC>(eps + o, cw, e[k]); obj_load4<VEC>(xt + o, cw, v);
+                f32x4 p;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float raw = __fdiv_rn(__fsub_rn(v[j], __fmul_rn(cs, e[k][j])), ca);
+                    inside[k] |= (raw >= -1.0f && raw <= 1.0f) ? (1u << j) : 0u;
+                    p[j] = fminf(fmaxf(raw, -1.0f), 1.0f);
+                }
+                *(f32x4*)&tile[r + 1][4 + 4 * q] = p;
+            }
+        }
+        if (tid < 64) {                                                          // wave 0: the row above and the row below the band
+            const int gy = rr ? ys + OBJ_TY : ys - 1;
+            if (gy >= 0 && gy < H && cw > 0) {
+                const size_t o = pbase + (size_t)gy * W + gx;
+                float ev[4], v[4];
+                obj_load4<VEC>(eps + o, cw, ev); obj_load4<VEC>(xt + o, cw, v);
+                f32x4 p;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) p[j] = fminf(fmaxf(__fdiv_rn(__fsub_rn(v[j], __fmul_rn(cs, ev[j])), ca), -1.0f), 1.0f);
+                *(f32x4*)&tile[rr ? OBJ_TY + 1 : 0][4 + 4 * q] = p;
+            }
+        } else if (tid < 64 + 2 * OBJ_TY) {                                      // wave 1: the column left and right of the tile
+            const int i = tid - 64, r = i >> 1, right = i & 1;
+            const int gy = ys + r, hx = right ? xs + OBJ_TX : xs - 1;
+            if (gy < H && hx >= 0 && hx < W) {
+                const size_t o = pbase + (size_t)gy * W + hx;
+                tile[r + 1][right ? OBJ_TX + 4 : 3] = fminf(fmaxf(__fdiv_rn(__fsub_rn(xt[o], __fmul_rn(cs, eps[o])), ca), -1.0f), 1.0f);
+            }
+        }
+        __syncthreads();
+        // ---- stencil from LDS --------------------------------------------------------------------------------------------------
+        const float coef = -__fdiv_rn(cs, ca);                                   // d raw / d eps
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int r = rr + 8 * k, gy = ys + r;
+            if (gy < H && cw > 0) {
+                const size_t o = pbase + (size_t)gy * W + gx;
+                float nz[4], xv[4];
+                obj_load4<VEC>(noise + o, cw, nz); obj_load4<VEC>(x0 + o, cw, xv);
+                const f32x4 cen = *(const f32x4*)&tile[r + 1][4 + 4 * q];
+                const f32x4 up = *(const f32x4*)&tile[r][4 + 4 * q], dn = *(const f32x4*)&tile[r + 2][4 + 4 * q];
+                const float row[6] = {tile[r + 1][3 + 4 * q], cen[0], cen[1], cen[2], cen[3], tile[r + 1][8 + 4 * q]};
+                const bool has_up = gy > 0, has_dn = gy + 1 < H;
+                f32x4 out;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float d = e[k][j] - nz[j];
+                    float g = 2.0f * d * inv_n;                                  // the op order of mse_partial_kernel
+                    if (j < cw) {
+                        const float p = row[j + 1];
+                        const bool has_l = gx + j > 0, has_r = gx + j + 1 < W;
+                        const float sv = (has_up ? sgnf(p - up[j]) : 0.f) - (has_dn ? sgnf(dn[j] - p) : 0.f);
+                        const float sh = (has_l ? sgnf(p - row[j]) : 0.f) - (has_r ? sgnf(row[j + 2] - p) : 0.f);
+                        const float dp = (c_l1 * sgnf(p - xv[j]) + c_tvh * sv) + c_tvw * sh;
+                        if ((inside[k] >> j) & 1u) g += dp * coef;
+                        const double dd = (double)e[k][j] - (double)nz[j];
+                        acc[0] += dd * dd;
+                        acc[1] += fabs((double)p - (double)xv[j]);
+                        if (has_dn) acc[2] += fabs((double)dn[j] - (double)p);
+                        if (has_r) acc[3] += fabs((double)row[j + 2] - (double)p);
+                    }
+                    out[j] = g;
+                }
+                if (d_eps) {
+                    if (VEC) *(f32x4*)(d_eps + o) = out;
+                    else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) if (j < cw) d_eps[o + j] = out[j];
+                    }
+                }
+            }
+        }
+        __syncthreads();                                                         // the next tile overwrites the LDS tile
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) acc[k] += __shfl_xor(acc[k], m);
+        if ((tid & 63) == 0) red[k][tid >> 6] = acc[k];
+    }
+    __syncthreads();
+    if (tid < 4) scratch[(size_t)blockIdx.x * 4 + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+}
+// one wave, fixed order (mse_final_kernel's scheme) over the 4 sums of every workgroup; loss[] = total, mse, l1, tv (l1, tv unweighted)
+__global__ void objective_final_kernel(const double* __restrict__ scratch, int nb, double inv_n, double inv_nh, double inv_nw, double recon_w,
+                                       double tv_w, float* __restrict__ loss)
+{
+    if (blockIdx.x) return;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = (int)threadIdx.x; i < nb; i += 64) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[k] += scratch[(size_t)i * 4 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) s[k] += __shfl_xor(s[k], m);
+    }
+    if (threadIdx.x == 0) {
+        const double mse = s[0] * inv_n, l1 = s[1] * inv_n, tv = s[2] * inv_nh + s[3] * inv_nw;
+        loss[0] = (float)(mse + recon_w * l1 + tv_w * tv); loss[1] = (float)mse; loss[2] = (float)l1; loss[3] = (float)tv;
+    }
+}
+// recon_w == tv_w == 0: the terms next to what mse_final_kernel wrote (total == mse; l1 and tv are not evaluated and read 0)
+__global__ void objective_mse_only_terms_kernel(float* __restrict__ loss)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) { loss[1] = loss[0]; loss[2] = 0.f; loss[3] = 0.f; }
+}
+hipError_t launch_diffusion_loss_grad(const float* eps, const float* noise, const float* xt, const float* x0, const float* a, const float* sg,
+                                      int B, int C, int H, int W, float recon_w, float tv_w, float* loss, float* d_eps, float* scratch,
+                                      hipStream_t s)
+{
+    const int64_t n = (int64_t)B * C * H * W;
+    if (recon_w == 0.f && tv_w == 0.f) {
+        const hipError_t e = launch_mse_loss_grad(eps, noise, n, loss, d_eps, scratch, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(objective_mse_only_terms_kernel, dim3(1), dim3(64), 0, s, loss);
+        return hipGetLastError();
+    }
+    const int nbx = (W + OBJ_TX - 1) / OBJ_TX, nby = (H + OBJ_TY - 1) / OBJ_TY;
+    const int64_t tiles = (int64_t)B * C * nby * nbx;
+    if (tiles > INT32_MAX) return hipErrorInvalidValue;
+    const int nb = (int)(tiles < OBJ_MAX_WG ? tiles : OBJ_MAX_WG);
+    const double nh = (double)B * C * (H - 1) * W, nw = (double)B * C * H * (W - 1);
+    const float inv_n = (float)(1.0 / (double)n);
+    const float c_l1 = (float)((double)recon_w / (double)n), c_tvh = (float)((double)tv_w / nh), c_tvw = (float)((double)tv_w / nw);
+    const uintptr_t bits = (uintptr_t)eps | (uintptr_t)noise | (uintptr_t)xt | (uintptr_t)x0 | (uintptr_t)d_eps;
+    if (W % 4 == 0 && (bits & 15) == 0)
+        hipLaunchKernelGGL(objective_partial_kernel<true>, dim3(nb), dim3(256), 0, s, eps, noise, xt, x0, a, sg, C, H, W, nby, nbx, (int)tiles,
+                           inv_n, c_l1, c_tvh, c_tvw, d_eps, (double*)scratch);
+    else
+        hipLaunchKernelGGL(objective_partial_kernel<false>, dim3(nb), dim3(256), 0, s, eps, noise, xt, x0, a, sg, C, H, W, nby, nbx, (int)tiles,
+                           inv_n, c_l1, c_tvh, c_tvw, d_eps, (double*)scratch);
+    hipLaunchKernelGGL(objective_final_kernel, dim3(1), dim3(64), 0, s, (const double*)scratch, nb, 1.0 / (double)n, 1.0 / nh, 1.0 / nw,
+                       (double)recon_w, (double)tv_w, loss);
     return hipGetLastError();
 }
 

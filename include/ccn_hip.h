@@ -258,6 +258,22 @@ int ccn_train_profile_read(ccn_trainer_t tr, const char** names, float* ms, int3
 int ccn_mse_loss_grad(const float* eps_dev, const float* target_dev, int64_t n, float* loss_dev, float* d_eps_dev,
                       float* scratch_dev, void* stream);
 
+/* The reference's default training objective (train/diffusion_train.py:124-129 with diffusion/scheduler.py:51-55) and its
+ * gradient in one pass, without storing x0_pred:
+ *     x0_pred = predict_x0_from_eps(x_t, t, eps_hat).clamp(-1, 1)
+ *     loss    = F.mse_loss(eps_hat, noise) + recon_w * F.l1_loss(x0_pred, x0) + tv_w * total_variation(x0_pred)
+ * eps_dev / noise_dev / x_t_dev / x0_dev / d_eps_dev: (B,C,H,W) fp32 NCHW; a_dev / s_dev: (B,) fp32, sqrt_alphas_cumprod[t_b] and
+ * sqrt_one_minus_alphas_cumprod[t_b] (what ccn_q_sample and ccn_predict_x0 take).  x0_pred is evaluated exactly as ccn_predict_x0
+ * does, the clamp passes gradient on -1 <= raw <= 1 (bounds included) and sgn(0) = 0, as torch's backward of clamp and abs.
+ * loss_dev[4] = total, mse, l1, tv; l1 and tv are reported UNWEIGHTED (total = mse + recon_w l1 + tv_w tv).  d_eps_dev = d total /
+ * d eps_hat (may be NULL).  recon_w, tv_w >= 0; with both 0 the pass is ccn_mse_loss_grad's (bit-identical d_eps and mse; l1 and
+ * tv are then not evaluated and read 0).  H, W >= 2 (CCN_EINVAL otherwise: torch's TV is NaN there).  scratch_dev: at least 8192
+ * floats, 8-byte aligned.  Sums are accumulated in fp64 in a fixed order: results are bit-reproducible.  Never synchronises. */
+int ccn_diffusion_loss_grad(const float* eps_dev, const float* noise_dev, const float* x_t_dev, const float* x0_dev,
+                            const float* a_dev, const float* s_dev, int32_t B, int32_t C, int32_t H, int32_t W,
+                            float recon_w, float tv_w, float* loss_dev /* [4]: total, mse, l1, tv */,
+                            float* d_eps_dev /* may be NULL */, float* scratch_dev, void* stream);
+
 /* One torch.optim.AdamW step over a flat buffer (train/diffusion_train.py:105,138): p *= 1 - lr*wd;
  * m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr/(1-b1^step) * m / (sqrt(v)/sqrt(1-b2^step) + eps). step >= 1. */
 int ccn_adamw_step(float* params_dev, const float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n,
