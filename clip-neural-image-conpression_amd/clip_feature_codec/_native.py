@@ -16,8 +16,9 @@ import torch
 CSRC = Path(__file__).resolve().parent.parent / "csrc"
 LIB_PATH = Path(os.environ.get("CCN_HIP_LIB", CSRC / "libccn_hip.so"))
 
-DTYPE_F32, DTYPE_BF16 = 0, 1
-_DTYPES = {"fp32": DTYPE_F32, "f32": DTYPE_F32, "float32": DTYPE_F32, "bf16": DTYPE_BF16, "bfloat16": DTYPE_BF16}
+DTYPE_F32, DTYPE_BF16, DTYPE_F16X3 = 0, 1, 2
+_DTYPES = {"fp32": DTYPE_F32, "f32": DTYPE_F32, "float32": DTYPE_F32, "bf16": DTYPE_BF16, "bfloat16": DTYPE_BF16,
+           "f16x3": DTYPE_F16X3}
 
 c_i32, c_i64, c_f32, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 

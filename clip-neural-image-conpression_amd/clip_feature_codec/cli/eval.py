@@ -161,7 +161,7 @@ def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstru
     return gather_metric_rows(mine, local, len(manifest), device)
 
 
-def main(argv=None) -> None:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Evaluate reconstruction quality on a store of images (MI355X build).")
     ap.add_argument("--store_dir", type=str, required=True)
     ap.add_argument("--weights", type=str, required=True)
@@ -172,7 +172,7 @@ def main(argv=None) -> None:
     ap.add_argument("--out_json", type=str, default=None)
     ap.add_argument("--batch", type=int, default=8, help="records per fused DDIM launch per GPU")
     ap.add_argument("--seed", type=int, default=None)
-    ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32")
+    ap.add_argument("--dtype", choices=["fp32", "bf16", "f16x3"], default="fp32")
     ap.add_argument("--timing", action="store_true", help="print set-up and loop wall time (records/s of the loop) to stderr")
     ap.add_argument("--workers", type=int, default=None, help="host threads for decode / metrics (default: this rank's share of the CPUs, 2..16)")
     ap.add_argument("--force-process-group", action="store_true",
@@ -181,7 +181,11 @@ def main(argv=None) -> None:
     ap.add_argument("--gpus", type=int, default=None,
                     help="shard the store over this many GPUs of the node: one process per GPU is started here unless a launcher "
                          "(torchrun) already did; default: the launcher's WORLD_SIZE, else 1")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None) -> None:
+    args = build_parser().parse_args(argv)
 
     from ..utils.launch import ensure_ranks, init_process_group, rank_env, single_rank_env
     if args.gpus is not None:

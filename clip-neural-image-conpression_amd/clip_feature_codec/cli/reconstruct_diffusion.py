@@ -4,7 +4,7 @@ Same flags, defaults and output as the reference CLI (cli/reconstruct_diffusion.
 ``--store_dir --bitstream --weights --out --steps --eta --size --device``; prints ``Saved to <out>``;
 the PNG is written from ``((clamp(x,-1,1)+1)*127.5).astype(uint8)`` (truncation).  Additions that
 default to the reference behaviour: ``--seed`` (reproducible CPU-generated start noise; the reference
-never seeds), ``--dtype {fp32,bf16}`` and the architecture is read from the checkpoint's shapes.
+never seeds), ``--dtype {fp32,bf16,f16x3}`` and the architecture is read from the checkpoint's shapes.
 """
 from __future__ import annotations
 
@@ -18,7 +18,7 @@ from PIL import Image
 from ._common import pick_device, load_codec_meta, load_embedding, build_model, build_sampler, start_noise
 
 
-def main(argv=None) -> None:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Reconstruct an image from a .clp bitstream via DDIM sampling (MI355X build).")
     ap.add_argument("--store_dir", type=str, required=True)
     ap.add_argument("--bitstream", type=str, required=True)
@@ -29,8 +29,12 @@ def main(argv=None) -> None:
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--device", type=str, default=None)
     ap.add_argument("--seed", type=int, default=None, help="seed of the CPU-generated start noise (default: unseeded, like the reference)")
-    ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32")
-    args = ap.parse_args(argv)
+    ap.add_argument("--dtype", choices=["fp32", "bf16", "f16x3"], default="fp32")
+    return ap
+
+
+def main(argv=None) -> None:
+    args = build_parser().parse_args(argv)
 
     device = pick_device(args.device)
     scale, zero = load_codec_meta(Path(args.store_dir))

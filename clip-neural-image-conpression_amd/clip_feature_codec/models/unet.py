@@ -100,7 +100,8 @@ class CLIPCondUNet(nn.Module):
         return net
 
     def set_compute_dtype(self, dtype: str) -> "CLIPCondUNet":
-        """'fp32' (parity mode, fp32 MFMA) or 'bf16' (throughput mode, bf16 MFMA + bf16 activations)."""
+        """'fp32' (parity mode, fp32 MFMA), 'bf16' (throughput mode, bf16 MFMA + bf16 activations) or 'f16x3' (fp32 storage and
+        fp32-grade results; the ResBlock convs and ConvTransposes multiply fp16 hi + lo operands on the fp16 MFMA; inference only)."""
         _native.dtype_code(dtype)
         self.compute_dtype = dtype
         return self

@@ -62,6 +62,8 @@ struct ConvW {
     void* w = nullptr;
     void* wfrag = nullptr;      // MFMA-fragment-ordered copy for the persistent 3x3 kernel (Cout_pad % 128 == 0), else null
     float* bias = nullptr;
+    bool split = false;         // f16x3 mode, layers on the ws / fr kernels: `w` holds fp16 hi + lo rows of the weights times 1 / inv_scale
+    float inv_scale = 1.f;
     // bf16 mode, CCN_ROUND_DIFFUSED_PHASES: further roundings of the same weights, used by DDIM step i as version i % nphase
     // (version 0 = w / wfrag above); see diffuse_round_phases()
     int nphase = 1;
@@ -136,6 +138,7 @@ struct RouteRec {
     const char* gn = "none";   // input GroupNorm: none, prologue (finalize launch + conv prologue), instat (in-kernel statistics),
                                // preact / preact_fused (GroupNorm + SiLU pass in front), weights (head2: folded into the weights)
     bool film = false, res = false;
+    int ops = -1;              // f16x3 plans only: 1 = split fp16 operands, 0 = the fp32 kernel; -1: not reported
 };
 
 constexpr size_t kMaxGraphsPerPlan = 4;
@@ -166,7 +169,8 @@ struct Plan {
 }  // namespace
 
 struct ccn_handle_s {
-    ccn_config_t cfg{};
+    ccn_config_t cfg{};                 // (dtype: the STORAGE type; CCN_DTYPE_F16X3 is fp32 storage with `split` set)
+    bool split = false;                 // CCN_DTYPE_F16X3: the ws / fr layers multiply fp16 hi + lo operand rows
     int elem = 4;                       // bytes per activation / weight element
     std::vector<ParamInfo> params;
     std::map<std::string, std::vector<float>> host;   // loaded fp32 copies until commit
@@ -380,6 +384,28 @@ extern "C" int ccn_internal_round_weights(const float* w, int O, int I, int taps
     }
     return 0;
 }
+// f16x3: the commit-time split of one weight tensor, exported for tests/test_split_host.py (not part of include/ccn_hip.h; no GPU
+// involved).  *scale = the power of two s with max|w| s in [2^13, 2^14) (1 for an all-zero tensor): it lifts the low halves of
+// all but the smallest weights out of fp16's subnormal range while hi stays 4x below its largest finite value.  hi = RNE_fp16(w s),
+// lo = RNE_fp16(w s - hi), as fp16 bit patterns: hi + lo = w s to 2^-22 relative (2^-25 absolute where lo is subnormal).
+extern "C" int ccn_internal_split_weights(const float* w, size_t n, float* scale, uint16_t* hi, uint16_t* lo)
+{
+    if ((!w && n) || !scale || ((!hi || !lo) && n)) return 1;
+    float mx = 0.f;
+    for (size_t i = 0; i < n; ++i) { const float v = std::fabs(w[i]); if (v > mx) mx = v; }
+    int e = 0;
+    float s = 1.f;
+    if (mx > 0.f && std::isfinite(mx)) { (void)std::frexp(mx, &e); s = std::ldexp(1.f, std::min(14 - e, 126)); }   // mx in [2^(e-1), 2^e)
+    *scale = s;
+    for (size_t i = 0; i < n; ++i) {
+        const float ws = w[i] * s;                              // exact
+        const _Float16 h = (_Float16)ws;
+        const _Float16 l = (_Float16)(ws - (float)h);           // the subtraction is exact
+        std::memcpy(hi + i, &h, 2);
+        std::memcpy(lo + i, &l, 2);
+    }
+    return 0;
+}
 namespace {
 
 // element (tap, o, i) of the packed [taps][Cout_pad][Cin_pad] tensor
@@ -401,6 +427,22 @@ int pack_and_upload(ccn_handle_s* h, ConvW& cw, int taps, F&& at)
     for (int t = 0; t < taps; ++t)
         for (int o = 0; o < cw.Cout; ++o)
             for (int i = 0; i < cw.Cin_pad; ++i) buf[((size_t)t * cw.Cout_pad + o) * cw.Cin_pad + i] = at(t, o, i);
+    // f16x3: the layers conv_kernel_for sends to the ws / fr kernels (fp32 storage never takes the persistent one) get the same
+    // [tap][Cout_pad][Cin_pad] geometry in 128-byte rows of 32 fp16 hi + 32 fp16 lo per 32-channel chunk, scaled per layer
+    cw.split = h->split && conv_ws_enabled() && conv_ws_supported(cw.kind, cw.BN);
+    cw.inv_scale = 1.f;
+    if (cw.split) {
+        std::vector<uint16_t> hi(n), lo(n), rows(2 * n);
+        float s = 1.f;
+        if (ccn_internal_split_weights(buf.data(), n, &s, hi.data(), lo.data())) return fail(CCN_EINVAL, "weight split failed");
+        cw.inv_scale = 1.f / s;
+        for (size_t i = 0; i < n; ++i) {
+            const size_t row = i / 32, c = i % 32;
+            rows[row * 64 + c] = hi[i];
+            rows[row * 64 + 32 + c] = lo[i];
+        }
+        return upload(h, rows.data(), n * 4, &cw.w);
+    }
     return upload(h, buf.data(), n * 4, &cw.w);
 }
 
@@ -525,7 +567,9 @@ struct PlanBuilder {
         r.fill(a);
         a.in = in.p; a.w = cw.w; a.wfrag = r.uses_frag() ? cw.wfrag : nullptr; a.bias = cw.bias; a.out = out.p;
         a.film = nullptr; a.res = res ? res->p : nullptr;
+        a.ops = cw.split ? 1 : 0; a.wscale_inv = cw.inv_scale;
         RouteRec rec;
+        if (h->split) rec.ops = a.ops;
         rec.kind = cw.kind; rec.th = r.th; rec.ksplit = r.ksplit; rec.n_nt = r.n_nt; rec.film = film_off >= 0; rec.res = res != nullptr;
         rec.gn = gn_ab ? "prologue" : "none";
         static const bool no_instat = diag_env("CCN_NO_INSTAT") != nullptr;       // diagnostics build only
@@ -763,6 +807,7 @@ int build_plan(ccn_handle_s* h, Plan* plan, void* ws, bool measure)
                     plan->ops.push_back(std::move(Lh));
                     RouteRec rec;
                     rec.name = L.name; rec.kind = KIND_HEAD; rec.kernel = "head2"; rec.th = 8; rec.gn = "weights";
+                    if (h->split) rec.ops = 0;
                     plan->routes.push_back(rec);
                     break;
                 }
@@ -905,6 +950,9 @@ int check_device_errors(ccn_handle_s* h)
     if (e & 2u)
         return fail(CCN_EHIP, "split-K partners ran on different XCDs (the hand-off took the agent-scope path: results are valid, but the "
                               "placement assumption of launch_conv_pr does not hold on this device / partition mode)");
+    if (e & 4u)
+        return fail(CCN_EHIP, "f16x3: an activation left the fp16 operand range (|x| >= 65520) and was saturated; the results of the "
+                              "launches enqueued since the last successful check are not fp32-grade: use dtype fp32 for this model");
     if (e) return fail(CCN_EHIP, "device-side error word " + std::to_string(e));
     return CCN_OK;
 }
@@ -932,7 +980,7 @@ int ccn_create(const ccn_config_t* cfg, ccn_handle_t* out)
 {
     if (!cfg || !out) return fail(CCN_EINVAL, "null argument");
     if (cfg->n_mult < 1 || cfg->n_mult > CCN_MAX_MULT) return fail(CCN_EINVAL, "n_mult out of range");
-    if (cfg->dtype != CCN_DTYPE_F32 && cfg->dtype != CCN_DTYPE_BF16) return fail(CCN_EINVAL, "unknown dtype");
+    if (cfg->dtype != CCN_DTYPE_F32 && cfg->dtype != CCN_DTYPE_BF16 && cfg->dtype != CCN_DTYPE_F16X3) return fail(CCN_EINVAL, "unknown dtype");
     if (cfg->base <= 0 || cfg->base % 8) return fail(CCN_EINVAL, "base must be a positive multiple of 8");
     if (cfg->img_ch < 1 || cfg->img_ch * 9 > 32) return fail(CCN_EINVAL, "img_ch must be 1..3");
     if (cfg->time_dim <= 0 || cfg->z_dim <= 0 || cfg->groups <= 0) return fail(CCN_EINVAL, "bad dims");
@@ -947,6 +995,10 @@ int ccn_create(const ccn_config_t* cfg, ccn_handle_t* out)
     if (ndev <= 0) return fail(CCN_EHIP, "no HIP device");
     std::unique_ptr<ccn_handle_s> h(new ccn_handle_s);
     h->cfg = *cfg;
+    // f16x3 is the fp32 mode in every respect but the operands of the ws / fr kernels: the plan, the workspace and every other
+    // kernel are chosen by the storage type
+    h->split = cfg->dtype == CCN_DTYPE_F16X3;
+    if (h->split) h->cfg.dtype = CCN_DTYPE_F32;
     h->elem = cfg->dtype == CCN_DTYPE_BF16 ? 2 : 4;
     h->G = cfg->groups;
     build_arch(h.get());
@@ -1342,7 +1394,7 @@ int ccn_read_activation(ccn_handle_t h, const char* name, float* out_dev, size_t
 
 // Test hook, not part of include/ccn_hip.h: one line per conv-family launch of the plan that ccn_read_activation reads (the one the
 // last ccn_forward / ccn_sample used), "<activation> <kind> <kernel> th=.. ksplit=.. n_nt=.. gn=.. film=0|1 res=0|1", as decided when
-// that plan was built.  snprintf-like: writes at most cap bytes (NUL-terminated) and returns the length of the whole report, or -1.
+// that plan was built; lines of an f16x3 plan end in " ops=f16x3" (split fp16 operands) or " ops=f32".  snprintf-like: writes at most cap bytes (NUL-terminated) and returns the length of the whole report, or -1.
 extern "C" int ccn_internal_plan_routes(ccn_handle_t h, char* buf, size_t cap)
 {
     if (!h || h->plans.empty()) return -1;
@@ -1350,9 +1402,11 @@ extern "C" int ccn_internal_plan_routes(ccn_handle_t h, char* buf, size_t cap)
     std::string text;
     for (const RouteRec& r : h->plans.back()->routes) {
         char line[256];
-        std::snprintf(line, sizeof(line), "%s %s %s th=%d ksplit=%d n_nt=%d gn=%s film=%d res=%d\n", r.name.c_str(), kinds[r.kind], r.kernel,
+        std::snprintf(line, sizeof(line), "%s %s %s th=%d ksplit=%d n_nt=%d gn=%s film=%d res=%d", r.name.c_str(), kinds[r.kind], r.kernel,
                       r.th, r.ksplit, r.n_nt, r.gn, r.film ? 1 : 0, r.res ? 1 : 0);
         text += line;
+        if (r.ops >= 0) text += r.ops ? " ops=f16x3" : " ops=f32";
+        text += "\n";
     }
     if (buf && cap) {
         const size_t n = std::min(text.size(), cap - 1);

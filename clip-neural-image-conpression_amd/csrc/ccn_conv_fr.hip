@@ -16,6 +16,10 @@
 // The workgroup decode, the operands' buffer descriptors, the stamps, the chunk-0 input prologue, the epilogue and the GroupNorm
 // partial-sum tail are the same in ccn_conv_ws.hip and are included from tile/*.inc (ccn_conv_tile.h says why as text).  Here: the
 // LDS layout with the private weight rings, the two roles and their loops.
+//
+// Three operand forms: T = float, __bf16 (storage type = operand type) and f16x3_t (ccn_device.h: fp32 storage, fp16 hi + lo rows in
+// LDS, three fp16 MFMAs per product).  The f16x3 form shares everything on the global side with the float form; its producers split
+// while they stage, and its consumers run tile/split_steps.inc instead of the step loop below.
 #include "ccn_conv_tile.h"
 
 namespace ccn {
@@ -41,6 +45,8 @@ __global__ __launch_bounds__(512) void conv_fr_kernel(const ConvArgs a)
     constexpr int BN = WN * NF * 32;
     constexpr int EPC = Vec16<T>::EPC;
     constexpr int CKE = 8 * EPC;
+    constexpr bool SPLIT = OperandForm<T>::SPLIT;       // f16x3: fp16 hi + lo operand rows (ccn_device.h)
+    [[maybe_unused]] unsigned ovf = 0;                  // ... and an activation that left the fp16 range while being staged
     constexpr int NA = 4, A0 = 4;               // waves 4..7 stage the input operand
     constexpr int NWAVES = 8;
     using G = TileGeom<TH>;
@@ -68,6 +74,10 @@ __global__ __launch_bounds__(512) void conv_fr_kernel(const ConvArgs a)
 
     // ------------------------------------------------------------------ epilogue pieces (used by every role after its loop)
 #include "tile/epilogue.inc"            // -> Cs, epi_init(), epi_all(); f1, f2, s1, s2
+    // f16x3 range guard: each role reports once it has staged its last input unit (the flag is not carried through a main loop)
+    [[maybe_unused]] auto report_ovf = [&]() __attribute__((always_inline)) {
+        if (__ballot(ovf != 0u) != 0ull && lane == 0 && a.err) __hip_atomic_fetch_or(a.err, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
     const bool do_epi = !CCN_DBG_BIT(a, 8);
 
     if (wave >= A0) {
@@ -106,17 +116,23 @@ __global__ __launch_bounds__(512) void conv_fr_kernel(const ConvArgs a)
                         if (a_off(i) != OOB) areg[i] = gk.template apply<true>(areg[i]);   // padding stays zero
                 }
             }
+            if constexpr (SPLIT) {                                 // f16x3: the split too happens outside the boundary, in place
+#pragma unroll
+                for (int i = 0; i < AIT; ++i) areg[i] = split_pack(areg[i], ovf);
+            }
             loop_barrier();                                        // consumers are done with chunk `chunk`
             if (!CCN_DBG_BIT(a, 1)) {
 #pragma unroll
                 for (int i = 0; i < AIT; ++i) {
                     const int px = (ptid >> 3) + NA * 8 * i;
-                    if (px < G::HROWS * HPITCH) *(u32x4*)(As + px * 128 + (((ck ^ (px >> 1)) & 7) << 4)) = areg[i];
+                    if constexpr (SPLIT) { if (px < G::HROWS * HPITCH) split_store(As + px * 128, px >> 1, ck, areg[i]); }
+                    else if (px < G::HROWS * HPITCH) *(u32x4*)(As + px * 128 + (((ck ^ (px >> 1)) & 7) << 4)) = areg[i];
                 }
             }
             loop_barrier();                                        // chunk `chunk + 1` visible
             if (!CCN_DBG_BIT(a, 1)) a_req_all(chunk + 2);
         }
+        if constexpr (SPLIT) report_ovf();
         stamp(2); stamp_wait();
         if (do_epi) {
             __syncthreads();                                       // matches the consumers' barrier: LDS is about to become the fp32 tile
@@ -125,6 +141,7 @@ __global__ __launch_bounds__(512) void conv_fr_kernel(const ConvArgs a)
         stamp(3);
     } else {
         // ------------------------------------------------------------------ consumers (4 waves)
+        if constexpr (SPLIT) report_ovf();
         __builtin_amdgcn_s_setprio(2);
         const int wm = wave / WN, wn = wave % WN;
         f32x16 acc[MF][NF];
@@ -171,7 +188,20 @@ __global__ __launch_bounds__(512) void conv_fr_kernel(const ConvArgs a)
         for (int chunk = 0; chunk < a.nchunk; ++chunk) {
 #pragma unroll
             for (int i = 0; i < MF; ++i) asm volatile("" : "+v"(prow[i]));    // keep the address math inside the loop
-            {
+            if constexpr (SPLIT) {
+                constexpr int NT = NTAPS;
+                constexpr int DPM = (PP + MF * NF - 1) / (MF * NF);
+                int abase[MF];
+                auto a_tap = [&](int tt) __attribute__((always_inline)) {
+#pragma unroll
+                    for (int i = 0; i < MF; ++i) abase[i] = rbase(prow[i] + toff[tt]);
+                };
+                auto b_tap = [&](int tt) __attribute__((always_inline)) { return b_wave + ((tg + tt) % NBUF) * (int)L::BW_BYTES; };
+                // as below: DMA(x) is issued during tap x-2; at the start of tap x the ring holds x (needed now) and x+1 (may fly)
+                auto tap_begin = [&](int tt) __attribute__((always_inline)) { b_dma(tg + tt + 2); };
+                auto tap_landed = [&](int) __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PP) : "memory"); };
+#include "tile/split_steps.inc"
+            } else {
                 constexpr int NSTEP = NTAPS * 4;                   // step = tap * 4 + kk
                 u32x4 av[2][MF], bv[2][NF];
                 int abase[MF];
@@ -251,8 +281,10 @@ template <typename T> static tile_fn_t pick_fr_t(int ntaps, int th, int bn)
     if (bn == 128) return conv_fr_kernel<T, 2, 2, 4>;
     return conv_fr_kernel<T, 2, 1, 4>;
 }
+// dtype: the storage type, or CCN_DTYPE_F16X3 = 2 for fp32 storage with split operand rows (ConvArgs::ops)
 static tile_fn_t pick_fr(int dtype, int ntaps, int th, int bn)
 {
+    if (dtype == 2) return pick_fr_t<f16x3_t>(ntaps, th, bn);
     return dtype == 0 ? pick_fr_t<float>(ntaps, th, bn) : pick_fr_t<__bf16>(ntaps, th, bn);
 }
 static size_t fr_lds(int /*ntaps*/, int th, int bn)
@@ -269,7 +301,8 @@ extern "C" int ccn_internal_dump_stamps_fr(const char* path) { return g_stamps.d
 hipError_t launch_conv_fr(int dtype, int bn, const ConvArgs& a, hipStream_t s)
 {
     const unsigned grid = (unsigned)(a.B * a.n_ty * a.n_tx * a.npar * a.n_nt);
-    return launch_tiled(pick_fr(dtype, a.ntaps, a.th, bn), grid, fr_lds(a.ntaps, a.th, bn), a, s, g_stamps);
+    if (a.ops && dtype != 0) return hipErrorInvalidValue;       // split operand rows exist for fp32 storage only
+    return launch_tiled(pick_fr(a.ops ? 2 : dtype, a.ntaps, a.th, bn), grid, fr_lds(a.ntaps, a.th, bn), a, s, g_stamps);
 }
 
 }  // namespace ccn

@@ -17,6 +17,7 @@
 //   tile/epilogue.inc          fp32 tile -> bias / FiLM / residual -> NHWC rows, running sums          ws, fr
 //   tile/acc_to_lds.inc        a consumer wave's accumulators -> fp32 tile                             ws, fr
 //   tile/gn_part_tail.inc      running sums -> GroupNorm partials -> optional in-kernel finalize       ws, fr, 4-wave
+//   tile/split_steps.inc       f16x3 operand form only: the consumers' MFMA steps over the staged taps   ws, fr
 //
 // What stays in each kernel file is what tells the kernels apart: the LDS ring layout of the main loop, the split of the waves
 // into roles with their stamps, and the main loops.  The 4-wave kernel's epilogue is deliberately its own (tile/epilogue.inc
@@ -48,10 +49,10 @@ template <int TH, int BN, int NWAVES> struct EpiLds {
 // ---- host side of the 8-wave kernels ----------------------------------------------------------------------------------
 typedef void (*tile_fn_t)(const ConvArgs);
 
-// raise the dynamic-LDS limit of every instantiation a pick table can return: 2 dtypes x {4, 9} taps x {4, 8} rows x BN {64, 128}
+// raise the dynamic-LDS limit of every instantiation a pick table can return: 3 operand forms (fp32, bf16, f16x3) x {4, 9} taps x {4, 8} rows x BN {64, 128}
 template <class Pick, class Lds> hipError_t tiled_prepare(Pick pick, Lds lds)
 {
-    for (int dt = 0; dt < 2; ++dt)
+    for (int dt = 0; dt < 3; ++dt)
         for (int ntaps = 4; ntaps <= 9; ntaps += 5)
             for (int th = 4; th <= 8; th += 4)
                 for (int bn = 64; bn <= 128; bn += 64) {

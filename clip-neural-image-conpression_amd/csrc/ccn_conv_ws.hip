@@ -19,6 +19,8 @@
 // The workgroup decode, the operands' buffer descriptors, the chunk-0 input prologue, the epilogue and the GroupNorm partial-sum
 // tail are the same in ccn_conv_fr.hip and are included from tile/*.inc (ccn_conv_tile.h says why as text).  Here: the LDS ring
 // layout, the three roles with their stamps, and their loops.
+//
+// Operand forms: T = float, __bf16, and f16x3_t (fp32 storage, fp16 hi + lo rows in LDS: ccn_device.h, ccn_conv_fr.hip).
 #include "ccn_conv_tile.h"
 
 namespace ccn {
@@ -43,6 +45,8 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(const ConvArgs a)
     constexpr int BN = WN * NF * 32;
     constexpr int EPC = Vec16<T>::EPC;
     constexpr int CKE = 8 * EPC;
+    constexpr bool SPLIT = OperandForm<T>::SPLIT;       // f16x3: fp16 hi + lo operand rows (ccn_device.h)
+    [[maybe_unused]] unsigned ovf = 0;                  // ... and an activation that left the fp16 range while being staged
     constexpr int NSPC = NTAPS / TPS;           // stages (barriers) per Cin chunk
     // producer waves 4..7: NB weight waves then NA input waves.  8-row tiles move 16 KB of weights per stage (one wave
     // keeps up) and carry the GroupNorm+SiLU VALU work on 1.7x more input, so they get 3 input waves; 4-row tiles 2 + 2.
@@ -87,6 +91,10 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(const ConvArgs a)
 
     // ------------------------------------------------------------------ epilogue pieces (used by every role after its loop)
 #include "tile/epilogue.inc"            // -> Cs, epi_init(), epi_all(); f1, f2, s1, s2
+    // f16x3 range guard: each role reports once it has staged its last input unit (the flag is not carried through a main loop)
+    [[maybe_unused]] auto report_ovf = [&]() __attribute__((always_inline)) {
+        if (__ballot(ovf != 0u) != 0ull && lane == 0 && a.err) __hip_atomic_fetch_or(a.err, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
     const bool do_epi = !CCN_DBG_BIT(a, 8);
 
     if (wave >= A0) {
@@ -138,7 +146,8 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(const ConvArgs a)
                             const bool real = a_off(i) != OOB && (chunk + 1) * CKE + ck * EPC < a.Cin;
                             u32x4 o = areg[i];
                             if (gn && real) o = gk.template apply<true>(areg[i]);
-                            *(u32x4*)(Ad + px * 128 + (((ck ^ (px >> 1)) & 7) << 4)) = o;
+                            if constexpr (SPLIT) split_put(Ad + px * 128, px >> 1, ck, o, ovf);
+                            else *(u32x4*)(Ad + px * 128 + (((ck ^ (px >> 1)) & 7) << 4)) = o;
                         }
                         a_req(chunk + 2, i);
                     }
@@ -147,6 +156,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(const ConvArgs a)
                 loop_barrier();
             }
         }
+        if constexpr (SPLIT) report_ovf();
         stamp(2); stamp_wait();
         if (do_epi) { epi_init(); epi_all(); }
         stamp(3);
@@ -154,6 +164,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(const ConvArgs a)
         // ------------------------------------------------------------------ B producers (NB waves): weights, ONE STAGE AHEAD IN REGISTERS
         // During stage s these waves write stage s+1 (requested a whole stage earlier) into the other stage buffer and
         // re-request the same registers for stage s+2.
+        if constexpr (SPLIT) report_ovf();
         const int ptid = tid - 256;
         constexpr int BU = BN * 8 / (NB * 64);                     // units per thread per tap
         unsigned boff[BU];
@@ -201,6 +212,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(const ConvArgs a)
         stamp(3);
     } else {
         // ------------------------------------------------------------------ consumers (4 waves): ds_read_b128 + MFMA only
+        if constexpr (SPLIT) report_ovf();
         __builtin_amdgcn_s_setprio(2);
         f32x16 acc[MF][NF];
 #pragma unroll
@@ -233,7 +245,18 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(const ConvArgs a)
 #pragma unroll
             for (int g = 0; g < NSPC; ++g, ++stage) {
                 const int b_off = 2 * L::A_BYTES + (stage & 1) * L::B_BYTES;
-                {
+                if constexpr (SPLIT) {
+                    constexpr int NT = TPS, DPM = 0;
+                    int abase[MF];
+                    auto a_tap = [&](int tt) __attribute__((always_inline)) {
+#pragma unroll
+                        for (int i = 0; i < MF; ++i) abase[i] = a_off + rbase(prow[i] + toff[g * TPS + tt]);
+                    };
+                    auto b_tap = [&](int tt) __attribute__((always_inline)) { return b_off + tt * (int)L::BT_BYTES; };
+                    auto tap_begin = [&](int) __attribute__((always_inline)) {};
+                    auto tap_landed = [&](int) __attribute__((always_inline)) {};
+#include "tile/split_steps.inc"
+                } else {
                     // fragments of step j+1 are requested before the MFMAs of step j (step = tap * 4 + kk)
                     constexpr int PF = 1;                         // fragment prefetch distance in steps (2 measured no faster: the loop is LDS-bandwidth bound)
                     constexpr int NSTEP = TPS * 4;
@@ -304,8 +327,10 @@ template <typename T> static tile_fn_t pick_ws_t(int ntaps, int th, int bn)
     if (th == 8) return bn == 128 ? conv_ws_kernel<T, 4, 2, 4, 1> : conv_ws_kernel<T, 4, 1, 4, 1>;
     return bn == 128 ? conv_ws_kernel<T, 2, 2, 4, 2> : conv_ws_kernel<T, 2, 1, 4, 2>;
 }
+// dtype: the storage type, or CCN_DTYPE_F16X3 = 2 for fp32 storage with split operand rows (ConvArgs::ops)
 static tile_fn_t pick_ws(int dtype, int ntaps, int th, int bn)
 {
+    if (dtype == 2) return pick_ws_t<f16x3_t>(ntaps, th, bn);
     return dtype == 0 ? pick_ws_t<float>(ntaps, th, bn) : pick_ws_t<__bf16>(ntaps, th, bn);
 }
 static size_t ws_lds(int ntaps, int th, int bn)
@@ -325,7 +350,8 @@ extern "C" int ccn_internal_dump_stamps(const char* path) { return g_stamps.dump
 hipError_t launch_conv_ws(int dtype, int bn, const ConvArgs& a, hipStream_t s)
 {
     const unsigned grid = (unsigned)(a.B * a.n_ty * a.n_tx * a.npar * a.n_nt);
-    return launch_tiled(pick_ws(dtype, a.ntaps, a.th, bn), grid, ws_lds(a.ntaps, a.th, bn), a, s, g_stamps);
+    if (a.ops && dtype != 0) return hipErrorInvalidValue;       // split operand rows exist for fp32 storage only
+    return launch_tiled(pick_ws(a.ops ? 2 : dtype, a.ntaps, a.th, bn), grid, ws_lds(a.ntaps, a.th, bn), a, s, g_stamps);
 }
 
 }  // namespace ccn

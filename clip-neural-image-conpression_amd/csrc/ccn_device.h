@@ -58,6 +58,58 @@ template <> __device__ __forceinline__ void mfma16<__bf16>(f32x16& acc, const u3
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
 }
 
+// ---- f16x3: fp32 in memory, fp16 hi + lo operand rows in LDS -----------------------------------------------------------------
+// The third operand form of the ws / fr kernels (CCN_DTYPE_F16X3).  Everything on the global side is the fp32 form's (the tag is
+// four bytes wide on purpose: every sizeof(T) in the address math stays an fp32 element, and Vec16 / GnCoef are the fp32 ones);
+// what differs is the 128-byte LDS row of a pixel's (an output channel's) 32-channel Cin chunk: 32 fp16 "hi" then 32 fp16 "lo",
+// x ~= hi + lo to 22-23 bits.  Sixteen-byte unit u of the row (u = 0..3 hi, 4..7 lo; channels 8 (u & 3) .. + 7) sits at the fp32
+// form's swizzled position (u ^ (row >> 1)) & 7, so the consumers' fragment reads are those of the other forms: read kk = 0, 1 is
+// the hi fragment of K step kk (lane half h holds k = 8h .. 8h + 7 of v_mfma_f32_32x32x16_f16), read 2 + kk its lo fragment.
+struct f16x3_t { float v; };
+template <> struct Vec16<f16x3_t> : Vec16<float> {};
+template <typename T> struct OperandForm { static constexpr bool SPLIT = false; };
+template <> struct OperandForm<f16x3_t> { static constexpr bool SPLIT = true; };
+
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// One 16-byte unit of the fp32 form (four channels) -> the same 16 bytes as {hi[0..3], lo[0..3]}.
+// hi = RNE(x) (v_cvt_f16_f32), lo = RNE(x - hi) (the subtraction is exact).  |x| >= 65520 would round to inf: hi saturates to the
+// largest finite fp16 and `ovf` is raised (-> bit 2 of the handle's error word); a NaN is flagged and staged as a finite value too.
+__device__ __forceinline__ u32x4 split_pack(const u32x4& o, unsigned& ovf)
+{
+    f16x4 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float x = __uint_as_float(o[e]);
+        if (!(fabsf(x) < 65520.0f)) ovf = 1u;
+        const float c = fminf(fmaxf(x, -65504.0f), 65504.0f);
+        const _Float16 hv = (_Float16)c;
+        hi[e] = hv;
+        lo[e] = (_Float16)(c - (float)hv);
+    }
+    const u32x2 h2 = __builtin_bit_cast(u32x2, hi), l2 = __builtin_bit_cast(u32x2, lo);
+    return u32x4{h2.x, h2.y, l2.x, l2.y};
+}
+// ... and into the row of its pixel (`row` = the row's first byte, sw = row index >> 1) as two 8-byte writes: channels 4 ck .. 4 ck + 3
+__device__ __forceinline__ void split_store(unsigned char* row, int sw, int ck, const u32x4& p)
+{
+    const int half = (ck & 1) << 3, u = ck >> 1;
+    *(u32x2*)(row + (((u ^ sw) & 7) << 4) + half) = u32x2{p.x, p.y};
+    *(u32x2*)(row + ((((u | 4) ^ sw) & 7) << 4) + half) = u32x2{p.z, p.w};
+}
+__device__ __forceinline__ void split_put(unsigned char* row, int sw, int ck, const u32x4& o, unsigned& ovf)
+{
+    split_store(row, sw, ck, split_pack(o, ovf));
+}
+
+// one v_mfma_f32_32x32x16_f16 on two fp16 fragments of a split row
+__device__ __forceinline__ void mfma_f16(f32x16& acc, const u32x4& a, const u32x4& b)
+{
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+}
+
 // v_mfma_f32_16x16x32_bf16 on quarter q (registers 4q .. 4q+3) of a 16-register accumulator tuple
 typedef float f32x4q __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void mfma16q(f32x16& acc, const int q, const u32x4& a, const u32x4& b) {
@@ -96,6 +148,7 @@ template <> struct GnCoef<float> {
         return Vec16<float>::pack(v);
     }
 };
+template <> struct GnCoef<f16x3_t> : GnCoef<float> {};     // f16x3: the parity mode's transform, bit for bit
 // NO packed-fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) here or anywhere in a producer wave: next to a
 // wave that streams MFMAs they are starved outright -- tools/ubench/dump_vs_mfma.hip: this transform goes from 150 to
 // >2300 cycles per 16 bytes as soon as one v_pk_mul_f32 is in it, while v_fma_f32 / v_mul_f32 / v_exp_f32 lose ~25 %.

@@ -139,12 +139,16 @@ struct ConvArgs {
     int ksplit;             // persistent kernel: 2 = split the Cin chunks over two workgroups per tile (small layers), else 1
     void* kpart;            // split-K: bf16 partial tensor, laid out like `out`
     unsigned* kflag;        // split-K: [tiles][4] hand-off flags, zero between launches
-    unsigned* err;          // device-visible error word of the handle (pinned host memory): bit 0 = a split-K hand-off timed out; or null
+    unsigned* err;          // device-visible error word of the handle (pinned host memory): bit 0 = a split-K hand-off timed out,
+                            // bit 2 = an activation left the fp16 range of an f16x3 operand row; or null
     int n_ty, n_tx, n_nt, nchunk, ntaps;
     int silu;               // SiLU after the prologue GroupNorm
     int cpg, G, nslot;      // output GroupNorm geometry
     // per tap: bits 0-1 = dy+1, bits 2-3 = dx+1, bits 4.. = weight tap index; convT: entry [parity*4 + tap]
     int tapinfo[16];
+    // (last, so that no other field moves)
+    int ops;                // operand form of the ws / fr kernels: 0 = the storage type's, 1 = f16x3 (fp32 storage, `w` in split rows)
+    float wscale_inv;       // f16x3: 1 / (power-of-two scale of the packed weights), applied to the accumulator before the bias
     __host__ __device__ int tapinfo_dy(int i) const { return (tapinfo[i] & 3) - 1; }
     __host__ __device__ int tapinfo_dx(int i) const { return ((tapinfo[i] >> 2) & 3) - 1; }
     __host__ __device__ int tapinfo_w(int i) const { return tapinfo[i] >> 4; }

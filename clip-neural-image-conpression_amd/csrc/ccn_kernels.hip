@@ -538,6 +538,7 @@ hipError_t launch_conv(int dtype, int kind, int bn, const ConvArgs& a, hipStream
     const ConvKernel k = conv_kernel_for(kind, bn, a);
     if (k == CK_STEM2) return launch_stem2(a, s);
     if (k == CK_PR && kind == KIND_C3S2) return launch_conv_pr(dtype, a, s);
+    if (a.ops && k != CK_WS && k != CK_FR) return hipErrorInvalidValue;      // split weight rows: those two kernels only
     if (k != CK_IGEMM) {
         static const int dbg = diag_env("CCN_DBG") ? atoi(diag_env("CCN_DBG")) : 0;
         ConvArgs d = a; d.dbg = dbg;

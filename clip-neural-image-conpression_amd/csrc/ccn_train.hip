@@ -886,6 +886,7 @@ int ccn_train_create(const ccn_config_t* cfg, ccn_trainer_t* out)
     if (!cfg || !out) return tfail(CCN_EINVAL, "null argument");
     if (cfg->n_mult <= 0 || cfg->n_mult > CCN_MAX_MULT || cfg->base <= 0 || cfg->time_dim <= 0 || cfg->z_dim <= 0 || cfg->img_ch <= 0 || cfg->img_ch > 3)
         return tfail(CCN_EINVAL, "bad config");
+    if (cfg->dtype == CCN_DTYPE_F16X3) return tfail(CCN_EINVAL, "training supports CCN_DTYPE_F32 (fp32) and CCN_DTYPE_BF16 (bf16); f16x3 is an inference mode");
     if (cfg->dtype != CCN_DTYPE_F32 && cfg->dtype != CCN_DTYPE_BF16) return tfail(CCN_EINVAL, "bad dtype");
     if (cfg->base % 8) return tfail(CCN_EINVAL, "training path needs base % 8 == 0");
     int ndev = 0;

@@ -1,6 +1,6 @@
 // Epilogue of the 8-wave kernels, run by all 512 threads after their loops: fp32 tile in LDS -> bias / FiLM / residual -> 16-byte
 // NHWC rows, with the running sums for the next GroupNorm.  Thread (o, ps) owns the 8 output channels nb .. nb + 7 of the pixels
-// ps, ps + PSL, ... of every 128-pixel pass.  Expects: decode.inc, E = EpiLds<TH, BN, 8>, T, EPC, smem, tid.
+// ps, ps + PSL, ... of every 128-pixel pass.  Expects: decode.inc, E = EpiLds<TH, BN, 8>, T, EPC, SPLIT, smem, tid.
 // Defines: Cs, CP, NOCT, PSL, NIT, NPASS, o, ps, nb, nvalid, f1, f2, s1, s2, outb, resb, epi_init(), epi_all().
 //
 // NOT for the 4-wave kernel (ccn_kernels.hip): that one computes fmaf(v + bias, f1, f2), this one folds the bias into the shift
@@ -61,6 +61,10 @@
                 const f32x4 c0 = *(const f32x4*)cs, c1 = *(const f32x4*)(cs + 4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { v[e] = c0[e]; v[4 + e] = c1[e]; }
+                if constexpr (SPLIT) {                    // f16x3: undo the weights' power-of-two scale (exact), before the bias
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] *= a.wscale_inv;
+                }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = fmaf(v[e], f1[e], f2[e]);
                 if (resb) {

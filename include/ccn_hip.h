@@ -36,6 +36,11 @@ extern "C" {
 
 #define CCN_DTYPE_F32     0   /* fp32 storage, fp32 MFMA (v_mfma_f32_32x32x2_f32): parity mode        */
 #define CCN_DTYPE_BF16    1   /* bf16 storage, bf16 MFMA (v_mfma_f32_16x16x32_bf16 / 32x32x16), fp32 accumulate */
+#define CCN_DTYPE_F16X3   2   /* fp32 storage; conv operands split into fp16 hi + lo, three v_mfma_f32_32x32x16_f16 per product,
+                                 fp32 accumulate: fp32-grade results from the fast MFMAs.  Inference only (ccn_train_create rejects
+                                 it); ccn_set_weight_rounding has no effect.  Activations must stay below 65520 in magnitude where a
+                                 ResBlock conv or ConvTranspose reads them: beyond that the operand saturates and the next call /
+                                 ccn_poll_errors fails once, naming fp32 as the mode to use. */
 
 #define CCN_MAX_MULT      8
 
