@@ -71,6 +71,9 @@ SIGNATURES = {
     "ccn_diffusion_loss_grad": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "ccn_adamw_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp]),
     "ccn_adamw_step_zero_grad": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp]),
+    "ccn_step_guard_init": (c_i32, [c_vp, c_f32, c_i32, c_i32, c_i32, c_vp]),
+    "ccn_grad_guard": (c_i32, [c_vp, c_i64, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp]),
+    "ccn_adamw_step_guarded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp]),
     "ccn_last_error": (ctypes.c_char_p, []),
     "ccn_version": (ctypes.c_char_p, []),
 }
@@ -468,6 +471,61 @@ def adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
         fn = lib.ccn_adamw_step_zero_grad if zero_grad else lib.ccn_adamw_step
         check(fn(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(beta1),
                  float(beta2), float(eps), float(weight_decay), int(step), current_stream(p.device)))
+
+
+# ---- step guard (ccn_step_guard_t of include/ccn_hip.h, viewed as 16 int32 words; words 0-5 are fp32) -----------------------------
+class StepGuardBlock(ctypes.Structure):
+    _fields_ = [("scale", c_f32), ("inv_scale", c_f32), ("grad_norm", c_f32), ("grad_mul", c_f32), ("bc1", c_f32), ("bc2_sqrt", c_f32),
+                ("apply", c_i32), ("good_steps", c_i32), ("skipped_steps", c_i32), ("growth_tracker", c_i32), ("reserved", c_i32 * 6)]
+
+
+GUARD_WORDS = ctypes.sizeof(StepGuardBlock) // 4
+GUARD_WORD = {name: getattr(StepGuardBlock, name).offset // 4 for name, _ in StepGuardBlock._fields_}
+GUARD_SCRATCH_FLOATS = 4096
+
+
+def _guard_block(block: torch.Tensor) -> torch.Tensor:
+    if not (isinstance(block, torch.Tensor) and block.is_cuda and block.dtype == torch.int32 and block.is_contiguous()
+            and block.numel() == GUARD_WORDS):
+        raise ValueError(f"the guard block must be a contiguous int32 HIP tensor of {GUARD_WORDS} words")
+    return block
+
+
+def step_guard_init(block: torch.Tensor, init_scale: float, growth_tracker: int = 0, good_steps: int = 0, skipped_steps: int = 0) -> None:
+    """Write the whole control block (GradScaler(init_scale), or its load_state_dict): one small launch, no sync."""
+    lib = load_library()
+    _guard_block(block)
+    with torch.cuda.device(block.device):
+        check(lib.ccn_step_guard_init(block.data_ptr(), float(init_scale), int(growth_tracker), int(good_steps), int(skipped_steps),
+                                      current_stream(block.device)))
+
+
+def grad_guard(g: torch.Tensor, block: torch.Tensor, scratch: torch.Tensor, max_grad_norm: float, beta1: float, beta2: float,
+               growth_factor: float, backoff_factor: float, growth_interval: int) -> None:
+    """scaler.step's decision + scaler.update() for the flat gradient buffer ``g`` (train/diffusion_train.py:138-139), left in ``block``."""
+    lib = load_library()
+    _guard_block(block)
+    if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous()):
+        raise ValueError("grads must be a contiguous fp32 HIP tensor")
+    if not (scratch.is_cuda and scratch.dtype == torch.float32 and scratch.numel() >= GUARD_SCRATCH_FLOATS):
+        raise ValueError(f"scratch must be an fp32 HIP tensor of at least {GUARD_SCRATCH_FLOATS} floats")
+    with torch.cuda.device(g.device):
+        check(lib.ccn_grad_guard(g.data_ptr(), g.numel(), block.data_ptr(), float(max_grad_norm), float(beta1), float(beta2),
+                                 float(growth_factor), float(backoff_factor), int(growth_interval), scratch.data_ptr(),
+                                 current_stream(g.device)))
+
+
+def adamw_step_guarded(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float, beta1: float, beta2: float,
+                       eps: float, weight_decay: float, block: torch.Tensor) -> None:
+    """The AdamW update under ``block``'s decision; the gradients are left at zero whether the step is applied or skipped."""
+    lib = load_library()
+    _guard_block(block)
+    for name, tns in (("params", p), ("grads", g), ("exp_avg", m), ("exp_avg_sq", v)):
+        if not (tns.is_cuda and tns.dtype == torch.float32 and tns.is_contiguous() and tns.numel() == p.numel()):
+            raise ValueError(f"{name} must be a contiguous fp32 HIP tensor of {p.numel()} elements")
+    with torch.cuda.device(p.device):
+        check(lib.ccn_adamw_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(beta1),
+                                         float(beta2), float(eps), float(weight_decay), block.data_ptr(), current_stream(p.device)))
 
 
 # ---- stateless ops --------------------------------------------------------------------------------

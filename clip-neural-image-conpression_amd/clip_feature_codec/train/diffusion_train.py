@@ -16,8 +16,13 @@ The reference's default objective adds two terms on ``x0_pred = predict_x0_from_
 ``recon_w * l1(x0_pred, x0) + tv_w * total_variation(x0_pred)``.  ``train_step(..., recon_w=, tv_w=)`` evaluates them and their
 gradient in the same single pass as the MSE (``ccn_diffusion_loss_grad``), and ``train_diffusion`` runs its batches through it.
 Still not provided: the CLIP-alignment term (``clip_w``, :129-136), which needs ``open_clip`` with downloaded weights
-(SURVEY.md section 8, row a18), and ``GradScaler`` (:137-139), which under bf16 changes nothing but the skipped step on
-non-finite gradients.
+(SURVEY.md section 8, row a18).
+
+The reference's ``scaler.scale(loss).backward(); scaler.step(opt); scaler.update()`` (:137-139) runs with this module's ``GradScaler``
+and ``FusedAdamW``: the loss scale, the skipped step on a non-finite gradient, the scale update and (optionally) gradient-norm
+clipping are decided on the device by one extra read of the flat gradient buffer (``ccn_grad_guard``), and the guarded AdamW
+kernel only reads that decision -- no host sync.  ``train_step(..., scaler=, max_grad_norm=)`` and
+``train_diffusion(..., grad_scaler=, max_grad_norm=)`` use it; everything is off by default.
 
 With ``torch.distributed`` initialised, ``train_step(..., ddp=True)`` averages the flat gradient buffer over the ranks
 with one all-reduce (RCCL over xGMI on a GPU node): the data-parallel step of BASELINE.json configs[4].
@@ -217,10 +222,51 @@ class FusedAdamW:
         self.exp_avg = torch.zeros_like(fp.flat)
         self.exp_avg_sq = torch.zeros_like(fp.flat)
         self.steps = 0
+        self._guard: Optional["GradScaler"] = None      # the guard of the last guarded step: its block holds the step count from then on
+        self._clip_guard: Optional["GradScaler"] = None
 
-    def step(self, zero_grad: bool = False) -> None:
-        """``zero_grad=True``: ``step()`` + ``zero_grad()`` as one pass over the buffers (``ccn_adamw_step_zero_grad``)."""
+    def clip_guard(self) -> "GradScaler":
+        """The internal guard of ``max_grad_norm`` without a scaler: scale 1, never grows, never backs off."""
+        if self._clip_guard is None:
+            self._clip_guard = GradScaler(init_scale=1.0, growth_factor=1.0, backoff_factor=1.0, growth_interval=2 ** 31 - 1)
+        return self._clip_guard
+
+    def step(self, zero_grad: bool = False, guard: Optional["GradScaler"] = None, max_grad_norm: Optional[float] = None) -> None:
+        """``zero_grad=True``: ``step()`` + ``zero_grad()`` as one pass over the buffers (``ccn_adamw_step_zero_grad``).
+
+        ``guard`` (a ``GradScaler``) and / or ``max_grad_norm`` > 0: the guarded step (train/diffusion_train.py:138-139).  The
+        gradient buffer holds ``d (scale * loss)``; ``ccn_grad_guard`` reads it once and decides on the device whether the step is
+        applied, then ``ccn_adamw_step_guarded`` applies ``g / scale * clip_coef`` or leaves parameters and moments untouched.  A
+        guarded step always consumes the gradients and leaves the buffer at zero.  AdamW's step count then lives in the guard's
+        control block (it advances on applied steps only); the first guarded step seeds it with the larger of ``self.steps`` and the
+        count the guard already holds (a ``GradScaler`` restored with ``load_state_dict`` resumes its run's count), and an unguarded
+        ``step()`` afterwards raises, because the host-side count would be wrong."""
         fp = self.state.fp
+        if guard is not None and not guard.enabled:
+            guard = None
+        if guard is None and max_grad_norm is not None and max_grad_norm > 0:
+            guard = self.clip_guard()
+        if guard is not None:
+            block = guard.block(fp.flat.device)
+            if self._guard is not guard:             # seed the count of applied steps, on the device
+                word = block[_native.GUARD_WORD["good_steps"]]
+                if self._guard is None:
+                    # the larger of this optimiser's count and the block's: a GradScaler restored with load_state_dict carries the
+                    # count of a resumed run (FusedAdamW has no state_dict of its own), a fresh one holds 0
+                    word.clamp_(min=self.steps)
+                else:
+                    word.copy_(self._guard.block(fp.flat.device)[_native.GUARD_WORD["good_steps"]])
+                self._guard = guard
+            _native.grad_guard(fp.grad, block, guard.scratch, max_grad_norm if max_grad_norm is not None else 0.0, self.betas[0],
+                               self.betas[1], guard.growth_factor, guard.backoff_factor, guard.growth_interval)
+            _native.adamw_step_guarded(fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
+                                       self.weight_decay, block)
+            fp.flat[:1].add_(0)
+            fp.rebind_grads()
+            return
+        if self._guard is not None:
+            raise RuntimeError("an unguarded step() after a guarded one: the count of applied steps lives in the guard's control block "
+                               "(skipped steps do not advance it), keep passing guard= / max_grad_norm=")
         self.steps += 1
         _native.adamw_step(fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
                            self.weight_decay, self.steps, zero_grad=zero_grad)
@@ -231,6 +277,99 @@ class FusedAdamW:
     def zero_grad(self, set_to_none: bool = False) -> None:
         self.state.fp.grad.zero_()
         self.state.fp.rebind_grads()
+
+
+class GradScaler:
+    """``torch.amp.GradScaler`` for ``FusedAdamW`` (train/diffusion_train.py:106,137-139), with its state in device memory.
+
+    ``scaler.scale(loss).backward(); scaler.step(opt); scaler.update()`` run unchanged.  ``step`` launches ``ccn_grad_guard`` (one read
+    of the flat gradient buffer: any non-finite element skips the step and multiplies the scale by ``backoff_factor``; after
+    ``growth_interval`` applied steps in a row the scale is multiplied by ``growth_factor``) and the guarded AdamW kernel; the host
+    never learns the decision, so nothing synchronises.  ``update()`` is a no-op: the guard kernel has already updated the scale.
+    ``step(opt, max_grad_norm=)`` also clips the unscaled gradient's L2 norm, as ``unscale_`` + ``clip_grad_norm_`` would.  The
+    gradients stay scaled in the buffer until the step consumes and zeroes them; read the unscaled norm from ``stats()``.
+    ``get_scale()``, ``state_dict()`` are host reads (they synchronise)."""
+
+    def __init__(self, init_scale: float = 65536.0, growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000,
+                 enabled: bool = True) -> None:
+        if not (init_scale > 0 and growth_factor > 0 and backoff_factor > 0 and growth_interval >= 1):
+            raise ValueError("init_scale, growth_factor, backoff_factor must be positive and growth_interval at least 1")
+        self.growth_factor, self.backoff_factor, self.growth_interval, self.enabled = float(growth_factor), float(backoff_factor), int(growth_interval), bool(enabled)
+        self._init = dict(scale=float(init_scale), _growth_tracker=0, good_steps=0, skipped_steps=0)
+        self._block: Optional[torch.Tensor] = None
+        self.scratch: Optional[torch.Tensor] = None
+
+    def block(self, device) -> torch.Tensor:
+        """The control block (``ccn_step_guard_t``) as 16 int32 words on ``device``; created and initialised on first use."""
+        if self._block is None:
+            device = torch.device(device)
+            if device.type != "cuda":
+                raise RuntimeError(f"the step guard lives on a HIP device, not on {device}")
+            self._block = torch.zeros(_native.GUARD_WORDS, dtype=torch.int32, device=device)
+            self.scratch = torch.empty(_native.GUARD_SCRATCH_FLOATS, dtype=torch.float32, device=device)
+            i = self._init
+            _native.step_guard_init(self._block, i["scale"], i["_growth_tracker"], i["good_steps"], i["skipped_steps"])
+        elif self._block.device != torch.device(device):
+            raise RuntimeError(f"this GradScaler lives on {self._block.device}, not on {device}")
+        return self._block
+
+    def _word(self, name: str, device=None) -> torch.Tensor:
+        blk = self.block(device if device is not None else self._block.device)
+        k = _native.GUARD_WORD[name]
+        return (blk.view(torch.float32) if k < 6 else blk)[k]
+
+    def scale_tensor(self, device) -> torch.Tensor:
+        """The device-resident loss scale, a 0-dim fp32 view of the control block."""
+        return self._word("scale", device)
+
+    def scale(self, loss: torch.Tensor) -> torch.Tensor:
+        return loss * self.scale_tensor(loss.device) if self.enabled else loss
+
+    def step(self, opt, max_grad_norm: Optional[float] = None) -> None:
+        if not isinstance(opt, FusedAdamW):
+            raise TypeError(f"this GradScaler drives FusedAdamW (the flat-buffer optimiser), not {type(opt).__name__}: "
+                            "use torch.amp.GradScaler with a torch.optim optimiser")
+        opt.state.wait_grad_sync()                  # the guard must see the all-reduced gradients
+        opt.step(zero_grad=True, guard=self, max_grad_norm=max_grad_norm)
+
+    def update(self) -> None:
+        """No-op: ``ccn_grad_guard`` updated the scale and the growth tracker when it took the decision."""
+
+    def stats(self) -> Dict[str, torch.Tensor]:
+        """0-dim views of the control block, no sync: the last step's unscaled ``grad_norm`` and ``applied`` (0 / 1), the current
+        ``scale`` and the counts of applied (``good_steps``) and ``skipped_steps``."""
+        if self._block is None:
+            raise RuntimeError("no step has run yet")
+        return dict(grad_norm=self._word("grad_norm"), applied=self._word("apply"), scale=self._word("scale"),
+                    good_steps=self._word("good_steps"), skipped_steps=self._word("skipped_steps"))
+
+    def get_scale(self) -> float:
+        """The current scale -- a host read (synchronises)."""
+        if not self.enabled:
+            return 1.0
+        return float(self._word("scale")) if self._block is not None else self._init["scale"]
+
+    def state_dict(self) -> dict:
+        """torch's keys plus the counts of applied / skipped steps -- a host read (synchronises)."""
+        if self._block is None:
+            st = dict(self._init)
+        else:
+            w = self._block.tolist()                # the one host read; the scale's bits are decoded on the host
+            st = dict(scale=torch.tensor(w[_native.GUARD_WORD["scale"]], dtype=torch.int32).view(torch.float32).item(),
+                      _growth_tracker=w[_native.GUARD_WORD["growth_tracker"]], good_steps=w[_native.GUARD_WORD["good_steps"]],
+                      skipped_steps=w[_native.GUARD_WORD["skipped_steps"]])
+        st.update(growth_factor=self.growth_factor, backoff_factor=self.backoff_factor, growth_interval=self.growth_interval)
+        return st
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.growth_factor = float(sd.get("growth_factor", self.growth_factor))
+        self.backoff_factor = float(sd.get("backoff_factor", self.backoff_factor))
+        self.growth_interval = int(sd.get("growth_interval", self.growth_interval))
+        self._init = dict(scale=float(sd["scale"]), _growth_tracker=int(sd.get("_growth_tracker", 0)), good_steps=int(sd.get("good_steps", 0)),
+                          skipped_steps=int(sd.get("skipped_steps", 0)))
+        if self._block is not None:
+            i = self._init
+            _native.step_guard_init(self._block, i["scale"], i["_growth_tracker"], i["good_steps"], i["skipped_steps"])
 
 
 def average_gradients(flat_grad: torch.Tensor) -> torch.Tensor:
@@ -245,13 +384,21 @@ def average_gradients(flat_grad: torch.Tensor) -> torch.Tensor:
 
 def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[torch.Tensor] = None,
                noise: Optional[torch.Tensor] = None, ddp=False, graph: bool = False, recon_w: float = 0.0,
-               tv_w: float = 0.0) -> torch.Tensor:
+               tv_w: float = 0.0, scaler: Optional[GradScaler] = None, max_grad_norm: Optional[float] = None) -> torch.Tensor:
     """One optimisation step; returns the (detached) loss.  ``t`` / ``noise`` default to the reference's draws.
 
     ``recon_w`` / ``tv_w`` (the reference's ``train_diffusion`` defaults are 0.05 and 1e-4): the loss becomes
     ``mse + recon_w * l1(x0_pred, x0) + tv_w * total_variation(x0_pred)`` with ``x0_pred = predict_x0_from_eps(...).clamp(-1, 1)``
     (train/diffusion_train.py:124-128), evaluated with its gradient by one kernel on the static buffers; the four terms are then
     in ``net.train_state().last_loss_terms``.  With both 0 (the default) the step is the epsilon-MSE step, launch for launch.
+
+    ``scaler`` (this module's ``GradScaler``; the reference trains with one, train/diffusion_train.py:106,137-139) and / or
+    ``max_grad_norm`` > 0, with a ``FusedAdamW``: ``d_eps`` is multiplied by the device-resident loss scale before the backward, and
+    after the gradient all-reduces the step runs guarded -- skipped (parameters and moments untouched, scale halved) when any
+    gradient element is non-finite, the unscaled gradient clipped to ``max_grad_norm`` otherwise.  Under data parallelism no extra
+    collective is needed: a non-finite element survives the all-reduce on every rank, so all ranks decide alike.  The returned
+    loss is the unscaled one.  With ``scaler=None`` (or a disabled one) and no ``max_grad_norm`` the step is what it was, launch
+    for launch.
 
     All tensors the library touches live at fixed addresses (``TrainState.static_buffers``), so with ``graph=True`` the forward and
     the backward are replayed as captured hipGraphs after the first step of a shape -- measured SLOWER than plain stream launches
@@ -260,6 +407,10 @@ def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[tor
     state: TrainState = net.train_state()
     fp = state.fp
     fp.rebind_grads()
+    guard = scaler if scaler is not None and scaler.enabled else None
+    clip = max_grad_norm is not None and max_grad_norm > 0
+    if (guard is not None or clip) and not isinstance(opt, FusedAdamW):
+        raise TypeError("scaler= / max_grad_norm= need a FusedAdamW: drive a torch.optim optimiser with torch.amp.GradScaler")
     sb = state.static_buffers(_native.require_dev(x0, "x0"), _native.require_dev(z, "z"))
     sb["x0"].copy_(x0); sb["z"].copy_(z)
     if t is None:
@@ -297,15 +448,25 @@ def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[tor
     if world > 1 or (have_pg and ddp == "always"):
         # data parallel: the flat gradient buffer is all-reduced bucket by bucket while the backward still runs (RCCL on its own
         # stream); d_eps is pre-scaled by 1 / world so that the sum is already the mean
-        d_eps.mul_(1.0 / world)
+        if guard is None:
+            d_eps.mul_(1.0 / world)
+        else:
+            # scale / world into a static one-element buffer (a one-element launch, no allocation), then ONE pass over d_eps
+            factor = sb.setdefault("scale_over_world", torch.empty((), dtype=torch.float32, device=d_eps.device))
+            torch.mul(guard.scale_tensor(d_eps.device), 1.0 / world, out=factor)
+            d_eps.mul_(factor)
         works = []
         state.trainer.backward(fp.flat, fp.grad, sb["x_t"], sb["z"], d_eps,
                                bucket_cb=lambda lo, hi: works.append(dist.all_reduce(fp.grad[lo:hi], async_op=True)))
         for w in works:
             w.wait()
     else:
+        if guard is not None:
+            d_eps.mul_(guard.scale_tensor(d_eps.device))
         state.trainer.backward(fp.flat, fp.grad, sb["x_t"], sb["z"], d_eps)
-    if isinstance(opt, FusedAdamW):
+    if guard is not None or clip:
+        opt.step(zero_grad=True, guard=guard, max_grad_norm=max_grad_norm)
+    elif isinstance(opt, FusedAdamW):
         opt.step(zero_grad=True)
     else:
         opt.step()
@@ -348,10 +509,12 @@ def total_variation(x: torch.Tensor) -> torch.Tensor:
 
 
 def autograd_objective_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: torch.Tensor, noise: torch.Tensor,
-                            recon_w: float = 0.0, tv_w: float = 0.0) -> torch.Tensor:
+                            recon_w: float = 0.0, tv_w: float = 0.0, scaler: Optional[GradScaler] = None,
+                            max_grad_norm: Optional[float] = None) -> torch.Tensor:
     """The loop body of train/diffusion_train.py:119-128,137-140 through autograd: the objective from torch ops on (B, 3, S, S), the
     library's forward and backward behind ``UNetFunction``, ``opt.step()`` and ``opt.zero_grad()`` as two passes.  What
-    ``train_step(recon_w=, tv_w=)`` fuses; kept as ``train_diffusion(fused_objective=False)`` and for A/B (tools/objective_ab.py)."""
+    ``train_step(recon_w=, tv_w=)`` fuses; kept as ``train_diffusion(fused_objective=False)`` and for A/B (tools/objective_ab.py).
+    With ``scaler`` the last lines are the reference's ``scaler.scale(loss).backward(); scaler.step(opt); scaler.update()``."""
     import torch.nn.functional as F
     state: TrainState = net.train_state()
     state.fp.rebind_grads()
@@ -366,8 +529,16 @@ def autograd_objective_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t:
             loss = loss + recon_w * F.l1_loss(x0_pred, x0)
         if tv_w > 0:
             loss = loss + tv_w * total_variation(x0_pred)
+    if scaler is not None and scaler.enabled:
+        scaler.scale(loss).backward()
+        scaler.step(opt, max_grad_norm=max_grad_norm)
+        scaler.update()
+        return loss.detach()                        # the guarded step left the gradient buffer at zero: no second pass over it
     loss.backward()
     state.wait_grad_sync()
+    if max_grad_norm is not None and max_grad_norm > 0:
+        opt.step(max_grad_norm=max_grad_norm)       # guarded (scale 1): consumes and zeroes the gradients as well
+        return loss.detach()
     opt.step()
     opt.zero_grad()
     return loss.detach()
@@ -376,7 +547,7 @@ def autograd_objective_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t:
 def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size: int = 8, lr: float = 2e-4, timesteps: int = 1000,
                     schedule: str = "cosine", recon_w: float = 0.05, clip_w: float = 0.1, tv_w: float = 1e-4, device: str = "cuda",
                     save_dir=None, base: int = 128, ch_mult=(1, 2, 2), dtype: str = "bf16", num_workers: int = 2, log=print,
-                    fused_objective: bool = True):
+                    fused_objective: bool = True, grad_scaler: bool = False, max_grad_norm: Optional[float] = None):
     """The reference's ``train_diffusion`` (same arguments, defaults, checkpoint names and log line) on the MI355X kernels.
 
     Per batch (train/diffusion_train.py:115-140): t ~ U{0..T-1}, noise ~ N, then ``train_step`` with the ``t`` / ``noise`` drawn here:
@@ -384,8 +555,11 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
     gradient from one kernel, the library's backward, the fused AdamW step.  The running loss is accumulated on the device and read
     once per epoch.  ``fused_objective=False`` keeps the earlier route for A/B: the same objective from torch ops on (B, 3, S, S)
     through autograd (``UNetFunction``), the loss read back every batch.  The CLIP-alignment term (clip_w, :129-136) needs
-    ``open_clip`` with downloaded weights: it is skipped with a note; ``GradScaler`` (:137-139) is not
-    reproduced.  Additions that default to the reference's behaviour: ``base`` / ``ch_mult`` / ``dtype``.  With
+    ``open_clip`` with downloaded weights: it is skipped with a note.  ``grad_scaler=True`` is the reference's
+    setting (its ``GradScaler``, :106,137-139): loss scaling with the skipped step on non-finite gradients, decided on the device
+    (``GradScaler`` above); it is off by default here because the fp32 gradient buffer does not need the scale, only the guard.
+    ``max_grad_norm`` > 0 clips the gradient's L2 norm in the same pass.  The number of skipped steps is logged per epoch, from the
+    same host read as the loss.  Additions that default to the reference's behaviour: ``base`` / ``ch_mult`` / ``dtype``.  With
     ``torch.distributed`` initialised the records are sharded over the ranks and the flat gradient buffer is all-reduced bucket
     by bucket while the backward runs.
     """
@@ -411,6 +585,8 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
     # data parallel: finished ranges of the flat gradient buffer are all-reduced (RCCL) while the backward still runs
     state.ddp_bucketed = ddp
     opt = FusedAdamW(net, lr=lr)
+    scaler = GradScaler() if grad_scaler else None
+    skipped_before = 0
     if clip_w > 0:
         try:
             import open_clip  # noqa: F401
@@ -430,16 +606,28 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
             t = torch.randint(0, timesteps, (b,), device=device, dtype=torch.long)
             noise = torch.randn_like(x0)
             if fused_objective:
-                loss = train_step(net, sch, opt, x0, z, t=t, noise=noise, ddp=ddp, recon_w=max(recon_w, 0.0), tv_w=max(tv_w, 0.0))
+                loss = train_step(net, sch, opt, x0, z, t=t, noise=noise, ddp=ddp, recon_w=max(recon_w, 0.0), tv_w=max(tv_w, 0.0),
+                                  scaler=scaler, max_grad_norm=max_grad_norm)
                 running_dev += loss.double() * b          # the loss is a view of a static buffer: consumed here, in stream order
             else:
-                running += float(autograd_objective_step(net, sch, opt, x0, z, t, noise, recon_w, tv_w)) * b
+                running += float(autograd_objective_step(net, sch, opt, x0, z, t, noise, recon_w, tv_w, scaler=scaler,
+                                                                 max_grad_norm=max_grad_norm)) * b
             seen += b
-        if fused_objective:
+        skipped, loss_scale = 0, 1.0
+        if opt._guard is not None:                        # the one host read of the epoch carries the guard's counters too
+            st = opt._guard.stats()
+            got = torch.stack([running_dev, st["skipped_steps"].double(), st["scale"].double()]).tolist()
+            skipped, loss_scale = int(got[1]) - skipped_before, got[2]
+            skipped_before = int(got[1])
+            if fused_objective:
+                running = got[0]
+        elif fused_objective:
             running = float(running_dev)                  # the one host read of the epoch
         if rank0:
             torch.save(net.state_dict(), save_dir / f"diffusion_unet_ep{ep + 1}.pt")
             log(f"[train] epoch {ep + 1}/{epochs} loss={running / max(seen, 1):.4f}")
+            if skipped:
+                log(f"[train] epoch {ep + 1}/{epochs}: {skipped} step(s) skipped on non-finite gradients, loss scale now {loss_scale:g}")
     if rank0:
         torch.save(net.state_dict(), final_path)
     return final_path

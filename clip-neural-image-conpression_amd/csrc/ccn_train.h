@@ -109,5 +109,13 @@ hipError_t launch_diffusion_loss_grad(const float* eps, const float* noise, cons
 // torch.optim.AdamW step (train/diffusion_train.py:105,138): decoupled weight decay, bias-corrected moments
 hipError_t launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
                         int step, hipStream_t s, bool zero_grad = false);
+// the step guard of train/diffusion_train.py:137-139 (GradScaler + clip_grad_norm_); `guard` is a ccn_step_guard_t in device memory
+// (include/ccn_hip.h).  scratch >= GUARD_MAX_WG doubles.
+constexpr int GUARD_MAX_WG = 2048;
+hipError_t launch_step_guard_init(void* guard, float scale, int tracker, int good, int skipped, hipStream_t s);
+hipError_t launch_grad_guard(const float* g, int64_t n, void* guard, float max_norm, float b1, float b2, float growth, float backoff,
+                             int interval, double* scratch, hipStream_t s);
+hipError_t launch_adamw_guarded(float* p, float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
+                                const void* guard, hipStream_t s);
 
 }  // namespace ccn

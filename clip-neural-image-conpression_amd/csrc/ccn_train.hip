@@ -1121,4 +1121,42 @@ int ccn_adamw_step_zero_grad(float* params_dev, float* grads_dev, float* exp_avg
     return CCN_OK;
 }
 
+int ccn_step_guard_init(void* guard_dev, float init_scale, int32_t growth_tracker0, int32_t good_steps0, int32_t skipped_steps0, void* stream)
+{
+    if (!guard_dev || ((uintptr_t)guard_dev & 3) != 0) return tfail(CCN_EINVAL, "guard_dev must be a 4-byte aligned device pointer");
+    if (!(init_scale > 0.f) || init_scale - init_scale != 0.f) return tfail(CCN_EINVAL, "init_scale must be positive and finite");
+    if (growth_tracker0 < 0 || good_steps0 < 0 || skipped_steps0 < 0) return tfail(CCN_EINVAL, "counters must be non-negative");
+    if (launch_step_guard_init(guard_dev, init_scale, growth_tracker0, good_steps0, skipped_steps0, (hipStream_t)stream) != hipSuccess)
+        return tfail(CCN_EHIP, "step guard init launch failed");
+    return CCN_OK;
+}
+
+int ccn_grad_guard(const float* grads_dev, int64_t n, void* guard_dev, float max_grad_norm, float beta1, float beta2, float growth_factor,
+                   float backoff_factor, int32_t growth_interval, float* scratch_dev, void* stream)
+{
+    if (!grads_dev || !guard_dev || !scratch_dev || n <= 0) return tfail(CCN_EINVAL, "bad argument");
+    if (((uintptr_t)grads_dev & 3) != 0 || ((uintptr_t)guard_dev & 3) != 0) return tfail(CCN_EINVAL, "grads_dev and guard_dev must be 4-byte aligned");
+    if (((uintptr_t)scratch_dev & 7) != 0) return tfail(CCN_EINVAL, "scratch_dev must be 8-byte aligned");
+    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return tfail(CCN_EINVAL, "betas must be in [0, 1)");
+    if (!(growth_factor > 0.f) || !(backoff_factor > 0.f) || growth_interval <= 0)
+        return tfail(CCN_EINVAL, "growth_factor, backoff_factor and growth_interval must be positive");
+    if (max_grad_norm != max_grad_norm) return tfail(CCN_EINVAL, "max_grad_norm is NaN");
+    if (launch_grad_guard(grads_dev, n, guard_dev, max_grad_norm, beta1, beta2, growth_factor, backoff_factor, growth_interval,
+                          (double*)scratch_dev, (hipStream_t)stream) != hipSuccess)
+        return tfail(CCN_EHIP, "grad guard launch failed");
+    return CCN_OK;
+}
+
+int ccn_adamw_step_guarded(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n, float lr, float beta1,
+                           float beta2, float eps, float weight_decay, const void* guard_dev, void* stream)
+{
+    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || !guard_dev || n <= 0) return tfail(CCN_EINVAL, "bad argument");
+    if ((((uintptr_t)params_dev | (uintptr_t)grads_dev | (uintptr_t)exp_avg_dev | (uintptr_t)exp_avg_sq_dev | (uintptr_t)guard_dev) & 3) != 0)
+        return tfail(CCN_EINVAL, "buffers must be 4-byte aligned");
+    if (launch_adamw_guarded(params_dev, grads_dev, exp_avg_dev, exp_avg_sq_dev, n, lr, beta1, beta2, eps, weight_decay, guard_dev,
+                             (hipStream_t)stream) != hipSuccess)
+        return tfail(CCN_EHIP, "guarded adamw launch failed");
+    return CCN_OK;
+}
+
 }  // extern "C"

@@ -13,8 +13,10 @@
 //   im2col27 / nchw_to_nhwc_pad   layout changes that let the stem / head weights use the same weight-gradient kernel.
 //   tlinear_*            conditioning MLP / FiLM linears, fp32.
 //   adamw_kernel, mse_loss_grad, objective_* (MSE + L1 + TV of the reference's default objective, one pass)
+//   grad_guard_* / adamw_guarded_kernel   GradScaler's skipped step and scale update, clip_grad_norm_, decided on the device
 #include "ccn_device.h"
 #include "ccn_train.h"
+#include "../../include/ccn_hip.h"
 #include <cstdlib>
 
 namespace ccn {
@@ -1654,6 +1656,191 @@ hipError_t launch_adamw(float* p, const float* g, float* m, float* v, int64_t n,
     const unsigned grid = (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
     if (zero_grad) hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid ? grid : 1), dim3(256), 0, s, p, (float*)g, m, v, n, lr, b1, b2, eps, wd, bc1, sqrtf(bc2));
     else hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid ? grid : 1), dim3(256), 0, s, p, (float*)g, m, v, n, lr, b1, b2, eps, wd, bc1, sqrtf(bc2));
+    return hipGetLastError();
+}
+
+// ---- the step guard: scaler.scale(loss).backward(); scaler.step(opt); scaler.update() (train/diffusion_train.py:137-139) ----------
+// The gradient buffer holds d (scale * loss).  One extra read of it decides the step on the device: grad_guard_partial_kernel sums
+// (g * inv_scale)^2 in fp64, grad_guard_final_kernel turns the sum into the decision and commits the scaler's state, and
+// adamw_guarded_kernel reads that decision.  fp64 cannot overflow on squares of fp32 values, so the sum is non-finite exactly when
+// an element is: no separate flag.  The flat range is walked as [head scalars][nvec 16-byte quads][tail scalars], head = floats up
+// to the first 16-byte boundary; workgroup 0's first threads take the head and the tail.
+__global__ void step_guard_init_kernel(ccn_step_guard_t* __restrict__ guard, float scale, int tracker, int good, int skipped)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    ccn_step_guard_t b{};
+    b.scale = scale; b.inv_scale = (float)(1.0 / (double)scale); b.grad_norm = 0.f; b.grad_mul = b.inv_scale; b.bc1 = 1.f; b.bc2_sqrt = 1.f;
+    b.apply = 0; b.good_steps = good; b.skipped_steps = skipped; b.growth_tracker = tracker;
+    *guard = b;
+}
+hipError_t launch_step_guard_init(void* guard, float scale, int tracker, int good, int skipped, hipStream_t s)
+{
+    hipLaunchKernelGGL(step_guard_init_kernel, dim3(1), dim3(64), 0, s, (ccn_step_guard_t*)guard, scale, tracker, good, skipped);
+    return hipGetLastError();
+}
+
+__device__ __forceinline__ double guard_sq(float g, float inv) { const float u = g * inv; return (double)u * (double)u; }
+
+__global__ __launch_bounds__(256) void grad_guard_partial_kernel(const float* __restrict__ g, int64_t n, int head, int64_t nvec,
+                                                                  const ccn_step_guard_t* __restrict__ guard, double* __restrict__ scratch)
+{
+    __shared__ double red[4];
+    const float inv = guard->inv_scale;
+    const f32x4* __restrict__ gv = (const f32x4*)(g + head);
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    double s = 0.0;
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (; i + 3 * stride < nvec; i += 4 * stride) {                 // four 16-byte loads in flight
+        f32x4 a[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a[u] = gv[i + u * stride];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s += guard_sq(a[u][e], inv);
+    }
+    for (; i < nvec; i += stride) {
+        const f32x4 a = gv[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s += guard_sq(a[e], inv);
+    }
+    if (blockIdx.x == 0) {
+        const int64_t tail0 = head + 4 * nvec;
+        const int t = (int)threadIdx.x;
+        if (t < head) s += guard_sq(g[t], inv);
+        else if (tail0 + (t - head) < n) s += guard_sq(g[tail0 + (t - head)], inv);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) scratch[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+// one wave, fixed order (mse_final_kernel's scheme); lane 0 then writes the decision and commits the state -- the AdamW kernel that
+// follows in stream order only reads the block
+__global__ void grad_guard_final_kernel(const double* __restrict__ scratch, int nb, ccn_step_guard_t* __restrict__ guard, float max_norm,
+                                        float b1, float b2, float growth, float backoff, int interval)
+{
+    if (blockIdx.x) return;
+    double s = 0.0;
+    for (int i = (int)threadIdx.x; i < nb; i += 64) s += scratch[i];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+    if (threadIdx.x) return;
+    ccn_step_guard_t b = *guard;
+    const bool ok = s - s == 0.0;                                     // finite (false for inf and NaN)
+    const float norm = (float)sqrt(s);
+    float coef = 1.0f;
+    if (ok && max_norm > 0.f) coef = fminf(1.0f, __fdiv_rn(max_norm, norm + 1e-6f));      // clip_grad_norm_'s clamped coefficient
+    const double step = (double)b.good_steps + 1.0;
+    b.apply = ok ? 1 : 0;
+    b.grad_norm = norm;
+    b.grad_mul = b.inv_scale * coef;
+    // launch_adamw's expressions, except that the powers are fp64 pow rounded to fp32 where the host calls powf: the two can differ
+    // by one fp32 ulp of the power
+    b.bc1 = 1.0f - (float)pow((double)b1, step);
+    b.bc2_sqrt = __fsqrt_rn(1.0f - (float)pow((double)b2, step));
+    if (ok) {
+        b.good_steps += 1;
+        if (++b.growth_tracker >= interval) {
+            const float grown = b.scale * growth;
+            if (grown - grown == 0.f) b.scale = grown;               // torch keeps the scale when growing would overflow
+            b.growth_tracker = 0;
+        }
+    } else {
+        b.skipped_steps += 1;
+        b.scale *= backoff;
+        b.growth_tracker = 0;
+    }
+    b.inv_scale = (float)(1.0 / (double)b.scale);
+    *guard = b;
+}
+hipError_t launch_grad_guard(const float* g, int64_t n, void* guard, float max_norm, float b1, float b2, float growth, float backoff,
+                             int interval, double* scratch, hipStream_t s)
+{
+    int64_t head = (int64_t)(((16 - ((uintptr_t)g & 15)) & 15) >> 2);
+    if (head > n) head = n;
+    const int64_t nvec = (n - head) / 4;
+    // the number of partials depends on n alone (not on the alignment): ceil(n / 4) quads, 256 per workgroup, at most GUARD_MAX_WG
+    const int64_t want = ((n + 3) / 4 + 255) / 256;
+    const int nb = (int)(want < GUARD_MAX_WG ? want : GUARD_MAX_WG);
+    hipLaunchKernelGGL(grad_guard_partial_kernel, dim3(nb), dim3(256), 0, s, g, n, (int)head, nvec, (const ccn_step_guard_t*)guard, scratch);
+    hipLaunchKernelGGL(grad_guard_final_kernel, dim3(1), dim3(64), 0, s, (const double*)scratch, nb, (ccn_step_guard_t*)guard, max_norm, b1, b2,
+                       growth, backoff, interval);
+    return hipGetLastError();
+}
+
+// adamw_kernel<true>'s arithmetic, in its op order, on g * grad_mul
+__device__ __forceinline__ void adamw_guarded_elem(float& p, float g, float& m, float& v, float mul, float decay, float b1, float b2, float eps,
+                                                   float bc2_sqrt, float step_size)
+{
+    const float gi = g * mul;
+    float pi = p * decay;
+    const float mi = b1 * m + (1.0f - b1) * gi;
+    const float vi = b2 * v + (1.0f - b2) * gi * gi;
+    m = mi; v = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi -= step_size * (mi / denom);
+    p = pi;
+}
+// VEC: the four buffers share their alignment modulo 16 bytes, so one head / quad / tail split serves all of them
+template <bool VEC>
+__global__ __launch_bounds__(256) void adamw_guarded_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                             int64_t n, int head, int64_t nvec, float lr, float b1, float b2, float eps, float wd,
+                                                             const ccn_step_guard_t* __restrict__ guard)
+{
+    const bool apply = guard->apply != 0;
+    const float mul = guard->grad_mul, bc2_sqrt = guard->bc2_sqrt, step_size = lr / guard->bc1, decay = 1.0f - lr * wd;
+    const int64_t stride = (int64_t)gridDim.x * 256, i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (!VEC) {
+        for (int64_t i = i0; i < n; i += stride) {
+            if (apply) { float pi = p[i], mi = m[i], vi = v[i]; adamw_guarded_elem(pi, g[i], mi, vi, mul, decay, b1, b2, eps, bc2_sqrt, step_size); p[i] = pi; m[i] = mi; v[i] = vi; }
+            g[i] = 0.f;
+        }
+        return;
+    }
+    f32x4* const pv = (f32x4*)(p + head); f32x4* const gv = (f32x4*)(g + head); f32x4* const mv = (f32x4*)(m + head); f32x4* const vv = (f32x4*)(v + head);
+    for (int64_t i = i0; i < nvec; i += stride) {
+        if (apply) {
+            const f32x4 gq = gv[i];
+            f32x4 pq = pv[i], mq = mv[i], vq = vv[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pe = pq[e], me = mq[e], ve = vq[e];
+                adamw_guarded_elem(pe, gq[e], me, ve, mul, decay, b1, b2, eps, bc2_sqrt, step_size);
+                pq[e] = pe; mq[e] = me; vq[e] = ve;
+            }
+            pv[i] = pq; mv[i] = mq; vv[i] = vq;
+        }
+        gv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (blockIdx.x == 0) {
+        const int64_t tail0 = head + 4 * nvec;
+        const int t = (int)threadIdx.x;
+        const int64_t i = t < head ? t : tail0 + (t - head);
+        if (i < n) {
+            if (apply) { float pi = p[i], mi = m[i], vi = v[i]; adamw_guarded_elem(pi, g[i], mi, vi, mul, decay, b1, b2, eps, bc2_sqrt, step_size); p[i] = pi; m[i] = mi; v[i] = vi; }
+            g[i] = 0.f;
+        }
+    }
+}
+hipError_t launch_adamw_guarded(float* p, float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
+                                const void* guard, hipStream_t s)
+{
+    const uintptr_t a = (uintptr_t)p & 15;
+    const bool vec = ((uintptr_t)g & 15) == a && ((uintptr_t)m & 15) == a && ((uintptr_t)v & 15) == a;
+    if (vec) {
+        int64_t head = (int64_t)(((16 - a) & 15) >> 2);
+        if (head > n) head = n;
+        const int64_t nvec = (n - head) / 4, want = (nvec + 255) / 256;
+        const unsigned grid = (unsigned)(want < 8192 ? (want > 0 ? want : 1) : 8192);
+        hipLaunchKernelGGL(adamw_guarded_kernel<true>, dim3(grid), dim3(256), 0, s, p, g, m, v, n, (int)head, nvec, lr, b1, b2, eps, wd,
+                           (const ccn_step_guard_t*)guard);
+    } else {
+        const unsigned grid = (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+        hipLaunchKernelGGL(adamw_guarded_kernel<false>, dim3(grid ? grid : 1), dim3(256), 0, s, p, g, m, v, n, 0, (int64_t)0, lr, b1, b2, eps, wd,
+                           (const ccn_step_guard_t*)guard);
+    }
     return hipGetLastError();
 }
 

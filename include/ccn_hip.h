@@ -288,6 +288,52 @@ int ccn_adamw_step(float* params_dev, const float* grads_dev, float* exp_avg_dev
 int ccn_adamw_step_zero_grad(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n,
                              float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, void* stream);
 
+/* ---- step guard: loss scaling, the skipped step on non-finite gradients, gradient-norm clipping ---------------------------- *
+ * The reference ends its loop body with `scaler.scale(loss).backward(); scaler.step(opt); scaler.update()`
+ * (train/diffusion_train.py:137-139).  Here the whole decision lives in this 64-byte control block in DEVICE memory: nothing is read
+ * back to the host, so the step stays asynchronous.  Semantics are torch's: torch.amp.GradScaler, then
+ * torch.nn.utils.clip_grad_norm_(norm_type=2), then torch.optim.AdamW whose step count advances on APPLIED steps only.
+ * A torch caller views the block as a tensor of 16 int32 words (words 0-5 reinterpreted as fp32). */
+typedef struct ccn_step_guard_s {
+    float scale;                /* the loss scale: d loss / d eps_hat is multiplied by it before the backward */
+    float inv_scale;            /* (float)(1 / (double)scale) */
+    float grad_norm;            /* last ccn_grad_guard: L2 norm of the UNSCALED gradient (inf / NaN on a skipped step) */
+    float grad_mul;             /* last ccn_grad_guard: inv_scale * clip coefficient -- what ccn_adamw_step_guarded multiplies g by */
+    float bc1;                  /* last ccn_grad_guard: 1 - beta1^step, step = good_steps (before the call) + 1 */
+    float bc2_sqrt;             /*                      sqrt(1 - beta2^step) */
+    int32_t apply;              /* last ccn_grad_guard: 1 = every gradient element finite, the step is applied; 0 = skipped */
+    int32_t good_steps;         /* applied steps so far (AdamW's step count) */
+    int32_t skipped_steps;      /* skipped steps so far */
+    int32_t growth_tracker;     /* consecutive applied steps since the scale last changed (GradScaler's _growth_tracker) */
+    int32_t reserved[6];
+} ccn_step_guard_t;
+
+/* scaler = GradScaler(init_scale) (train/diffusion_train.py:106), or its load_state_dict: writes the whole block (one small launch on
+ * `stream`, no host memory is read later).  init_scale > 0 and finite; the three counters >= 0. */
+int ccn_step_guard_init(void* guard_dev, float init_scale, int32_t growth_tracker0, int32_t good_steps0,
+                        int32_t skipped_steps0, void* stream);
+
+/* The decision of scaler.step + scaler.update (train/diffusion_train.py:138-139) for the n gradients of a flat buffer, which hold
+ * d (scale * loss): one read of the buffer sums (g * inv_scale)^2 in fp64 (a fixed number of per-workgroup partials that depends on
+ * n only, added in a fixed order, no atomics: bit-reproducible), then one wave writes into the block
+ *     apply     = the sum is finite (fp64 cannot overflow here, so: no element is inf or NaN)
+ *     grad_norm = sqrt(sum);  grad_mul = inv_scale * min(1, max_grad_norm / (grad_norm + 1e-6))   (max_grad_norm <= 0: no clipping)
+ *     bc1, bc2_sqrt for step = good_steps + 1
+ * and commits the state: good_steps += apply, skipped_steps += !apply, and GradScaler.update(): on a skip scale *= backoff_factor and
+ * growth_tracker = 0, otherwise ++growth_tracker and, when it reaches growth_interval, scale *= growth_factor (if that is finite) and
+ * growth_tracker = 0.  The gradients themselves are not touched.  scratch_dev: at least 4096 floats, 8-byte aligned.
+ * 0 <= beta < 1, growth_factor and backoff_factor > 0, growth_interval >= 1.  Never synchronises, allocates nothing: capturable. */
+int ccn_grad_guard(const float* grads_dev, int64_t n, void* guard_dev, float max_grad_norm, float beta1, float beta2,
+                   float growth_factor, float backoff_factor, int32_t growth_interval, float* scratch_dev, void* stream);
+
+/* opt.step() + opt.zero_grad() (train/diffusion_train.py:138,140) under the decision ccn_grad_guard left in the block, which this
+ * call only reads: with apply == 1 it is ccn_adamw_step_zero_grad with g * grad_mul for g and the block's bias corrections; with
+ * apply == 0 parameters and both moments stay bit for bit (no weight decay either) and the gradients are only zeroed.  16-byte
+ * accesses when the four buffers share their alignment modulo 16 bytes, 4-byte accesses otherwise.  Never synchronises. */
+int ccn_adamw_step_guarded(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, const void* guard_dev,
+                           void* stream);
+
 const char* ccn_last_error(void);
 const char* ccn_version(void);
 
