@@ -74,6 +74,9 @@ SIGNATURES = {
     "ccn_step_guard_init": (c_i32, [c_vp, c_f32, c_i32, c_i32, c_i32, c_vp]),
     "ccn_grad_guard": (c_i32, [c_vp, c_i64, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp]),
     "ccn_adamw_step_guarded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp]),
+    "ccn_ema_init": (c_i32, [c_vp, c_i32, c_vp]),
+    "ccn_adamw_step_ema": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, ctypes.c_double, c_i32,
+                                   c_vp, c_vp, c_vp]),
     "ccn_last_error": (ctypes.c_char_p, []),
     "ccn_version": (ctypes.c_char_p, []),
 }
@@ -526,6 +529,50 @@ def adamw_step_guarded(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: tor
     with torch.cuda.device(p.device):
         check(lib.ccn_adamw_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(beta1),
                                          float(beta2), float(eps), float(weight_decay), block.data_ptr(), current_stream(p.device)))
+
+
+# ---- weight EMA (ccn_ema_state_t of include/ccn_hip.h, viewed as 8 int32 words; word 0 is fp32) -------------------------------------
+class EmaStateBlock(ctypes.Structure):
+    _fields_ = [("weight", c_f32), ("apply", c_i32), ("first", c_i32), ("updates", c_i32), ("reserved", c_i32 * 4)]
+
+
+EMA_WORDS = ctypes.sizeof(EmaStateBlock) // 4
+EMA_WORD = {name: getattr(EmaStateBlock, name).offset // 4 for name, _ in EmaStateBlock._fields_}
+
+
+def _ema_block(block: torch.Tensor) -> torch.Tensor:
+    if not (isinstance(block, torch.Tensor) and block.is_cuda and block.dtype == torch.int32 and block.is_contiguous()
+            and block.numel() == EMA_WORDS):
+        raise ValueError(f"the EMA state block must be a contiguous int32 HIP tensor of {EMA_WORDS} words")
+    return block
+
+
+def ema_init(block: torch.Tensor, updates: int = 0) -> None:
+    """Write the whole EMA state block (AveragedModel's n_averaged = ``updates``): one small launch, no sync."""
+    lib = load_library()
+    _ema_block(block)
+    with torch.cuda.device(block.device):
+        check(lib.ccn_ema_init(block.data_ptr(), int(updates), current_stream(block.device)))
+
+
+def adamw_step_ema(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, ema: torch.Tensor, lr: float, beta1: float,
+                   beta2: float, eps: float, weight_decay: float, step: int, ema_decay: float, ema_block: torch.Tensor,
+                   zero_grad: bool = False, ema_warmup: bool = False, guard_block: Optional[torch.Tensor] = None) -> None:
+    """The AdamW update (``adamw_step``'s, or ``adamw_step_guarded``'s under ``guard_block``) and the EMA of the updated parameters
+    into ``ema``, one pass; a skipped step leaves the average and its count of updates alone."""
+    lib = load_library()
+    _ema_block(ema_block)
+    if guard_block is not None:
+        _guard_block(guard_block)
+    for name, tns in (("params", p), ("grads", g), ("exp_avg", m), ("exp_avg_sq", v), ("ema", ema)):
+        if not (isinstance(tns, torch.Tensor) and tns.is_cuda and tns.dtype == torch.float32 and tns.is_contiguous()
+                and tns.numel() == p.numel()):
+            raise ValueError(f"{name} must be a contiguous fp32 HIP tensor of {p.numel()} elements")
+    with torch.cuda.device(p.device):
+        check(lib.ccn_adamw_step_ema(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), p.numel(), float(lr),
+                                     float(beta1), float(beta2), float(eps), float(weight_decay), int(step), int(bool(zero_grad)),
+                                     float(ema_decay), int(bool(ema_warmup)), ptr(guard_block), ema_block.data_ptr(),
+                                     current_stream(p.device)))
 
 
 # ---- stateless ops --------------------------------------------------------------------------------

@@ -24,6 +24,12 @@ clipping are decided on the device by one extra read of the flat gradient buffer
 kernel only reads that decision -- no host sync.  ``train_step(..., scaler=, max_grad_norm=)`` and
 ``train_diffusion(..., grad_scaler=, max_grad_norm=)`` use it; everything is off by default.
 
+``FusedAdamW(net, ema_decay=)`` also keeps an exponential moving average of the parameters -- the weights a diffusion decoder is
+sampled from (``torch.optim.swa_utils.AveragedModel`` with ``get_ema_multi_avg_fn(decay)``).  The average is taken inside the AdamW
+kernel, which reads the guard's decision on the device: a skipped step neither moves the average nor counts as an update.
+``opt.ema_state_dict()`` is the checkpoint to evaluate, ``with opt.ema_weights():`` runs this model on the averaged weights, and
+``opt.state_dict()`` / ``load_state_dict()`` with ``train_diffusion(resume=)`` continue a run that stopped.
+
 With ``torch.distributed`` initialised, ``train_step(..., ddp=True)`` averages the flat gradient buffer over the ranks
 with one all-reduce (RCCL over xGMI on a GPU node): the data-parallel step of BASELINE.json configs[4].
 """
@@ -213,9 +219,19 @@ class TrainState:
 
 
 class FusedAdamW:
-    """``torch.optim.AdamW`` semantics over the flat buffers, one kernel launch per step (train/diffusion_train.py:105,138)."""
+    """``torch.optim.AdamW`` semantics over the flat buffers, one kernel launch per step (train/diffusion_train.py:105,138).
 
-    def __init__(self, net, lr: float = 2e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2) -> None:
+    ``ema_decay`` (0 <= decay < 1): the same pass also keeps ``self.ema``, the exponential moving average of the parameters that
+    ``AveragedModel(net, multi_avg_fn=get_ema_multi_avg_fn(ema_decay))`` with ``update_parameters`` after every applied step would
+    hold: the first update copies the parameters, later ones are ``ema.lerp_(p, 1 - decay)``.  ``ema_warmup``: the decay of update
+    ``u`` (from 0) is ``min(ema_decay, (1 + u) / (10 + u))``.  The count of updates lives in ``self.ema_block`` on the device and
+    does not advance on a skipped step.  Without ``ema_decay`` nothing is allocated and every step is what it was."""
+
+    def __init__(self, net, lr: float = 2e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False) -> None:
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), not {ema_decay}")
+        self.net = net
         self.state: TrainState = net.train_state()
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         fp = self.state.fp
@@ -224,6 +240,15 @@ class FusedAdamW:
         self.steps = 0
         self._guard: Optional["GradScaler"] = None      # the guard of the last guarded step: its block holds the step count from then on
         self._clip_guard: Optional["GradScaler"] = None
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema: Optional[torch.Tensor] = None
+        self.ema_block: Optional[torch.Tensor] = None
+        self._ema_swapped = False
+        if self.ema_decay is not None:
+            self.ema = fp.flat.detach().clone()
+            self.ema_block = torch.zeros(_native.EMA_WORDS, dtype=torch.int32, device=fp.flat.device)
+            _native.ema_init(self.ema_block, 0)
 
     def clip_guard(self) -> "GradScaler":
         """The internal guard of ``max_grad_norm`` without a scaler: scale 1, never grows, never backs off."""
@@ -242,6 +267,9 @@ class FusedAdamW:
         count the guard already holds (a ``GradScaler`` restored with ``load_state_dict`` resumes its run's count), and an unguarded
         ``step()`` afterwards raises, because the host-side count would be wrong."""
         fp = self.state.fp
+        if self._ema_swapped:
+            raise RuntimeError("step() inside `with opt.ema_weights():` -- the flat buffer holds the averaged weights there, leave the "
+                               "context before training on")
         if guard is not None and not guard.enabled:
             guard = None
         if guard is None and max_grad_norm is not None and max_grad_norm > 0:
@@ -259,8 +287,13 @@ class FusedAdamW:
                 self._guard = guard
             _native.grad_guard(fp.grad, block, guard.scratch, max_grad_norm if max_grad_norm is not None else 0.0, self.betas[0],
                                self.betas[1], guard.growth_factor, guard.backoff_factor, guard.growth_interval)
-            _native.adamw_step_guarded(fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
-                                       self.weight_decay, block)
+            if self.ema is not None:
+                _native.adamw_step_ema(fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq, self.ema, self.lr, self.betas[0], self.betas[1],
+                                       self.eps, self.weight_decay, 0, self.ema_decay, self.ema_block, zero_grad=True,
+                                       ema_warmup=self.ema_warmup, guard_block=block)
+            else:
+                _native.adamw_step_guarded(fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
+                                           self.weight_decay, block)
             fp.flat[:1].add_(0)
             fp.rebind_grads()
             return
@@ -268,8 +301,13 @@ class FusedAdamW:
             raise RuntimeError("an unguarded step() after a guarded one: the count of applied steps lives in the guard's control block "
                                "(skipped steps do not advance it), keep passing guard= / max_grad_norm=")
         self.steps += 1
-        _native.adamw_step(fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
-                           self.weight_decay, self.steps, zero_grad=zero_grad)
+        if self.ema is not None:
+            _native.adamw_step_ema(fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq, self.ema, self.lr, self.betas[0], self.betas[1], self.eps,
+                                   self.weight_decay, self.steps, self.ema_decay, self.ema_block, zero_grad=zero_grad,
+                                   ema_warmup=self.ema_warmup)
+        else:
+            _native.adamw_step(fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
+                               self.weight_decay, self.steps, zero_grad=zero_grad)
         fp.flat[:1].add_(0)    # the kernel wrote behind torch's back: bump the (shared) version counter so that a stale forward is detected
         if zero_grad:
             fp.rebind_grads()
@@ -277,6 +315,101 @@ class FusedAdamW:
     def zero_grad(self, set_to_none: bool = False) -> None:
         self.state.fp.grad.zero_()
         self.state.fp.rebind_grads()
+
+    # ---- the averaged weights ------------------------------------------------------------------------------------------------
+    def _need_ema(self) -> None:
+        if self.ema is None:
+            raise RuntimeError("this FusedAdamW keeps no EMA: construct it with ema_decay=")
+
+    def ema_updates(self) -> int:
+        """EMA updates done so far (AveragedModel's ``n_averaged``) -- a host read (synchronises)."""
+        self._need_ema()
+        return int(self.ema_block[_native.EMA_WORD["updates"]])
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """``net.state_dict()`` with the averaged parameters: same keys, shapes and order, values cloned from ``self.ema`` -- the
+        checkpoint to sample from (loads with ``CLIPCondUNet.from_state_dict``, ``cli.eval``, ``cli.reconstruct_diffusion``)."""
+        self._need_ema()
+        if self._ema_swapped:
+            raise RuntimeError("ema_state_dict() inside `with opt.ema_weights():` -- the buffers are swapped there")
+        where = {name: (off, shape) for name, shape, off in self.state.trainer.layout}
+        out = {}
+        for key, val in self.net.state_dict().items():
+            if key in where:
+                off, shape = where[key]
+                out[key] = self.ema[off:off + val.numel()].view(tuple(shape)).clone()
+            else:
+                out[key] = val.detach().clone()
+        return out
+
+    def _swap_ema(self) -> None:
+        """Exchange the contents of the flat parameter buffer and ``self.ema`` through a 4 MiB chunk (no second full-size buffer).
+        The copies into ``flat`` bump its version counter: ``net.native()`` re-commits its weights from what the buffer then holds."""
+        flat, ema = self.state.fp.flat, self.ema
+        n = flat.numel()
+        chunk = min(n, 1 << 20)
+        tmp = torch.empty(chunk, dtype=torch.float32, device=flat.device)
+        with torch.no_grad():
+            for lo in range(0, n, chunk):
+                a, b = flat[lo:lo + chunk], ema[lo:lo + chunk]
+                t = tmp[:a.numel()]
+                t.copy_(a); a.copy_(b); b.copy_(t)
+
+    def ema_weights(self):
+        """Context manager: inside it the model's parameters ARE the averaged weights (``net.eval()`` and the samplers see them);
+        the raw iterate is parked in ``self.ema`` and swapped back on exit, also on an exception.  ``step()`` inside it raises."""
+        import contextlib
+        self._need_ema()
+
+        @contextlib.contextmanager
+        def ctx():
+            if self._ema_swapped:
+                raise RuntimeError("ema_weights() is not re-entrant")
+            self._swap_ema()
+            self._ema_swapped = True
+            try:
+                yield self.net
+            finally:
+                self._swap_ema()
+                self._ema_swapped = False
+        return ctx()
+
+    # ---- resumable state --------------------------------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        """Everything a resumed run needs: hyper-parameters, the count of applied steps (the guard block's when a guard owns it),
+        both moments and, with an EMA, the average and its count of updates.  Host reads (synchronises); tensors are clones."""
+        if self._ema_swapped:
+            raise RuntimeError("state_dict() inside `with opt.ema_weights():` -- the buffers are swapped there")
+        steps = self.steps
+        if self._guard is not None:
+            steps = int(self._guard.block(self.exp_avg.device)[_native.GUARD_WORD["good_steps"]])
+        sd = dict(lr=self.lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.weight_decay, steps=int(steps),
+                  exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone())
+        if self.ema is not None:
+            sd.update(ema=self.ema.clone(), ema_updates=self.ema_updates(), ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Copies into the existing buffers (their addresses stay), re-initialises the EMA block and sets the step count; a guarded
+        step afterwards seeds the guard's count with it (``step``'s seeding rule)."""
+        if self._ema_swapped:
+            raise RuntimeError("load_state_dict() inside `with opt.ema_weights():`")
+        n = self.exp_avg.numel()
+        for key in ("exp_avg", "exp_avg_sq") + (("ema",) if "ema" in sd else ()):
+            if tuple(sd[key].shape) != (n,):
+                raise ValueError(f"{key} has {tuple(sd[key].shape)} elements, this optimiser's model has {n} parameters")
+        if "ema" in sd and self.ema is None:
+            raise ValueError("the state holds an EMA but this FusedAdamW was built without ema_decay=")
+        if "ema" not in sd and self.ema is not None:
+            raise ValueError("this FusedAdamW was built with ema_decay= but the state holds no EMA")
+        self.lr, self.betas, self.eps, self.weight_decay = sd["lr"], tuple(sd["betas"]), sd["eps"], sd["weight_decay"]
+        self.exp_avg.copy_(sd["exp_avg"]); self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        if self.ema is not None:
+            self.ema.copy_(sd["ema"])
+            self.ema_decay, self.ema_warmup = float(sd["ema_decay"]), bool(sd["ema_warmup"])
+            _native.ema_init(self.ema_block, int(sd["ema_updates"]))
+        self.steps = int(sd["steps"])
+        self._guard = None
 
 
 class GradScaler:
@@ -384,8 +517,12 @@ def average_gradients(flat_grad: torch.Tensor) -> torch.Tensor:
 
 def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[torch.Tensor] = None,
                noise: Optional[torch.Tensor] = None, ddp=False, graph: bool = False, recon_w: float = 0.0,
-               tv_w: float = 0.0, scaler: Optional[GradScaler] = None, max_grad_norm: Optional[float] = None) -> torch.Tensor:
+               tv_w: float = 0.0, scaler: Optional[GradScaler] = None, max_grad_norm: Optional[float] = None,
+               ema_decay: Optional[float] = None) -> torch.Tensor:
     """One optimisation step; returns the (detached) loss.  ``t`` / ``noise`` default to the reference's draws.
+
+    The weight EMA belongs to the optimiser (``FusedAdamW(net, ema_decay=)``) and needs no argument here; ``ema_decay`` is only
+    checked: a ``TypeError`` with any other optimiser, a ``ValueError`` if it is not the optimiser's own.
 
     ``recon_w`` / ``tv_w`` (the reference's ``train_diffusion`` defaults are 0.05 and 1e-4): the loss becomes
     ``mse + recon_w * l1(x0_pred, x0) + tv_w * total_variation(x0_pred)`` with ``x0_pred = predict_x0_from_eps(...).clamp(-1, 1)``
@@ -407,6 +544,12 @@ def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[tor
     state: TrainState = net.train_state()
     fp = state.fp
     fp.rebind_grads()
+    if ema_decay is not None:
+        if not isinstance(opt, FusedAdamW):
+            raise TypeError(f"ema_decay= needs a FusedAdamW(net, ema_decay=), not {type(opt).__name__}: average a torch.optim optimiser's "
+                            "weights with torch.optim.swa_utils.AveragedModel")
+        if opt.ema_decay != float(ema_decay):
+            raise ValueError(f"ema_decay={ema_decay} but the optimiser was built with ema_decay={opt.ema_decay}")
     guard = scaler if scaler is not None and scaler.enabled else None
     clip = max_grad_norm is not None and max_grad_norm > 0
     if (guard is not None or clip) and not isinstance(opt, FusedAdamW):
@@ -547,7 +690,8 @@ def autograd_objective_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t:
 def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size: int = 8, lr: float = 2e-4, timesteps: int = 1000,
                     schedule: str = "cosine", recon_w: float = 0.05, clip_w: float = 0.1, tv_w: float = 1e-4, device: str = "cuda",
                     save_dir=None, base: int = 128, ch_mult=(1, 2, 2), dtype: str = "bf16", num_workers: int = 2, log=print,
-                    fused_objective: bool = True, grad_scaler: bool = False, max_grad_norm: Optional[float] = None):
+                    fused_objective: bool = True, grad_scaler: bool = False, max_grad_norm: Optional[float] = None,
+                    ema_decay: Optional[float] = None, ema_warmup: bool = False, resume=None):
     """The reference's ``train_diffusion`` (same arguments, defaults, checkpoint names and log line) on the MI355X kernels.
 
     Per batch (train/diffusion_train.py:115-140): t ~ U{0..T-1}, noise ~ N, then ``train_step`` with the ``t`` / ``noise`` drawn here:
@@ -562,7 +706,14 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
     same host read as the loss.  Additions that default to the reference's behaviour: ``base`` / ``ch_mult`` / ``dtype``.  With
     ``torch.distributed`` initialised the records are sharded over the ranks and the flat gradient buffer is all-reduced bucket
     by bucket while the backward runs.
+
+    ``ema_decay``: ``FusedAdamW`` keeps the moving average of the weights and rank 0 also writes ``diffusion_unet_ep{N}_ema.pt`` and
+    ``diffusion_unet_final_ema.pt`` -- the checkpoints to sample from; the reference's file names keep holding the raw iterate.
+    Every epoch rank 0 also writes ``train_state.pt`` (to a temporary name, then ``os.replace``): epoch, weights, optimiser and scaler
+    state, torch's CPU and device RNG states.  ``resume=<that file>`` restores all of it on every rank and continues with the next
+    epoch (same ``[train] epoch k/N`` numbering); a file of another architecture or parameter count is refused.
     """
+    import os
     from pathlib import Path
     import torch.distributed as dist
     from ..models.unet import CLIPCondUNet
@@ -576,6 +727,13 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
                                      pin_memory=True)
     z_dim = ds[0][1].numel()
     net = CLIPCondUNet(z_dim=z_dim, base=base, ch_mult=tuple(ch_mult), img_ch=3, dtype=dtype).to(device)
+    ck = None
+    if resume is not None:
+        from ..models.unet import infer_arch
+        ck = torch.load(resume, map_location="cpu", weights_only=True)
+        if infer_arch(ck["net"]) != net.arch:
+            raise ValueError(f"{resume} holds a model of architecture {infer_arch(ck['net'])}, this run builds {net.arch}")
+        net.load_state_dict(ck["net"], strict=True)        # the optimiser's load_state_dict below refuses another parameter count
     if ddp:                                                    # same initial weights on every rank
         for p in net.parameters():
             dist.broadcast(p.data, src=0)
@@ -584,9 +742,19 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
     state = net.train_state(device)
     # data parallel: finished ranges of the flat gradient buffer are all-reduced (RCCL) while the backward still runs
     state.ddp_bucketed = ddp
-    opt = FusedAdamW(net, lr=lr)
+    opt = FusedAdamW(net, lr=lr, ema_decay=ema_decay, ema_warmup=ema_warmup)
     scaler = GradScaler() if grad_scaler else None
-    skipped_before = 0
+    skipped_before, first_ep = 0, 0
+    if ck is not None:
+        if (ck["scaler"] is None) != (scaler is None):
+            raise ValueError(f"{resume} was written {'with' if ck['scaler'] is not None else 'without'} grad_scaler, this run is the reverse")
+        opt.load_state_dict(ck["opt"])          # the hyper-parameters of the stopped run included: `lr` is then the file's
+        if scaler is not None:
+            scaler.load_state_dict(ck["scaler"])
+            skipped_before = int(ck["scaler"]["skipped_steps"])
+        torch.set_rng_state(ck["rng_cpu"])
+        torch.cuda.set_rng_state(ck["rng_device"], device)
+        first_ep = int(ck["epoch"])
     if clip_w > 0:
         try:
             import open_clip  # noqa: F401
@@ -595,7 +763,7 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
             log(f"[train] clip_w={clip_w} ignored: {exc}")
     rank0 = not ddp or dist.get_rank() == 0
     final_path = save_dir / "diffusion_unet_final.pt"
-    for ep in range(epochs):
+    for ep in range(first_ep, epochs):
         if sampler is not None:
             sampler.set_epoch(ep)
         running, seen = 0.0, 0
@@ -625,9 +793,17 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
             running = float(running_dev)                  # the one host read of the epoch
         if rank0:
             torch.save(net.state_dict(), save_dir / f"diffusion_unet_ep{ep + 1}.pt")
+            if opt.ema is not None:
+                torch.save(opt.ema_state_dict(), save_dir / f"diffusion_unet_ep{ep + 1}_ema.pt")
+            tmp_path = save_dir / "train_state.pt.tmp"
+            torch.save(dict(epoch=ep + 1, net=net.state_dict(), opt=opt.state_dict(), scaler=None if scaler is None else scaler.state_dict(),
+                            rng_cpu=torch.get_rng_state(), rng_device=torch.cuda.get_rng_state(device)), tmp_path)
+            os.replace(tmp_path, save_dir / "train_state.pt")
             log(f"[train] epoch {ep + 1}/{epochs} loss={running / max(seen, 1):.4f}")
             if skipped:
                 log(f"[train] epoch {ep + 1}/{epochs}: {skipped} step(s) skipped on non-finite gradients, loss scale now {loss_scale:g}")
     if rank0:
         torch.save(net.state_dict(), final_path)
+        if opt.ema is not None:
+            torch.save(opt.ema_state_dict(), save_dir / "diffusion_unet_final_ema.pt")
     return final_path

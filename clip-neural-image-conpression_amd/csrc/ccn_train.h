@@ -117,5 +117,11 @@ hipError_t launch_grad_guard(const float* g, int64_t n, void* guard, float max_n
                              int interval, double* scratch, hipStream_t s);
 hipError_t launch_adamw_guarded(float* p, float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
                                 const void* guard, hipStream_t s);
+// weight EMA fused into the AdamW pass (torch.optim.swa_utils.AveragedModel + get_ema_multi_avg_fn): `ema_state` is a ccn_ema_state_t
+// in device memory, `guard` NULL or the block launch_grad_guard has just written; w = 1 - decay in fp32.  Two launches: the one-wave
+// tick that writes `ema_state`, then the fused pass (launch_adamw's arithmetic without a guard, launch_adamw_guarded's with one).
+hipError_t launch_ema_init(void* ema_state, int updates, hipStream_t s);
+hipError_t launch_adamw_ema(float* p, float* g, float* m, float* v, float* ema, int64_t n, float lr, float b1, float b2, float eps, float wd,
+                            int step, bool zero_grad, float w, bool warmup, const void* guard, void* ema_state, hipStream_t s);
 
 }  // namespace ccn

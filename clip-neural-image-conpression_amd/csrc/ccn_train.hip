@@ -1159,4 +1159,33 @@ int ccn_adamw_step_guarded(float* params_dev, float* grads_dev, float* exp_avg_d
     return CCN_OK;
 }
 
+int ccn_ema_init(void* ema_state_dev, int32_t updates0, void* stream)
+{
+    if (!ema_state_dev || ((uintptr_t)ema_state_dev & 3) != 0) return tfail(CCN_EINVAL, "ema_state_dev must be a 4-byte aligned device pointer");
+    if (updates0 < 0) return tfail(CCN_EINVAL, "updates0 must be non-negative");
+    if (launch_ema_init(ema_state_dev, updates0, (hipStream_t)stream) != hipSuccess) return tfail(CCN_EHIP, "ema init launch failed");
+    return CCN_OK;
+}
+
+int ccn_adamw_step_ema(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* ema_dev, int64_t n, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, int32_t step, int32_t zero_grad, double ema_decay,
+                       int32_t ema_warmup, const void* guard_dev, void* ema_state_dev, void* stream)
+{
+    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || !ema_dev || !ema_state_dev)
+        return tfail(CCN_EINVAL, "a buffer or the EMA state block is NULL");
+    if (n < 0) return tfail(CCN_EINVAL, "n is negative");
+    if (!(ema_decay >= 0.0 && ema_decay < 1.0)) return tfail(CCN_EINVAL, "ema_decay must be in [0, 1)");
+    if (guard_dev && !zero_grad) return tfail(CCN_EINVAL, "a guarded step consumes the gradients: zero_grad must be non-zero with guard_dev");
+    if (!guard_dev && step <= 0) return tfail(CCN_EINVAL, "step must be at least 1 without guard_dev");
+    if ((((uintptr_t)params_dev | (uintptr_t)grads_dev | (uintptr_t)exp_avg_dev | (uintptr_t)exp_avg_sq_dev | (uintptr_t)ema_dev |
+          (uintptr_t)guard_dev | (uintptr_t)ema_state_dev) & 3) != 0)
+        return tfail(CCN_EINVAL, "buffers must be 4-byte aligned");
+    if (n == 0) return CCN_OK;                       // nothing to average: no launch, the count of updates stays
+    const float w = (float)(1.0 - ema_decay);        // the weight get_ema_multi_avg_fn(decay) hands to lerp_, rounded once to fp32
+    if (launch_adamw_ema(params_dev, grads_dev, exp_avg_dev, exp_avg_sq_dev, ema_dev, n, lr, beta1, beta2, eps, weight_decay, step,
+                         zero_grad != 0, w, ema_warmup != 0, guard_dev, ema_state_dev, (hipStream_t)stream) != hipSuccess)
+        return tfail(CCN_EHIP, "adamw + ema launch failed");
+    return CCN_OK;
+}
+
 }  // extern "C"

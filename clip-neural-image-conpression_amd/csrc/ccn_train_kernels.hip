@@ -1844,4 +1844,146 @@ hipError_t launch_adamw_guarded(float* p, float* g, float* m, float* v, int64_t 
     return hipGetLastError();
 }
 
+// ---- weight EMA fused into the AdamW pass (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn(decay)) -----------------
+// ema_tick_kernel is the only writer of the 32-byte ccn_ema_state_t, as grad_guard_final_kernel is of the guard block; it runs before
+// adamw_ema_kernel, which only reads the block.  A skipped step (guard->apply == 0) is no update: neither the average nor the count
+// of updates (the warm-up's clock) moves.
+__global__ void ema_init_kernel(ccn_ema_state_t* __restrict__ st, int updates)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    ccn_ema_state_t b{};
+    b.updates = updates;
+    *st = b;
+}
+hipError_t launch_ema_init(void* ema_state, int updates, hipStream_t s)
+{
+    hipLaunchKernelGGL(ema_init_kernel, dim3(1), dim3(64), 0, s, (ccn_ema_state_t*)ema_state, updates);
+    return hipGetLastError();
+}
+__global__ void ema_tick_kernel(ccn_ema_state_t* __restrict__ st, const ccn_step_guard_t* __restrict__ guard, float w, int warmup)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    const bool apply = guard ? guard->apply != 0 : true;
+    if (!apply) { st->apply = 0; return; }
+    const int u = st->updates;
+    st->apply = 1;
+    st->first = u == 0 ? 1 : 0;
+    // decay_u = min(decay, (1 + u) / (10 + u)) as its complement 1 - decay_u = max(w, 9 / (10 + u)): no 1 - x cancellation
+    st->weight = warmup ? fmaxf(w, __fdiv_rn(9.0f, (float)(10 + u))) : w;
+    st->updates = u + 1;
+}
+
+// adamw_kernel<ZERO>'s arithmetic, expression for expression
+__device__ __forceinline__ void adamw_plain_elem(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float wd,
+                                                 float bc1, float bc2_sqrt)
+{
+    const float gi = g;
+    float pi = p * (1.0f - lr * wd);
+    const float mi = b1 * m + (1.0f - b1) * gi;
+    const float vi = b2 * v + (1.0f - b2) * gi * gi;
+    m = mi; v = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi -= (lr / bc1) * (mi / denom);
+    p = pi;
+}
+struct AdamwEmaCoef {
+    float lr, b1, b2, eps, wd, bc1, bc2_sqrt;       // bc1, bc2_sqrt: the host's when !GUARDED, the guard block's otherwise
+    float mul, decay, step_size;                    // GUARDED only (adamw_guarded_kernel's)
+    float weight; bool first;
+};
+template <bool GUARDED>
+__device__ __forceinline__ void adamw_ema_elem(float& p, float g, float& m, float& v, float& e, const AdamwEmaCoef& c)
+{
+    if (GUARDED) adamw_guarded_elem(p, g, m, v, c.mul, c.decay, c.b1, c.b2, c.eps, c.bc2_sqrt, c.step_size);
+    else adamw_plain_elem(p, g, m, v, c.lr, c.b1, c.b2, c.eps, c.wd, c.bc1, c.bc2_sqrt);
+    e = c.first ? p : fmaf(c.weight, p - e, e);       // the first update copies (AveragedModel's n_averaged == 0), later ones lerp
+}
+template <bool GUARDED, bool ZERO>
+__device__ __forceinline__ void adamw_ema_scalar(float* p, float* g, float* m, float* v, float* ema, int64_t i, bool apply, const AdamwEmaCoef& c)
+{
+    if (apply) {
+        float pi = p[i], mi = m[i], vi = v[i], ei = c.first ? 0.f : ema[i];
+        adamw_ema_elem<GUARDED>(pi, g[i], mi, vi, ei, c);
+        p[i] = pi; m[i] = mi; v[i] = vi; ema[i] = ei;
+    }
+    if (ZERO) g[i] = 0.f;
+}
+// VEC: the five buffers share their alignment modulo 16 bytes; [head scalars][nvec 16-byte quads][tail scalars] as adamw_guarded_kernel.
+// One quad of each buffer per thread and trip: five 16-byte loads in flight at 8 waves per SIMD already cover the HBM latency.
+template <bool GUARDED, bool ZERO, bool VEC>
+__global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                         float* __restrict__ ema, int64_t n, int head, int64_t nvec, float lr, float b1, float b2,
+                                                         float eps, float wd, float bc1, float bc2_sqrt,
+                                                         const ccn_step_guard_t* __restrict__ guard, const ccn_ema_state_t* __restrict__ st)
+{
+    const bool apply = st->apply != 0;                // the tick copied the guard's decision (1 without a guard)
+    AdamwEmaCoef c;
+    c.lr = lr; c.b1 = b1; c.b2 = b2; c.eps = eps; c.wd = wd; c.bc1 = bc1; c.bc2_sqrt = bc2_sqrt;
+    c.mul = 1.0f; c.decay = 1.0f; c.step_size = 0.f;
+    if (GUARDED) { c.mul = guard->grad_mul; c.bc2_sqrt = guard->bc2_sqrt; c.step_size = lr / guard->bc1; c.decay = 1.0f - lr * wd; }
+    c.weight = st->weight; c.first = st->first != 0;
+    const int64_t stride = (int64_t)gridDim.x * 256, i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (!VEC) {
+        for (int64_t i = i0; i < n; i += stride) adamw_ema_scalar<GUARDED, ZERO>(p, g, m, v, ema, i, apply, c);
+        return;
+    }
+    f32x4* const pv = (f32x4*)(p + head); f32x4* const gv = (f32x4*)(g + head); f32x4* const mv = (f32x4*)(m + head);
+    f32x4* const vv = (f32x4*)(v + head); f32x4* const ev = (f32x4*)(ema + head);
+    for (int64_t i = i0; i < nvec; i += stride) {
+        if (apply) {
+            const f32x4 gq = gv[i];
+            f32x4 pq = pv[i], mq = mv[i], vq = vv[i], eq = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (!c.first) eq = ev[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pe = pq[e], me = mq[e], ve = vq[e], ee = eq[e];
+                adamw_ema_elem<GUARDED>(pe, gq[e], me, ve, ee, c);
+                pq[e] = pe; mq[e] = me; vq[e] = ve; eq[e] = ee;
+            }
+            pv[i] = pq; mv[i] = mq; vv[i] = vq; ev[i] = eq;
+        }
+        if (ZERO) gv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (blockIdx.x == 0) {
+        const int64_t tail0 = head + 4 * nvec;
+        const int t = (int)threadIdx.x;
+        const int64_t i = t < head ? t : tail0 + (t - head);
+        if (i < n) adamw_ema_scalar<GUARDED, ZERO>(p, g, m, v, ema, i, apply, c);
+    }
+}
+template <bool GUARDED, bool ZERO>
+static void launch_adamw_ema_kernel(bool vec, unsigned grid, hipStream_t s, float* p, float* g, float* m, float* v, float* ema, int64_t n, int head,
+                                    int64_t nvec, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                                    const ccn_step_guard_t* guard, const ccn_ema_state_t* st)
+{
+    if (vec) hipLaunchKernelGGL((adamw_ema_kernel<GUARDED, ZERO, true>), dim3(grid), dim3(256), 0, s, p, g, m, v, ema, n, head, nvec, lr, b1, b2, eps,
+                                wd, bc1, bc2_sqrt, guard, st);
+    else hipLaunchKernelGGL((adamw_ema_kernel<GUARDED, ZERO, false>), dim3(grid), dim3(256), 0, s, p, g, m, v, ema, n, 0, (int64_t)0, lr, b1, b2, eps,
+                            wd, bc1, bc2_sqrt, guard, st);
+}
+hipError_t launch_adamw_ema(float* p, float* g, float* m, float* v, float* ema, int64_t n, float lr, float b1, float b2, float eps, float wd,
+                            int step, bool zero_grad, float w, bool warmup, const void* guard, void* ema_state, hipStream_t s)
+{
+    hipLaunchKernelGGL(ema_tick_kernel, dim3(1), dim3(64), 0, s, (ccn_ema_state_t*)ema_state, (const ccn_step_guard_t*)guard, w, warmup ? 1 : 0);
+    const uintptr_t a = (uintptr_t)p & 15;
+    const bool vec = ((uintptr_t)g & 15) == a && ((uintptr_t)m & 15) == a && ((uintptr_t)v & 15) == a && ((uintptr_t)ema & 15) == a;
+    int64_t head = 0, nvec = 0, want = (n + 255) / 256;
+    if (vec) {
+        head = (int64_t)(((16 - a) & 15) >> 2);
+        if (head > n) head = n;
+        nvec = (n - head) / 4; want = (nvec + 255) / 256;
+    }
+    const unsigned grid = (unsigned)(want < 8192 ? (want > 0 ? want : 1) : 8192);
+    const ccn_step_guard_t* gd = (const ccn_step_guard_t*)guard;
+    const ccn_ema_state_t* st = (const ccn_ema_state_t*)ema_state;
+    if (gd) {
+        launch_adamw_ema_kernel<true, true>(vec, grid, s, p, g, m, v, ema, n, (int)head, nvec, lr, b1, b2, eps, wd, 1.0f, 1.0f, gd, st);
+    } else {
+        const float bc1 = 1.0f - powf(b1, (float)step), bc2 = 1.0f - powf(b2, (float)step);      // launch_adamw's
+        if (zero_grad) launch_adamw_ema_kernel<false, true>(vec, grid, s, p, g, m, v, ema, n, (int)head, nvec, lr, b1, b2, eps, wd, bc1, sqrtf(bc2), gd, st);
+        else launch_adamw_ema_kernel<false, false>(vec, grid, s, p, g, m, v, ema, n, (int)head, nvec, lr, b1, b2, eps, wd, bc1, sqrtf(bc2), gd, st);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace ccn

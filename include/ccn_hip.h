@@ -334,6 +334,48 @@ int ccn_adamw_step_guarded(float* params_dev, float* grads_dev, float* exp_avg_d
                            float lr, float beta1, float beta2, float eps, float weight_decay, const void* guard_dev,
                            void* stream);
 
+/* ---- weight EMA fused into the AdamW step ------------------------------------------------------------------------------------- *
+ * A diffusion decoder is sampled from an exponential moving average of its parameters: in torch,
+ *     ema = torch.optim.swa_utils.AveragedModel(net, multi_avg_fn=get_ema_multi_avg_fn(decay))
+ *     ... opt.step(); ema.update_parameters(net)
+ * (swa_utils.py: the first update_parameters copies the parameters, every later one is `ema.lerp_(p, 1 - decay)`; n_averaged counts
+ * them).  Under the step guard above the host does not know whether a step was applied, so the average is taken on the device, in
+ * the AdamW pass itself, and this 32-byte block in DEVICE memory is its state.  A torch caller views it as 8 int32 words (word 0
+ * reinterpreted as fp32). */
+typedef struct ccn_ema_state_s {
+    float weight;               /* last ccn_adamw_step_ema: the lerp weight of this update, 1 - decay_u */
+    int32_t apply;              /* last ccn_adamw_step_ema: 1 = the step was applied and averaged; 0 = skipped (the guard's apply) */
+    int32_t first;              /* last applied update was the first one: ema = p (AveragedModel's n_averaged == 0 branch) */
+    int32_t updates;            /* EMA updates done so far (AveragedModel.n_averaged) */
+    int32_t reserved[4];
+} ccn_ema_state_t;
+
+/* AveragedModel(...)'s n_averaged = 0, or its load_state_dict: writes the whole block with updates = updates0 >= 0 (one small
+ * launch on `stream`).  The average itself is the caller's buffer: with updates0 == 0 its contents do not matter. */
+int ccn_ema_init(void* ema_state_dev, int32_t updates0, void* stream);
+
+/* opt.step() [+ opt.zero_grad()] (train/diffusion_train.py:138,140) followed by ema.update_parameters(net), as one pass over the five
+ * flat buffers.  Two launches: a one-wave tick, the only writer of the block, sets
+ *     apply  = guard_dev ? guard->apply : 1
+ *     if apply:  first = (updates == 0);  weight = ema_warmup ? max(w, 9 / (10 + updates)) : w;  updates += 1
+ * with w = (float)(1.0 - ema_decay), the fp32 weight get_ema_multi_avg_fn(decay) hands to lerp_ (ema_decay is a double so that
+ * Python's 1 - decay is formed exactly as torch forms it); the warm-up is decay_u = min(decay, (1 + u) / (10 + u)), written as
+ * its complement.  Then the fused kernel: guard_dev == NULL: ccn_adamw_step's (zero_grad == 0) or ccn_adamw_step_zero_grad's update
+ * with bias corrections for `step`; guard_dev != NULL: ccn_adamw_step_guarded's under the block ccn_grad_guard has just written
+ * (`step` ignored, zero_grad must be non-zero).  p, m, v (and g) end with the same bits as from those entries.  Per element then
+ * ema = p_new on the first update, ema = fma(weight, p_new - ema, ema) afterwards.  With apply == 0 parameters, moments and average
+ * stay bit for bit (the average is neither read nor written), the count of updates does not move, and the gradients are zeroed.
+ * 16-byte accesses when the five buffers share their alignment modulo 16 bytes, 4-byte accesses otherwise.  n == 0 does nothing.
+ * CCN_EINVAL: a NULL buffer or block, n < 0, ema_decay outside [0, 1), zero_grad == 0 with a guard, step < 1 without one.
+ * Never synchronises, allocates nothing: capturable. */
+int ccn_adamw_step_ema(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* ema_dev, int64_t n,
+                       float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int32_t step,            /* used when guard_dev == NULL, as ccn_adamw_step's */
+                       int32_t zero_grad,       /* must be non-zero when guard_dev != NULL */
+                       double ema_decay, int32_t ema_warmup,
+                       const void* guard_dev    /* NULL, or the block ccn_grad_guard has just written */,
+                       void* ema_state_dev, void* stream);
+
 const char* ccn_last_error(void);
 const char* ccn_version(void);
 
