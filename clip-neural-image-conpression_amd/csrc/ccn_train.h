@@ -61,6 +61,8 @@ hipError_t launch_film_bwd_finalize(const float2* fpart, int nblk, const float* 
 hipError_t launch_colsum_from_pairs(const float2* part, int rows, int C, float* db, hipStream_t s);
 // per-channel sum over (B, HW) of an NHWC tensor, added to `db` (bias gradients); scratch: B * nblk * C floats
 hipError_t launch_colsum(int dtype, const void* dy, float* scratch, float* db, int B, int HW, int C, hipStream_t s);
+// row blocks (grid.y) of the finalize launch of either form, for `rows` rows of partial sums
+int colsum_finalize_ygrid(int rows);
 // per-channel sum of an NCHW fp32 tensor, added to db
 hipError_t launch_nchw_chansum(const float* x, float* db, int B, int C, int64_t hw, hipStream_t s);
 

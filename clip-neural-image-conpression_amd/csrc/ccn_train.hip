@@ -66,6 +66,10 @@ const char* kTrainFamilies[TF_COUNT] = {"weight_repack", "conditioning_fwd_bwd",
                                         "weight_grad_reduce", "bias_grad", "groupnorm_silu_film_bwd", "stem_head_weight_grad"};
 struct Mark { int fam; hipEvent_t ev; double flops, bytes; };
 
+// one launch decision of a launching walk, kept for the test hook ccn_internal_train_routes (formatted there, not here)
+enum { RN_CONV = 0, RN_NORM, RN_GNBWD, RN_WGRAD, RN_COLSUM };
+struct RouteNote { int what, kind; const char* name; int v[5]; };
+
 struct ShapeInfo { size_t scr_wg = 0, scr_gn = 0, scr_film = 0, scr_col = 0, tensors = 0, total = 0; PackDesc* packs = nullptr; int n_packs = 0, n_packs_fwd = 0; };
 
 }  // namespace
@@ -102,6 +106,8 @@ struct ccn_trainer_s {
     std::vector<Mark> marks;
     // state of the last forward (checked by backward)
     int fB = 0, fH = 0, fW = 0; void* fws = nullptr;
+    // launch decisions of the last launching forward walk and of the backward walks since (a graph replay leaves the captured walk's)
+    std::vector<RouteNote> route_log;
 };
 
 namespace {
@@ -320,6 +326,10 @@ struct Walk {
         if (hipEventRecord(e, tr->side) != hipSuccess || hipStreamWaitEvent(st, e, 0) != hipSuccess) { err = "stream join failed"; return false; }
         return true;
     }
+    void note(int what, int kind, const char* name, int v0 = 0, int v1 = 0, int v2 = 0, int v3 = 0, int v4 = 0)
+    {
+        if (launch) tr->route_log.push_back({what, kind, name, {v0, v1, v2, v3, v4}});
+    }
     void* take(size_t bytes) { off = align_up(off, 256); void* p = base ? base + off : nullptr; off += bytes; return p; }
     TT new_tensor(int C, int h, int w) { TT t; t.C = C; t.H = h; t.W = w; t.p = take((size_t)B * h * w * C * tr->elem); return t; }
     int groups_for(int C) const { return C < tr->G ? C : tr->G; }
@@ -375,6 +385,7 @@ struct Walk {
         if (!launch) return true;
         const int kind = r.q.kind, K = r.q.Cin, N = r.q.Cout;
         mark(fam, 2.0 * B * r.g.Hout * r.g.Wout * (double)N * (kind == KIND_CT4 ? 4 : (kind == KIND_STEM ? 1 : r.g.ntaps)) * (kind == KIND_STEM ? 9.0 * K : (double)K));
+        note(RN_CONV, kind, conv_kernel_name(conv_kernel_for(kind, r.q.BN, a)), fam == TF_CONV_FWD ? 1 : 0, a.th, r.q.BN, a.n_nt, r.q.four ? 1 : 0);
         return ok(launch_conv(tr->cfg.dtype, kind, r.q.BN, a, st), "conv");
     }
     bool conv_fwd(const TConvW& w, const TT& in, TT& out, const float2* gn_ab, const float* film, const TT* res, bool want_part, const void* in_override = nullptr)
@@ -415,10 +426,12 @@ struct Walk {
             // statistics in the conv itself; the side stream's pass writes the activated tensor AND the tables the backward pass reads
             const GsIn gs{x.part, x.n_sp, x.n_nt, x.bn, cpg, par(n.pg), par(n.pb), 1.0 / count};
             if (!fork()) return false;
+            note(RN_NORM, 0, "side-fused", x.n_sp * x.n_nt);
             if (!ok(launch_gn_act_fused(dt, x.p, xa.p, B, x.H * x.W, x.C, x.part, G, x.n_sp, x.n_nt, x.bn, cpg, count, par(n.pg), par(n.pb), 1e-5f, tr->side, ab, stats),
                     "gn_act_fused")) return false;
             return run_conv(TF_CONV_FWD, r, w.pd_f, w.pf_f, par(w.pb), x.p, &y, y.p, nullptr, film_r, res_p, true, nullptr, &gs);
         }
+        note(RN_NORM, 0, "side-stats+act", x.n_sp * x.n_nt);
         if (!ok(launch_gn_stats(x.part, B, G, x.n_sp, x.n_nt, x.bn, cpg, x.C, count, par(n.pg), par(n.pb), 1e-5f, ab, stats, st), "gn_stats")) return false;
         if (!fork()) return false;
         if (!ok(launch_gn_act(dt, x.p, ab, xa.p, B, x.H * x.W, x.C, tr->side), "gn_act")) return false;
@@ -450,10 +463,12 @@ struct Walk {
         // every workgroup redoes the reduction of G x slots partial sums: worth it while that is a few KB (below the 256-pixel level);
         // at 256 px (256+ slots per group, 1024 workgroups per sample) the separate 5-us statistics launch stays
         if ((long)t.n_sp * t.n_nt > 128) {
+            note(RN_NORM, 0, "stats+act", t.n_sp * t.n_nt);
             mark(TF_GN_STATS);
             if (!ok(launch_gn_stats(t.part, B, G, t.n_sp, t.n_nt, t.bn, cpg, t.C, (double)cpg * t.H * t.W, par(n.pg), par(n.pb), 1e-5f, ab, stats, st), "gn_stats")) return false;
             return preact(t, ab, out);
         }
+        note(RN_NORM, 0, "fused", t.n_sp * t.n_nt);
         mark(TF_PREACT, 0.0, 2.0 * B * t.H * t.W * t.C * tr->elem);
         return ok(launch_gn_act_fused(tr->cfg.dtype, t.p, out.p, B, t.H * t.W, t.C, t.part, G, t.n_sp, t.n_nt, t.bn, cpg, (double)cpg * t.H * t.W,
                                       par(n.pg), par(n.pb), 1e-5f, st, ab, stats), "gn_act_fused");
@@ -464,6 +479,7 @@ struct Walk {
         ab = (float2*)take((size_t)B * t.C * sizeof(float2));
         stats = (float2*)take((size_t)B * G * sizeof(float2));
         if (!launch) return true;
+        note(RN_NORM, 0, "prologue", t.n_sp * t.n_nt);
         mark(TF_GN_STATS);
         return ok(launch_gn_stats(t.part, B, G, t.n_sp, t.n_nt, t.bn, cpg, t.C, (double)cpg * t.H * t.W, par(n.pg), par(n.pb), 1e-5f, ab, stats, st), "gn_stats");
     }
@@ -487,6 +503,7 @@ struct Walk {
 
     bool forward(const float* x_t, const float* z, const int64_t* t, float* eps)
     {
+        if (launch) tr->route_log.clear();
         if (launch && eps) tr->sync_used = 0;                    // (fork events of this call; a wait keeps the record it saw when it was enqueued)
         if (launch) {
             mark(TF_PACK);
@@ -581,6 +598,7 @@ struct Walk {
                         a.in = x.p; a.bias = par(tr->head.pb); a.B = B; a.Hin = H; a.Win = W; a.Cin = tr->head.Cin; a.Cout = tr->head.Cout;
                         a.Hout = H; a.Wout = W; a.eps_out = eps;
                         mark(TF_CONV_FWD, 2.0 * B * H * W * (double)tr->head.Cout * 9.0 * tr->head.Cin);
+                        note(RN_CONV, KIND_HEAD, "head2", 1);
                         if (!ok(launch_head2(a, ab_o, par(tr->head.pw), scratch, 0, st), "head")) return false;
                         break;
                     }
@@ -613,8 +631,15 @@ struct Walk {
         want(need.scr_col, (size_t)B * gg.nblk * w.Cout * 4);
         if (!launch || bias_done) return true;
         mark(TF_BIAS);
+        note_colsum(gg);
         if (g_sum_rows > 0) return ok(launch_colsum_from_pairs(scr_film, g_sum_rows, w.Cout, grad(w.pb), st), "bias_grad");
         return ok(launch_colsum(tr->cfg.dtype, dy, scr_col, grad(w.pb), B, Hdy * Wdy, w.Cout, st), "bias_grad");
+    }
+    // the bias-gradient launch that follows: from the GroupNorm backward's pairs, or launch_colsum on the gradient tensor (geometry gg)
+    void note_colsum(const GnBwdGeom& gg)
+    {
+        const int rows = g_sum_rows > 0 ? g_sum_rows : B * gg.nblk;
+        note(RN_COLSUM, 0, g_sum_rows > 0 ? "pairs" : "dy", rows, colsum_finalize_ygrid(rows));
     }
     float* grad_or_null(int i) const { return Gd ? grad(i) : nullptr; }
     // kind: the forward conv's family (KIND_STEM = 1x1 on an im2col'ed input); Cin / Cout as stored (multiples of 8), Civ / Cov the
@@ -634,6 +659,7 @@ struct Walk {
         if (!launch) return true;
         if (!fork_side()) return false;
         mark(TF_WGRAD, 2.0 * B * g.Hout * g.Wout * (double)Cov * (kind == KIND_CT4 ? 4 : (kind == KIND_STEM ? 1 : 9)) * Civ);
+        note(RN_WGRAD, kind, "", a.nsplit, B * a.n_ty * a.n_tx, Cin, Cout);
         if (!ok(launch_wgrad(tr->cfg.dtype, kind, a, wg_stream), "wgrad")) return false;
         mark(TF_WGRAD_REDUCE);
         return ok(launch_wgrad_reduce(scr_wg, a.nsplit, a.taps_w, Cout, Cin, Cov, Civ, kind == KIND_CT4 ? 1 : 0, gdst, wg_stream), "wgrad_reduce");
@@ -654,6 +680,7 @@ struct Walk {
         const int dt = tr->cfg.dtype;
         // algorithmic HBM bytes: pass 1 reads x and dA, pass 2 reads them again (+ the residual gradient) and writes dx
         mark(TF_GN_BWD, 0.0, (double)B * HW * x.C * tr->elem * (addend ? 6.0 : 5.0));
+        note(RN_GNBWD, 0, "", x.C, HW, gg.ppb / gg.pstep, gg.nblk, HW % gg.ppb);
         // (round 3: the three passes as ONE launch with one 1024-thread workgroup per (sample, group) for the levels below 256 px was
         // built, parity-green, and 0.95 ms SLOWER per step (2.47 vs 1.53 ms for the family): a group's channels are 32-128 contiguous
         // bytes per pixel, so 32 workgroups pull uncoalesced 32-byte segments at a few tens of GB/s each; docs/EXPERIMENTS.md R3.5)
@@ -769,6 +796,7 @@ struct Walk {
                         mark(TF_SMALL);
                         if (!ok(launch_im2col27(dt, x_t, col, B, c.img_ch, H, W, st), "stem_im2col")) return false;
                         mark(TF_BIAS);
+                        note_colsum(gg);
                         if (g_sum_rows > 0) { if (!ok(launch_colsum_from_pairs(scr_film, g_sum_rows, w.Cout, grad(w.pb), st), "stem_bias")) return false; }
                         else if (!ok(launch_colsum(dt, g.p, scr_col, grad(w.pb), B, H * W, w.Cout, st), "stem_bias")) return false;
                     }
@@ -1052,6 +1080,40 @@ int ccn_train_backward_bucketed(ccn_trainer_t tr, const float* params_dev, float
     tr->sync_used = 0;
     if (!w.backward(x_t_dev, z_dev, d_eps_dev) || !w.join_side()) return tfail(CCN_EHIP, w.err);
     return CCN_OK;
+}
+
+// Test hook, not part of include/ccn_hip.h (ccn_internal_plan_routes' counterpart for the training step): one line per launch decision
+// of the last launching forward walk and the backward walks since, in launch order, taken where the launch is made:
+//   conv fwd|dgrad <KIND> <kernel> th= bn= n_nt= four=     (kernel: conv_kernel_name(conv_kernel_for(..)), or head2)
+//   norm fused|stats+act|prologue|side-fused|side-stats+act slots=
+//   gnbwd C= HW= iters= nblk= tail=                        (pixel passes per workgroup; pixels of the partial last block)
+//   wgrad <KIND> nsplit= tiles= cin= cout=
+//   colsum src=dy|pairs rows= ygrid=
+// A graph replay leaves the captured walk's lines.  snprintf-like: writes at most cap bytes (NUL-terminated) and returns the length of the
+// whole report, or -1.
+int ccn_internal_train_routes(ccn_trainer_t tr, char* buf, size_t cap)
+{
+    if (!tr) return -1;
+    static const char* kinds[] = {"C3S1", "C3S2", "CT4", "STEM", "HEAD"};
+    std::string text;
+    for (const RouteNote& r : tr->route_log) {
+        char line[192];
+        const char* kind = r.kind >= 0 && r.kind < 5 ? kinds[r.kind] : "?";
+        switch (r.what) {
+            case RN_CONV: std::snprintf(line, sizeof(line), "conv %s %s %s th=%d bn=%d n_nt=%d four=%d\n", r.v[0] ? "fwd" : "dgrad", kind, r.name, r.v[1], r.v[2], r.v[3], r.v[4]); break;
+            case RN_NORM: std::snprintf(line, sizeof(line), "norm %s slots=%d\n", r.name, r.v[0]); break;
+            case RN_GNBWD: std::snprintf(line, sizeof(line), "gnbwd C=%d HW=%d iters=%d nblk=%d tail=%d\n", r.v[0], r.v[1], r.v[2], r.v[3], r.v[4]); break;
+            case RN_WGRAD: std::snprintf(line, sizeof(line), "wgrad %s nsplit=%d tiles=%d cin=%d cout=%d\n", kind, r.v[0], r.v[1], r.v[2], r.v[3]); break;
+            default: std::snprintf(line, sizeof(line), "colsum src=%s rows=%d ygrid=%d\n", r.name, r.v[0], r.v[1]); break;
+        }
+        text += line;
+    }
+    if (buf && cap) {
+        const size_t n = text.size() < cap - 1 ? text.size() : cap - 1;
+        std::memcpy(buf, text.data(), n);
+        buf[n] = 0;
+    }
+    return (int)text.size();
 }
 
 int ccn_train_profile_enable(ccn_trainer_t tr, int32_t on)

@@ -684,9 +684,10 @@ __global__ __launch_bounds__(256) void colsum_pair_finalize_kernel(const float2*
         atomicAdd(db + c, (float)t);
     }
 }
+int colsum_finalize_ygrid(int rows) { return rows >= 512 ? 8 : (rows >= 64 ? 4 : 1); }
 hipError_t launch_colsum_from_pairs(const float2* part, int rows, int C, float* db, hipStream_t s)
 {
-    const int chunks = rows >= 512 ? 8 : (rows >= 64 ? 4 : 1);
+    const int chunks = colsum_finalize_ygrid(rows);
     hipLaunchKernelGGL(colsum_pair_finalize_kernel, dim3((C + 15) / 16, chunks), dim3(256), 0, s, part, rows, C, db);
     return hipGetLastError();
 }
@@ -697,7 +698,7 @@ hipError_t launch_colsum(int dtype, const void* dy, float* scratch, float* db, i
     const dim3 grid(g.nblk, B, g.zblocks);
     if (dtype == 0) hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, scratch, HW, C, g.nslb, g.pstep, g.ppb, g.nblk);
     else hipLaunchKernelGGL(colsum_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)dy, scratch, HW, C, g.nslb, g.pstep, g.ppb, g.nblk);
-    hipLaunchKernelGGL(colsum_finalize_kernel, dim3((C + 15) / 16, B * g.nblk >= 512 ? 8 : (B * g.nblk >= 64 ? 4 : 1)), dim3(256), 0, s, scratch, B * g.nblk, C, db);
+    hipLaunchKernelGGL(colsum_finalize_kernel, dim3((C + 15) / 16, colsum_finalize_ygrid(B * g.nblk)), dim3(256), 0, s, scratch, B * g.nblk, C, db);
     return hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE (see oracle/__init__.py): only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may
 import this.  Gradients come from torch autograd applied to the functional forward of oracle/ref_unet.py on the CPU in
-fp32; the optimiser update is restated elementwise.
+fp32 (float64 on request: loss_and_grads(dtype=torch.float64)); the optimiser update is restated elementwise.
 
 Reference lines followed (relative to /root/reference/src/clip_feature_codec/):
   q_sample                 diffusion/scheduler.py:46-49
@@ -14,7 +14,7 @@ Pinned by tests/golden/train_step.npz (made by running the reference's own modul
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -24,12 +24,22 @@ from . import ref_unet, ref_diffusion
 SD = Dict[str, torch.Tensor]
 
 
-def loss_and_grads(sd: SD, x_t: torch.Tensor, z: torch.Tensor, t: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, SD, torch.Tensor]:
-    """mse_loss(unet(x_t, z, t), target), d loss / d every entry of ``sd``, and eps_hat."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in sd.items()}
-    eps = ref_unet.unet_forward(leaves, x_t, z, t)
+def loss_and_grads(sd: SD, x_t: torch.Tensor, z: torch.Tensor, t: torch.Tensor, target: torch.Tensor, dtype: torch.dtype = torch.float32,
+                   temb: Optional[torch.Tensor] = None, d_eps_mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, SD, torch.Tensor]:
+    """mse_loss(unet(x_t, z, t), target), d loss / d every entry of ``sd``, and eps_hat.
+
+    ``dtype=torch.float64``: every leaf, input and intermediate in float64 (the reference the fp32 kernels are measured against).
+    ``temb``: a (B, time_dim) timestep embedding used as given (ref_unet.cond_vector) -- the device's own, for exact-operand comparisons.
+    ``d_eps_mask``: multiplies d loss / d eps_hat before the backward pass (what a backward kernel that skips pixels would see)."""
+    leaves = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in sd.items()}
+    x_t, z, target = x_t.to(dtype), z.to(dtype), target.to(dtype)
+    eps = ref_unet.unet_forward(leaves, x_t, z, t, temb=temb)
     loss = F.mse_loss(eps, target)
-    grads = torch.autograd.grad(loss, list(leaves.values()))
+    if d_eps_mask is None:
+        grads = torch.autograd.grad(loss, list(leaves.values()))
+    else:
+        (d_eps,) = torch.autograd.grad(loss, eps, retain_graph=True)
+        grads = torch.autograd.grad(eps, list(leaves.values()), grad_outputs=d_eps * d_eps_mask.to(dtype))
     return loss.detach(), {k: g for k, g in zip(leaves, grads)}, eps.detach()
 
 

@@ -55,9 +55,11 @@ def timestep_embedding(t: torch.Tensor, dim: int, max_period: int = 10000) -> to
     return emb
 
 
-def cond_vector(sd: SD, z_clip: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+def cond_vector(sd: SD, z_clip: torch.Tensor, t: torch.Tensor, temb: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``temb``: a (B, time_dim) embedding to use instead of ``timestep_embedding(t, time_dim)`` (exact-operand comparisons hand in
+    the one the device computed, so that the rounding of cos / sin at up to 999 rad is not counted against the layers behind it)."""
     time_dim = sd["time_proj.0.weight"].shape[1]
-    temb = timestep_embedding(t, time_dim).to(z_clip.dtype)
+    temb = (timestep_embedding(t, time_dim) if temb is None else temb).to(z_clip.dtype)
     temb = F.linear(F.silu(F.linear(temb, sd["time_proj.0.weight"], sd["time_proj.0.bias"])),
                     sd["time_proj.2.weight"], sd["time_proj.2.bias"])
     zemb = F.silu(F.linear(z_clip, sd["z_proj.0.weight"], sd["z_proj.0.bias"]))
@@ -89,12 +91,12 @@ def resblock(sd: SD, p: str, x: torch.Tensor, h: torch.Tensor, tap: Optional[Cal
 
 
 def unet_forward(sd: SD, x_t: torch.Tensor, z_clip: torch.Tensor, t: torch.Tensor,
-                 tap: Optional[Callable] = None) -> torch.Tensor:
-    """eps_hat = UNet(x_t, z, t).  ``tap(name, tensor)`` receives intermediates."""
+                 tap: Optional[Callable] = None, *, temb: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """eps_hat = UNet(x_t, z, t).  ``tap(name, tensor)`` receives intermediates; ``temb`` replaces the timestep embedding (cond_vector)."""
     n_stage = 0
     while f"down.{3 * n_stage + 2}.weight" in sd:
         n_stage += 1
-    h = cond_vector(sd, z_clip, t)
+    h = cond_vector(sd, z_clip, t, temb)
     if tap:
         tap("h", h)
     x = F.conv2d(x_t, sd["in_conv.weight"], sd["in_conv.bias"], padding=1)
