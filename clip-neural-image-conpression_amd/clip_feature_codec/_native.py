@@ -463,13 +463,19 @@ def diffusion_loss_grad(eps: torch.Tensor, noise: torch.Tensor, x_t: torch.Tenso
     return terms, d
 
 
+def _flat_buffers(p: torch.Tensor, typed: bool = False, **named: torch.Tensor) -> None:
+    """Every optimiser buffer is a contiguous fp32 HIP tensor of ``p.numel()`` elements (``typed``: a non-tensor is a ValueError too)."""
+    for name, tns in named.items():
+        if not ((isinstance(tns, torch.Tensor) or not typed) and tns.is_cuda and tns.dtype == torch.float32 and tns.is_contiguous()
+                and tns.numel() == p.numel()):
+            raise ValueError(f"{name} must be a contiguous fp32 HIP tensor of {p.numel()} elements")
+
+
 def adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float, beta1: float, beta2: float,
                eps: float, weight_decay: float, step: int, zero_grad: bool = False) -> None:
     """One torch.optim.AdamW update over flat fp32 buffers, in place; ``zero_grad``: the gradients are left at zero by the same pass."""
     lib = load_library()
-    for name, tns in (("params", p), ("grads", g), ("exp_avg", m), ("exp_avg_sq", v)):
-        if not (tns.is_cuda and tns.dtype == torch.float32 and tns.is_contiguous() and tns.numel() == p.numel()):
-            raise ValueError(f"{name} must be a contiguous fp32 HIP tensor of {p.numel()} elements")
+    _flat_buffers(p, params=p, grads=g, exp_avg=m, exp_avg_sq=v)
     with torch.cuda.device(p.device):
         fn = lib.ccn_adamw_step_zero_grad if zero_grad else lib.ccn_adamw_step
         check(fn(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(beta1),
@@ -523,9 +529,7 @@ def adamw_step_guarded(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: tor
     """The AdamW update under ``block``'s decision; the gradients are left at zero whether the step is applied or skipped."""
     lib = load_library()
     _guard_block(block)
-    for name, tns in (("params", p), ("grads", g), ("exp_avg", m), ("exp_avg_sq", v)):
-        if not (tns.is_cuda and tns.dtype == torch.float32 and tns.is_contiguous() and tns.numel() == p.numel()):
-            raise ValueError(f"{name} must be a contiguous fp32 HIP tensor of {p.numel()} elements")
+    _flat_buffers(p, params=p, grads=g, exp_avg=m, exp_avg_sq=v)
     with torch.cuda.device(p.device):
         check(lib.ccn_adamw_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(beta1),
                                          float(beta2), float(eps), float(weight_decay), block.data_ptr(), current_stream(p.device)))
@@ -564,10 +568,7 @@ def adamw_step_ema(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.T
     _ema_block(ema_block)
     if guard_block is not None:
         _guard_block(guard_block)
-    for name, tns in (("params", p), ("grads", g), ("exp_avg", m), ("exp_avg_sq", v), ("ema", ema)):
-        if not (isinstance(tns, torch.Tensor) and tns.is_cuda and tns.dtype == torch.float32 and tns.is_contiguous()
-                and tns.numel() == p.numel()):
-            raise ValueError(f"{name} must be a contiguous fp32 HIP tensor of {p.numel()} elements")
+    _flat_buffers(p, typed=True, params=p, grads=g, exp_avg=m, exp_avg_sq=v, ema=ema)
     with torch.cuda.device(p.device):
         check(lib.ccn_adamw_step_ema(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), p.numel(), float(lr),
                                      float(beta1), float(beta2), float(eps), float(weight_decay), int(step), int(bool(zero_grad)),

@@ -287,27 +287,23 @@ class FusedAdamW:
                 self._guard = guard
             _native.grad_guard(fp.grad, block, guard.scratch, max_grad_norm if max_grad_norm is not None else 0.0, self.betas[0],
                                self.betas[1], guard.growth_factor, guard.backoff_factor, guard.growth_interval)
-            if self.ema is not None:
-                _native.adamw_step_ema(fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq, self.ema, self.lr, self.betas[0], self.betas[1],
-                                       self.eps, self.weight_decay, 0, self.ema_decay, self.ema_block, zero_grad=True,
-                                       ema_warmup=self.ema_warmup, guard_block=block)
-            else:
-                _native.adamw_step_guarded(fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
-                                           self.weight_decay, block)
-            fp.flat[:1].add_(0)
-            fp.rebind_grads()
-            return
-        if self._guard is not None:
+            step, zero_grad = 0, True                # the count is the block's; a guarded step consumes the gradients
+        elif self._guard is not None:
             raise RuntimeError("an unguarded step() after a guarded one: the count of applied steps lives in the guard's control block "
                                "(skipped steps do not advance it), keep passing guard= / max_grad_norm=")
-        self.steps += 1
-        if self.ema is not None:
-            _native.adamw_step_ema(fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq, self.ema, self.lr, self.betas[0], self.betas[1], self.eps,
-                                   self.weight_decay, self.steps, self.ema_decay, self.ema_block, zero_grad=zero_grad,
-                                   ema_warmup=self.ema_warmup)
         else:
-            _native.adamw_step(fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
-                               self.weight_decay, self.steps, zero_grad=zero_grad)
+            block = None
+            self.steps += 1
+            step = self.steps
+        bufs = (fp.flat, fp.grad, self.exp_avg, self.exp_avg_sq)
+        hyper = (self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay)
+        if self.ema is not None:
+            _native.adamw_step_ema(*bufs, self.ema, *hyper, step, self.ema_decay, self.ema_block, zero_grad=zero_grad,
+                                   ema_warmup=self.ema_warmup, guard_block=block)
+        elif block is not None:
+            _native.adamw_step_guarded(*bufs, *hyper, block)
+        else:
+            _native.adamw_step(*bufs, *hyper, step, zero_grad=zero_grad)
         fp.flat[:1].add_(0)    # the kernel wrote behind torch's back: bump the (shared) version counter so that a stale forward is detected
         if zero_grad:
             fp.rebind_grads()

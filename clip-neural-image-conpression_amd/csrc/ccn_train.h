@@ -99,31 +99,4 @@ hipError_t launch_tlinear_dx(const float* dy, int lddy, const float* W, float* d
 hipError_t launch_silu_bwd(float* du, const float* dy, const float* u, int64_t n, hipStream_t s);
 hipError_t launch_add2(float* y, const float* a, const float* b, int64_t n, hipStream_t s);
 
-// ---- loss and optimiser ---------------------------------------------------------------------------------------------------
-// loss = mean((eps - target)^2) (F.mse_loss, train/diffusion_train.py:124); d_eps = 2 (eps - target) / n; scratch >= 1024 floats
-hipError_t launch_mse_loss_grad(const float* eps, const float* target, int64_t n, float* loss, float* d_eps, float* scratch, hipStream_t s);
-// the reference's default objective (train/diffusion_train.py:124-129): mse + recon_w L1(x0_pred, x0) + tv_w TV(x0_pred) with
-// x0_pred = clamp((x_t - s eps) / a, -1, 1) recomputed per tile; loss[4] = total, mse, l1, tv; scratch >= 8192 floats, 8-byte aligned.
-// recon_w == tv_w == 0 runs launch_mse_loss_grad itself.
-hipError_t launch_diffusion_loss_grad(const float* eps, const float* noise, const float* xt, const float* x0, const float* a, const float* sg,
-                                      int B, int C, int H, int W, float recon_w, float tv_w, float* loss, float* d_eps, float* scratch,
-                                      hipStream_t s);
-// torch.optim.AdamW step (train/diffusion_train.py:105,138): decoupled weight decay, bias-corrected moments
-hipError_t launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
-                        int step, hipStream_t s, bool zero_grad = false);
-// the step guard of train/diffusion_train.py:137-139 (GradScaler + clip_grad_norm_); `guard` is a ccn_step_guard_t in device memory
-// (include/ccn_hip.h).  scratch >= GUARD_MAX_WG doubles.
-constexpr int GUARD_MAX_WG = 2048;
-hipError_t launch_step_guard_init(void* guard, float scale, int tracker, int good, int skipped, hipStream_t s);
-hipError_t launch_grad_guard(const float* g, int64_t n, void* guard, float max_norm, float b1, float b2, float growth, float backoff,
-                             int interval, double* scratch, hipStream_t s);
-hipError_t launch_adamw_guarded(float* p, float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
-                                const void* guard, hipStream_t s);
-// weight EMA fused into the AdamW pass (torch.optim.swa_utils.AveragedModel + get_ema_multi_avg_fn): `ema_state` is a ccn_ema_state_t
-// in device memory, `guard` NULL or the block launch_grad_guard has just written; w = 1 - decay in fp32.  Two launches: the one-wave
-// tick that writes `ema_state`, then the fused pass (launch_adamw's arithmetic without a guard, launch_adamw_guarded's with one).
-hipError_t launch_ema_init(void* ema_state, int updates, hipStream_t s);
-hipError_t launch_adamw_ema(float* p, float* g, float* m, float* v, float* ema, int64_t n, float lr, float b1, float b2, float eps, float wd,
-                            int step, bool zero_grad, float w, bool warmup, const void* guard, void* ema_state, hipStream_t s);
-
 }  // namespace ccn

@@ -1,4 +1,5 @@
-// Host side of the training step: ccn_train_* of include/ccn_hip.h.
+// Host side of the training step: ccn_train_* of include/ccn_hip.h, everything that works on a ccn_trainer_t.  (The loss, the step
+// guard, AdamW and the EMA take raw buffers and no handle: ccn_optim.hip.)
 //
 // Reference: the loop body of train/diffusion_train.py:119-124,137-140 -- eps_hat = net(x_t, z, t); loss = mse(eps_hat, noise);
 // loss.backward(); opt.step().  ccn_train_forward is CLIPCondUNet.forward (models/unet.py:81-106) with every tensor the
@@ -1139,114 +1140,6 @@ int ccn_train_profile_read(ccn_trainer_t tr, const char** names, float* ms, int3
     }
     *n = TF_COUNT;
     tr->marks.clear(); tr->ev_used = 0;
-    return CCN_OK;
-}
-
-int ccn_mse_loss_grad(const float* eps_dev, const float* target_dev, int64_t n, float* loss_dev, float* d_eps_dev, float* scratch_dev, void* stream)
-{
-    if (!eps_dev || !target_dev || !loss_dev || !scratch_dev || n <= 0) return tfail(CCN_EINVAL, "bad argument");
-    if (launch_mse_loss_grad(eps_dev, target_dev, n, loss_dev, d_eps_dev, scratch_dev, (hipStream_t)stream) != hipSuccess) return tfail(CCN_EHIP, "mse launch failed");
-    return CCN_OK;
-}
-
-int ccn_diffusion_loss_grad(const float* eps_dev, const float* noise_dev, const float* x_t_dev, const float* x0_dev, const float* a_dev,
-                            const float* s_dev, int32_t B, int32_t C, int32_t H, int32_t W, float recon_w, float tv_w, float* loss_dev,
-                            float* d_eps_dev, float* scratch_dev, void* stream)
-{
-    if (!eps_dev || !noise_dev || !x_t_dev || !x0_dev || !a_dev || !s_dev || !loss_dev || !scratch_dev || B <= 0 || C <= 0)
-        return tfail(CCN_EINVAL, "bad argument");
-    if (H < 2 || W < 2) return tfail(CCN_EINVAL, "H and W must be at least 2 (the total variation of a one-pixel-wide image is a mean over nothing)");
-    if (!(recon_w >= 0.f) || !(tv_w >= 0.f)) return tfail(CCN_EINVAL, "recon_w and tv_w must be non-negative");
-    if (((uintptr_t)scratch_dev & 7) != 0) return tfail(CCN_EINVAL, "scratch_dev must be 8-byte aligned");
-    if ((int64_t)B * C * H * W > (int64_t)1 << 40) return tfail(CCN_EINVAL, "tensor too large");
-    if (launch_diffusion_loss_grad(eps_dev, noise_dev, x_t_dev, x0_dev, a_dev, s_dev, B, C, H, W, recon_w, tv_w, loss_dev, d_eps_dev, scratch_dev,
-                                   (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "objective launch failed");
-    return CCN_OK;
-}
-
-int ccn_adamw_step(float* params_dev, const float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n, float lr, float beta1, float beta2,
-                   float eps, float weight_decay, int32_t step, void* stream)
-{
-    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || n <= 0 || step <= 0) return tfail(CCN_EINVAL, "bad argument");
-    if (launch_adamw(params_dev, grads_dev, exp_avg_dev, exp_avg_sq_dev, n, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "adamw launch failed");
-    return CCN_OK;
-}
-
-int ccn_adamw_step_zero_grad(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n, float lr, float beta1, float beta2,
-                   float eps, float weight_decay, int32_t step, void* stream)
-{
-    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || n <= 0 || step <= 0) return tfail(CCN_EINVAL, "bad argument");
-    if (launch_adamw(params_dev, grads_dev, exp_avg_dev, exp_avg_sq_dev, n, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream, true) != hipSuccess)
-        return tfail(CCN_EHIP, "adamw launch failed");
-    return CCN_OK;
-}
-
-int ccn_step_guard_init(void* guard_dev, float init_scale, int32_t growth_tracker0, int32_t good_steps0, int32_t skipped_steps0, void* stream)
-{
-    if (!guard_dev || ((uintptr_t)guard_dev & 3) != 0) return tfail(CCN_EINVAL, "guard_dev must be a 4-byte aligned device pointer");
-    if (!(init_scale > 0.f) || init_scale - init_scale != 0.f) return tfail(CCN_EINVAL, "init_scale must be positive and finite");
-    if (growth_tracker0 < 0 || good_steps0 < 0 || skipped_steps0 < 0) return tfail(CCN_EINVAL, "counters must be non-negative");
-    if (launch_step_guard_init(guard_dev, init_scale, growth_tracker0, good_steps0, skipped_steps0, (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "step guard init launch failed");
-    return CCN_OK;
-}
-
-int ccn_grad_guard(const float* grads_dev, int64_t n, void* guard_dev, float max_grad_norm, float beta1, float beta2, float growth_factor,
-                   float backoff_factor, int32_t growth_interval, float* scratch_dev, void* stream)
-{
-    if (!grads_dev || !guard_dev || !scratch_dev || n <= 0) return tfail(CCN_EINVAL, "bad argument");
-    if (((uintptr_t)grads_dev & 3) != 0 || ((uintptr_t)guard_dev & 3) != 0) return tfail(CCN_EINVAL, "grads_dev and guard_dev must be 4-byte aligned");
-    if (((uintptr_t)scratch_dev & 7) != 0) return tfail(CCN_EINVAL, "scratch_dev must be 8-byte aligned");
-    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return tfail(CCN_EINVAL, "betas must be in [0, 1)");
-    if (!(growth_factor > 0.f) || !(backoff_factor > 0.f) || growth_interval <= 0)
-        return tfail(CCN_EINVAL, "growth_factor, backoff_factor and growth_interval must be positive");
-    if (max_grad_norm != max_grad_norm) return tfail(CCN_EINVAL, "max_grad_norm is NaN");
-    if (launch_grad_guard(grads_dev, n, guard_dev, max_grad_norm, beta1, beta2, growth_factor, backoff_factor, growth_interval,
-                          (double*)scratch_dev, (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "grad guard launch failed");
-    return CCN_OK;
-}
-
-int ccn_adamw_step_guarded(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n, float lr, float beta1,
-                           float beta2, float eps, float weight_decay, const void* guard_dev, void* stream)
-{
-    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || !guard_dev || n <= 0) return tfail(CCN_EINVAL, "bad argument");
-    if ((((uintptr_t)params_dev | (uintptr_t)grads_dev | (uintptr_t)exp_avg_dev | (uintptr_t)exp_avg_sq_dev | (uintptr_t)guard_dev) & 3) != 0)
-        return tfail(CCN_EINVAL, "buffers must be 4-byte aligned");
-    if (launch_adamw_guarded(params_dev, grads_dev, exp_avg_dev, exp_avg_sq_dev, n, lr, beta1, beta2, eps, weight_decay, guard_dev,
-                             (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "guarded adamw launch failed");
-    return CCN_OK;
-}
-
-int ccn_ema_init(void* ema_state_dev, int32_t updates0, void* stream)
-{
-    if (!ema_state_dev || ((uintptr_t)ema_state_dev & 3) != 0) return tfail(CCN_EINVAL, "ema_state_dev must be a 4-byte aligned device pointer");
-    if (updates0 < 0) return tfail(CCN_EINVAL, "updates0 must be non-negative");
-    if (launch_ema_init(ema_state_dev, updates0, (hipStream_t)stream) != hipSuccess) return tfail(CCN_EHIP, "ema init launch failed");
-    return CCN_OK;
-}
-
-int ccn_adamw_step_ema(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* ema_dev, int64_t n, float lr,
-                       float beta1, float beta2, float eps, float weight_decay, int32_t step, int32_t zero_grad, double ema_decay,
-                       int32_t ema_warmup, const void* guard_dev, void* ema_state_dev, void* stream)
-{
-    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || !ema_dev || !ema_state_dev)
-        return tfail(CCN_EINVAL, "a buffer or the EMA state block is NULL");
-    if (n < 0) return tfail(CCN_EINVAL, "n is negative");
-    if (!(ema_decay >= 0.0 && ema_decay < 1.0)) return tfail(CCN_EINVAL, "ema_decay must be in [0, 1)");
-    if (guard_dev && !zero_grad) return tfail(CCN_EINVAL, "a guarded step consumes the gradients: zero_grad must be non-zero with guard_dev");
-    if (!guard_dev && step <= 0) return tfail(CCN_EINVAL, "step must be at least 1 without guard_dev");
-    if ((((uintptr_t)params_dev | (uintptr_t)grads_dev | (uintptr_t)exp_avg_dev | (uintptr_t)exp_avg_sq_dev | (uintptr_t)ema_dev |
-          (uintptr_t)guard_dev | (uintptr_t)ema_state_dev) & 3) != 0)
-        return tfail(CCN_EINVAL, "buffers must be 4-byte aligned");
-    if (n == 0) return CCN_OK;                       // nothing to average: no launch, the count of updates stays
-    const float w = (float)(1.0 - ema_decay);        // the weight get_ema_multi_avg_fn(decay) hands to lerp_, rounded once to fp32
-    if (launch_adamw_ema(params_dev, grads_dev, exp_avg_dev, exp_avg_sq_dev, ema_dev, n, lr, beta1, beta2, eps, weight_decay, step,
-                         zero_grad != 0, w, ema_warmup != 0, guard_dev, ema_state_dev, (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "adamw + ema launch failed");
     return CCN_OK;
 }
 

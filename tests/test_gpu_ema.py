@@ -27,7 +27,7 @@ GW = _native.GUARD_WORD
 EW = _native.EMA_WORD
 PAD = 4                   # floats of padding before and after every buffer's range
 SENTINEL = 7.0
-GRID_CAP = 8192           # launch_adamw_ema's cap: workgroups of 256 threads, one 16-byte quad of each buffer per thread and trip
+GRID_CAP = 8192           # launch_adamw's cap: workgroups of 256 threads, one 16-byte quad of each buffer per thread and trip
 N_BIG = 4 * (GRID_CAP * 256 * 2 + 77) + 3          # two trips of the capped grid plus a ragged rest
 Z5 = (0, 0, 0, 0, 0)
 # (n, element offsets of p, g, m, v, ema off their 16-byte boundary): equal offsets keep the 16-byte kernel (with a scalar head),

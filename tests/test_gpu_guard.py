@@ -24,7 +24,7 @@ DEV = "cuda:0"
 GOLD = np.load(ROOT / "tests" / "golden" / "train_step.npz")
 H = guard_ref.HYPER
 W = _native.GUARD_WORD
-GRID_CAP = 2048          # GUARD_MAX_WG of csrc/ccn_train.h: workgroups of 256 threads, one 16-byte quad per thread and trip
+GRID_CAP = 2048          # GUARD_MAX_WG of csrc/ccn_optim.hip: workgroups of 256 threads, one 16-byte quad per thread and trip
 # 9 trips of the capped grid plus a ragged rest: the four-loads-in-flight loop and the single-load loop behind it both run twice
 N_BIG = 4 * (GRID_CAP * 256 * 9 + 77) + 3
 

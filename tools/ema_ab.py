@@ -13,8 +13,8 @@ optimiser:
 Prints ms per step of every round, the median / min / max per arm, and ema_fused - plain / ema_torch - plain in microseconds next to
 their floors at the measured 6.29 TB/s copy rate: 2 x 4 bytes per parameter fused, 3 x 4 bytes plus a launch
 for the separate pass.
---trace: the optimiser tail of ONE step of each arm from HIP events around the launches (synchronising; lr = 0 and zero gradients,
-so the parameters stay put).
+--trace: the optimiser tail of ONE step from HIP events around the launches (synchronising; lr = 0 and zero gradients, so the
+parameters stay put): every AdamW entry point -- plain, with the EMA, under a guard (with and without the guard's own reduction), both.
 """
 import argparse
 import statistics
@@ -60,13 +60,30 @@ def trace(opt, decay):
         _native.adamw_step_ema(fp.flat, fp.grad, opt.exp_avg, opt.exp_avg_sq, opt.ema, 0.0, b1, b2, opt.eps, 0.0, 1, decay, opt.ema_block,
                                zero_grad=True)
 
-    rows = [("ccn_adamw_step_zero_grad (plain tail)", plain), ("ccn_adamw_step_ema (tick + fused pass)", fused),
+    block = torch.zeros(_native.GUARD_WORDS, dtype=torch.int32, device=fp.flat.device)
+    scratch = torch.empty(_native.GUARD_SCRATCH_FLOATS, device=fp.flat.device)
+    _native.step_guard_init(block, 1.0)
+
+    def guard():
+        _native.grad_guard(fp.grad, block, scratch, 1.0, b1, b2, 2.0, 0.5, 2000)
+
+    def guarded():
+        _native.adamw_step_guarded(fp.flat, fp.grad, opt.exp_avg, opt.exp_avg_sq, 0.0, b1, b2, opt.eps, 0.0, block)
+
+    def guarded_fused():
+        _native.adamw_step_ema(fp.flat, fp.grad, opt.exp_avg, opt.exp_avg_sq, opt.ema, 0.0, b1, b2, opt.eps, 0.0, 0, decay, opt.ema_block,
+                               zero_grad=True, guard_block=block)
+
+    rows = [("ccn_adamw_step (plain tail, keeps g)", lambda: _native.adamw_step(fp.flat, fp.grad, opt.exp_avg, opt.exp_avg_sq, 0.0, b1, b2, opt.eps, 0.0, 1)),
+            ("ccn_adamw_step_zero_grad (plain tail)", plain), ("ccn_adamw_step_ema (tick + fused pass)", fused),
+            ("ccn_grad_guard + ccn_adamw_step_guarded", lambda: (guard(), guarded())), ("ccn_adamw_step_guarded alone", guarded),
+            ("ccn_grad_guard + ccn_adamw_step_ema", lambda: (guard(), guarded_fused())), ("ccn_adamw_step_ema under a guard, alone", guarded_fused),
             ("ema.lerp_(flat, w) alone", lambda: opt.ema.lerp_(fp.flat, w)),
             ("plain tail + lerp_ back to back", lambda: (plain(), opt.ema.lerp_(fp.flat, w)))]
     n = fp.grad.numel()
     print(f"launch by launch ({n} parameters, {n * 4 / 1e6:.1f} MB per pass over one buffer; lr = 0 so the parameters stay put):")
     for name, fn in rows:
-        print(f"  {name:40s} {timed(fn):8.1f} us")
+        print(f"  {name:42s} {timed(fn):8.1f} us")
 
 
 def main():
