@@ -1,6 +1,8 @@
 // Host side of libccn_hip.so: the C ABI of include/ccn_hip.h.
 //
-// A handle owns the repacked weights of one CLIPCondUNet.  ccn_forward / ccn_sample build (once per
+// A handle owns the repacked weights of one CLIPCondUNet: build_arch's description of the network (ccn_arch.h, shared with the
+// training handle) plus, per conv, the committed operands in every weight version (ConvW).  ccn_commit_params walks the conv list
+// once, one weight version at a time.  ccn_forward / ccn_sample build (once per
 // shape and workspace address) a *plan*: the fixed list of kernel launches of one UNet evaluation with
 // every activation, GroupNorm partial-sum and scale/shift buffer placed in the caller's workspace.
 // ccn_sample replays the plan `steps` times -- conditioning (timestep MLP, z projection, all FiLM
@@ -8,6 +10,7 @@
 // (diffusion/ddim.py:25,32) -- either launch by launch or as one captured hipGraph.
 #include "../../include/ccn_hip.h"
 #include "ccn_internal.h"
+#include "ccn_arch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -50,36 +53,24 @@ uint16_t f2bf_host(float f)
     return (uint16_t)(u >> 16);
 }
 
-struct ParamInfo {
-    std::string name;
-    std::vector<int64_t> shape;
-    size_t numel() const { size_t n = 1; for (auto d : shape) n *= (size_t)d; return n; }
-};
-
-struct ConvW {
-    int kind = KIND_C3S1;
-    int Cin = 0, Cout = 0, Cin_pad = 0, Cout_pad = 0, BN = 0, ntaps_w = 0;
+// a conv of the description (ccn_arch.h) and its committed operands
+struct ConvW : ArchConv {
+    ConvW() {}
+    ConvW(const ArchConv& c) : ArchConv(c) {}
+    int Cin_pad = 0, Cout_pad = 0, BN = 0, ntaps_w = 0;
     void* w = nullptr;
     void* wfrag = nullptr;      // MFMA-fragment-ordered copy for the persistent 3x3 kernel (Cout_pad % 128 == 0), else null
     float* bias = nullptr;
     bool split = false;         // f16x3 mode, layers on the ws / fr kernels: `w` holds fp16 hi + lo rows of the weights times 1 / inv_scale
     float inv_scale = 1.f;
     // bf16 mode, CCN_ROUND_DIFFUSED_PHASES: further roundings of the same weights, used by DDIM step i as version i % nphase
-    // (version 0 = w / wfrag above); see diffuse_round_phases()
+    // (version 0 = w / wfrag above); see round_version()
     int nphase = 1;
     void* w_ph[7] = {};
     void* wfrag_ph[7] = {};
 };
 struct NormW { int C = 0; float* gamma = nullptr; float* beta = nullptr; };
-struct ResW {
-    std::string prefix;
-    int C = 0;
-    NormW n1, n2;
-    ConvW c1, c2;
-    int film_off = 0;   // row offset into the concatenated FiLM linear: [off, off+C) scale, [off+C, off+2C) shift
-};
-enum LType { L_STEM, L_RES, L_DOWN, L_UP, L_HEAD };
-struct Layer { LType type; std::string name; int idx; };
+struct ResW { NormW n1, n2; };
 
 struct TensorRef {
     void* p = nullptr;
@@ -172,24 +163,20 @@ struct ccn_handle_s {
     ccn_config_t cfg{};                 // (dtype: the STORAGE type; CCN_DTYPE_F16X3 is fp32 storage with `split` set)
     bool split = false;                 // CCN_DTYPE_F16X3: the ws / fr layers multiply fp16 hi + lo operand rows
     int elem = 4;                       // bytes per activation / weight element
-    std::vector<ParamInfo> params;
-    std::map<std::string, std::vector<float>> host;   // loaded fp32 copies until commit
+    Arch arch;                          // parameters, convs, ResBlocks, layer list: build_arch, ccn_arch.h
+    std::map<std::string, std::vector<float>> host;   // loaded fp32 copies until commit (ccn_commit_params only reads them)
     bool committed = false;
     std::vector<void*> dev_allocs;
-    // model
-    ConvW stem, head;
-    NormW out_norm;
+    // model: device state per arch.convs / arch.res entry
+    std::vector<ConvW> convs;
     std::vector<ResW> res;
-    std::vector<ConvW> downs, ups;
-    std::vector<Layer> layers;
+    NormW out_norm;
     float *tp0_w = nullptr, *tp0_b = nullptr, *tp2_w = nullptr, *tp2_b = nullptr, *zp_w = nullptr, *zp_b = nullptr;
     float *film_w = nullptr, *film_b = nullptr;
     float* head_w_f32 = nullptr;       // (img_ch, C, 3, 3) fp32 copy of out.weight for the dedicated head kernel
-    int F = 0;                          // rows of the concatenated FiLM linear
     int G = 8;
     int weight_rounding = CCN_ROUND_DIFFUSED_PHASES;   // how bf16 mode rounds the conv weights in ccn_commit_params (ccn_set_weight_rounding)
-    std::map<std::string, std::vector<float>> host_ph[7];   // versions 1.. of the rounded conv weights until commit
-    int nphase = 1;                                     // versions per conv weight of the committed model (diffuse_round_phases)
+    int nphase = 1;                                     // versions per conv weight of the committed model (round_version)
     std::vector<std::unique_ptr<Plan>> plans;
     hipStream_t cap_stream = nullptr;
     unsigned* err_host = nullptr;       // pinned, device-mapped error word the kernels OR into (ConvArgs::err)
@@ -205,62 +192,6 @@ struct ccn_handle_s {
 
 namespace {
 
-// ---- architecture -> parameter list (models/unet.py:45-79 registration order) -------------------------
-void add_res_params(std::vector<ParamInfo>& v, const std::string& p, int c, int d)
-{
-    v.push_back({p + ".norm1.weight", {c}}); v.push_back({p + ".norm1.bias", {c}});
-    v.push_back({p + ".conv1.weight", {c, c, 3, 3}}); v.push_back({p + ".conv1.bias", {c}});
-    v.push_back({p + ".norm2.weight", {c}}); v.push_back({p + ".norm2.bias", {c}});
-    v.push_back({p + ".conv2.weight", {c, c, 3, 3}}); v.push_back({p + ".conv2.bias", {c}});
-    v.push_back({p + ".film.to_scale.weight", {c, d}}); v.push_back({p + ".film.to_scale.bias", {c}});
-    v.push_back({p + ".film.to_shift.weight", {c, d}}); v.push_back({p + ".film.to_shift.bias", {c}});
-}
-
-void build_arch(ccn_handle_s* h)
-{
-    const ccn_config_t& c = h->cfg;
-    auto& v = h->params;
-    const int td = c.time_dim;
-    v.push_back({"time_proj.0.weight", {td * 4, td}}); v.push_back({"time_proj.0.bias", {td * 4}});
-    v.push_back({"time_proj.2.weight", {td, td * 4}}); v.push_back({"time_proj.2.bias", {td}});
-    v.push_back({"z_proj.0.weight", {td, c.z_dim}}); v.push_back({"z_proj.0.bias", {td}});
-    v.push_back({"in_conv.weight", {c.base, c.img_ch, 3, 3}}); v.push_back({"in_conv.bias", {c.base}});
-    h->layers.push_back({L_STEM, "in_conv", 0});
-    int ch = c.base, film_off = 0;
-    auto add_res = [&](const std::string& name, int cc) {
-        add_res_params(v, name, cc, td);
-        ResW r; r.prefix = name; r.C = cc; r.film_off = film_off; film_off += 2 * cc;
-        h->res.push_back(r);
-        h->layers.push_back({L_RES, name, (int)h->res.size() - 1});
-    };
-    for (int i = 0; i < c.n_mult; ++i) {
-        const int m = c.ch_mult[i];
-        add_res("down." + std::to_string(3 * i), ch);
-        add_res("down." + std::to_string(3 * i + 1), ch);
-        const std::string dn = "down." + std::to_string(3 * i + 2);
-        v.push_back({dn + ".weight", {ch * m, ch, 3, 3}}); v.push_back({dn + ".bias", {ch * m}});
-        ConvW d; d.kind = KIND_C3S2; d.Cin = ch; d.Cout = ch * m; h->downs.push_back(d);
-        h->layers.push_back({L_DOWN, dn, i});
-        ch *= m;
-    }
-    add_res("mid1", ch);
-    add_res("mid2", ch);
-    for (int i = 0; i < c.n_mult; ++i) {
-        const int m = c.ch_mult[c.n_mult - 1 - i];
-        add_res("up." + std::to_string(3 * i), ch);
-        add_res("up." + std::to_string(3 * i + 1), ch);
-        const std::string un = "up." + std::to_string(3 * i + 2);
-        v.push_back({un + ".weight", {ch, ch / m, 4, 4}}); v.push_back({un + ".bias", {ch / m}});
-        ConvW u; u.kind = KIND_CT4; u.Cin = ch; u.Cout = ch / m; h->ups.push_back(u);
-        h->layers.push_back({L_UP, un, i});
-        ch /= m;
-    }
-    v.push_back({"out_norm.weight", {ch}}); v.push_back({"out_norm.bias", {ch}});
-    v.push_back({"out.weight", {c.img_ch, ch, 3, 3}}); v.push_back({"out.bias", {c.img_ch}});
-    h->layers.push_back({L_HEAD, "out", 0});
-    h->F = film_off;
-}
-
 // ---- weight repacking ------------------------------------------------------------------------------------
 int upload(ccn_handle_s* h, const void* src, size_t bytes, void** dst)
 {
@@ -271,9 +202,10 @@ int upload(ccn_handle_s* h, const void* src, size_t bytes, void** dst)
     *dst = p;
     return CCN_OK;
 }
-int upload_f32(ccn_handle_s* h, const std::string& name, float** dst)
+const std::vector<float>& host_param(const ccn_handle_s* h, int i) { return h->host.at(h->arch.params[i].name); }
+int upload_f32(ccn_handle_s* h, int param, float** dst)
 {
-    const auto& v = h->host.at(name);
+    const auto& v = host_param(h, param);
     return upload(h, v.data(), v.size() * 4, (void**)dst);
 }
 
@@ -293,14 +225,14 @@ float bf16_value(float f)
 // walk over K = 9 Cin roundings, the same way in all 50 steps, and the reconstructions lose 0.33 % contrast (+0.11 % PSNR against
 // the fp32 mode, above north_star's 0.1 % gate; tools/weight_rounding_probe.py, profiles/r03_weight_rounding_probe.txt).  With
 // diffusion the same bf16 kernels land within 0.04 % mean / 0.075 % max.  Costs nothing at run time: the values are ordinary bf16.
-// The weights are replaced IN PLACE by bf16-representable fp32 values, so every packer below rounds them exactly.
+// `w` is replaced by bf16-representable fp32 values, so every packer below rounds them exactly.
 // ConvTranspose2d (Cin, Cout, 4, 4): an output pixel of parity (py, px) sees only 4 of the 16 taps (ky in {1,3} or {0,2}), so the
 // diffusion runs per (output channel, parity) over (cin, those 4 taps).
-void diffuse_round_conv(std::vector<float>& w, int O, int I, int taps)        // Conv2d (O, I, k, k)
+void diffuse_round_conv(float* w, int O, int I, int taps)                     // Conv2d (O, I, k, k)
 {
     for (int o = 0; o < O; ++o) {
         double err = 0.0;
-        float* row = w.data() + (size_t)o * I * taps;
+        float* row = w + (size_t)o * I * taps;
         for (size_t k = 0; k < (size_t)I * taps; ++k) {
             const double t = (double)row[k] + err;
             const float r = bf16_value((float)t);
@@ -309,7 +241,7 @@ void diffuse_round_conv(std::vector<float>& w, int O, int I, int taps)        //
         }
     }
 }
-void diffuse_round_convT(std::vector<float>& w, int I, int O)                 // ConvTranspose2d (I, O, 4, 4), stride 2, padding 1
+void diffuse_round_convT(float* w, int I, int O)                              // ConvTranspose2d (I, O, 4, 4), stride 2, padding 1
 {
     static const int kk2[2][2] = {{1, 3}, {0, 2}};                            // kernel indices feeding even / odd outputs (fill_taps)
     for (int o = 0; o < O; ++o)
@@ -341,47 +273,30 @@ void diffuse_round_convT(std::vector<float>& w, int I, int O)                 //
 int phases_for(const ccn_handle_s* h)
 {
     size_t total = 0;
-    for (auto& p : h->params) if (p.shape.size() == 4) total += p.numel();
+    for (auto& p : h->arch.params) if (p.shape.size() == 4) total += p.numel();
     return total > (size_t)100000000 ? 4 : 8;
 }
-void diffuse_round_phases(ccn_handle_s* h, const ParamInfo& p)
+// Version k of one conv weight, the one implementation of the recurrence above: out = round((k + 1) w - sum), then sum += out.
+// `sum` is the float64 running sum W_0 + ... + W_{k-1} (zeros for k = 0, where the operand is w itself: the plain CCN_ROUND_DIFFUSED
+// rounding).  `w` is a Conv2d (O, I, taps) or -- convT -- a ConvTranspose2d (I, O, 4, 4) weight of n elements and is only read.
+void round_version(const float* w, size_t n, bool convT, int O, int I, int taps, int k, double* sum, float* out)
 {
-    auto& w0 = h->host.at(p.name);
-    const std::vector<float> orig = w0;
-    const bool convT = p.shape[2] == 4;
-    auto round_one = [&](std::vector<float>& w) {
-        if (convT) diffuse_round_convT(w, (int)p.shape[0], (int)p.shape[1]);
-        else diffuse_round_conv(w, (int)p.shape[0], (int)p.shape[1], (int)(p.shape[2] * p.shape[3]));
-    };
-    round_one(w0);
-    std::vector<double> sum(orig.size());
-    for (size_t i = 0; i < orig.size(); ++i) sum[i] = (double)w0[i];
-    for (int k = 1; k < h->nphase; ++k) {
-        std::vector<float> wk(orig.size());
-        for (size_t i = 0; i < orig.size(); ++i) wk[i] = (float)((double)(k + 1) * (double)orig[i] - sum[i]);
-        round_one(wk);
-        for (size_t i = 0; i < orig.size(); ++i) sum[i] += (double)wk[i];
-        h->host_ph[k - 1][p.name] = std::move(wk);
-    }
+    for (size_t i = 0; i < n; ++i) out[i] = (float)((double)(k + 1) * (double)w[i] - sum[i]);
+    if (convT) diffuse_round_convT(out, I, O); else diffuse_round_conv(out, O, I, taps);
+    for (size_t i = 0; i < n; ++i) sum[i] += (double)out[i];
 }
 
 }  // namespace
 // Host-only arithmetic of the bf16 weight rounding, exported for tests/test_host_logic.py (not part of include/ccn_hip.h; no GPU
 // involved): `w` is a Conv2d (O, I, taps) or -- convT != 0 -- a ConvTranspose2d (I, O, 4, 4) weight; out[p] receives version p of
-// `phases` versions (phases == 1: the plain error-diffused rounding), each bf16-representable fp32.
+// `phases` versions (phases == 1: the plain error-diffused rounding), each bf16-representable fp32.  The versions come from
+// round_version, the routine ccn_commit_params packs from.
 extern "C" int ccn_internal_round_weights(const float* w, int O, int I, int taps, int convT, int phases, float* out)
 {
     if (!w || !out || O <= 0 || I <= 0 || phases < 1 || phases > 8 || (convT && taps != 16)) return 1;
     const size_t n = (size_t)O * I * taps;
-    std::vector<float> orig(w, w + n);
     std::vector<double> sum(n, 0.0);
-    for (int k = 0; k < phases; ++k) {
-        std::vector<float> wk(n);
-        for (size_t i = 0; i < n; ++i) wk[i] = (float)((double)(k + 1) * (double)orig[i] - sum[i]);
-        if (convT) diffuse_round_convT(wk, I, O); else diffuse_round_conv(wk, O, I, taps);
-        for (size_t i = 0; i < n; ++i) sum[i] += (double)wk[i];
-        std::memcpy(out + (size_t)k * n, wk.data(), n * 4);
-    }
+    for (int k = 0; k < phases; ++k) round_version(w, n, convT != 0, O, I, taps, k, sum.data(), out + (size_t)k * n);
     return 0;
 }
 // f16x3: the commit-time split of one weight tensor, exported for tests/test_split_host.py (not part of include/ccn_hip.h; no GPU
@@ -408,9 +323,12 @@ extern "C" int ccn_internal_split_weights(const float* w, size_t n, float* scale
 }
 namespace {
 
+// The packers: one version of a conv's weights `w` (fp32, the layout of its parameter) into the operand layouts of its kernels.
+// The device pointers go to *dw (every kernel's [taps][Cout_pad][Cin_pad] operand) and *dfrag (fragment order of the persistent /
+// register-weight kernels, where the layer has one); the operand geometry goes into `cw`, the same for every version.
 // element (tap, o, i) of the packed [taps][Cout_pad][Cin_pad] tensor
 template <typename F>
-int pack_and_upload(ccn_handle_s* h, ConvW& cw, int taps, F&& at)
+int pack_and_upload(ccn_handle_s* h, ConvW& cw, int taps, F&& at, void** dw)
 {
     cw.BN = conv_bn_for(cw.Cout, cw.kind);
     cw.Cout_pad = (int)align_up(cw.Cout, cw.BN);
@@ -421,7 +339,7 @@ int pack_and_upload(ccn_handle_s* h, ConvW& cw, int taps, F&& at)
         for (int t = 0; t < taps; ++t)
             for (int o = 0; o < cw.Cout; ++o)
                 for (int i = 0; i < cw.Cin_pad; ++i) buf[((size_t)t * cw.Cout_pad + o) * cw.Cin_pad + i] = f2bf_host(at(t, o, i));
-        return upload(h, buf.data(), n * 2, &cw.w);
+        return upload(h, buf.data(), n * 2, dw);
     }
     std::vector<float> buf(n, 0.f);
     for (int t = 0; t < taps; ++t)
@@ -441,18 +359,17 @@ int pack_and_upload(ccn_handle_s* h, ConvW& cw, int taps, F&& at)
             rows[row * 64 + c] = hi[i];
             rows[row * 64 + 32 + c] = lo[i];
         }
-        return upload(h, rows.data(), n * 4, &cw.w);
+        return upload(h, rows.data(), n * 4, dw);
     }
-    return upload(h, buf.data(), n * 4, &cw.w);
+    return upload(h, buf.data(), n * 4, dw);
 }
 
-int pack_conv3(ccn_handle_s* h, ConvW& cw, const std::string& name)     // Conv2d weight (O, I, 3, 3)
+int pack_conv3(ccn_handle_s* h, ConvW& cw, const float* w, void** dw, void** dfrag)     // Conv2d weight (O, I, 3, 3)
 {
-    const float* w = h->host.at(name + ".weight").data();
     const int cke = conv_cin_chunk(h->cfg.dtype);
     cw.Cin_pad = (int)align_up(cw.Cin, cke);
     const int I = cw.Cin;
-    int rc = pack_and_upload(h, cw, 9, [&](int t, int o, int i) { return i < I ? w[((size_t)o * I + i) * 9 + t] : 0.f; });
+    int rc = pack_and_upload(h, cw, 9, [&](int t, int o, int i) { return i < I ? w[((size_t)o * I + i) * 9 + t] : 0.f; }, dw);
     if (rc) return rc;
     if (cw.kind == KIND_C3S2 && cw.BN == 128 && h->cfg.dtype == CCN_DTYPE_BF16) {
         // plane-pass order for the persistent kernel (ccn_conv_pr.hip, NTAPS == 2): prs2_frag_index / prs2_tap (ccn_internal.h), the tenth
@@ -465,7 +382,7 @@ int pack_conv3(ccn_handle_s* h, ConvW& cw, const std::string& name)     // Conv2
                     const int tp = prs2_tap(ps >> 1, ps & 1);
                     if (tp >= 0) fr[prs2_frag_index(ps >> 1, ps & 1, o, i, cw.Cout_pad)] = f2bf_host(w[((size_t)o * I + i) * 9 + tp]);
                 }
-        if ((rc = upload(h, fr.data(), fr.size() * 2, &cw.wfrag))) return rc;
+        return upload(h, fr.data(), fr.size() * 2, dfrag);
     }
     if (cw.kind == KIND_C3S1 && cw.BN == 128 && h->cfg.dtype == CCN_DTYPE_BF16) {
         // fragment order of the persistent kernel's 3x3 form (pr3_frag_index, ccn_internal.h): one wave load = 1 KiB contiguous
@@ -474,17 +391,16 @@ int pack_conv3(ccn_handle_s* h, ConvW& cw, const std::string& name)     // Conv2
         for (int o = 0; o < O; ++o)
             for (int i = 0; i < I; ++i)
                 for (int t = 0; t < 9; ++t) fr[pr3_frag_index(o, i, t, cw.Cout_pad)] = f2bf_host(w[((size_t)o * I + i) * 9 + t]);
-        if ((rc = upload(h, fr.data(), fr.size() * 2, &cw.wfrag))) return rc;
+        return upload(h, fr.data(), fr.size() * 2, dfrag);
     }
-    return upload_f32(h, name + ".bias", &cw.bias);
+    return CCN_OK;
 }
-int pack_convT(ccn_handle_s* h, ConvW& cw, const std::string& name)     // ConvTranspose2d weight (I, O, 4, 4)
+int pack_convT(ccn_handle_s* h, ConvW& cw, const float* w, void** dw, void** dfrag)     // ConvTranspose2d weight (I, O, 4, 4)
 {
-    const float* w = h->host.at(name + ".weight").data();
     const int cke = conv_cin_chunk(h->cfg.dtype);
     cw.Cin_pad = (int)align_up(cw.Cin, cke);
     const int I = cw.Cin, O = cw.Cout;
-    int rc = pack_and_upload(h, cw, 16, [&](int t, int o, int i) { return i < I ? w[((size_t)i * O + o) * 16 + t] : 0.f; });
+    int rc = pack_and_upload(h, cw, 16, [&](int t, int o, int i) { return i < I ? w[((size_t)i * O + o) * 16 + t] : 0.f; }, dw);
     if (rc) return rc;
     if (cw.BN == 128 && h->cfg.dtype == CCN_DTYPE_BF16) {
         // fragment order for ccn_conv_pr.hip: [parity][chunk][Cout_pad/32][tap 0..3][kk][lane][8] = prct_frag_index, tap -> kernel
@@ -496,22 +412,20 @@ int pack_convT(ccn_handle_s* h, ConvW& cw, const std::string& name)     // ConvT
             for (int i = 0; i < I; ++i)
                 for (int pt = 0; pt < 16; ++pt)
                     fr[prct_frag_index(pt >> 2, pt & 3, o, i, cw.Cout_pad, nch)] = f2bf_host(w[((size_t)i * O + o) * 16 + prct_tap(pt >> 2, pt & 3)]);
-        if ((rc = upload(h, fr.data(), fr.size() * 2, &cw.wfrag))) return rc;
+        return upload(h, fr.data(), fr.size() * 2, dfrag);
     }
-    return upload_f32(h, name + ".bias", &cw.bias);
+    return CCN_OK;
 }
-int pack_stem(ccn_handle_s* h, ConvW& cw, const std::string& name)      // Conv2d weight (O, img_ch, 3, 3) as K = I*9
+int pack_stem(ccn_handle_s* h, ConvW& cw, const float* w, const float* bias, void** dw, void** dfrag)     // Conv2d weight (O, img_ch, 3, 3) as K = I*9
 {
-    const float* w = h->host.at(name + ".weight").data();
     const int cke = conv_cin_chunk(h->cfg.dtype);
     cw.Cin_pad = cke;
     const int K = cw.Cin * 9;
-    int rc = pack_and_upload(h, cw, 1, [&](int, int o, int k) { return k < K ? w[(size_t)o * K + k] : 0.f; });
+    int rc = pack_and_upload(h, cw, 1, [&](int, int o, int k) { return k < K ? w[(size_t)o * K + k] : 0.f; }, dw);
     if (rc) return rc;
     if (stem2_supported(h->cfg.dtype, cw.Cin, cw.Cout, h->G)) {
         // fragment order for ccn_stem.hip: [Cout/32][k-step 2][lane = h*32 + r][8 bf16]; lane (r, h) holds output channel
         // j*32 + r, k = 16 s + 8 h + e; k = K is the bias (multiplied by a constant-one im2col element)
-        const float* bias = h->host.at(name + ".bias").data();
         const int nt = cw.Cout / 32;
         std::vector<uint16_t> fr((size_t)nt * 2 * 64 * 8, 0);
         for (int j = 0; j < nt; ++j)
@@ -522,9 +436,14 @@ int pack_stem(ccn_handle_s* h, ConvW& cw, const std::string& name)      // Conv2
                         const float v = k < K ? w[(size_t)o * K + k] : (k == K ? bias[o] : 0.f);
                         fr[(((size_t)j * 2 + s) * 64 + ln) * 8 + e] = f2bf_host(v);
                     }
-        if ((rc = upload(h, fr.data(), fr.size() * 2, &cw.wfrag))) return rc;
+        return upload(h, fr.data(), fr.size() * 2, dfrag);
     }
-    return upload_f32(h, name + ".bias", &cw.bias);
+    return CCN_OK;
+}
+int pack_conv(ccn_handle_s* h, ConvW& cw, const float* w, const float* bias, void** dw, void** dfrag)
+{
+    if (cw.kind == KIND_STEM) return pack_stem(h, cw, w, bias, dw, dfrag);
+    return cw.kind == KIND_CT4 ? pack_convT(h, cw, w, dw, dfrag) : pack_conv3(h, cw, w, dw, dfrag);
 }
 
 // ---- plan -------------------------------------------------------------------------------------------------
@@ -534,7 +453,7 @@ struct PlanBuilder {
     Bump bump;
     int B;
     int film_stride;     // floats between consecutive samples' FiLM rows
-    PlanBuilder(ccn_handle_s* h_, Plan* p, void* ws, bool measure) : h(h_), plan(p), bump(ws, measure), B(p->B), film_stride(h_->F) {}
+    PlanBuilder(ccn_handle_s* h_, Plan* p, void* ws, bool measure) : h(h_), plan(p), bump(ws, measure), B(p->B), film_stride(h_->arch.F) {}
 
     TensorRef new_tensor(int C, int H, int W)
     {
@@ -614,7 +533,7 @@ struct PlanBuilder {
         Launch L{family, 2.0 * macs, bytes, nullptr};
         L.fn = [=](hipStream_t s, const StepCtx& c) -> hipError_t {
             ConvArgs k = *ap;                                 // read at launch time: gn() may have fused its finalize in
-            if (cwv.nphase > 1 && (c.step % cwv.nphase)) {    // DDIM step i runs on weight version i % nphase (diffuse_round_phases)
+            if (cwv.nphase > 1 && (c.step % cwv.nphase)) {    // DDIM step i runs on weight version i % nphase (round_version)
                 const int v = c.step % cwv.nphase - 1;
                 k.w = cwv.w_ph[v];
                 if (frag_used) k.wfrag = cwv.wfrag_ph[v];
@@ -695,30 +614,33 @@ struct PlanBuilder {
     }
 
     // x + conv2(SiLU(GN2(FiLM(conv1(SiLU(GN1(x))))))) -- models/blocks.py:40-44
-    TensorRef resblock(const ResW& r, const TensorRef& x, bool out_feeds_gn, int film_off = -2)
+    TensorRef resblock(int ri, const TensorRef& x, bool out_feeds_gn, int film_off = -2)
     {
+        const ArchRes& r = h->arch.res[ri];
+        const ConvW &c1 = h->convs[r.c1], &c2 = h->convs[r.c2];
+        const NormW &n1 = h->res[ri].n1, &n2 = h->res[ri].n2;
         // pre-pass only where the conv kernel would redo the transform per N tile AND has no idle VALU for it: the persistent
         // kernel's producers absorb it up to 4 N tiles (measured at the 512-channel level of C2, 4-row tiles: 69.5 vs 68.8
         // images/s against pre-pass + finalize-free conv; CCN_PREACT_PR=1 restores the pre-pass in front of it for A/B runs)
         static const bool preact_pr = diag_env("CCN_PREACT_PR") != nullptr;
-        const bool pre = conv_wants_preact(r.c1.kind, r.c1.BN, r.c1.Cout_pad / r.c1.BN) && r.C / (h->elem == 2 ? 8 : 4) <= 256 &&
-                         (preact_pr || r.c1.Cout_pad / r.c1.BN >= 6 || !route(r.c1, x.H, x.W, false, false, false).pr);
+        const bool pre = conv_wants_preact(c1.kind, c1.BN, c1.Cout_pad / c1.BN) && r.C / (h->elem == 2 ? 8 : 4) <= 256 &&
+                         (preact_pr || c1.Cout_pad / c1.BN >= 6 || !route(c1, x.H, x.W, false, false, false).pr);
         static const bool fuse_act = !diag_env("CCN_NO_FUSED_GNACT");       // finalize folded into the pre-pass (A/B switch)
         const bool f1 = pre && fuse_act && x.n_sp > 0, f2 = pre && fuse_act;     // (n_sp, not the pointer: null while measuring)
         TensorRef y = new_tensor(r.C, x.H, x.W);
-        if (f1) { TensorRef xa = preact_fused(x, r.n1); conv(r.c1, F_C3S1, xa, y, nullptr, film_off == -2 ? r.film_off : film_off, nullptr, true); }
+        if (f1) { TensorRef xa = preact_fused(x, n1); conv(c1, F_C3S1, xa, y, nullptr, film_off == -2 ? r.film_off : film_off, nullptr, true); }
         else if (pre) {
-            const float2* ab1 = gn(x, r.n1);
-            TensorRef xa = preact(x, ab1); conv(r.c1, F_C3S1, xa, y, nullptr, film_off == -2 ? r.film_off : film_off, nullptr, true);
-        } else conv(r.c1, F_C3S1, x, y, nullptr, film_off == -2 ? r.film_off : film_off, nullptr, true, false, false, &r.n1);
+            const float2* ab1 = gn(x, n1);
+            TensorRef xa = preact(x, ab1); conv(c1, F_C3S1, xa, y, nullptr, film_off == -2 ? r.film_off : film_off, nullptr, true);
+        } else conv(c1, F_C3S1, x, y, nullptr, film_off == -2 ? r.film_off : film_off, nullptr, true, false, false, &n1);
         label(r.prefix + ".film", f1 ? "preact_fused" : (pre ? "preact" : nullptr));
         plan->named[r.prefix + ".film"] = y;
         TensorRef o = new_tensor(r.C, x.H, x.W);
-        if (f2) { TensorRef ya = preact_fused(y, r.n2); conv(r.c2, F_C3S1, ya, o, nullptr, -1, &x, out_feeds_gn); }
+        if (f2) { TensorRef ya = preact_fused(y, n2); conv(c2, F_C3S1, ya, o, nullptr, -1, &x, out_feeds_gn); }
         else if (pre) {
-            const float2* ab2 = gn(y, r.n2);
-            TensorRef ya = preact(y, ab2); conv(r.c2, F_C3S1, ya, o, nullptr, -1, &x, out_feeds_gn);
-        } else conv(r.c2, F_C3S1, y, o, nullptr, -1, &x, out_feeds_gn, false, false, &r.n2);
+            const float2* ab2 = gn(y, n2);
+            TensorRef ya = preact(y, ab2); conv(c2, F_C3S1, ya, o, nullptr, -1, &x, out_feeds_gn);
+        } else conv(c2, F_C3S1, y, o, nullptr, -1, &x, out_feeds_gn, false, false, &n2);
         label(r.prefix, f2 ? "preact_fused" : (pre ? "preact" : nullptr));
         plan->named[r.prefix] = o;
         return o;
@@ -736,7 +658,7 @@ int build_plan(ccn_handle_s* h, Plan* plan, void* ws, bool measure)
     plan->t1 = (float*)pb.bump.take((size_t)TR * c.time_dim * 4 * 4);
     plan->tp = (float*)pb.bump.take((size_t)TR * c.time_dim * 4);
     plan->zp = (float*)pb.bump.take((size_t)B * c.time_dim * 4);
-    plan->film = (float*)pb.bump.take((size_t)FR * h->F * 4);
+    plan->film = (float*)pb.bump.take((size_t)FR * h->arch.F * 4);
     plan->zbuf = (float*)pb.bump.take((size_t)B * c.z_dim * 4);
     plan->xstate = (float*)pb.bump.take((size_t)B * c.img_ch * H * W * 4);
     plan->counters = (unsigned*)pb.bump.take((size_t)kMaxNorms * B * 4);
@@ -746,25 +668,27 @@ int build_plan(ccn_handle_s* h, Plan* plan, void* ws, bool measure)
     TensorRef img; img.C = c.img_ch; img.H = H; img.W = W;     // NCHW fp32, pointer supplied per call
     TensorRef x;
     std::vector<TensorRef> skips;
-    const size_t nl = h->layers.size();
+    const std::vector<ArchLayer>& layers = h->arch.layers;
+    const size_t nl = layers.size();
     for (size_t li = 0; li < nl; ++li) {
-        const Layer& L = h->layers[li];
-        const bool next_is_gn = li + 1 < nl && (h->layers[li + 1].type == L_RES || h->layers[li + 1].type == L_HEAD);
+        const ArchLayer& L = layers[li];
+        const bool next_is_gn = li + 1 < nl && (layers[li + 1].type == L_RES || layers[li + 1].type == L_HEAD);
         switch (L.type) {
             case L_STEM: {
-                x = pb.new_tensor(h->stem.Cout, H, W);
-                pb.conv(h->stem, F_STEM, img, x, nullptr, -1, nullptr, next_is_gn, true, false);
+                const ConvW& cw = h->convs[L.idx];
+                x = pb.new_tensor(cw.Cout, H, W);
+                pb.conv(cw, F_STEM, img, x, nullptr, -1, nullptr, next_is_gn, true, false);
                 pb.label(L.name);
                 plan->named[L.name] = x;
                 break;
             }
             case L_RES: {
-                x = pb.resblock(h->res[L.idx], x, next_is_gn);
+                x = pb.resblock(L.idx, x, next_is_gn);
                 break;
             }
             case L_DOWN: {
                 skips.push_back(x);
-                const ConvW& cw = h->downs[L.idx];
+                const ConvW& cw = h->convs[L.idx];
                 if ((x.H % 2) || (x.W % 2)) return fail(CCN_EINVAL, "H and W must be divisible by 2^len(ch_mult)");
                 TensorRef o = pb.new_tensor(cw.Cout, x.H / 2, x.W / 2);
                 pb.conv(cw, F_C3S2, x, o, nullptr, -1, nullptr, next_is_gn);
@@ -774,7 +698,7 @@ int build_plan(ccn_handle_s* h, Plan* plan, void* ws, bool measure)
                 break;
             }
             case L_UP: {
-                const ConvW& cw = h->ups[L.idx];
+                const ConvW& cw = h->convs[L.idx];
                 TensorRef o = pb.new_tensor(cw.Cout, x.H * 2, x.W * 2);
                 TensorRef sk = skips.back(); skips.pop_back();
                 if (sk.C != cw.Cout || sk.H != o.H || sk.W != o.W) return fail(CCN_EINVAL, "skip shape mismatch");
@@ -785,18 +709,19 @@ int build_plan(ccn_handle_s* h, Plan* plan, void* ws, bool measure)
                 break;
             }
             case L_HEAD: {
+                const ConvW& hd = h->convs[L.idx];
                 static const bool no_head2 = diag_env("CCN_NO_HEAD2") != nullptr;
-                if (!no_head2 && head2_supported(c.dtype, h->head.Cin, h->head.Cout, h->G)) {
+                if (!no_head2 && head2_supported(c.dtype, hd.Cin, hd.Cout, h->G)) {
                     // dedicated kernel pair: out_norm's finalize folded into per-sample head weights, taps in the N dimension
                     std::shared_ptr<ConvArgs> ap(new ConvArgs());
                     ConvArgs& a = *ap;
-                    a.in = x.p; a.bias = h->head.bias; a.B = B; a.Hin = H; a.Win = W; a.Cin = h->head.Cin; a.Cout = h->head.Cout;
+                    a.in = x.p; a.bias = hd.bias; a.B = B; a.Hin = H; a.Win = W; a.Cin = hd.Cin; a.Cout = hd.Cout;
                     a.Hout = H; a.Wout = W;
                     const float2* ab = pb.gn(x, h->out_norm);
                     void* scratch = pb.bump.take(head2_scratch_bytes(B, x.C));
                     const float* wf = h->head_w_f32;
-                    const double macs = (double)B * H * W * h->head.Cout * 9.0 * h->head.Cin;
-                    Launch Lh{F_HEAD, 2.0 * macs, ((double)B * H * W * x.C + 9.0 * x.C * h->head.Cout) * h->elem + 3.0 * (double)B * H * W * h->head.Cout * 4, nullptr};
+                    const double macs = (double)B * H * W * hd.Cout * 9.0 * hd.Cin;
+                    Launch Lh{F_HEAD, 2.0 * macs, ((double)B * H * W * x.C + 9.0 * x.C * hd.Cout) * h->elem + 3.0 * (double)B * H * W * hd.Cout * 4, nullptr};
                     Lh.fn = [=](hipStream_t s, const StepCtx& sc) -> hipError_t {
                         ConvArgs k = *ap;
                         k.x_state = sc.x_state; k.eps_out = sc.eps_out; k.do_ddim = sc.do_ddim;
@@ -813,7 +738,7 @@ int build_plan(ccn_handle_s* h, Plan* plan, void* ws, bool measure)
                 }
                 const float2* ab = pb.gn(x, h->out_norm);
                 TensorRef none;
-                pb.conv(h->head, F_HEAD, x, none, ab, -1, nullptr, false, false, true);
+                pb.conv(hd, F_HEAD, x, none, ab, -1, nullptr, false, false, true);
                 pb.label(L.name);
                 break;
             }
@@ -919,8 +844,8 @@ int run_conditioning(ccn_handle_s* h, Plan* p, hipStream_t s, const int64_t* t_i
         return launch_linear(p->t1, nullptr, 1, TR, h->tp2_w, h->tp2_b, p->tp, TR, 4 * td, td, 0, st); }});
     v.push_back({F_COND, 2.0 * B * c.z_dim * td, 0, [=](hipStream_t st, const StepCtx&) {
         return launch_linear(z, nullptr, 1, B, h->zp_w, h->zp_b, p->zp, B, c.z_dim, td, 1, st); }});
-    v.push_back({F_COND, 2.0 * FR * td * (double)h->F, 0, [=](hipStream_t st, const StepCtx&) {
-        return launch_linear(p->tp, p->zp, a_div, B, h->film_w, h->film_b, p->film, FR, td, h->F, 0, st); }});
+    v.push_back({F_COND, 2.0 * FR * td * (double)h->arch.F, 0, [=](hipStream_t st, const StepCtx&) {
+        return launch_linear(p->tp, p->zp, a_div, B, h->film_w, h->film_b, p->film, FR, td, h->arch.F, 0, st); }});
     StepCtx c0;
     for (auto& L : v) { int rc = run_launch(h, L, s, c0); if (rc) return rc; }
     return CCN_OK;
@@ -1001,8 +926,10 @@ int ccn_create(const ccn_config_t* cfg, ccn_handle_t* out)
     if (h->split) h->cfg.dtype = CCN_DTYPE_F32;
     h->elem = cfg->dtype == CCN_DTYPE_BF16 ? 2 : 4;
     h->G = cfg->groups;
-    build_arch(h.get());
-    for (auto& r : h->res)
+    h->arch = build_arch(h->cfg);
+    h->convs.assign(h->arch.convs.begin(), h->arch.convs.end());
+    h->res.resize(h->arch.res.size());
+    for (auto& r : h->arch.res)
         if (r.C % (r.C < h->G ? r.C : h->G)) return fail(CCN_EINVAL, "channel count not divisible by GroupNorm groups");
     HIPCHK(conv_prepare());
     HIPCHK(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
@@ -1030,15 +957,15 @@ int ccn_destroy(ccn_handle_t h)
 int ccn_num_params(ccn_handle_t h, int32_t* n)
 {
     if (!h || !n) return fail(CCN_EINVAL, "null argument");
-    *n = (int32_t)h->params.size();
+    *n = (int32_t)h->arch.params.size();
     return CCN_OK;
 }
 
 int ccn_param_info(ccn_handle_t h, int32_t i, const char** name, int64_t shape[4], int32_t* ndim)
 {
     if (!h || !name || !shape || !ndim) return fail(CCN_EINVAL, "null argument");
-    if (i < 0 || i >= (int32_t)h->params.size()) return fail(CCN_EINVAL, "parameter index out of range");
-    const ParamInfo& p = h->params[i];
+    if (i < 0 || i >= (int32_t)h->arch.params.size()) return fail(CCN_EINVAL, "parameter index out of range");
+    const ArchParam& p = h->arch.params[i];
     *name = p.name.c_str();
     *ndim = (int32_t)p.shape.size();
     for (size_t k = 0; k < 4; ++k) shape[k] = k < p.shape.size() ? p.shape[k] : 1;
@@ -1048,8 +975,8 @@ int ccn_param_info(ccn_handle_t h, int32_t i, const char** name, int64_t shape[4
 int ccn_load_param(ccn_handle_t h, const char* name, const float* data, const int64_t* shape, int32_t ndim)
 {
     if (!h || !name || !data || !shape) return fail(CCN_EINVAL, "null argument");
-    const ParamInfo* pi = nullptr;
-    for (auto& p : h->params) if (p.name == name) { pi = &p; break; }
+    const ArchParam* pi = nullptr;
+    for (auto& p : h->arch.params) if (p.name == name) { pi = &p; break; }
     if (!pi) return fail(CCN_EWEIGHTS, std::string("Unexpected key in state_dict: ") + name);
     if ((size_t)ndim != pi->shape.size()) return fail(CCN_EWEIGHTS, std::string("size mismatch for ") + name);
     for (int k = 0; k < ndim; ++k)
@@ -1079,8 +1006,9 @@ int ccn_set_weight_rounding(ccn_handle_t h, int32_t mode)
 int ccn_commit_params(ccn_handle_t h)
 {
     if (!h) return fail(CCN_EINVAL, "null handle");
+    const Arch& a = h->arch;
     std::string missing;
-    for (auto& p : h->params)
+    for (auto& p : a.params)
         if (!h->host.count(p.name)) missing += (missing.empty() ? "" : ", ") + p.name;
     if (!missing.empty()) return fail(CCN_EWEIGHTS, "Missing key(s) in state_dict: " + missing);
     drop_plans(h, 0);                                             // drains the device first: replays may still read the old weights
@@ -1088,78 +1016,51 @@ int ccn_commit_params(ccn_handle_t h)
     h->dev_allocs.clear();
     const ccn_config_t& c = h->cfg;
     int rc;
-    for (auto& m : h->host_ph) m.clear();
-    const bool phases = c.dtype == CCN_DTYPE_BF16 && h->weight_rounding == CCN_ROUND_DIFFUSED_PHASES;
-    h->nphase = phases ? phases_for(h) : 1;
-    if (c.dtype == CCN_DTYPE_BF16 && h->weight_rounding != CCN_ROUND_NEAREST) {
+    // bf16 mode rounds the conv weights with error diffusion (round_version) unless CCN_ROUND_NEAREST asks for the packers' own
+    // independent rounding; CCN_ROUND_DIFFUSED is one version.  h->host is only read: a commit that fails half-way leaves the loaded
+    // weights as they were.  Per conv, one version at a time is formed, packed, uploaded and dropped again.
+    const bool diffuse = c.dtype == CCN_DTYPE_BF16 && h->weight_rounding != CCN_ROUND_NEAREST;
+    h->nphase = diffuse && h->weight_rounding == CCN_ROUND_DIFFUSED_PHASES ? phases_for(h) : 1;
+    for (size_t ci = 0; ci < a.convs.size(); ++ci) {
+        ConvW& cw = h->convs[ci] = ConvW(a.convs[ci]);
+        const std::vector<float>&w = host_param(h, cw.pw), &b = host_param(h, cw.pb);
+        if ((rc = upload_f32(h, cw.pb, &cw.bias))) return rc;
         // (the head keeps fp32 weights: head_prep_kernel scales them per sample and rounds them with a carry along the steps)
-        for (auto& p : h->params) {
-            if (p.shape.size() != 4 || p.name == "out.weight") continue;
-            if (phases) { diffuse_round_phases(h, p); continue; }
-            auto& w = h->host.at(p.name);
-            const bool convT = p.shape[2] == 4;                               // up.N.weight: (Cin, Cout, 4, 4)
-            if (convT) diffuse_round_convT(w, (int)p.shape[0], (int)p.shape[1]);
-            else diffuse_round_conv(w, (int)p.shape[0], (int)p.shape[1], (int)(p.shape[2] * p.shape[3]));
+        const bool dif = diffuse && cw.kind != KIND_HEAD;
+        cw.nphase = dif ? h->nphase : 1;
+        std::vector<double> sum(dif ? w.size() : 0, 0.0);
+        std::vector<float> wk(dif ? w.size() : 0);
+        for (int k = 0; k < cw.nphase; ++k) {
+            if (dif) round_version(w.data(), w.size(), cw.kind == KIND_CT4, cw.Cout, cw.Cin, cw.kind == KIND_CT4 ? 16 : 9, k, sum.data(), wk.data());
+            if ((rc = pack_conv(h, cw, dif ? wk.data() : w.data(), b.data(), k ? &cw.w_ph[k - 1] : &cw.w, k ? &cw.wfrag_ph[k - 1] : &cw.wfrag))) return rc;
         }
+        if (cw.kind == KIND_HEAD && (rc = upload_f32(h, cw.pw, &h->head_w_f32))) return rc;
     }
-    // pack version k >= 1 of a conv's weights with the packer that made version 0 (a scratch ConvW receives the device pointers)
-    auto pack_phases = [&](ConvW& cw, const std::string& name, int (*packer)(ccn_handle_s*, ConvW&, const std::string&)) -> int {
-        cw.nphase = 1;
-        if (!phases) return CCN_OK;
-        for (int k = 1; k < h->nphase; ++k) {
-            std::swap(h->host.at(name + ".weight"), h->host_ph[k - 1].at(name + ".weight"));
-            ConvW t = cw;
-            const int rc = packer(h, t, name);
-            std::swap(h->host.at(name + ".weight"), h->host_ph[k - 1].at(name + ".weight"));
-            if (rc) return rc;
-            cw.w_ph[k - 1] = t.w; cw.wfrag_ph[k - 1] = t.wfrag;
-        }
-        cw.nphase = h->nphase;
-        return CCN_OK;
-    };
-    h->stem = ConvW(); h->stem.kind = KIND_STEM; h->stem.Cin = c.img_ch; h->stem.Cout = c.base;
-    if ((rc = pack_stem(h, h->stem, "in_conv"))) return rc;
-    if ((rc = pack_phases(h->stem, "in_conv", pack_stem))) return rc;
-    for (auto& r : h->res) {
-        r.c1 = ConvW(); r.c1.kind = KIND_C3S1; r.c1.Cin = r.C; r.c1.Cout = r.C;
-        r.c2 = r.c1;
-        if ((rc = pack_conv3(h, r.c1, r.prefix + ".conv1"))) return rc;
-        if ((rc = pack_conv3(h, r.c2, r.prefix + ".conv2"))) return rc;
-        if ((rc = pack_phases(r.c1, r.prefix + ".conv1", pack_conv3))) return rc;
-        if ((rc = pack_phases(r.c2, r.prefix + ".conv2", pack_conv3))) return rc;
-        r.n1.C = r.n2.C = r.C;
-        if ((rc = upload_f32(h, r.prefix + ".norm1.weight", &r.n1.gamma))) return rc;
-        if ((rc = upload_f32(h, r.prefix + ".norm1.bias", &r.n1.beta))) return rc;
-        if ((rc = upload_f32(h, r.prefix + ".norm2.weight", &r.n2.gamma))) return rc;
-        if ((rc = upload_f32(h, r.prefix + ".norm2.bias", &r.n2.beta))) return rc;
+    for (size_t ri = 0; ri < a.res.size(); ++ri) {
+        const ArchRes& r = a.res[ri];
+        ResW& rw = h->res[ri];
+        rw.n1.C = rw.n2.C = r.C;
+        if ((rc = upload_f32(h, r.n1.pg, &rw.n1.gamma))) return rc;
+        if ((rc = upload_f32(h, r.n1.pb, &rw.n1.beta))) return rc;
+        if ((rc = upload_f32(h, r.n2.pg, &rw.n2.gamma))) return rc;
+        if ((rc = upload_f32(h, r.n2.pb, &rw.n2.beta))) return rc;
     }
-    for (size_t i = 0; i < h->downs.size(); ++i) {
-        if ((rc = pack_conv3(h, h->downs[i], "down." + std::to_string(3 * i + 2)))) return rc;
-        if ((rc = pack_phases(h->downs[i], "down." + std::to_string(3 * i + 2), pack_conv3))) return rc;
-    }
-    for (size_t i = 0; i < h->ups.size(); ++i) {
-        if ((rc = pack_convT(h, h->ups[i], "up." + std::to_string(3 * i + 2)))) return rc;
-        if ((rc = pack_phases(h->ups[i], "up." + std::to_string(3 * i + 2), pack_convT))) return rc;
-    }
-    h->head = ConvW(); h->head.kind = KIND_HEAD; h->head.Cin = c.base; h->head.Cout = c.img_ch;
-    if ((rc = pack_conv3(h, h->head, "out"))) return rc;
-    if ((rc = upload_f32(h, "out.weight", &h->head_w_f32))) return rc;
-    h->out_norm.C = c.base;
-    if ((rc = upload_f32(h, "out_norm.weight", &h->out_norm.gamma))) return rc;
-    if ((rc = upload_f32(h, "out_norm.bias", &h->out_norm.beta))) return rc;
-    if ((rc = upload_f32(h, "time_proj.0.weight", &h->tp0_w))) return rc;
-    if ((rc = upload_f32(h, "time_proj.0.bias", &h->tp0_b))) return rc;
-    if ((rc = upload_f32(h, "time_proj.2.weight", &h->tp2_w))) return rc;
-    if ((rc = upload_f32(h, "time_proj.2.bias", &h->tp2_b))) return rc;
-    if ((rc = upload_f32(h, "z_proj.0.weight", &h->zp_w))) return rc;
-    if ((rc = upload_f32(h, "z_proj.0.bias", &h->zp_b))) return rc;
+    h->out_norm.C = a.out_norm.C;
+    if ((rc = upload_f32(h, a.out_norm.pg, &h->out_norm.gamma))) return rc;
+    if ((rc = upload_f32(h, a.out_norm.pb, &h->out_norm.beta))) return rc;
+    if ((rc = upload_f32(h, a.tp0.pw, &h->tp0_w))) return rc;
+    if ((rc = upload_f32(h, a.tp0.pb, &h->tp0_b))) return rc;
+    if ((rc = upload_f32(h, a.tp2.pw, &h->tp2_w))) return rc;
+    if ((rc = upload_f32(h, a.tp2.pb, &h->tp2_b))) return rc;
+    if ((rc = upload_f32(h, a.zp.pw, &h->zp_w))) return rc;
+    if ((rc = upload_f32(h, a.zp.pb, &h->zp_b))) return rc;
     // all FiLM linears as one (F x time_dim) matrix: per block [to_scale rows | to_shift rows]
-    std::vector<float> fw((size_t)h->F * c.time_dim), fb((size_t)h->F);
-    for (auto& r : h->res) {
-        const char* parts[2] = {".film.to_scale", ".film.to_shift"};
+    std::vector<float> fw((size_t)a.F * c.time_dim), fb((size_t)a.F);
+    for (auto& r : a.res) {
+        const ArchLin* parts[2] = {&r.fs, &r.fh};
         for (int q = 0; q < 2; ++q) {
-            const auto& w = h->host.at(r.prefix + parts[q] + ".weight");
-            const auto& b = h->host.at(r.prefix + parts[q] + ".bias");
+            const auto& w = host_param(h, parts[q]->pw);
+            const auto& b = host_param(h, parts[q]->pb);
             std::memcpy(&fw[(size_t)(r.film_off + q * r.C) * c.time_dim], w.data(), w.size() * 4);
             std::memcpy(&fb[(size_t)(r.film_off + q * r.C)], b.data(), b.size() * 4);
         }
@@ -1168,7 +1069,6 @@ int ccn_commit_params(ccn_handle_t h)
     if ((rc = upload(h, fb.data(), fb.size() * 4, (void**)&h->film_b))) return rc;
     HIPCHK(hipDeviceSynchronize());
     h->host.clear();
-    for (auto& m : h->host_ph) m.clear();
     h->committed = true;
     return CCN_OK;
 }
@@ -1340,8 +1240,8 @@ int ccn_resblock_forward(ccn_handle_t h, const char* prefix, const float* x_dev,
     if (rc) return rc;
     if (!prefix || !x_dev || !cond_dev || !y_dev || !workspace_dev) return fail(CCN_EINVAL, "null pointer");
     if (B <= 0 || H <= 0 || W <= 0) return fail(CCN_EINVAL, "bad shape");
-    const ResW* r = nullptr;
-    for (auto& q : h->res) if (q.prefix == prefix) { r = &q; break; }
+    const ArchRes* r = nullptr;
+    for (auto& q : h->arch.res) if (q.prefix == prefix) { r = &q; break; }
     if (!r) return fail(CCN_EINVAL, std::string("no ResBlock with prefix ") + prefix);
     if ((uintptr_t)workspace_dev & 255) return fail(CCN_EWORKSPACE, "workspace must be 256-byte aligned");
     hipStream_t s = (hipStream_t)stream;
@@ -1360,7 +1260,7 @@ int ccn_resblock_forward(ccn_handle_t h, const char* prefix, const float* x_dev,
         x = pb.new_tensor(r->C, H, W);
         x.part = (float2*)pb.bump.take((size_t)B * G * nslot * sizeof(float2));
         x.n_sp = nslot; x.n_nt = 1; x.bn = 1 << 30;
-        o = pb.resblock(*r, x, false, 0);
+        o = pb.resblock((int)(r - h->arch.res.data()), x, false, 0);
         if (pb.bump.off > workspace_bytes) return fail(CCN_EWORKSPACE, "workspace too small: need " + std::to_string(pb.bump.off));
     }
     HIPCHK(hipMemsetAsync(tmp.counters, 0, (size_t)8 * B * 4, s));
@@ -1465,7 +1365,7 @@ int ccn_algorithmic_work(ccn_handle_t h, int32_t B, int32_t H, int32_t W, double
     double f = 0, b = 0;
     for (auto& L : p.ops) if (L.family <= F_HEAD) { f += L.flops; b += L.bytes; }
     const ccn_config_t& c = h->cfg;
-    f += 2.0 * B * ((double)c.time_dim * 4 * c.time_dim * 2 + (double)c.z_dim * c.time_dim + (double)c.time_dim * h->F);
+    f += 2.0 * B * ((double)c.time_dim * 4 * c.time_dim * 2 + (double)c.z_dim * c.time_dim + (double)c.time_dim * h->arch.F);
     *flops = f; *bytes = b;
     return CCN_OK;
 }

@@ -5,6 +5,8 @@
 // loss.backward(); opt.step().  ccn_train_forward is CLIPCondUNet.forward (models/unet.py:81-106) with every tensor the
 // backward needs kept in the caller's workspace; ccn_train_backward takes d loss / d eps_hat and ACCUMULATES the gradient of
 // every parameter into a flat fp32 buffer laid out like the flat parameter buffer (the order of CLIPCondUNet.state_dict()).
+// The network itself -- parameters with their flat offsets, convs, ResBlocks, layer list -- is build_arch's description
+// (ccn_arch.h), shared with the inference handle; this file adds the per-conv operands and repack descriptors (TConvW).
 //
 // Parameters are read from the caller's flat fp32 buffer on every call (they change with every optimiser step) and repacked on
 // the device into the operand layouts of the convolution kernels.  Activations and activation gradients are NHWC in the
@@ -15,6 +17,7 @@
 // bump allocator, so the forward walk of ccn_train_backward (launches disabled) finds the tensors the forward call wrote.
 #include "../../include/ccn_hip.h"
 #include "ccn_train.h"
+#include "ccn_arch.h"
 
 #include <climits>
 #include <cmath>
@@ -40,22 +43,15 @@ int tfail(int code, const std::string& msg) { ccn_internal_set_error(msg.c_str()
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-struct PInfo { std::string name; std::vector<int64_t> shape; size_t off = 0; size_t numel() const { size_t n = 1; for (auto d : shape) n *= (size_t)d; return n; } };
-
-struct TConvW {
-    int kind = KIND_C3S1, Cin = 0, Cout = 0;
-    int pw = -1, pb = -1;                       // parameter indices (weight, bias)
+// a conv of the description (ccn_arch.h) and the training step's operands for it
+struct TConvW : ArchConv {
+    TConvW(const ArchConv& c) : ArchConv(c) {}
     int BN = 0, Cin_pad = 0, Cout_pad = 0;      // forward operand
     int dkind = KIND_C3S1, dBN = 0, dCin_pad = 0, dCout_pad = 0, dtaps = 9;   // data-gradient operand (roles of Cin / Cout swapped)
     void* wf = nullptr; void* wd = nullptr;
     void* wf_frag = nullptr; void* wd_frag = nullptr;   // 3x3 s1, bf16: fragment-ordered operands for the persistent kernel, else null
     PackDesc pd_f{}, pd_d{}, pf_f{}, pf_d{};             // repack descriptors: plain / fragment, forward / data gradient
 };
-struct TNorm { int C = 0, pg = -1, pb = -1; };
-struct TLin { int pw = -1, pb = -1, N = 0, K = 0; };
-struct TRes { int C = 0; TNorm n1, n2; TConvW c1, c2; TLin fs, fh; int film_off = 0; };
-enum LType { L_STEM, L_RES, L_DOWN, L_UP, L_HEAD };
-struct Layer { LType type; int idx; };
 
 struct TT {                                     // an NHWC activation and the partial sums of the GroupNorm that reads it
     void* p = nullptr; int C = 0, H = 0, W = 0;
@@ -78,15 +74,8 @@ struct ShapeInfo { size_t scr_wg = 0, scr_gn = 0, scr_film = 0, scr_col = 0, ten
 struct ccn_trainer_s {
     ccn_config_t cfg{};
     int elem = 4, G = 8;
-    std::vector<PInfo> params;
-    size_t total = 0;
-    TConvW stem, head;
-    TNorm out_norm;
-    TLin tp0, tp2, zp;
-    std::vector<TRes> res;
-    std::vector<TConvW> downs, ups;
-    std::vector<Layer> layers;
-    int F = 0;
+    Arch arch;                            // parameters (with the flat layout's offsets), convs, ResBlocks, layer list: build_arch, ccn_arch.h
+    std::vector<TConvW> convs;            // one per arch.convs entry
     float* zero_bias = nullptr;
     // captured hipGraphs of one forward / one backward, keyed by every pointer argument (ccn_train_set_graph)
     struct TGraph { std::vector<const void*> key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
@@ -113,67 +102,6 @@ struct ccn_trainer_s {
 
 namespace {
 
-int add_param(ccn_trainer_s* tr, const std::string& name, std::vector<int64_t> shape)
-{
-    PInfo p; p.name = name; p.shape = std::move(shape); p.off = tr->total;
-    tr->total += align_up(p.numel(), 4);                    // 16-byte aligned views
-    tr->params.push_back(p);
-    return (int)tr->params.size() - 1;
-}
-
-// models/unet.py:45-79 registration order (the key order of state_dict())
-void build_arch(ccn_trainer_s* tr)
-{
-    const ccn_config_t& c = tr->cfg;
-    const int td = c.time_dim;
-    auto lin = [&](const std::string& n, int N, int K) { TLin l; l.N = N; l.K = K; l.pw = add_param(tr, n + ".weight", {N, K}); l.pb = add_param(tr, n + ".bias", {N}); return l; };
-    auto conv = [&](const std::string& n, int kind, int Cin, int Cout) {
-        TConvW w; w.kind = kind; w.Cin = Cin; w.Cout = Cout;
-        if (kind == KIND_CT4) w.pw = add_param(tr, n + ".weight", {Cin, Cout, 4, 4});
-        else w.pw = add_param(tr, n + ".weight", {Cout, Cin, 3, 3});
-        w.pb = add_param(tr, n + ".bias", {Cout});
-        return w;
-    };
-    auto norm = [&](const std::string& n, int C) { TNorm g; g.C = C; g.pg = add_param(tr, n + ".weight", {C}); g.pb = add_param(tr, n + ".bias", {C}); return g; };
-    tr->tp0 = lin("time_proj.0", td * 4, td);
-    tr->tp2 = lin("time_proj.2", td, td * 4);
-    tr->zp = lin("z_proj.0", td, c.z_dim);
-    tr->stem = conv("in_conv", KIND_STEM, c.img_ch, c.base);
-    tr->layers.push_back({L_STEM, 0});
-    int ch = c.base, film_off = 0;
-    auto add_res = [&](const std::string& name, int cc) {
-        TRes r; r.C = cc;
-        r.n1 = norm(name + ".norm1", cc); r.c1 = conv(name + ".conv1", KIND_C3S1, cc, cc);
-        r.n2 = norm(name + ".norm2", cc); r.c2 = conv(name + ".conv2", KIND_C3S1, cc, cc);
-        r.fs = lin(name + ".film.to_scale", cc, td); r.fh = lin(name + ".film.to_shift", cc, td);
-        r.film_off = film_off; film_off += 2 * cc;
-        tr->res.push_back(r);
-        tr->layers.push_back({L_RES, (int)tr->res.size() - 1});
-    };
-    for (int i = 0; i < c.n_mult; ++i) {
-        const int m = c.ch_mult[i];
-        add_res("down." + std::to_string(3 * i), ch);
-        add_res("down." + std::to_string(3 * i + 1), ch);
-        tr->downs.push_back(conv("down." + std::to_string(3 * i + 2), KIND_C3S2, ch, ch * m));
-        tr->layers.push_back({L_DOWN, i});
-        ch *= m;
-    }
-    add_res("mid1", ch);
-    add_res("mid2", ch);
-    for (int i = 0; i < c.n_mult; ++i) {
-        const int m = c.ch_mult[c.n_mult - 1 - i];
-        add_res("up." + std::to_string(3 * i), ch);
-        add_res("up." + std::to_string(3 * i + 1), ch);
-        tr->ups.push_back(conv("up." + std::to_string(3 * i + 2), KIND_CT4, ch, ch / m));
-        tr->layers.push_back({L_UP, i});
-        ch /= m;
-    }
-    tr->out_norm = norm("out_norm", ch);
-    tr->head = conv("out", KIND_HEAD, ch, c.img_ch);
-    tr->layers.push_back({L_HEAD, 0});
-    tr->F = film_off;
-}
-
 bool alloc_dev(ccn_trainer_s* tr, size_t bytes, void** out, std::string& err)
 {
     void* p = nullptr;
@@ -193,7 +121,7 @@ bool setup_conv(ccn_trainer_s* tr, TConvW& w, std::string& err)
     w.Cin_pad = fkind == KIND_STEM ? cke : (int)align_up(w.Cin, cke);
     const int ftaps = fkind == KIND_CT4 ? 16 : (fkind == KIND_STEM ? 1 : 9);
     if (!alloc_dev(tr, (size_t)ftaps * w.Cout_pad * w.Cin_pad * tr->elem, &w.wf, err)) return false;
-    const long long src = (long long)tr->params[w.pw].off;
+    const long long src = (long long)tr->arch.params[w.pw].off;
     switch (fkind) {
         case KIND_CT4: w.pd_f = {src, w.wf, PK_CONVT, w.Cout, w.Cin, 16, w.Cout_pad, w.Cin_pad}; break;
         case KIND_STEM: w.pd_f = {src, w.wf, PK_STEM, w.Cout, w.Cin, 1, w.Cout_pad, w.Cin_pad}; break;
@@ -203,7 +131,7 @@ bool setup_conv(ccn_trainer_s* tr, TConvW& w, std::string& err)
         // bf16: the register-weight stem kernel (ccn_stem.hip) instead of the generic one on an im2col tile
         if (stem2_supported(tr->cfg.dtype, w.Cin, w.Cout, tr->G)) {
             if (!alloc_dev(tr, (size_t)w.Cout * 32 * 2, &w.wf_frag, err)) return false;
-            w.pf_f = {src, w.wf_frag, PK_FRAG_STEM, w.Cout, w.Cin, 1, w.Cout, 32, (long long)tr->params[w.pb].off};
+            w.pf_f = {src, w.wf_frag, PK_FRAG_STEM, w.Cout, w.Cin, 1, w.Cout, 32, (long long)tr->arch.params[w.pb].off};
         }
         return true;                                         // the image needs no gradient
     }
@@ -334,8 +262,8 @@ struct Walk {
     void* take(size_t bytes) { off = align_up(off, 256); void* p = base ? base + off : nullptr; off += bytes; return p; }
     TT new_tensor(int C, int h, int w) { TT t; t.C = C; t.H = h; t.W = w; t.p = take((size_t)B * h * w * C * tr->elem); return t; }
     int groups_for(int C) const { return C < tr->G ? C : tr->G; }
-    const float* par(int i) const { return P + tr->params[i].off; }
-    float* grad(int i) const { return Gd + tr->params[i].off; }
+    const float* par(int i) const { return P + tr->arch.params[i].off; }
+    float* grad(int i) const { return Gd + tr->arch.params[i].off; }
     bool ok(hipError_t e, const char* what) { if (e != hipSuccess) { err = std::string(what) + ": " + hipGetErrorString(e); return false; } return true; }
 
     void place_scratch(const ShapeInfo& si)
@@ -374,7 +302,7 @@ struct Walk {
             a.gs_part = gs->part; a.gs_gamma = gs->gamma; a.gs_beta = gs->beta; a.gs_inv_count = gs->inv_count;
             a.gs_nsp = gs->n_sp; a.gs_nnt = gs->n_nt; a.gs_bn = gs->bn; a.gs_cpg = gs->cpg;
         }
-        a.film_bstride = tr->F;
+        a.film_bstride = tr->arch.F;
         a.eps_out = eps_out;
         // (measured and dropped: capping the data-gradient convs' persistent grid to the CUs the side stream's weight-gradient kernel
         // leaves free -- 192 / 160 / 128 workgroups: 652-658 vs 663 images/s uncapped; docs/EXPERIMENTS.md R3.12)
@@ -407,7 +335,7 @@ struct Walk {
     }
     // `r`: the conv's route, decided before anything is enqueued.  Launching walks only (side_pre_ok); allocation order of the pre-pass form,
     // which the never-launching measuring / replay walks go through: activated tensor -- by the caller --, tables, conv output, partial sums
-    bool norm_conv_fwd_side(const TT& x, const TNorm& n, const TConvW& w, const ConvRoute& r, float2*& ab, float2*& stats, const TT& xa, TT& y,
+    bool norm_conv_fwd_side(const TT& x, const ArchNorm& n, const TConvW& w, const ConvRoute& r, float2*& ab, float2*& stats, const TT& xa, TT& y,
                             const float* film_r, const TT* res)
     {
         const int G = groups_for(x.C), cpg = x.C / G;
@@ -455,7 +383,7 @@ struct Walk {
     // GroupNorm statistics AND the pre-activated tensor SiLU(GN(t)) in one launch (round 3: 29 gn_stats launches of a step gone):
     // every workgroup of the pass reduces the producer's partial sums itself, the first one of each sample also writes the scale /
     // shift table and (mean, rstd) for the backward pass
-    bool gn_fwd_preact(const TT& t, const TNorm& n, float2*& ab, float2*& stats, const TT& out)
+    bool gn_fwd_preact(const TT& t, const ArchNorm& n, float2*& ab, float2*& stats, const TT& out)
     {
         const int G = groups_for(t.C), cpg = t.C / G;
         ab = (float2*)take((size_t)B * t.C * sizeof(float2));
@@ -474,7 +402,7 @@ struct Walk {
         return ok(launch_gn_act_fused(tr->cfg.dtype, t.p, out.p, B, t.H * t.W, t.C, t.part, G, t.n_sp, t.n_nt, t.bn, cpg, (double)cpg * t.H * t.W,
                                       par(n.pg), par(n.pb), 1e-5f, st, ab, stats), "gn_act_fused");
     }
-    bool gn_fwd(const TT& t, const TNorm& n, float2*& ab, float2*& stats)
+    bool gn_fwd(const TT& t, const ArchNorm& n, float2*& ab, float2*& stats)
     {
         const int G = groups_for(t.C), cpg = t.C / G;
         ab = (float2*)take((size_t)B * t.C * sizeof(float2));
@@ -491,15 +419,15 @@ struct Walk {
         const int td = c.time_dim;
         temb = (float*)take((size_t)B * td * 4); u0 = (float*)take((size_t)B * td * 16); t1 = (float*)take((size_t)B * td * 16);
         tp = (float*)take((size_t)B * td * 4); uz = (float*)take((size_t)B * td * 4); zpv = (float*)take((size_t)B * td * 4);
-        hv = (float*)take((size_t)B * td * 4); film = (float*)take((size_t)B * tr->F * 4);
+        hv = (float*)take((size_t)B * td * 4); film = (float*)take((size_t)B * tr->arch.F * 4);
         if (!launch) return true;
         mark(TF_COND);
         if (!ok(launch_temb_i64(t, temb, B, td, st), "temb")) return false;
-        if (!ok(launch_tlinear_fwd(temb, td, par(tr->tp0.pw), par(tr->tp0.pb), t1, 4 * td, u0, B, td, 4 * td, 1, st), "time_proj.0")) return false;
-        if (!ok(launch_tlinear_fwd(t1, 4 * td, par(tr->tp2.pw), par(tr->tp2.pb), tp, td, nullptr, B, 4 * td, td, 0, st), "time_proj.2")) return false;
-        if (!ok(launch_tlinear_fwd(z, c.z_dim, par(tr->zp.pw), par(tr->zp.pb), zpv, td, uz, B, c.z_dim, td, 1, st), "z_proj")) return false;
+        if (!ok(launch_tlinear_fwd(temb, td, par(tr->arch.tp0.pw), par(tr->arch.tp0.pb), t1, 4 * td, u0, B, td, 4 * td, 1, st), "time_proj.0")) return false;
+        if (!ok(launch_tlinear_fwd(t1, 4 * td, par(tr->arch.tp2.pw), par(tr->arch.tp2.pb), tp, td, nullptr, B, 4 * td, td, 0, st), "time_proj.2")) return false;
+        if (!ok(launch_tlinear_fwd(z, c.z_dim, par(tr->arch.zp.pw), par(tr->arch.zp.pb), zpv, td, uz, B, c.z_dim, td, 1, st), "z_proj")) return false;
         if (!ok(launch_add2(hv, tp, zpv, (int64_t)B * td, st), "h")) return false;
-        return ok(launch_film_group_fwd(P, tr->lin_descs, tr->n_lin, tr->max_lin_n, hv, film, B, td, tr->F, st), "film");
+        return ok(launch_film_group_fwd(P, tr->lin_descs, tr->n_lin, tr->max_lin_n, hv, film, B, td, tr->arch.F, st), "film");
     }
 
     bool forward(const float* x_t, const float* z, const int64_t* t, float* eps)
@@ -526,16 +454,18 @@ struct Walk {
         if (!conditioning(z, t)) return false;
         TT x; std::vector<TT> skips;
         TT img; img.C = tr->cfg.img_ch; img.H = H; img.W = W;
-        for (const Layer& L : tr->layers) {
+        for (const ArchLayer& L : tr->arch.layers) {
             switch (L.type) {
                 case L_STEM: {
-                    x = new_tensor(tr->stem.Cout, H, W);
-                    if (!conv_fwd(tr->stem, img, x, nullptr, nullptr, nullptr, true, x_t)) return false;
+                    const TConvW& w = tr->convs[L.idx];
+                    x = new_tensor(w.Cout, H, W);
+                    if (!conv_fwd(w, img, x, nullptr, nullptr, nullptr, true, x_t)) return false;
                     stem_out = x;
                     break;
                 }
                 case L_RES: {
-                    const TRes& r = tr->res[L.idx];
+                    const ArchRes& r = tr->arch.res[L.idx];
+                    const TConvW &c1 = tr->convs[r.c1], &c2 = tr->convs[r.c2];
                     // The activated tensors SiLU(GN(.)) are written once by a pre-pass and kept: the forward conv AND the weight-gradient
                     // kernel then stage plain copies.  Redoing the transform while staging costs both of them VALU issue slots next to
                     // their MFMAs (per pixel tile the weight-gradient kernel spent more cycles in exp/rcp than in MFMAs); the pre-pass is
@@ -547,28 +477,28 @@ struct Walk {
                     // allocation sequence as the pre-pass form -- activated tensor, tables, conv output -- so the measuring and replay walks,
                     // which never launch, need not know which one ran.
                     const float* film_r = film ? film + r.film_off : nullptr;
-                    const ConvRoute r1 = fwd_route(r.c1, x.H, x.W, true, film_r != nullptr, false), r2 = fwd_route(r.c2, x.H, x.W, true, false, true);
+                    const ConvRoute r1 = fwd_route(c1, x.H, x.W, true, film_r != nullptr, false), r2 = fwd_route(c2, x.H, x.W, true, false, true);
                     if (s.pre && side_pre_ok() && r1.pr && r2.pr) {
                         s.xa = new_tensor(r.C, x.H, x.W);
-                        if (!norm_conv_fwd_side(x, r.n1, r.c1, r1, s.ab1, s.st1, s.xa, s.y, film_r, nullptr)) return false;
+                        if (!norm_conv_fwd_side(x, r.n1, c1, r1, s.ab1, s.st1, s.xa, s.y, film_r, nullptr)) return false;
                         s.ya = new_tensor(r.C, x.H, x.W);
-                        if (!norm_conv_fwd_side(s.y, r.n2, r.c2, r2, s.ab2, s.st2, s.ya, s.o, nullptr, &x)) return false;
+                        if (!norm_conv_fwd_side(s.y, r.n2, c2, r2, s.ab2, s.st2, s.ya, s.o, nullptr, &x)) return false;
                     } else {
                     if (s.pre) { s.xa = new_tensor(r.C, x.H, x.W); if (!gn_fwd_preact(x, r.n1, s.ab1, s.st1, s.xa)) return false; }
                     else if (!gn_fwd(x, r.n1, s.ab1, s.st1)) return false;
                     s.y = new_tensor(r.C, x.H, x.W);
-                    if (!conv_fwd(r.c1, s.pre ? s.xa : x, s.y, s.pre ? nullptr : s.ab1, film_r, nullptr, true)) return false;
+                    if (!conv_fwd(c1, s.pre ? s.xa : x, s.y, s.pre ? nullptr : s.ab1, film_r, nullptr, true)) return false;
                     if (s.pre) { s.ya = new_tensor(r.C, x.H, x.W); if (!gn_fwd_preact(s.y, r.n2, s.ab2, s.st2, s.ya)) return false; }
                     else if (!gn_fwd(s.y, r.n2, s.ab2, s.st2)) return false;
                     s.o = new_tensor(r.C, x.H, x.W);
-                    if (!conv_fwd(r.c2, s.pre ? s.ya : s.y, s.o, s.pre ? nullptr : s.ab2, nullptr, &x, true)) return false;
+                    if (!conv_fwd(c2, s.pre ? s.ya : s.y, s.o, s.pre ? nullptr : s.ab2, nullptr, &x, true)) return false;
                     }
                     rs.push_back(s);
                     x = s.o;
                     break;
                 }
                 case L_DOWN: {
-                    const TConvW& w = tr->downs[L.idx];
+                    const TConvW& w = tr->convs[L.idx];
                     skips.push_back(x);
                     TT o = new_tensor(w.Cout, x.H / 2, x.W / 2);
                     if (!conv_fwd(w, x, o, nullptr, nullptr, nullptr, true)) return false;
@@ -577,7 +507,7 @@ struct Walk {
                     break;
                 }
                 case L_UP: {
-                    const TConvW& w = tr->ups[L.idx];
+                    const TConvW& w = tr->convs[L.idx];
                     TT o = new_tensor(w.Cout, x.H * 2, x.W * 2);
                     TT sk = skips.back(); skips.pop_back();
                     if (!conv_fwd(w, x, o, nullptr, nullptr, &sk, true)) return false;
@@ -586,26 +516,27 @@ struct Walk {
                     break;
                 }
                 case L_HEAD: {
+                    const TConvW& hd = tr->convs[L.idx];
                     head_in = x;
-                    if (!gn_fwd(x, tr->out_norm, ab_o, st_o)) return false;
+                    if (!gn_fwd(x, tr->arch.out_norm, ab_o, st_o)) return false;
                     // bf16: the inference plan's head kernels (out_norm folded into per-sample weights, nine taps in the N dimension) instead
                     // of the generic kernel: 20 instead of 45 us.  (Same allocation in every walk: the scratch is taken whenever the kernel
                     // would be chosen, which depends on the configuration only.)
                     static const bool no_head2 = diag_env("CCN_TRAIN_NO_HEAD2") != nullptr;      // A/B switch
-                    if (!no_head2 && head2_supported(tr->cfg.dtype, tr->head.Cin, tr->head.Cout, tr->G) && (double)B * H * W * x.C * 2 < 2.0e9) {
+                    if (!no_head2 && head2_supported(tr->cfg.dtype, hd.Cin, hd.Cout, tr->G) && (double)B * H * W * x.C * 2 < 2.0e9) {
                         void* scratch = take(head2_scratch_bytes(B, x.C));
                         if (!launch) break;
                         ConvArgs a{};
-                        a.in = x.p; a.bias = par(tr->head.pb); a.B = B; a.Hin = H; a.Win = W; a.Cin = tr->head.Cin; a.Cout = tr->head.Cout;
+                        a.in = x.p; a.bias = par(hd.pb); a.B = B; a.Hin = H; a.Win = W; a.Cin = hd.Cin; a.Cout = hd.Cout;
                         a.Hout = H; a.Wout = W; a.eps_out = eps;
-                        mark(TF_CONV_FWD, 2.0 * B * H * W * (double)tr->head.Cout * 9.0 * tr->head.Cin);
+                        mark(TF_CONV_FWD, 2.0 * B * H * W * (double)hd.Cout * 9.0 * hd.Cin);
                         note(RN_CONV, KIND_HEAD, "head2", 1);
-                        if (!ok(launch_head2(a, ab_o, par(tr->head.pw), scratch, 0, st), "head")) return false;
+                        if (!ok(launch_head2(a, ab_o, par(hd.pw), scratch, 0, st), "head")) return false;
                         break;
                     }
                     TT none;
-                    if (!run_conv(TF_CONV_FWD, fwd_route(tr->head, x.H, x.W, ab_o != nullptr, false, false), tr->head.pd_f, tr->head.pf_f,
-                                  launch ? par(tr->head.pb) : nullptr, x.p, &none, nullptr, ab_o, nullptr, nullptr, false, eps)) return false;
+                    if (!run_conv(TF_CONV_FWD, fwd_route(hd, x.H, x.W, ab_o != nullptr, false, false), hd.pd_f, hd.pf_f,
+                                  launch ? par(hd.pb) : nullptr, x.p, &none, nullptr, ab_o, nullptr, nullptr, false, eps)) return false;
                     break;
                 }
             }
@@ -666,7 +597,7 @@ struct Walk {
         return ok(launch_wgrad_reduce(scr_wg, a.nsplit, a.taps_w, Cout, Cin, Cov, Civ, kind == KIND_CT4 ? 1 : 0, gdst, wg_stream), "wgrad_reduce");
     }
     // GroupNorm(+SiLU) backward of the norm reading tensor `x`: dA -> out (may alias dA)
-    bool gn_bwd(const TT& x, const TNorm& n, const float2* ab, const float2* stats, const void* dA, void* out, bool silu, const void* addend,
+    bool gn_bwd(const TT& x, const ArchNorm& n, const float2* ab, const float2* stats, const void* dA, void* out, bool silu, const void* addend,
                 int film_off, float* film_bias = nullptr)
     {
         const int G = groups_for(x.C), cpg = x.C / G, HW = x.H * x.W;
@@ -687,9 +618,9 @@ struct Walk {
         // bytes per pixel, so 32 workgroups pull uncoalesced 32-byte segments at a few tens of GB/s each; docs/EXPERIMENTS.md R3.5)
         if (!ok(launch_gn_bwd_reduce(dt, x.p, dA, ab, stats, scr_gn, B, HW, x.C, cpg, G, silu ? 1 : 0, st), "gn_bwd_reduce")) return false;
         if (!ok(launch_gn_bwd_finalize(scr_gn, gg.nblk, B, x.C, cpg, G, (double)cpg * HW, par(n.pg), gstat, grad(n.pg), grad(n.pb), st), "gn_bwd_finalize")) return false;
-        if (!ok(launch_gn_bwd_apply(dt, x.p, dA, ab, stats, gstat, addend, out, film_r, tr->F, scr_film, B, HW, x.C, cpg, G, silu ? 1 : 0, st), "gn_bwd_apply"))
+        if (!ok(launch_gn_bwd_apply(dt, x.p, dA, ab, stats, gstat, addend, out, film_r, tr->arch.F, scr_film, B, HW, x.C, cpg, G, silu ? 1 : 0, st), "gn_bwd_apply"))
             return false;
-        if (film_r) return ok(launch_film_bwd_finalize(scr_film, gg.nblk, film_r, tr->F, dfilm_r, film_bias, B, x.C, st), "film_bwd");
+        if (film_r) return ok(launch_film_bwd_finalize(scr_film, gg.nblk, film_r, tr->arch.F, dfilm_r, film_bias, B, x.C, st), "film_bwd");
         return true;
     }
     bool flush_bucket(long long lo, bool force)
@@ -702,7 +633,7 @@ struct Walk {
         hi_pending = lo;
         return true;
     }
-    bool lin_bwd(const TLin& l, const float* dy, int lddy, const float* x, int ldx, float* dx, int lddx, int accumulate)
+    bool lin_bwd(const ArchLin& l, const float* dy, int lddy, const float* x, int ldx, float* dx, int lddx, int accumulate)
     {
         if (!launch) return true;
         if (!ok(launch_tlinear_dw(dy, lddy, x, ldx, grad(l.pw), grad(l.pb), B, l.K, l.N, st), "linear_dw")) return false;
@@ -714,9 +645,9 @@ struct Walk {
     {
         const ccn_config_t& c = tr->cfg;
         const int td = c.time_dim, dt = c.dtype;
-        dfilm = (float*)take((size_t)B * tr->F * 4); dh = (float*)take((size_t)B * td * 4);
+        dfilm = (float*)take((size_t)B * tr->arch.F * 4); dh = (float*)take((size_t)B * td * 4);
         dt1 = (float*)take((size_t)B * td * 16); du0 = (float*)take((size_t)B * td * 16); duz = (float*)take((size_t)B * td * 4);
-        hi_pending = (long long)tr->total;
+        hi_pending = (long long)tr->arch.total;
         if (launch && tr->pack_dg_pending) {                   // the data-gradient operands repacked beside the forward pass
             if (hipStreamWaitEvent(st, tr->pack_dg_done, 0) != hipSuccess) { err = "stream wait failed"; return false; }
             tr->pack_dg_pending = false;
@@ -725,11 +656,11 @@ struct Walk {
         TT g;                                                  // gradient w.r.t. the current tensor
         std::vector<void*> dskip;                              // gradients waiting at the skip connections (pushed by the up path)
         int ri = (int)rs.size() - 1, di = (int)down_in.size() - 1, ui = (int)up_in.size() - 1;
-        for (int li = (int)tr->layers.size() - 1; li >= 0; --li) {
-            const Layer& L = tr->layers[li];
+        for (int li = (int)tr->arch.layers.size() - 1; li >= 0; --li) {
+            const ArchLayer& L = tr->arch.layers[li];
             switch (L.type) {
                 case L_HEAD: {
-                    const TConvW& w = tr->head;
+                    const TConvW& w = tr->convs[L.idx];
                     const TT& u = head_in;
                     // out.weight: the generic kernel on d eps as an NHWC tensor (channels padded to 8), A = out_norm(u) without SiLU
                     void* de = take((size_t)B * H * W * 8 * tr->elem);
@@ -741,11 +672,11 @@ struct Walk {
                     if (!wgrad_generic(KIND_C3S1, u.p, H, W, u.C, u.C, ab_o, 0, de, 8, c.img_ch, grad_or_null(w.pw))) return false;
                     g = new_tensor(u.C, H, W);
                     if (!conv_dgrad(w, d_eps, H, W, g.p, nullptr)) return false;
-                    if (!gn_bwd(u, tr->out_norm, ab_o, st_o, g.p, g.p, false, nullptr, -1)) return false;
+                    if (!gn_bwd(u, tr->arch.out_norm, ab_o, st_o, g.p, g.p, false, nullptr, -1)) return false;
                     break;
                 }
                 case L_UP: {
-                    const TConvW& w = tr->ups[L.idx];
+                    const TConvW& w = tr->convs[L.idx];
                     const TT& xin = up_in[ui]; --ui;
                     dskip.push_back(g.p);                       // x = convT(xin) + skip
                     if (!conv_wgrad(w, xin, nullptr, g.p, g.H, g.W)) return false;
@@ -755,7 +686,7 @@ struct Walk {
                     break;
                 }
                 case L_DOWN: {
-                    const TConvW& w = tr->downs[L.idx];
+                    const TConvW& w = tr->convs[L.idx];
                     const TT& xin = down_in[di]; --di;
                     if (!conv_wgrad(w, xin, nullptr, g.p, g.H, g.W)) return false;
                     TT d = new_tensor(xin.C, xin.H, xin.W);
@@ -765,30 +696,31 @@ struct Walk {
                     break;
                 }
                 case L_RES: {
-                    const TRes& r = tr->res[L.idx];
+                    const ArchRes& r = tr->arch.res[L.idx];
+                    const TConvW &c1 = tr->convs[r.c1], &c2 = tr->convs[r.c2];
                     const ResSave& s = rs[ri]; --ri;
                     // out = x + conv2(A2), A2 = silu(gn2(F)), F = film(conv1(A1)), A1 = silu(gn1(x))
-                    if (!conv_wgrad(r.c2, s.pre ? s.ya : s.y, s.pre ? nullptr : s.ab2, g.p, g.H, g.W)) return false;
+                    if (!conv_wgrad(c2, s.pre ? s.ya : s.y, s.pre ? nullptr : s.ab2, g.p, g.H, g.W)) return false;
                     TT g1 = new_tensor(r.C, g.H, g.W);
-                    if (!conv_dgrad(r.c2, g.p, g.H, g.W, g1.p, nullptr)) return false;
-                    if (!gn_bwd(s.y, r.n2, s.ab2, s.st2, g1.p, g1.p, true, nullptr, r.film_off, launch ? grad(r.c1.pb) : nullptr)) return false;
+                    if (!conv_dgrad(c2, g.p, g.H, g.W, g1.p, nullptr)) return false;
+                    if (!gn_bwd(s.y, r.n2, s.ab2, s.st2, g1.p, g1.p, true, nullptr, r.film_off, launch ? grad(c1.pb) : nullptr)) return false;
                     if (launch && bucket_cb) {
                         // bucketed mode: this block's FiLM linears now (side stream) instead of one grouped launch at the end, so that the
                         // block's whole parameter range is complete when its bucket is handed out
                         if (!fork_side()) return false;
                         const LinDesc* d2 = tr->lin_descs + 2 * L.idx;
-                        if (!ok(launch_film_group_dw(Gd, d2, 2, r.C, dfilm, hv, B, td, tr->F, wg_stream), "film_dw")) return false;
-                        if (!ok(launch_film_group_dx(P, d2, 2, dfilm, dh, B, td, tr->F, wg_stream), "film_dx")) return false;
+                        if (!ok(launch_film_group_dw(Gd, d2, 2, r.C, dfilm, hv, B, td, tr->arch.F, wg_stream), "film_dw")) return false;
+                        if (!ok(launch_film_group_dx(P, d2, 2, dfilm, dh, B, td, tr->arch.F, wg_stream), "film_dx")) return false;
                     }
-                    if (!conv_wgrad(r.c1, s.pre ? s.xa : s.x, s.pre ? nullptr : s.ab1, g1.p, g.H, g.W, true)) return false;
+                    if (!conv_wgrad(c1, s.pre ? s.xa : s.x, s.pre ? nullptr : s.ab1, g1.p, g.H, g.W, true)) return false;
                     TT g2 = new_tensor(r.C, g.H, g.W);
-                    if (!conv_dgrad(r.c1, g1.p, g.H, g.W, g2.p, nullptr)) return false;
+                    if (!conv_dgrad(c1, g1.p, g.H, g.W, g2.p, nullptr)) return false;
                     if (!gn_bwd(s.x, r.n1, s.ab1, s.st1, g2.p, g2.p, true, g.p, -1)) return false;
                     g = g2;
                     break;
                 }
                 case L_STEM: {
-                    const TConvW& w = tr->stem;
+                    const TConvW& w = tr->convs[L.idx];
                     // in_conv.weight: 1x1 weight gradient against the im2col of the image (27 of 32 columns)
                     const GnBwdGeom gg = gn_bwd_geom(dt, B, H * W, w.Cout);
                     want(need.scr_col, (size_t)B * gg.nblk * w.Cout * 4);
@@ -806,15 +738,9 @@ struct Walk {
                 }
             }
             if (bucket_cb) {
-                int first = 0;                                  // first parameter of this layer: everything from its offset up is complete
-                switch (L.type) {
-                    case L_HEAD: first = tr->out_norm.pg; break;
-                    case L_UP: first = tr->ups[L.idx].pw; break;
-                    case L_DOWN: first = tr->downs[L.idx].pw; break;
-                    case L_RES: first = tr->res[L.idx].n1.pg; break;
-                    case L_STEM: first = tr->stem.pw; break;
-                }
-                if (L.type != L_STEM && !flush_bucket((long long)tr->params[first].off, false)) return false;
+                // first parameter of this layer: everything from its offset up is complete
+                const int first = L.type == L_HEAD ? tr->arch.out_norm.pg : (L.type == L_RES ? tr->arch.res[L.idx].n1.pg : tr->convs[L.idx].pw);
+                if (L.type != L_STEM && !flush_bucket((long long)tr->arch.params[first].off, false)) return false;
             }
         }
         // conditioning: film_r = h W_r^T + b_r for every block; h = time_proj(temb(t)) + z_proj(z)
@@ -824,14 +750,14 @@ struct Walk {
             if (!join_side()) return false;                      // dh was accumulated block by block on the side stream
         } else {
             if (hipMemsetAsync(dh, 0, (size_t)B * td * 4, st) != hipSuccess) { err = "hipMemsetAsync failed"; return false; }
-            if (!ok(launch_film_group_dw(Gd, tr->lin_descs, tr->n_lin, tr->max_lin_n, dfilm, hv, B, td, tr->F, st), "film_dw")) return false;
-            if (!ok(launch_film_group_dx(P, tr->lin_descs, tr->n_lin, dfilm, dh, B, td, tr->F, st), "film_dx")) return false;
+            if (!ok(launch_film_group_dw(Gd, tr->lin_descs, tr->n_lin, tr->max_lin_n, dfilm, hv, B, td, tr->arch.F, st), "film_dw")) return false;
+            if (!ok(launch_film_group_dx(P, tr->lin_descs, tr->n_lin, dfilm, dh, B, td, tr->arch.F, st), "film_dx")) return false;
         }
-        if (!lin_bwd(tr->tp2, dh, td, t1, 4 * td, dt1, 4 * td, 0)) return false;
+        if (!lin_bwd(tr->arch.tp2, dh, td, t1, 4 * td, dt1, 4 * td, 0)) return false;
         if (!ok(launch_silu_bwd(du0, dt1, u0, (int64_t)B * 4 * td, st), "silu_bwd")) return false;
-        if (!lin_bwd(tr->tp0, du0, 4 * td, temb, td, nullptr, 0, 0)) return false;
+        if (!lin_bwd(tr->arch.tp0, du0, 4 * td, temb, td, nullptr, 0, 0)) return false;
         if (!ok(launch_silu_bwd(duz, dh, uz, (int64_t)B * td, st), "silu_bwd")) return false;
-        if (!lin_bwd(tr->zp, duz, td, z, c.z_dim, nullptr, 0, 0)) return false;
+        if (!lin_bwd(tr->arch.zp, duz, td, z, c.z_dim, nullptr, 0, 0)) return false;
         return flush_bucket(0, true);
     }
 };
@@ -924,15 +850,13 @@ int ccn_train_create(const ccn_config_t* cfg, ccn_trainer_t* out)
     tr->cfg = *cfg;
     tr->elem = cfg->dtype == CCN_DTYPE_BF16 ? 2 : 4;
     tr->G = cfg->groups > 0 ? cfg->groups : 8;
-    build_arch(tr);
+    tr->arch = build_arch(tr->cfg);
+    tr->convs.assign(tr->arch.convs.begin(), tr->arch.convs.end());
     std::string err;
     bool good = true;
-    good = good && setup_conv(tr, tr->stem, err) && setup_conv(tr, tr->head, err);
-    for (TRes& r : tr->res) good = good && setup_conv(tr, r.c1, err) && setup_conv(tr, r.c2, err);
-    for (TConvW& w : tr->downs) good = good && setup_conv(tr, w, err);
-    for (TConvW& w : tr->ups) good = good && setup_conv(tr, w, err);
+    for (TConvW& w : tr->convs) good = good && setup_conv(tr, w, err);
     int maxc = cfg->base;
-    for (const TRes& r : tr->res) if (r.C > maxc) maxc = r.C;
+    for (const ArchRes& r : tr->arch.res) if (r.C > maxc) maxc = r.C;
     void* zb = nullptr;
     good = good && alloc_dev(tr, (size_t)(maxc + 256) * 4, &zb, err);
     if (good && hipMemset(zb, 0, (size_t)(maxc + 256) * 4) != hipSuccess) { good = false; err = "hipMemset failed"; }
@@ -942,9 +866,9 @@ int ccn_train_create(const ccn_config_t* cfg, ccn_trainer_t* out)
     if (good) {
         // descriptor tables of the grouped launches (offsets into the caller's flat buffers are fixed by the architecture)
         std::vector<LinDesc> ld;
-        for (const TRes& r : tr->res) {
-            ld.push_back({(long long)tr->params[r.fs.pw].off, (long long)tr->params[r.fs.pb].off, r.C, r.film_off});
-            ld.push_back({(long long)tr->params[r.fh.pw].off, (long long)tr->params[r.fh.pb].off, r.C, r.film_off + r.C});
+        for (const ArchRes& r : tr->arch.res) {
+            ld.push_back({(long long)tr->arch.params[r.fs.pw].off, (long long)tr->arch.params[r.fs.pb].off, r.C, r.film_off});
+            ld.push_back({(long long)tr->arch.params[r.fh.pw].off, (long long)tr->arch.params[r.fh.pb].off, r.C, r.film_off + r.C});
             if (r.C > tr->max_lin_n) tr->max_lin_n = r.C;
         }
         void* ldd = nullptr;
@@ -976,15 +900,15 @@ int ccn_train_destroy(ccn_trainer_t tr)
 int ccn_train_num_params(ccn_trainer_t tr, int32_t* n, int64_t* total_floats)
 {
     if (!tr || !n) return tfail(CCN_EINVAL, "null argument");
-    *n = (int32_t)tr->params.size();
-    if (total_floats) *total_floats = (int64_t)tr->total;
+    *n = (int32_t)tr->arch.params.size();
+    if (total_floats) *total_floats = (int64_t)tr->arch.total;
     return CCN_OK;
 }
 
 int ccn_train_param_info(ccn_trainer_t tr, int32_t i, const char** name, int64_t shape[4], int32_t* ndim, int64_t* offset)
 {
-    if (!tr || i < 0 || i >= (int32_t)tr->params.size()) return tfail(CCN_EINVAL, "parameter index out of range");
-    const PInfo& p = tr->params[i];
+    if (!tr || i < 0 || i >= (int32_t)tr->arch.params.size()) return tfail(CCN_EINVAL, "parameter index out of range");
+    const ArchParam& p = tr->arch.params[i];
     if (name) *name = p.name.c_str();
     if (ndim) *ndim = (int32_t)p.shape.size();
     if (shape) for (size_t k = 0; k < p.shape.size() && k < 4; ++k) shape[k] = p.shape[k];

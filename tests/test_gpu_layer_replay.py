@@ -115,7 +115,7 @@ def plan_routes(nat):
 
 
 def round_weights(w, convT, version):
-    """Version `version` of the error-diffused bf16 rounding of one conv weight (ccn_commit_params, diffuse_round_phases)."""
+    """Version `version` of the error-diffused bf16 rounding of one conv weight (ccn_commit_params: round_version)."""
     w = np.ascontiguousarray(w, np.float32)
     if convT:
         I, O, taps = w.shape[0], w.shape[1], 16

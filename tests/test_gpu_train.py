@@ -178,6 +178,26 @@ def test_torch_optimizer_drop_in_and_eval_after_training():
     assert float((e.cpu() - ref).abs().max()) < 1e-4
 
 
+@pytest.mark.parametrize("base,ch_mult", [(32, (1, 2)), (48, (1, 2)), (128, (1, 2, 2))])
+def test_both_handles_describe_the_network_like_the_python_spec(base, ch_mult):
+    """The inference and the training handle start from one description of the network (csrc/ccn_arch.h): names and shapes of both, in
+    order, are those of synth.unet_param_spec (the state_dict() order); every offset of the training layout is the running sum of
+    numel rounded up to 4 floats, and `total` is its end.  Handles only: nothing is committed or launched."""
+    spec = [(k, tuple(s)) for k, s in synth.unet_param_spec(512, base, ch_mult)]
+    nat = _native.NativeUNet(512, base, ch_mult, 256, 3, device=DEV)
+    tr = _native.NativeTrainer(512, base, ch_mult, 256, 3, device=DEV)
+    try:
+        assert nat.param_spec() == spec
+        assert [(k, s) for k, s, _ in tr.layout] == spec
+        off = 0
+        for k, s, o in tr.layout:
+            assert o == off, (k, o, off)
+            off += (int(np.prod(s)) + 3) // 4 * 4
+        assert tr.total == off
+    finally:
+        nat.close(); tr.close()
+
+
 def test_backward_requires_matching_forward():
     tr = _native.NativeTrainer(512, 32, (1, 2), 256, 3, device=DEV)
     flat = torch.zeros(tr.total, device=DEV); x = torch.zeros((1, 3, 32, 32), device=DEV); z = torch.zeros((1, 512), device=DEV)

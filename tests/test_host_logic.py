@@ -190,16 +190,76 @@ def test_uint8_metric_path_equals_the_float_path(tmp_path):
     assert cli_eval.default_workers(n + 1) == 2
 
 
+def _closed_form_weights(shape, scale):
+    """((i * 2654435761 mod 2^32) / 2^32 - 0.5) * scale in float64, cast once: no RNG stream to drift between numpy versions."""
+    i = np.arange(int(np.prod(shape)), dtype=np.uint64)
+    u = (i * np.uint64(2654435761)) % np.uint64(1 << 32)
+    return ((u.astype(np.float64) / 2.0 ** 32 - 0.5) * scale).astype(np.float32).reshape(shape)
+
+
+def _bf16_rne(x):
+    """fp32 -> the nearest bf16 (ties to even) as fp32, in the `+ 0x7fff + lsb` integer form (finite inputs)."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+    u = (u + np.uint64(0x7FFF) + ((u >> np.uint64(16)) & np.uint64(1))) & np.uint64(0xFFFF0000)
+    return u.astype(np.uint32).view(np.float32)
+
+
+def _diffuse_rows(x):
+    """Error diffusion along axis 1 of (rows, K) fp32: every element is rounded after the float64 error of its predecessors was added."""
+    err = np.zeros(x.shape[0], np.float64)
+    out = np.empty_like(x)
+    for k in range(x.shape[1]):
+        t = x[:, k].astype(np.float64) + err
+        r = _bf16_rne(t.astype(np.float32))
+        err = t - r.astype(np.float64)
+        out[:, k] = r
+    return out
+
+
+_KK2 = [[1, 3], [0, 2]]                                # ConvTranspose2d kernel indices feeding even / odd outputs (stride 2, padding 1)
+
+
+def _diffuse_conv(x):
+    """Conv2d (O, I, ky, kx): each output channel walked over (cin, ky, kx)."""
+    return _diffuse_rows(x.reshape(x.shape[0], -1)).reshape(x.shape)
+
+
+def _diffuse_convT(x):
+    """ConvTranspose2d (I, O, 4, 4): each (output channel, output parity) walked over (cin, that parity's four taps)."""
+    out = np.empty_like(x)
+    for par in range(4):
+        ky, kx = _KK2[par >> 1], _KK2[par & 1]
+        taps = [(ky[t >> 1], kx[t & 1]) for t in range(4)]
+        rows = np.stack([x[:, :, a, b] for a, b in taps], axis=-1).transpose(1, 0, 2)          # (O, I, 4)
+        r = _diffuse_rows(np.ascontiguousarray(rows).reshape(x.shape[1], -1)).reshape(rows.shape).transpose(1, 0, 2)
+        for t, (a, b) in enumerate(taps):
+            out[:, :, a, b] = r[:, :, t]
+    return out
+
+
+def _round_versions(w, phases, diffuse):
+    """W_k = round((k + 1) W - (W_0 + ... + W_{k-1})), the running sum in float64, the operand of `round` cast to fp32."""
+    run = np.zeros(w.shape, np.float64)
+    out = np.empty((phases,) + w.shape, np.float32)
+    for k in range(phases):
+        out[k] = diffuse(((k + 1) * w.astype(np.float64) - run).astype(np.float32))
+        run += out[k]
+    return out
+
+
 def test_bf16_weight_rounding_arithmetic_on_the_host():
-    """ccn_set_weight_rounding's arithmetic (ccn_api.hip: diffuse_round_conv / _convT / _phases), run on the HOST through an internal
-    export of the library (no GPU call).  Properties the PSNR gate relies on:
+    """ccn_set_weight_rounding's arithmetic (ccn_api.hip: round_version over diffuse_round_conv / _convT, the routine
+    ccn_commit_params packs every weight version from), run on the HOST through an internal export of the library (no GPU call).
+    Properties the PSNR gate relies on:
       * every rounded weight is bf16-representable and within one bf16 ulp (at the tensor's largest magnitude: a small weight
         absorbs the carried error of a large neighbour) of the fp32 weight;
       * within every output channel, EVERY prefix sum of the rounded weights along (cin, ky, kx) is within half an ulp of the fp32
         prefix sum (independent rounding drifts like a random walk: ~sqrt(K) half-ulps);
       * along the phases, the running sum W_0 + ... + W_k has the same property against (k + 1) W, so the MEAN weight over a period of
         four steps is four times closer to the fp32 weight than one rounding;
-      * ConvTranspose2d: the diffusion runs per (output channel, output parity) over the four taps that parity sees."""
+      * ConvTranspose2d: the diffusion runs per (output channel, output parity) over the four taps that parity sees.
+    And the bits themselves, pinned from outside: all eight versions of a Conv2d and of a ConvTranspose2d weight equal an independent
+    numpy restatement of the recurrence (the helpers above) bit for bit."""
     import ctypes
     from clip_feature_codec import _native
     lib = ctypes.CDLL(str(_native.LIB_PATH))
@@ -249,3 +309,12 @@ def test_bf16_weight_rounding_arithmetic_on_the_host():
         sel = np.stack([(ot[0] - wt.astype(np.float64))[:, :, ky[t >> 1], kx[t & 1]] for t in range(4)], axis=-1)   # (Ci, Co, 4)
         drift = np.cumsum(np.transpose(sel, (1, 0, 2)).reshape(Co, -1), axis=1)
         assert np.abs(drift).max() <= bt, (par, np.abs(drift).max(), bt)
+
+    # exact: the library's versions against the numpy restatement, weights from a closed form
+    for shape, convT, diffuse in (((24, 40, 3, 3), 0, _diffuse_conv), ((20, 12, 4, 4), 1, _diffuse_convT)):
+        wc = _closed_form_weights(shape, 0.25)
+        Oc, Ic = (shape[1], shape[0]) if convT else (shape[0], shape[1])
+        got = np.empty((8,) + shape, np.float32)
+        assert fn(wc.ctypes.data, Oc, Ic, shape[2] * shape[3], convT, 8, got.ctypes.data) == 0
+        want = _round_versions(wc, 8, diffuse)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (shape, int((got.view(np.uint32) != want.view(np.uint32)).sum()))
