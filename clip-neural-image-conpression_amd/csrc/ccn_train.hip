@@ -13,8 +13,9 @@
 // handle's arithmetic type (fp32 parity mode / bf16); GroupNorm statistics, FiLM, the conditioning MLP, all parameter
 // gradients and the optimiser state are fp32.
 //
-// Layout of the workspace: [shared scratch regions][tensors in allocation order].  Every call walks the fixed layer list with a
-// bump allocator, so the forward walk of ccn_train_backward (launches disabled) finds the tensors the forward call wrote.
+// The workspace is planned once per shape (StepPlan: a byte offset for every tensor, table and scratch region, no two of them
+// overlapping, and the geometry of every launch) and cached in the handle; forward and backward calls launch from that plan, so the
+// backward reads the forward's tensors at the offsets the plan names.
 #include "../../include/ccn_hip.h"
 #include "ccn_train.h"
 #include "ccn_arch.h"
@@ -53,21 +54,62 @@ struct TConvW : ArchConv {
     PackDesc pd_f{}, pd_d{}, pf_f{}, pf_d{};             // repack descriptors: plain / fragment, forward / data gradient
 };
 
-struct TT {                                     // an NHWC activation and the partial sums of the GroupNorm that reads it
-    void* p = nullptr; int C = 0, H = 0, W = 0;
-    float2* part = nullptr; int n_sp = 0, n_nt = 0, bn = 0;
-};
-
 enum { TF_PACK = 0, TF_COND, TF_CONV_FWD, TF_GN_STATS, TF_PREACT, TF_CONV_DGRAD, TF_WGRAD, TF_WGRAD_REDUCE, TF_BIAS, TF_GN_BWD, TF_SMALL, TF_COUNT };
 const char* kTrainFamilies[TF_COUNT] = {"weight_repack", "conditioning_fwd_bwd", "conv_forward", "gn_stats", "gn_silu_prepass", "conv_data_grad", "conv_weight_grad",
                                         "weight_grad_reduce", "bias_grad", "groupnorm_silu_film_bwd", "stem_head_weight_grad"};
 struct Mark { int fam; hipEvent_t ev; double flops, bytes; };
 
-// one launch decision of a launching walk, kept for the test hook ccn_internal_train_routes (formatted there, not here)
+// one launch decision of a forward / backward call, kept for the test hook ccn_internal_train_routes (formatted there, not here)
 enum { RN_CONV = 0, RN_NORM, RN_GNBWD, RN_WGRAD, RN_COLSUM };
 struct RouteNote { int what, kind; const char* name; int v[5]; };
 
-struct ShapeInfo { size_t scr_wg = 0, scr_gn = 0, scr_film = 0, scr_col = 0, tensors = 0, total = 0; PackDesc* packs = nullptr; int n_packs = 0, n_packs_fwd = 0; };
+// ---- the step plan: everything that is a function of (configuration, B, H, W, kernel choice) ------------------------------------------
+// Built once per shape by Planner, which sees no stream, parameter or workspace pointer; Step (below) launches from it and computes no
+// size or geometry of its own.  Every `size_t` that names a tensor or a table is a byte offset from the workspace base.
+struct Region { std::string name; size_t off, bytes; };
+struct Tensor {                                 // an NHWC activation and the partial sums of the GroupNorm that reads it
+    size_t off = 0; int C = 0, H = 0, W = 0;
+    size_t part = 0; int n_sp = 0, n_nt = 0, bn = 0;
+};
+struct ConvPlan { ConvRoute r; ConvArgs a; int fam; double flops; };   // a: what ConvRoute::fill sets, and the operand(s) the route consumes
+struct NormPlan {                               // a forward GroupNorm: its tables and the shape's part of the choice between its launch forms
+    int G = 0, cpg = 0, HW = 0, slots = 0;
+    double count = 0, inv_count = 0, act_bytes = 0;
+    size_t ab = 0, st = 0;                      // scale / shift per (sample, channel); (mean, rstd) per (sample, group)
+    bool separate_stats = false;                // more than 128 partial-sum slots: statistics as a launch of their own
+    bool in_conv = false;                       // side form: the consuming conv forms the statistics itself
+};
+struct WgPlan { WgArgs a; int kind, nsplit[2], tiles, Cov, Civ; double flops; };   // nsplit: alone / beside the main stream's kernels
+struct GnBwdPlan { GnBwdGeom gg; int silu; double bytes; size_t gstat; };
+struct BiasPlan { GnBwdGeom gg; int HW, C, rows; bool pairs; };   // pairs: from the GroupNorm backward's per-block channel sums (`rows` of them)
+struct LayerPlan {
+    // forward.  x: the layer's input; ResBlock: xa = SiLU(GN1(x)), y = FiLM(conv1), ya = SiLU(GN2(y)); o: the layer's output
+    Tensor x, xa, y, ya, o;
+    size_t skip = 0;                            // ConvTranspose: the skip tensor its epilogue adds
+    NormPlan n1, n2;                            // ResBlock; head: n1 = out_norm
+    ConvPlan c1{}, c2{};                        // c2: ResBlock only
+    bool pre = false;                           // ResBlock: the pre-pass kernel takes its channels (activated tensors are written and kept)
+    bool both_pr = false;                       // ... and both convs run on the persistent kernel: the side form may be chosen at run time
+    bool head2 = false; size_t head2_scratch = 0;
+    // backward.  g: gradient w.r.t. o (head: the caller's d eps); ResBlock: g1 w.r.t. y, g2 w.r.t. x; the others: g2 w.r.t. x
+    size_t g = 0, g1 = 0, g2 = 0;
+    size_t dskip = 0;                           // stride-2 conv: the gradient that waits at its skip connection
+    size_t de = 0, col = 0;                     // head: d eps as NHWC; stem: im2col of the image
+    WgPlan w1{}, w2{};
+    BiasPlan bias{};
+    ConvPlan d1{}, d2{};
+    GnBwdPlan gb1{}, gb2{};
+};
+struct StepPlan {
+    int B = 0, H = 0, W = 0; int64_t HW = 0;
+    std::vector<Region> regions; size_t total = 0;
+    size_t scr_wg = 0, scr_gn = 0, scr_film = 0, scr_col = 0;                       // shared scratch, sized for the largest user
+    size_t temb = 0, u0 = 0, t1 = 0, tp = 0, uz = 0, zpv = 0, hv = 0, film = 0;     // conditioning
+    size_t dfilm = 0, dh = 0, dt1 = 0, du0 = 0, duz = 0, dh_bytes = 0;
+    std::vector<LayerPlan> layers;              // one per arch.layers entry
+    std::vector<PackDesc> pack_list;            // one per conv launch, the forward's first
+    PackDesc* packs = nullptr; int n_packs = 0, n_packs_fwd = 0;                    // the same on the device
+};
 
 }  // namespace
 
@@ -89,14 +131,14 @@ struct ccn_trainer_s {
     std::vector<hipEvent_t> sync_pool; size_t sync_used = 0;
     LinDesc* lin_descs = nullptr; int n_lin = 0, max_lin_n = 0;
     std::vector<void*> allocs;
-    std::map<std::string, ShapeInfo> shapes;
+    std::map<std::string, StepPlan> shapes;     // shape_key -> the plan of that shape
     // profiling (ccn_train_profile_*): an event before every group of launches; the time up to the next event is the group's
     bool profiling = false;
     std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
     std::vector<Mark> marks;
     // state of the last forward (checked by backward)
     int fB = 0, fH = 0, fW = 0; void* fws = nullptr;
-    // launch decisions of the last launching forward walk and of the backward walks since (a graph replay leaves the captured walk's)
+    // launch decisions of the last forward call and of the backward calls since (a graph replay leaves the captured call's)
     std::vector<RouteNote> route_log;
 };
 
@@ -182,97 +224,31 @@ bool setup_conv(ccn_trainer_s* tr, TConvW& w, std::string& err)
     return true;
 }
 
-// One walk over the layer list.  `launch` off: only the allocation sequence (and the scratch maxima) are reproduced.
-struct Walk {
-    ccn_trainer_s* tr;
-    int B, H, W;
-    char* base; size_t off = 0;
-    bool launch;
-    hipStream_t st;
-    const float* P; float* Gd;            // flat parameters / gradients
-    ShapeInfo need;                       // scratch maxima seen by this walk
-    float *scr_wg = nullptr, *scr_col = nullptr; float2 *scr_gn = nullptr, *scr_film = nullptr;
-    std::string err;
-    // conditioning buffers
-    float *temb = nullptr, *u0 = nullptr, *t1 = nullptr, *tp = nullptr, *uz = nullptr, *zpv = nullptr, *hv = nullptr, *film = nullptr;
-    float *dfilm = nullptr, *dh = nullptr, *dt1 = nullptr, *du0 = nullptr, *duz = nullptr;
-    // saved by the forward walk
-    struct ResSave { TT x, y, o, xa, ya; bool pre = false; float2 *ab1, *st1, *ab2, *st2; };
-    std::vector<ResSave> rs;
-    TT stem_out; std::vector<TT> down_in, down_out, up_in, up_out;
-    TT head_in; float2 *ab_o = nullptr, *st_o = nullptr;
-    std::vector<PackDesc> pack_list;      // repacks this shape needs, collected by the measuring walk (one per conv launch)
-    int g_sum_rows = 0;                   // > 0: scr_film holds per-block channel sums of the current gradient tensor (rows = B * blocks)
 
-    Walk(ccn_trainer_s* t, int B_, int H_, int W_, void* ws, bool l, hipStream_t s, const float* p, float* g)
-        : tr(t), B(B_), H(H_), W(W_), base((char*)ws), launch(l), st(s), P(p), Gd(g) {}
+// ---- planner: one pass over the layer list, forward then backward, that places every region and fixes every launch's geometry ---------
+struct Planner {
+    const ccn_trainer_s* tr;
+    const int B, H, W;
+    StepPlan& pl;
+    size_t off = 0;
 
-    // profiling: the launches that follow belong to family `fam` (flops: their algorithmic work); fam < 0 closes the sequence
-    void mark(int fam, double flops = 0.0, double bytes = 0.0)
+    Planner(const ccn_trainer_s* t, StepPlan& p) : tr(t), B(p.B), H(p.H), W(p.W), pl(p) {}
+
+    size_t take(const std::string& name, size_t bytes)
     {
-        if (!launch || !tr->profiling) return;
-        if (tr->ev_used == tr->ev_pool.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; tr->ev_pool.push_back(e); }
-        hipEvent_t e = tr->ev_pool[tr->ev_used++];
-        if (hipEventRecord(e, st) != hipSuccess) return;
-        tr->marks.push_back({fam, e, flops, bytes});
+        off = align_up(off, 256);
+        pl.regions.push_back({name, off, bytes});
+        off += bytes;
+        return off - bytes;
     }
-    // fork: the side stream continues from this point of the main stream; join: the main stream waits for everything on the side
-    hipStream_t wg_stream = nullptr;
-    // bucketed backward: cb(user, lo, hi) as soon as the gradients of flat range [lo, hi) are complete in stream order on `st`
-    ccn_grad_ready_cb bucket_cb = nullptr; void* bucket_user = nullptr; long long bucket_floats = 0, hi_pending = 0;
-    const PackDesc* shape_packs = nullptr; int n_shape_packs = 0, n_shape_packs_fwd = 0;
-    hipEvent_t sync_event_fwd()
+    Tensor tensor(const std::string& name, int C, int h, int w)
     {
-        // (the forward call's own fork event: the pool is reset at the start of every backward call, after this event has done its work)
-        if (!tr->fwd_fork && hipEventCreateWithFlags(&tr->fwd_fork, hipEventDisableTiming) != hipSuccess) tr->fwd_fork = nullptr;
-        return tr->fwd_fork;
+        Tensor t; t.C = C; t.H = h; t.W = w; t.off = take(name, (size_t)B * h * w * C * tr->elem);
+        return t;
     }
-    bool side_active() const
-    {
-        static const bool off_ = diag_env("CCN_TRAIN_NO_SIDE_STREAM") != nullptr;
-        return !off_ && !tr->profiling && tr->side != nullptr;
-    }
-    bool fork_side()
-    {
-        wg_stream = st;
-        if (!side_active()) return true;
-        if (tr->sync_used == tr->sync_pool.size()) { hipEvent_t e; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return true; tr->sync_pool.push_back(e); }
-        hipEvent_t e = tr->sync_pool[tr->sync_used++];
-        if (hipEventRecord(e, st) != hipSuccess || hipStreamWaitEvent(tr->side, e, 0) != hipSuccess) { err = "stream fork failed"; return false; }
-        wg_stream = tr->side;
-        return true;
-    }
-    hipEvent_t sync_event()
-    {
-        if (tr->sync_used == tr->sync_pool.size()) { hipEvent_t e; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr; tr->sync_pool.push_back(e); }
-        return tr->sync_pool[tr->sync_used++];
-    }
-    bool join_side()
-    {
-        if (!tr->side || tr->sync_used == 0) return true;
-        if (tr->sync_used == tr->sync_pool.size()) { hipEvent_t e; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { err = "event create failed"; return false; } tr->sync_pool.push_back(e); }
-        hipEvent_t e = tr->sync_pool[tr->sync_used++];
-        if (hipEventRecord(e, tr->side) != hipSuccess || hipStreamWaitEvent(st, e, 0) != hipSuccess) { err = "stream join failed"; return false; }
-        return true;
-    }
-    void note(int what, int kind, const char* name, int v0 = 0, int v1 = 0, int v2 = 0, int v3 = 0, int v4 = 0)
-    {
-        if (launch) tr->route_log.push_back({what, kind, name, {v0, v1, v2, v3, v4}});
-    }
-    void* take(size_t bytes) { off = align_up(off, 256); void* p = base ? base + off : nullptr; off += bytes; return p; }
-    TT new_tensor(int C, int h, int w) { TT t; t.C = C; t.H = h; t.W = w; t.p = take((size_t)B * h * w * C * tr->elem); return t; }
+    static void want(size_t& slot, size_t bytes) { if (bytes > slot) slot = bytes; }
     int groups_for(int C) const { return C < tr->G ? C : tr->G; }
-    const float* par(int i) const { return P + tr->arch.params[i].off; }
-    float* grad(int i) const { return Gd + tr->arch.params[i].off; }
-    bool ok(hipError_t e, const char* what) { if (e != hipSuccess) { err = std::string(what) + ": " + hipGetErrorString(e); return false; } return true; }
 
-    void place_scratch(const ShapeInfo& si)
-    {
-        scr_wg = (float*)take(si.scr_wg); scr_gn = (float2*)take(si.scr_gn); scr_film = (float2*)take(si.scr_film);
-        scr_col = (float*)take(si.scr_col);
-    }
-
-    // ---- forward pieces --------------------------------------------------------------------------------------------------
     // The training step's policy for conv_route: the stride-2 conv, the ConvTranspose and the 4x4 data-gradient form on the persistent
     // kernel from CCN_TRAIN_PR2_MIN (64) eight-row tiles, no split-K.  `four`: the 4x4 form of KIND_C3S2.
     ConvRoute route(int kind, bool four, const PackDesc& frag, int BN, int K, int Kpad, int N, int Npad, int Hin, int Win, bool gn_ab, bool film, bool res) const
@@ -282,185 +258,113 @@ struct Walk {
                                        false, false, !diag_env("CCN_TRAIN_NO_STEM2")};
         return conv_route({tr->cfg.dtype, kind, four, BN, K, Kpad, N, Npad, B, Hin, Win, tr->G, frag.dst != nullptr, gn_ab, res, film}, policy);
     }
-    ConvRoute fwd_route(const TConvW& w, int Hin, int Win, bool gn_ab, bool film, bool res) const
+    // one conv launch on route `r`; `out`: the tensor whose consuming GroupNorm wants the epilogue's partial sums, or null
+    ConvPlan conv(int fam, const ConvRoute& r, const PackDesc& plain, const PackDesc& frag, Tensor* out, const std::string& name)
     {
-        return route(w.kind, false, w.pf_f, w.BN, w.Cin, w.Cin_pad, w.Cout, w.Cout_pad, Hin, Win, gn_ab, film, res);
-    }
-    // launch of the conv kernels on route `r`
-    // input GroupNorm formed inside the persistent kernel from the producer's partial sums (its GS = 1; only where r.gs_ok)
-    struct GsIn { const float2* part; int n_sp, n_nt, bn, cpg; const float* gamma; const float* beta; double inv_count; };
-    bool run_conv(int fam, const ConvRoute& r, const PackDesc& plain, const PackDesc& frag, const float* bias, const void* in, TT* out, void* out_p,
-                  const float2* gn_ab, const float* film, const void* res, bool want_part, float* eps_out, const GsIn* gs = nullptr)
-    {
-        if (!base) pack_list.push_back(r.uses_frag() ? frag : plain);   // measuring walk: this shape's repack list
-        ConvArgs a{};
-        r.fill(a);
-        a.in = in; a.w = plain.dst; a.wfrag = r.uses_frag() ? frag.dst : nullptr; a.bias = bias; a.out = out_p;
-        a.gn_ab = gn_ab; a.film = film; a.res = res;
-        if (gs) {
-            a.gn_ab = nullptr;
-            a.gs_part = gs->part; a.gs_gamma = gs->gamma; a.gs_beta = gs->beta; a.gs_inv_count = gs->inv_count;
-            a.gs_nsp = gs->n_sp; a.gs_nnt = gs->n_nt; a.gs_bn = gs->bn; a.gs_cpg = gs->cpg;
-        }
-        a.film_bstride = tr->arch.F;
-        a.eps_out = eps_out;
-        // (measured and dropped: capping the data-gradient convs' persistent grid to the CUs the side stream's weight-gradient kernel
-        // leaves free -- 192 / 160 / 128 workgroups: 652-658 vs 663 images/s uncapped; docs/EXPERIMENTS.md R3.12)
-        if (want_part && out) {
-            out->part = (float2*)take((size_t)B * a.G * a.nslot * sizeof(float2));
+        ConvPlan c{};
+        c.r = r; c.fam = fam;
+        r.fill(c.a);
+        c.a.w = plain.dst; c.a.wfrag = r.uses_frag() ? frag.dst : nullptr;
+        pl.pack_list.push_back(r.uses_frag() ? frag : plain);
+        if (out) {
+            out->part = take(name + ".part", (size_t)B * c.a.G * c.a.nslot * sizeof(float2));
             out->n_sp = r.part_nsp; out->n_nt = r.part_nnt; out->bn = r.part_bn;
-            a.part = out->part;
         }
-        if (!launch) return true;
-        const int kind = r.q.kind, K = r.q.Cin, N = r.q.Cout;
-        mark(fam, 2.0 * B * r.g.Hout * r.g.Wout * (double)N * (kind == KIND_CT4 ? 4 : (kind == KIND_STEM ? 1 : r.g.ntaps)) * (kind == KIND_STEM ? 9.0 * K : (double)K));
-        note(RN_CONV, kind, conv_kernel_name(conv_kernel_for(kind, r.q.BN, a)), fam == TF_CONV_FWD ? 1 : 0, a.th, r.q.BN, a.n_nt, r.q.four ? 1 : 0);
-        return ok(launch_conv(tr->cfg.dtype, kind, r.q.BN, a, st), "conv");
+        const int kind = r.q.kind;
+        c.flops = 2.0 * B * r.g.Hout * r.g.Wout * (double)r.q.Cout * (kind == KIND_CT4 ? 4 : (kind == KIND_STEM ? 1 : r.g.ntaps)) * (kind == KIND_STEM ? 9.0 * r.q.Cin : (double)r.q.Cin);
+        return c;
     }
-    bool conv_fwd(const TConvW& w, const TT& in, TT& out, const float2* gn_ab, const float* film, const TT* res, bool want_part, const void* in_override = nullptr)
+    ConvPlan conv_fwd(const TConvW& w, const Tensor& in, Tensor* out, bool gn_ab, bool film, bool res, const std::string& name)
     {
-        return run_conv(TF_CONV_FWD, fwd_route(w, in.H, in.W, gn_ab != nullptr, film != nullptr, res != nullptr), w.pd_f, w.pf_f, launch ? par(w.pb) : nullptr,
-                        in_override ? in_override : in.p, &out, out.p, gn_ab, film, res ? res->p : nullptr, want_part, nullptr);
-    }
-    // ---- forward ResBlock conv with its GroupNorm + SiLU, side-stream form (bf16, plain stream launches) --------------------------------
-    // The conv transforms its raw input in its producer waves (the inference kernels' prologue: statistics formed in-kernel from the
-    // partial sums where they are few, else from the table of a 5-us statistics launch), so the pass that WRITES the activated tensor
-    // -- which only the weight-gradient kernel reads, in the backward pass -- leaves the forward's critical path: it runs on the side
-    // stream beside the convs (HBM-bound next to MFMA-bound).  The backward pass waits for pack_dg_done, recorded after the last of them.
-    bool fwd_side_used = false;
-    bool side_pre_ok() const
-    {
-        static const bool off_ = diag_env("CCN_TRAIN_NO_SIDE_PRE") != nullptr;       // A/B switch
-        return launch && !off_ && side_active() && !tr->use_graph && tr->pack_dg_done && tr->elem == 2;
-    }
-    // `r`: the conv's route, decided before anything is enqueued.  Launching walks only (side_pre_ok); allocation order of the pre-pass form,
-    // which the never-launching measuring / replay walks go through: activated tensor -- by the caller --, tables, conv output, partial sums
-    bool norm_conv_fwd_side(const TT& x, const ArchNorm& n, const TConvW& w, const ConvRoute& r, float2*& ab, float2*& stats, const TT& xa, TT& y,
-                            const float* film_r, const TT* res)
-    {
-        const int G = groups_for(x.C), cpg = x.C / G;
-        ab = (float2*)take((size_t)B * x.C * sizeof(float2));
-        stats = (float2*)take((size_t)B * G * sizeof(float2));
-        y = new_tensor(w.Cout, x.H, x.W);
-        const double count = (double)cpg * x.H * x.W;
-        auto fork = [&]() -> bool {
-            hipEvent_t e = sync_event();
-            if (!e || hipEventRecord(e, st) != hipSuccess || hipStreamWaitEvent(tr->side, e, 0) != hipSuccess) { err = "stream fork failed"; return false; }
-            fwd_side_used = true;
-            return true;
-        };
-        const int dt = tr->cfg.dtype;
-        const void* res_p = res ? res->p : nullptr;
-        if (r.gs_ok && conv_in_kernel_stats(dt, x.C, G, x.n_sp, x.bn)) {
-            // statistics in the conv itself; the side stream's pass writes the activated tensor AND the tables the backward pass reads
-            const GsIn gs{x.part, x.n_sp, x.n_nt, x.bn, cpg, par(n.pg), par(n.pb), 1.0 / count};
-            if (!fork()) return false;
-            note(RN_NORM, 0, "side-fused", x.n_sp * x.n_nt);
-            if (!ok(launch_gn_act_fused(dt, x.p, xa.p, B, x.H * x.W, x.C, x.part, G, x.n_sp, x.n_nt, x.bn, cpg, count, par(n.pg), par(n.pb), 1e-5f, tr->side, ab, stats),
-                    "gn_act_fused")) return false;
-            return run_conv(TF_CONV_FWD, r, w.pd_f, w.pf_f, par(w.pb), x.p, &y, y.p, nullptr, film_r, res_p, true, nullptr, &gs);
-        }
-        note(RN_NORM, 0, "side-stats+act", x.n_sp * x.n_nt);
-        if (!ok(launch_gn_stats(x.part, B, G, x.n_sp, x.n_nt, x.bn, cpg, x.C, count, par(n.pg), par(n.pb), 1e-5f, ab, stats, st), "gn_stats")) return false;
-        if (!fork()) return false;
-        if (!ok(launch_gn_act(dt, x.p, ab, xa.p, B, x.H * x.W, x.C, tr->side), "gn_act")) return false;
-        return run_conv(TF_CONV_FWD, r, w.pd_f, w.pf_f, par(w.pb), x.p, &y, y.p, ab, film_r, res_p, true, nullptr);
+        return conv(TF_CONV_FWD, route(w.kind, false, w.pf_f, w.BN, w.Cin, w.Cin_pad, w.Cout, w.Cout_pad, in.H, in.W, gn_ab, film, res), w.pd_f, w.pf_f, out, name);
     }
     // dX = conv'(dY): N = the forward conv's Cin
-    bool conv_dgrad(const TConvW& w, const void* dy, int Hdy, int Wdy, void* dx, const void* res)
+    ConvPlan conv_dgrad(const TConvW& w, int Hdy, int Wdy, bool res)
     {
-        g_sum_rows = 0;                                         // the gradient tensor that follows comes out of a conv: no channel sums
-        const ConvRoute r = route(w.dkind, w.kind == KIND_CT4, w.pf_d, w.dBN, w.kind == KIND_HEAD ? tr->cfg.img_ch : w.Cout, w.dCin_pad, w.Cin, w.dCout_pad,
-                                  Hdy, Wdy, false, false, res != nullptr);
-        return run_conv(TF_CONV_DGRAD, r, w.pd_d, w.pf_d, tr->zero_bias, dy, nullptr, dx, nullptr, nullptr, res, false, nullptr);
+        pair_rows = 0;                                          // the gradient tensor that follows comes out of a conv: no channel sums
+        return conv(TF_CONV_DGRAD, route(w.dkind, w.kind == KIND_CT4, w.pf_d, w.dBN, w.kind == KIND_HEAD ? tr->cfg.img_ch : w.Cout, w.dCin_pad, w.Cin, w.dCout_pad, Hdy, Wdy,
+                                         false, false, res), w.pd_d, w.pf_d, nullptr, "");
     }
-    bool preact(const TT& t, const float2* ab, const TT& out)
+    // the GroupNorm reading `t`, whose consumer is `c` (null: none that could form the statistics itself)
+    NormPlan norm(const Tensor& t, const ConvPlan* c, const std::string& name)
     {
-        if (!launch) return true;
-        mark(TF_PREACT, 0.0, 2.0 * B * t.H * t.W * t.C * tr->elem);
-        return ok(launch_gn_act(tr->cfg.dtype, t.p, ab, out.p, B, t.H * t.W, t.C, st), "gn_act");
+        NormPlan n;
+        n.G = groups_for(t.C); n.cpg = t.C / n.G; n.HW = t.H * t.W; n.slots = t.n_sp * t.n_nt;
+        n.count = (double)n.cpg * t.H * t.W; n.inv_count = 1.0 / n.count;
+        n.act_bytes = 2.0 * B * t.H * t.W * t.C * tr->elem;
+        n.ab = take(name + ".ab", (size_t)B * t.C * sizeof(float2));
+        n.st = take(name + ".st", (size_t)B * n.G * sizeof(float2));
+        // every workgroup of the fused pass redoes the reduction of G x slots partial sums: worth it while that is a few KB (below the
+        // 256-pixel level); at 256 px (256+ slots per group, 1024 workgroups per sample) the separate 5-us statistics launch stays
+        n.separate_stats = (long)t.n_sp * t.n_nt > 128;
+        n.in_conv = c && c->r.gs_ok && conv_in_kernel_stats(tr->cfg.dtype, t.C, n.G, t.n_sp, t.bn);
+        return n;
     }
-    // GroupNorm statistics AND the pre-activated tensor SiLU(GN(t)) in one launch (round 3: 29 gn_stats launches of a step gone):
-    // every workgroup of the pass reduces the producer's partial sums itself, the first one of each sample also writes the scale /
-    // shift table and (mean, rstd) for the backward pass
-    bool gn_fwd_preact(const TT& t, const ArchNorm& n, float2*& ab, float2*& stats, const TT& out)
+    // kind: the forward conv's family (KIND_STEM = 1x1 on an im2col'ed input); Cin / Cout as stored (multiples of 8), Civ / Cov the
+    // channels that exist in the parameter
+    WgPlan wgrad(int kind, int Hin, int Win, int Cin, int Civ, int silu, int Cout, int Cov)
     {
-        const int G = groups_for(t.C), cpg = t.C / G;
-        ab = (float2*)take((size_t)B * t.C * sizeof(float2));
-        stats = (float2*)take((size_t)B * G * sizeof(float2));
-        if (!launch) return true;
-        // every workgroup redoes the reduction of G x slots partial sums: worth it while that is a few KB (below the 256-pixel level);
-        // at 256 px (256+ slots per group, 1024 workgroups per sample) the separate 5-us statistics launch stays
-        if ((long)t.n_sp * t.n_nt > 128) {
-            note(RN_NORM, 0, "stats+act", t.n_sp * t.n_nt);
-            mark(TF_GN_STATS);
-            if (!ok(launch_gn_stats(t.part, B, G, t.n_sp, t.n_nt, t.bn, cpg, t.C, (double)cpg * t.H * t.W, par(n.pg), par(n.pb), 1e-5f, ab, stats, st), "gn_stats")) return false;
-            return preact(t, ab, out);
-        }
-        note(RN_NORM, 0, "fused", t.n_sp * t.n_nt);
-        mark(TF_PREACT, 0.0, 2.0 * B * t.H * t.W * t.C * tr->elem);
-        return ok(launch_gn_act_fused(tr->cfg.dtype, t.p, out.p, B, t.H * t.W, t.C, t.part, G, t.n_sp, t.n_nt, t.bn, cpg, (double)cpg * t.H * t.W,
-                                      par(n.pg), par(n.pb), 1e-5f, st, ab, stats), "gn_act_fused");
+        const ConvGeom g = conv_geom(kind, false, Hin, Win, 4);
+        WgPlan w{};
+        WgArgs& a = w.a;
+        a.silu = silu;
+        a.B = B; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = g.Hout; a.Wout = g.Wout; a.Cout = Cout;
+        a.MH = g.MH; a.MW = g.MW; a.OS = g.OS; a.npar = g.npar; a.ntaps = g.ntaps; a.taps_w = kind == KIND_CT4 ? 16 : (kind == KIND_STEM ? 1 : 9);
+        a.n_ty = g.n_ty; a.n_tx = g.n_tx;
+        fill_taps(a.tapinfo, kind, false);
+        w.kind = kind; w.Cov = Cov; w.Civ = Civ; w.tiles = B * g.n_ty * g.n_tx;
+        w.nsplit[0] = wgrad_nsplit(tr->cfg.dtype, kind, B, g.MH, g.MW, Cin, Cout, false);
+        w.nsplit[1] = wgrad_nsplit(tr->cfg.dtype, kind, B, g.MH, g.MW, Cin, Cout, true);
+        want(pl.scr_wg, (size_t)(w.nsplit[0] > w.nsplit[1] ? w.nsplit[0] : w.nsplit[1]) * a.taps_w * Cout * Cin * 4);
+        w.flops = 2.0 * B * g.Hout * g.Wout * (double)Cov * (kind == KIND_CT4 ? 4 : (kind == KIND_STEM ? 1 : 9)) * Civ;
+        return w;
     }
-    bool gn_fwd(const TT& t, const ArchNorm& n, float2*& ab, float2*& stats)
+    // > 0: scr_film holds per-block channel sums of the current gradient tensor (rows = B * blocks); a conv's output has none
+    int pair_rows = 0;
+    // bias gradient of a conv from its output gradient (C channels, HW pixels)
+    BiasPlan bias(int HW, int C)
     {
-        const int G = groups_for(t.C), cpg = t.C / G;
-        ab = (float2*)take((size_t)B * t.C * sizeof(float2));
-        stats = (float2*)take((size_t)B * G * sizeof(float2));
-        if (!launch) return true;
-        note(RN_NORM, 0, "prologue", t.n_sp * t.n_nt);
-        mark(TF_GN_STATS);
-        return ok(launch_gn_stats(t.part, B, G, t.n_sp, t.n_nt, t.bn, cpg, t.C, (double)cpg * t.H * t.W, par(n.pg), par(n.pb), 1e-5f, ab, stats, st), "gn_stats");
+        BiasPlan b{gn_bwd_geom(tr->cfg.dtype, B, HW, C), HW, C, 0, pair_rows > 0};
+        b.rows = b.pairs ? pair_rows : B * b.gg.nblk;
+        want(pl.scr_col, (size_t)B * b.gg.nblk * C * 4);
+        return b;
+    }
+    // GroupNorm(+SiLU) backward of the norm reading `x`; without FiLM its apply pass leaves the channel sums of its output
+    GnBwdPlan gn_bwd(const Tensor& x, const NormPlan& n, bool silu, bool addend, bool film, const std::string& name)
+    {
+        GnBwdPlan g{};
+        g.gg = gn_bwd_geom(tr->cfg.dtype, B, x.H * x.W, x.C);
+        g.silu = silu ? 1 : 0;
+        want(pl.scr_gn, (size_t)B * g.gg.nblk * x.C * sizeof(float2));
+        want(pl.scr_film, (size_t)B * g.gg.nblk * x.C * sizeof(float2));
+        pair_rows = film ? 0 : B * g.gg.nblk;
+        g.gstat = take(name + ".gstat", (size_t)B * n.G * sizeof(float2));
+        // algorithmic HBM bytes: pass 1 reads x and dA, pass 2 reads them again (+ the residual gradient) and writes dx
+        g.bytes = (double)B * x.H * x.W * x.C * tr->elem * (addend ? 6.0 : 5.0);
+        return g;
     }
 
-    bool conditioning(const float* z, const int64_t* t)
+    void forward()
     {
-        const ccn_config_t& c = tr->cfg;
-        const int td = c.time_dim;
-        temb = (float*)take((size_t)B * td * 4); u0 = (float*)take((size_t)B * td * 16); t1 = (float*)take((size_t)B * td * 16);
-        tp = (float*)take((size_t)B * td * 4); uz = (float*)take((size_t)B * td * 4); zpv = (float*)take((size_t)B * td * 4);
-        hv = (float*)take((size_t)B * td * 4); film = (float*)take((size_t)B * tr->arch.F * 4);
-        if (!launch) return true;
-        mark(TF_COND);
-        if (!ok(launch_temb_i64(t, temb, B, td, st), "temb")) return false;
-        if (!ok(launch_tlinear_fwd(temb, td, par(tr->arch.tp0.pw), par(tr->arch.tp0.pb), t1, 4 * td, u0, B, td, 4 * td, 1, st), "time_proj.0")) return false;
-        if (!ok(launch_tlinear_fwd(t1, 4 * td, par(tr->arch.tp2.pw), par(tr->arch.tp2.pb), tp, td, nullptr, B, 4 * td, td, 0, st), "time_proj.2")) return false;
-        if (!ok(launch_tlinear_fwd(z, c.z_dim, par(tr->arch.zp.pw), par(tr->arch.zp.pb), zpv, td, uz, B, c.z_dim, td, 1, st), "z_proj")) return false;
-        if (!ok(launch_add2(hv, tp, zpv, (int64_t)B * td, st), "h")) return false;
-        return ok(launch_film_group_fwd(P, tr->lin_descs, tr->n_lin, tr->max_lin_n, hv, film, B, td, tr->arch.F, st), "film");
-    }
-
-    bool forward(const float* x_t, const float* z, const int64_t* t, float* eps)
-    {
-        if (launch) tr->route_log.clear();
-        if (launch && eps) tr->sync_used = 0;                    // (fork events of this call; a wait keeps the record it saw when it was enqueued)
-        if (launch) {
-            mark(TF_PACK);
-            // The forward convs' operands now, on this stream; the data-gradient convs' operands (the other half of the 0.18 ms repack)
-            // on the side stream beside the forward pass -- the backward pass waits for them (pack_dg_done).  One launch under a graph
-            // capture (the side branch would have to rejoin inside the forward's graph) and while profiling.
-            static const bool no_split = diag_env("CCN_TRAIN_NO_PACK_SPLIT") != nullptr;     // A/B switch
-            const bool split = !no_split && side_active() && tr->pack_dg_done && !tr->use_graph && n_shape_packs_fwd > 0 && n_shape_packs_fwd < n_shape_packs;
-            if (!ok(launch_pack_group(tr->cfg.dtype, P, shape_packs, split ? n_shape_packs_fwd : n_shape_packs, st), "pack")) return false;
-            tr->pack_dg_pending = false;
-            if (split) {
-                hipEvent_t e = sync_event_fwd();
-                if (!e || hipEventRecord(e, st) != hipSuccess || hipStreamWaitEvent(tr->side, e, 0) != hipSuccess) { err = "stream fork failed"; return false; }
-                if (!ok(launch_pack_group(tr->cfg.dtype, P, shape_packs + n_shape_packs_fwd, n_shape_packs - n_shape_packs_fwd, tr->side), "pack")) return false;
-                if (hipEventRecord(tr->pack_dg_done, tr->side) != hipSuccess) { err = "event record failed"; return false; }
-                tr->pack_dg_pending = true;
-            }
-        }
-        if (!conditioning(z, t)) return false;
-        TT x; std::vector<TT> skips;
-        TT img; img.C = tr->cfg.img_ch; img.H = H; img.W = W;
-        for (const ArchLayer& L : tr->arch.layers) {
+        const int td = tr->cfg.time_dim;
+        pl.temb = take("temb", (size_t)B * td * 4); pl.u0 = take("u0", (size_t)B * td * 16); pl.t1 = take("t1", (size_t)B * td * 16);
+        pl.tp = take("tp", (size_t)B * td * 4); pl.uz = take("uz", (size_t)B * td * 4); pl.zpv = take("zpv", (size_t)B * td * 4);
+        pl.hv = take("h", (size_t)B * td * 4); pl.film = take("film", (size_t)B * tr->arch.F * 4);
+        Tensor x; std::vector<Tensor> skips;
+        Tensor img; img.C = tr->cfg.img_ch; img.H = H; img.W = W;
+        for (size_t li = 0; li < tr->arch.layers.size(); ++li) {
+            const ArchLayer& L = tr->arch.layers[li];
+            LayerPlan& lp = pl.layers[li];
+            const std::string n = L.name + ".";
+            lp.x = x;
             switch (L.type) {
-                case L_STEM: {
-                    const TConvW& w = tr->convs[L.idx];
-                    x = new_tensor(w.Cout, H, W);
-                    if (!conv_fwd(w, img, x, nullptr, nullptr, nullptr, true, x_t)) return false;
-                    stem_out = x;
+                case L_STEM: case L_DOWN: case L_UP: {
+                    const Tensor& in = L.type == L_STEM ? img : x;
+                    if (L.type == L_DOWN) skips.push_back(x);
+                    if (L.type == L_UP) { lp.skip = skips.back().off; skips.pop_back(); }
+                    lp.o = tensor(n + "o", tr->convs[L.idx].Cout, L.type == L_DOWN ? in.H / 2 : (L.type == L_UP ? in.H * 2 : in.H),
+                                  L.type == L_DOWN ? in.W / 2 : (L.type == L_UP ? in.W * 2 : in.W));
+                    lp.c1 = conv_fwd(tr->convs[L.idx], in, &lp.o, false, false, L.type == L_UP, n + "o");
                     break;
                 }
                 case L_RES: {
@@ -471,161 +375,418 @@ struct Walk {
                     // their MFMAs (per pixel tile the weight-gradient kernel spent more cycles in exp/rcp than in MFMAs); the pre-pass is
                     // one HBM-bound read + write per norm.  Layers the pre-pass kernel cannot take keep the fused prologue.
                     static const bool no_pre = diag_env("CCN_TRAIN_NO_PREACT") != nullptr;       // A/B switch
-                    ResSave s; s.x = x;
-                    s.pre = !no_pre && r.C / (tr->elem == 2 ? 8 : 4) <= 256;
-                    // Side form where both convs run on the persistent kernel (their input GroupNorm in the prologue either way).  Same
-                    // allocation sequence as the pre-pass form -- activated tensor, tables, conv output -- so the measuring and replay walks,
-                    // which never launch, need not know which one ran.
-                    const float* film_r = film ? film + r.film_off : nullptr;
-                    const ConvRoute r1 = fwd_route(c1, x.H, x.W, true, film_r != nullptr, false), r2 = fwd_route(c2, x.H, x.W, true, false, true);
-                    if (s.pre && side_pre_ok() && r1.pr && r2.pr) {
-                        s.xa = new_tensor(r.C, x.H, x.W);
-                        if (!norm_conv_fwd_side(x, r.n1, c1, r1, s.ab1, s.st1, s.xa, s.y, film_r, nullptr)) return false;
-                        s.ya = new_tensor(r.C, x.H, x.W);
-                        if (!norm_conv_fwd_side(s.y, r.n2, c2, r2, s.ab2, s.st2, s.ya, s.o, nullptr, &x)) return false;
-                    } else {
-                    if (s.pre) { s.xa = new_tensor(r.C, x.H, x.W); if (!gn_fwd_preact(x, r.n1, s.ab1, s.st1, s.xa)) return false; }
-                    else if (!gn_fwd(x, r.n1, s.ab1, s.st1)) return false;
-                    s.y = new_tensor(r.C, x.H, x.W);
-                    if (!conv_fwd(c1, s.pre ? s.xa : x, s.y, s.pre ? nullptr : s.ab1, film_r, nullptr, true)) return false;
-                    if (s.pre) { s.ya = new_tensor(r.C, x.H, x.W); if (!gn_fwd_preact(s.y, r.n2, s.ab2, s.st2, s.ya)) return false; }
-                    else if (!gn_fwd(s.y, r.n2, s.ab2, s.st2)) return false;
-                    s.o = new_tensor(r.C, x.H, x.W);
-                    if (!conv_fwd(c2, s.pre ? s.ya : s.y, s.o, s.pre ? nullptr : s.ab2, nullptr, &x, true)) return false;
-                    }
-                    rs.push_back(s);
-                    x = s.o;
-                    break;
-                }
-                case L_DOWN: {
-                    const TConvW& w = tr->convs[L.idx];
-                    skips.push_back(x);
-                    TT o = new_tensor(w.Cout, x.H / 2, x.W / 2);
-                    if (!conv_fwd(w, x, o, nullptr, nullptr, nullptr, true)) return false;
-                    down_in.push_back(x); down_out.push_back(o);
-                    x = o;
-                    break;
-                }
-                case L_UP: {
-                    const TConvW& w = tr->convs[L.idx];
-                    TT o = new_tensor(w.Cout, x.H * 2, x.W * 2);
-                    TT sk = skips.back(); skips.pop_back();
-                    if (!conv_fwd(w, x, o, nullptr, nullptr, &sk, true)) return false;
-                    up_in.push_back(x); up_out.push_back(o);
-                    x = o;
+                    lp.pre = !no_pre && r.C / (tr->elem == 2 ? 8 : 4) <= 256;
+                    // (a 3x3 s1 conv's route does not depend on whether its input GroupNorm comes as a table, so one route serves the
+                    // prologue, the pre-pass and the side form)
+                    if (lp.pre) lp.xa = tensor(n + "xa", r.C, x.H, x.W);
+                    lp.y = tensor(n + "y", r.C, x.H, x.W);
+                    lp.c1 = conv_fwd(c1, x, &lp.y, true, true, false, n + "y");
+                    lp.n1 = norm(x, &lp.c1, n + "n1");
+                    if (lp.pre) lp.ya = tensor(n + "ya", r.C, x.H, x.W);
+                    lp.o = tensor(n + "o", r.C, x.H, x.W);
+                    lp.c2 = conv_fwd(c2, lp.y, &lp.o, true, false, true, n + "o");
+                    lp.n2 = norm(lp.y, &lp.c2, n + "n2");
+                    lp.both_pr = lp.c1.r.pr && lp.c2.r.pr;
                     break;
                 }
                 case L_HEAD: {
                     const TConvW& hd = tr->convs[L.idx];
-                    head_in = x;
-                    if (!gn_fwd(x, tr->arch.out_norm, ab_o, st_o)) return false;
+                    lp.n1 = norm(x, nullptr, "out_norm");
                     // bf16: the inference plan's head kernels (out_norm folded into per-sample weights, nine taps in the N dimension) instead
-                    // of the generic kernel: 20 instead of 45 us.  (Same allocation in every walk: the scratch is taken whenever the kernel
-                    // would be chosen, which depends on the configuration only.)
+                    // of the generic kernel: 20 instead of 45 us
                     static const bool no_head2 = diag_env("CCN_TRAIN_NO_HEAD2") != nullptr;      // A/B switch
-                    if (!no_head2 && head2_supported(tr->cfg.dtype, hd.Cin, hd.Cout, tr->G) && (double)B * H * W * x.C * 2 < 2.0e9) {
-                        void* scratch = take(head2_scratch_bytes(B, x.C));
-                        if (!launch) break;
-                        ConvArgs a{};
-                        a.in = x.p; a.bias = par(hd.pb); a.B = B; a.Hin = H; a.Win = W; a.Cin = hd.Cin; a.Cout = hd.Cout;
-                        a.Hout = H; a.Wout = W; a.eps_out = eps;
-                        mark(TF_CONV_FWD, 2.0 * B * H * W * (double)hd.Cout * 9.0 * hd.Cin);
-                        note(RN_CONV, KIND_HEAD, "head2", 1);
-                        if (!ok(launch_head2(a, ab_o, par(hd.pw), scratch, 0, st), "head")) return false;
+                    lp.head2 = !no_head2 && head2_supported(tr->cfg.dtype, hd.Cin, hd.Cout, tr->G) && (double)B * H * W * x.C * 2 < 2.0e9;
+                    if (lp.head2) {
+                        lp.head2_scratch = take(n + "head2", head2_scratch_bytes(B, x.C));
+                        lp.c1.a.B = B; lp.c1.a.Hin = H; lp.c1.a.Win = W; lp.c1.a.Cin = hd.Cin; lp.c1.a.Cout = hd.Cout; lp.c1.a.Hout = H; lp.c1.a.Wout = W;
+                        lp.c1.fam = TF_CONV_FWD; lp.c1.flops = 2.0 * B * H * W * (double)hd.Cout * 9.0 * hd.Cin;
+                    } else lp.c1 = conv_fwd(hd, x, nullptr, true, false, false, "");
+                    break;
+                }
+            }
+            x = lp.o;
+        }
+    }
+
+    void backward()
+    {
+        const ccn_config_t& c = tr->cfg;
+        const int td = c.time_dim;
+        pl.dh_bytes = (size_t)B * td * 4;
+        pl.dfilm = take("dfilm", (size_t)B * tr->arch.F * 4); pl.dh = take("dh", pl.dh_bytes);
+        pl.dt1 = take("dt1", (size_t)B * td * 16); pl.du0 = take("du0", (size_t)B * td * 16); pl.duz = take("duz", (size_t)B * td * 4);
+        Tensor g;                                              // gradient w.r.t. the current tensor
+        std::vector<size_t> dskip;                             // gradients waiting at the skip connections (pushed by the up path)
+        for (int li = (int)tr->arch.layers.size() - 1; li >= 0; --li) {
+            const ArchLayer& L = tr->arch.layers[li];
+            LayerPlan& lp = pl.layers[li];
+            const std::string n = L.name + ".";
+            const Tensor& x = lp.x;
+            lp.g = g.off;
+            switch (L.type) {
+                case L_HEAD: {
+                    // out.weight: the generic kernel on d eps as an NHWC tensor (channels padded to 8), A = out_norm(u) without SiLU
+                    lp.de = take(n + "de", (size_t)B * H * W * 8 * tr->elem);
+                    lp.w1 = wgrad(KIND_C3S1, H, W, x.C, x.C, 0, 8, c.img_ch);
+                    g = tensor(n + "g", x.C, H, W);
+                    lp.d1 = conv_dgrad(tr->convs[L.idx], H, W, false);
+                    lp.gb1 = gn_bwd(x, lp.n1, false, false, false, "out_norm");
+                    break;
+                }
+                case L_UP: case L_DOWN: {
+                    const TConvW& w = tr->convs[L.idx];
+                    if (L.type == L_UP) dskip.push_back(g.off);                     // x = convT(xin) + skip
+                    lp.w1 = wgrad(w.kind, x.H, x.W, w.Cin, w.Cin, 1, w.Cout, w.Cout);
+                    lp.bias = bias(g.H * g.W, w.Cout);
+                    if (L.type == L_DOWN) { lp.dskip = dskip.back(); dskip.pop_back(); }
+                    lp.d1 = conv_dgrad(w, g.H, g.W, L.type == L_DOWN);
+                    g = tensor(n + "g", x.C, x.H, x.W);
+                    break;
+                }
+                case L_RES: {
+                    const ArchRes& r = tr->arch.res[L.idx];
+                    const TConvW &c1 = tr->convs[r.c1], &c2 = tr->convs[r.c2];
+                    // out = x + conv2(A2), A2 = silu(gn2(F)), F = film(conv1(A1)), A1 = silu(gn1(x))
+                    lp.w2 = wgrad(c2.kind, x.H, x.W, c2.Cin, c2.Cin, 1, c2.Cout, c2.Cout);
+                    lp.bias = bias(g.H * g.W, c2.Cout);
+                    lp.g1 = take(n + "g1", (size_t)B * g.H * g.W * r.C * tr->elem);
+                    lp.d2 = conv_dgrad(c2, g.H, g.W, false);
+                    lp.gb2 = gn_bwd(lp.y, lp.n2, true, false, true, n + "n2");
+                    // (conv1's bias gradient comes out of the FiLM finalize of that pass)
+                    lp.w1 = wgrad(c1.kind, x.H, x.W, c1.Cin, c1.Cin, 1, c1.Cout, c1.Cout);
+                    want(pl.scr_col, (size_t)B * gn_bwd_geom(c.dtype, B, g.H * g.W, c1.Cout).nblk * c1.Cout * 4);
+                    lp.g2 = take(n + "g2", (size_t)B * g.H * g.W * r.C * tr->elem);
+                    lp.d1 = conv_dgrad(c1, g.H, g.W, false);
+                    lp.gb1 = gn_bwd(x, lp.n1, true, true, false, n + "n1");
+                    g.off = lp.g2;
+                    break;
+                }
+                case L_STEM: {
+                    const TConvW& w = tr->convs[L.idx];
+                    // in_conv.weight: 1x1 weight gradient against the im2col of the image (27 of 32 columns)
+                    lp.bias = bias(H * W, w.Cout);
+                    lp.col = take(n + "col", (size_t)B * H * W * 32 * tr->elem);
+                    lp.w1 = wgrad(KIND_STEM, H, W, 32, c.img_ch * 9, 0, w.Cout, w.Cout);
+                    break;
+                }
+            }
+            if (L.type != L_RES && L.type != L_STEM) lp.g2 = g.off;
+        }
+    }
+
+    void run()
+    {
+        pl.layers.assign(tr->arch.layers.size(), LayerPlan{});
+        pl.HW = (int64_t)H * W;
+        forward();
+        pl.n_packs_fwd = (int)pl.pack_list.size();               // the forward convs' operands come first in the list
+        backward();
+        pl.scr_wg = take("scr_wg", pl.scr_wg); pl.scr_gn = take("scr_gn", pl.scr_gn);
+        pl.scr_film = take("scr_film", pl.scr_film); pl.scr_col = take("scr_col", pl.scr_col);
+        pl.total = align_up(off, 256) + 5 * 256;
+    }
+};
+
+// ---- launcher: one forward or backward call, enqueued from the plan -----------------------------------------------------------------------
+// Adds pointers (workspace base + planned offset, parameters, gradients), the stream, film_bstride and eps_out; the choices it makes are
+// the run-time ones: side stream or not, side or pre-pass form of a ResBlock, the pack split, the bucket callback.
+struct Step {
+    ccn_trainer_s* tr;
+    const StepPlan& pl;
+    char* ws;
+    hipStream_t st;
+    const float* P; float* Gd;            // flat parameters / gradients
+    const int B;
+    std::string err;
+    hipStream_t wg_stream = nullptr;      // where the weight gradients go: the side stream after fork_side, else `st`
+    // bucketed backward: cb(user, lo, hi) as soon as the gradients of flat range [lo, hi) are complete in stream order on `st`
+    ccn_grad_ready_cb bucket_cb = nullptr; void* bucket_user = nullptr; long long bucket_floats = 0, hi_pending = 0;
+    bool fwd_side_used = false;
+
+    Step(ccn_trainer_s* t, const StepPlan& p, void* w, hipStream_t s, const float* par_, float* g)
+        : tr(t), pl(p), ws((char*)w), st(s), P(par_), Gd(g), B(p.B) {}
+
+    template <typename T = void> T* at(size_t off) const { return (T*)(ws + off); }
+    const float* par(int i) const { return P + tr->arch.params[i].off; }
+    float* grad(int i) const { return Gd + tr->arch.params[i].off; }
+    float* grad_or_null(int i) const { return Gd ? grad(i) : nullptr; }
+    bool ok(hipError_t e, const char* what) { if (e != hipSuccess) { err = std::string(what) + ": " + hipGetErrorString(e); return false; } return true; }
+    bool ok(hipError_t e, const ArchLin& l) { const std::string& n = tr->arch.params[l.pw].name; return ok(e, n.substr(0, n.rfind('.')).c_str()); }
+
+    // profiling: the launches that follow belong to family `fam` (flops: their algorithmic work); fam < 0 closes the sequence
+    void mark(int fam, double flops = 0.0, double bytes = 0.0)
+    {
+        if (!tr->profiling) return;
+        if (tr->ev_used == tr->ev_pool.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; tr->ev_pool.push_back(e); }
+        hipEvent_t e = tr->ev_pool[tr->ev_used++];
+        if (hipEventRecord(e, st) != hipSuccess) return;
+        tr->marks.push_back({fam, e, flops, bytes});
+    }
+    void note(int what, int kind, const char* name, int v0 = 0, int v1 = 0, int v2 = 0, int v3 = 0, int v4 = 0)
+    {
+        tr->route_log.push_back({what, kind, name, {v0, v1, v2, v3, v4}});
+    }
+
+    // ---- streams ---------------------------------------------------------------------------------------------------------------------------
+    // `to` continues from this point of `from`: an event (`own`, else the next of the pool, which every backward call and every forward
+    // call that returns eps starts over) recorded on `from` and waited for on `to`
+    enum { ORD_OK = 0, ORD_NO_EVENT, ORD_FAILED };
+    int order(hipStream_t from, hipStream_t to, hipEvent_t own = nullptr)
+    {
+        hipEvent_t e = own;
+        if (!e) {
+            if (tr->sync_used == tr->sync_pool.size()) {
+                if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return ORD_NO_EVENT;
+                tr->sync_pool.push_back(e);
+            }
+            e = tr->sync_pool[tr->sync_used++];
+        }
+        return hipEventRecord(e, from) == hipSuccess && hipStreamWaitEvent(to, e, 0) == hipSuccess ? ORD_OK : ORD_FAILED;
+    }
+    bool side_active() const
+    {
+        static const bool off_ = diag_env("CCN_TRAIN_NO_SIDE_STREAM") != nullptr;
+        return !off_ && !tr->profiling && tr->side != nullptr;
+    }
+    // fork: the side stream continues from this point of the main stream; join: the main stream waits for everything on the side
+    bool fork_side()
+    {
+        wg_stream = st;
+        if (!side_active()) return true;
+        const int o = order(st, tr->side);
+        if (o == ORD_NO_EVENT) return true;
+        if (o == ORD_FAILED) { err = "stream fork failed"; return false; }
+        wg_stream = tr->side;
+        return true;
+    }
+    bool join_side()
+    {
+        if (!tr->side || tr->sync_used == 0) return true;
+        const int o = order(tr->side, st);
+        if (o != ORD_OK) { err = o == ORD_NO_EVENT ? "event create failed" : "stream join failed"; return false; }
+        return true;
+    }
+
+    // ---- forward pieces --------------------------------------------------------------------------------------------------
+    // input GroupNorm formed inside the persistent kernel from the producer's partial sums (its GS = 1; only where n.in_conv)
+    bool run_conv(const ConvPlan& c, const float* bias, const void* in, void* out, float2* part, const float2* gn_ab, const float* film, const void* res,
+                  float* eps_out, const Tensor* gs_x = nullptr, const NormPlan* gs_n = nullptr, const ArchNorm* gs_p = nullptr)
+    {
+        ConvArgs a = c.a;
+        a.in = in; a.bias = bias; a.out = out; a.part = part;
+        a.gn_ab = gn_ab; a.film = film; a.res = res;
+        if (gs_x) {
+            a.gn_ab = nullptr;
+            a.gs_part = at<float2>(gs_x->part); a.gs_gamma = par(gs_p->pg); a.gs_beta = par(gs_p->pb); a.gs_inv_count = gs_n->inv_count;
+            a.gs_nsp = gs_x->n_sp; a.gs_nnt = gs_x->n_nt; a.gs_bn = gs_x->bn; a.gs_cpg = gs_n->cpg;
+        }
+        a.film_bstride = tr->arch.F;
+        a.eps_out = eps_out;
+        // (measured and dropped: capping the data-gradient convs' persistent grid to the CUs the side stream's weight-gradient kernel
+        // leaves free -- 192 / 160 / 128 workgroups: 652-658 vs 663 images/s uncapped; docs/EXPERIMENTS.md R3.12)
+        const ConvQuery& q = c.r.q;
+        mark(c.fam, c.flops);
+        note(RN_CONV, q.kind, conv_kernel_name(conv_kernel_for(q.kind, q.BN, a)), c.fam == TF_CONV_FWD ? 1 : 0, a.th, q.BN, a.n_nt, q.four ? 1 : 0);
+        return ok(launch_conv(tr->cfg.dtype, q.kind, q.BN, a, st), "conv");
+    }
+    bool conv_fwd(const TConvW& w, const ConvPlan& c, const void* in, const Tensor& out, const float2* gn_ab, const float* film, const void* res)
+    {
+        return run_conv(c, par(w.pb), in, at(out.off), at<float2>(out.part), gn_ab, film, res, nullptr);
+    }
+    // ---- forward ResBlock conv with its GroupNorm + SiLU, side-stream form (bf16, plain stream launches) --------------------------------
+    // The conv transforms its raw input in its producer waves (the inference kernels' prologue: statistics formed in-kernel from the
+    // partial sums where they are few, else from the table of a 5-us statistics launch), so the pass that WRITES the activated tensor
+    // -- which only the weight-gradient kernel reads, in the backward pass -- leaves the forward's critical path: it runs on the side
+    // stream beside the convs (HBM-bound next to MFMA-bound).  The backward pass waits for pack_dg_done, recorded after the last of them.
+    bool side_pre_ok() const
+    {
+        static const bool off_ = diag_env("CCN_TRAIN_NO_SIDE_PRE") != nullptr;       // A/B switch
+        return !off_ && side_active() && !tr->use_graph && tr->pack_dg_done && tr->elem == 2;
+    }
+    bool fork_fwd_side()
+    {
+        if (order(st, tr->side) != ORD_OK) { err = "stream fork failed"; return false; }
+        fwd_side_used = true;
+        return true;
+    }
+    bool norm_conv_fwd_side(const Tensor& x, const ArchNorm& an, const NormPlan& n, const TConvW& w, const ConvPlan& c, const Tensor& xa, const Tensor& y,
+                            const float* film_r, const void* res)
+    {
+        const int dt = tr->cfg.dtype, HW = n.HW;
+        float2 *ab = at<float2>(n.ab), *stats = at<float2>(n.st), *part = at<float2>(x.part);
+        if (n.in_conv) {
+            // statistics in the conv itself; the side stream's pass writes the activated tensor AND the tables the backward pass reads
+            if (!fork_fwd_side()) return false;
+            note(RN_NORM, 0, "side-fused", n.slots);
+            if (!ok(launch_gn_act_fused(dt, at(x.off), at(xa.off), B, HW, x.C, part, n.G, x.n_sp, x.n_nt, x.bn, n.cpg, n.count, par(an.pg), par(an.pb), 1e-5f, tr->side, ab, stats),
+                    "gn_act_fused")) return false;
+            return run_conv(c, par(w.pb), at(x.off), at(y.off), at<float2>(y.part), nullptr, film_r, res, nullptr, &x, &n, &an);
+        }
+        note(RN_NORM, 0, "side-stats+act", n.slots);
+        if (!ok(launch_gn_stats(part, B, n.G, x.n_sp, x.n_nt, x.bn, n.cpg, x.C, n.count, par(an.pg), par(an.pb), 1e-5f, ab, stats, st), "gn_stats")) return false;
+        if (!fork_fwd_side()) return false;
+        if (!ok(launch_gn_act(dt, at(x.off), ab, at(xa.off), B, HW, x.C, tr->side), "gn_act")) return false;
+        return run_conv(c, par(w.pb), at(x.off), at(y.off), at<float2>(y.part), ab, film_r, res, nullptr);
+    }
+    // The GroupNorm reading `t` on the main stream.  With `out`: statistics AND the pre-activated tensor SiLU(GN(t)) in one launch (round 3:
+    // 29 gn_stats launches of a step gone) -- every workgroup of the pass reduces the producer's partial sums itself, the first one of
+    // each sample also writes the scale / shift table and (mean, rstd) for the backward pass -- or, with many slots, as two.  Without:
+    // the tables only, for the consuming conv's prologue.
+    bool norm_fwd(const Tensor& t, const ArchNorm& an, const NormPlan& n, const Tensor* out)
+    {
+        const int dt = tr->cfg.dtype, HW = n.HW;
+        float2 *ab = at<float2>(n.ab), *stats = at<float2>(n.st), *part = at<float2>(t.part);
+        if (out && !n.separate_stats) {
+            note(RN_NORM, 0, "fused", n.slots);
+            mark(TF_PREACT, 0.0, n.act_bytes);
+            return ok(launch_gn_act_fused(dt, at(t.off), at(out->off), B, HW, t.C, part, n.G, t.n_sp, t.n_nt, t.bn, n.cpg, n.count, par(an.pg), par(an.pb), 1e-5f, st, ab, stats),
+                      "gn_act_fused");
+        }
+        note(RN_NORM, 0, out ? "stats+act" : "prologue", n.slots);
+        mark(TF_GN_STATS);
+        if (!ok(launch_gn_stats(part, B, n.G, t.n_sp, t.n_nt, t.bn, n.cpg, t.C, n.count, par(an.pg), par(an.pb), 1e-5f, ab, stats, st), "gn_stats")) return false;
+        if (!out) return true;
+        mark(TF_PREACT, 0.0, n.act_bytes);
+        return ok(launch_gn_act(dt, at(t.off), ab, at(out->off), B, HW, t.C, st), "gn_act");
+    }
+
+    bool conditioning(const float* z, const int64_t* t)
+    {
+        const ccn_config_t& c = tr->cfg;
+        const Arch& A = tr->arch;
+        const int td = c.time_dim;
+        float *temb = at<float>(pl.temb), *t1 = at<float>(pl.t1), *tp = at<float>(pl.tp), *zpv = at<float>(pl.zpv), *hv = at<float>(pl.hv);
+        mark(TF_COND);
+        if (!ok(launch_temb_i64(t, temb, B, td, st), "temb")) return false;
+        if (!ok(launch_tlinear_fwd(temb, td, par(A.tp0.pw), par(A.tp0.pb), t1, 4 * td, at<float>(pl.u0), B, td, 4 * td, 1, st), A.tp0)) return false;
+        if (!ok(launch_tlinear_fwd(t1, 4 * td, par(A.tp2.pw), par(A.tp2.pb), tp, td, nullptr, B, 4 * td, td, 0, st), A.tp2)) return false;
+        if (!ok(launch_tlinear_fwd(z, c.z_dim, par(A.zp.pw), par(A.zp.pb), zpv, td, at<float>(pl.uz), B, c.z_dim, td, 1, st), A.zp)) return false;
+        if (!ok(launch_add2(hv, tp, zpv, (int64_t)B * td, st), "h")) return false;
+        return ok(launch_film_group_fwd(P, tr->lin_descs, tr->n_lin, tr->max_lin_n, hv, at<float>(pl.film), B, td, A.F, st), "film");
+    }
+
+    bool forward(const float* x_t, const float* z, const int64_t* t, float* eps)
+    {
+        tr->route_log.clear();
+        tr->sync_used = 0;                                       // (fork events of this call; a wait keeps the record it saw when it was enqueued)
+        mark(TF_PACK);
+        // The forward convs' operands now, on this stream; the data-gradient convs' operands (the other half of the 0.18 ms repack)
+        // on the side stream beside the forward pass -- the backward pass waits for them (pack_dg_done).  One launch under a graph
+        // capture (the side branch would have to rejoin inside the forward's graph) and while profiling.
+        static const bool no_split = diag_env("CCN_TRAIN_NO_PACK_SPLIT") != nullptr;     // A/B switch
+        const bool split = !no_split && side_active() && tr->pack_dg_done && !tr->use_graph && pl.n_packs_fwd > 0 && pl.n_packs_fwd < pl.n_packs;
+        if (!ok(launch_pack_group(tr->cfg.dtype, P, pl.packs, split ? pl.n_packs_fwd : pl.n_packs, st), "pack")) return false;
+        tr->pack_dg_pending = false;
+        if (split) {
+            // (the forward call's own fork event: the pool starts over with every backward call, after this event has done its work)
+            if (!tr->fwd_fork && hipEventCreateWithFlags(&tr->fwd_fork, hipEventDisableTiming) != hipSuccess) tr->fwd_fork = nullptr;
+            if (!tr->fwd_fork || order(st, tr->side, tr->fwd_fork) != ORD_OK) { err = "stream fork failed"; return false; }
+            if (!ok(launch_pack_group(tr->cfg.dtype, P, pl.packs + pl.n_packs_fwd, pl.n_packs - pl.n_packs_fwd, tr->side), "pack")) return false;
+            if (hipEventRecord(tr->pack_dg_done, tr->side) != hipSuccess) { err = "event record failed"; return false; }
+            tr->pack_dg_pending = true;
+        }
+        if (!conditioning(z, t)) return false;
+        const float* film = at<float>(pl.film);
+        for (size_t li = 0; li < tr->arch.layers.size(); ++li) {
+            const ArchLayer& L = tr->arch.layers[li];
+            const LayerPlan& lp = pl.layers[li];
+            switch (L.type) {
+                case L_STEM: case L_DOWN: case L_UP:             // one conv: of the image; into the next level; back up, plus the skip
+                    if (!conv_fwd(tr->convs[L.idx], lp.c1, L.type == L_STEM ? (const void*)x_t : at(lp.x.off), lp.o, nullptr, nullptr,
+                                  L.type == L_UP ? at(lp.skip) : nullptr)) return false;
+                    break;
+                case L_RES: {
+                    const ArchRes& r = tr->arch.res[L.idx];
+                    const TConvW &c1 = tr->convs[r.c1], &c2 = tr->convs[r.c2];
+                    const float* film_r = film + r.film_off;
+                    // Side form where both convs run on the persistent kernel (their input GroupNorm in the prologue either way), over the
+                    // same planned tensors and tables as the pre-pass form
+                    if (lp.pre && lp.both_pr && side_pre_ok()) {
+                        if (!norm_conv_fwd_side(lp.x, r.n1, lp.n1, c1, lp.c1, lp.xa, lp.y, film_r, nullptr)) return false;
+                        if (!norm_conv_fwd_side(lp.y, r.n2, lp.n2, c2, lp.c2, lp.ya, lp.o, nullptr, at(lp.x.off))) return false;
                         break;
                     }
-                    TT none;
-                    if (!run_conv(TF_CONV_FWD, fwd_route(hd, x.H, x.W, ab_o != nullptr, false, false), hd.pd_f, hd.pf_f,
-                                  launch ? par(hd.pb) : nullptr, x.p, &none, nullptr, ab_o, nullptr, nullptr, false, eps)) return false;
+                    if (!norm_fwd(lp.x, r.n1, lp.n1, lp.pre ? &lp.xa : nullptr)) return false;
+                    if (!conv_fwd(c1, lp.c1, at(lp.pre ? lp.xa.off : lp.x.off), lp.y, lp.pre ? nullptr : at<float2>(lp.n1.ab), film_r, nullptr)) return false;
+                    if (!norm_fwd(lp.y, r.n2, lp.n2, lp.pre ? &lp.ya : nullptr)) return false;
+                    if (!conv_fwd(c2, lp.c2, at(lp.pre ? lp.ya.off : lp.y.off), lp.o, lp.pre ? nullptr : at<float2>(lp.n2.ab), nullptr, at(lp.x.off))) return false;
+                    break;
+                }
+                case L_HEAD: {
+                    const TConvW& hd = tr->convs[L.idx];
+                    if (!norm_fwd(lp.x, tr->arch.out_norm, lp.n1, nullptr)) return false;
+                    if (lp.head2) {
+                        ConvArgs a = lp.c1.a;
+                        a.in = at(lp.x.off); a.bias = par(hd.pb); a.eps_out = eps;
+                        mark(lp.c1.fam, lp.c1.flops);
+                        note(RN_CONV, KIND_HEAD, "head2", 1);
+                        if (!ok(launch_head2(a, at<float2>(lp.n1.ab), par(hd.pw), at(lp.head2_scratch), 0, st), "head")) return false;
+                    } else if (!run_conv(lp.c1, par(hd.pb), at(lp.x.off), nullptr, nullptr, at<float2>(lp.n1.ab), nullptr, nullptr, eps)) return false;
                     break;
                 }
             }
         }
-        if (launch && (fwd_side_used || tr->pack_dg_pending)) {
+        if (fwd_side_used || tr->pack_dg_pending) {
             // Everything this forward put on the side stream -- the data-gradient operands' repack (reads the parameters), the activated-
             // tensor passes (write into the workspace) -- is joined HERE, on the caller's stream: the side work ended long before the
             // last convs of the main chain do, so the wait is free, and whatever the caller does next with the parameters or the
             // workspace (an optimizer step without a backward pass, freeing the workspace) is ordered behind it.
-            if (hipEventRecord(tr->pack_dg_done, tr->side) != hipSuccess || hipStreamWaitEvent(st, tr->pack_dg_done, 0) != hipSuccess) { err = "stream join failed"; return false; }
+            if (order(tr->side, st, tr->pack_dg_done) != ORD_OK) { err = "stream join failed"; return false; }
             tr->pack_dg_pending = false;
         }
         return true;
     }
 
     // ---- backward pieces ---------------------------------------------------------------------------------------------------
-    void want(size_t& slot, size_t bytes) { if (bytes > slot) slot = bytes; }
-
-    // dW (and db) of a conv: A = act(GN(x)) redone on the fly, dY given
-    bool conv_wgrad(const TConvW& w, const TT& xin, const float2* gn_ab, const void* dy, int Hdy, int Wdy, bool bias_done = false)
+    // dW of a conv from A (`gn_ab`: act(GN(x)) redone on the fly) and dY; weight gradients run on the side stream where there is one
+    bool wgrad(const WgPlan& w, const void* x, const float2* gn_ab, const void* dy, float* gdst)
     {
-        if (!wgrad_generic(w.kind, xin.p, xin.H, xin.W, w.Cin, w.Cin, gn_ab, 1, dy, w.Cout, w.Cout, grad_or_null(w.pw))) return false;
-        const GnBwdGeom gg = gn_bwd_geom(tr->cfg.dtype, B, Hdy * Wdy, w.Cout);
-        want(need.scr_col, (size_t)B * gg.nblk * w.Cout * 4);
-        if (!launch || bias_done) return true;
-        mark(TF_BIAS);
-        note_colsum(gg);
-        if (g_sum_rows > 0) return ok(launch_colsum_from_pairs(scr_film, g_sum_rows, w.Cout, grad(w.pb), st), "bias_grad");
-        return ok(launch_colsum(tr->cfg.dtype, dy, scr_col, grad(w.pb), B, Hdy * Wdy, w.Cout, st), "bias_grad");
-    }
-    // the bias-gradient launch that follows: from the GroupNorm backward's pairs, or launch_colsum on the gradient tensor (geometry gg)
-    void note_colsum(const GnBwdGeom& gg)
-    {
-        const int rows = g_sum_rows > 0 ? g_sum_rows : B * gg.nblk;
-        note(RN_COLSUM, 0, g_sum_rows > 0 ? "pairs" : "dy", rows, colsum_finalize_ygrid(rows));
-    }
-    float* grad_or_null(int i) const { return Gd ? grad(i) : nullptr; }
-    // kind: the forward conv's family (KIND_STEM = 1x1 on an im2col'ed input); Cin / Cout as stored (multiples of 8), Civ / Cov the
-    // channels that exist in the parameter
-    bool wgrad_generic(int kind, const void* x, int Hin, int Win, int Cin, int Civ, const float2* gn_ab, int silu, const void* dy, int Cout, int Cov, float* gdst)
-    {
-        const ConvGeom g = conv_geom(kind, false, Hin, Win, 4);
-        WgArgs a{};
-        a.x = x; a.gn_ab = gn_ab; a.silu = silu; a.dy = dy; a.part = scr_wg;
-        a.B = B; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = g.Hout; a.Wout = g.Wout; a.Cout = Cout;
-        a.MH = g.MH; a.MW = g.MW; a.OS = g.OS; a.npar = g.npar; a.ntaps = g.ntaps; a.taps_w = kind == KIND_CT4 ? 16 : (kind == KIND_STEM ? 1 : 9);
-        a.n_ty = g.n_ty; a.n_tx = g.n_tx;
-        const int ns_alone = wgrad_nsplit(tr->cfg.dtype, kind, B, g.MH, g.MW, Cin, Cout, false), ns_conc = wgrad_nsplit(tr->cfg.dtype, kind, B, g.MH, g.MW, Cin, Cout, true);
-        a.nsplit = side_active() ? ns_conc : ns_alone;
-        fill_taps(a.tapinfo, kind, false);
-        want(need.scr_wg, (size_t)(ns_alone > ns_conc ? ns_alone : ns_conc) * a.taps_w * Cout * Cin * 4);
-        if (!launch) return true;
+        WgArgs a = w.a;
+        float* scr_wg = at<float>(pl.scr_wg);
+        a.x = x; a.gn_ab = gn_ab; a.dy = dy; a.part = scr_wg;
+        a.nsplit = w.nsplit[side_active() ? 1 : 0];
         if (!fork_side()) return false;
-        mark(TF_WGRAD, 2.0 * B * g.Hout * g.Wout * (double)Cov * (kind == KIND_CT4 ? 4 : (kind == KIND_STEM ? 1 : 9)) * Civ);
-        note(RN_WGRAD, kind, "", a.nsplit, B * a.n_ty * a.n_tx, Cin, Cout);
-        if (!ok(launch_wgrad(tr->cfg.dtype, kind, a, wg_stream), "wgrad")) return false;
+        mark(TF_WGRAD, w.flops);
+        note(RN_WGRAD, w.kind, "", a.nsplit, w.tiles, a.Cin, a.Cout);
+        if (!ok(launch_wgrad(tr->cfg.dtype, w.kind, a, wg_stream), "wgrad")) return false;
         mark(TF_WGRAD_REDUCE);
-        return ok(launch_wgrad_reduce(scr_wg, a.nsplit, a.taps_w, Cout, Cin, Cov, Civ, kind == KIND_CT4 ? 1 : 0, gdst, wg_stream), "wgrad_reduce");
+        return ok(launch_wgrad_reduce(scr_wg, a.nsplit, a.taps_w, a.Cout, a.Cin, w.Cov, w.Civ, w.kind == KIND_CT4 ? 1 : 0, gdst, wg_stream), "wgrad_reduce");
     }
-    // GroupNorm(+SiLU) backward of the norm reading tensor `x`: dA -> out (may alias dA)
-    bool gn_bwd(const TT& x, const ArchNorm& n, const float2* ab, const float2* stats, const void* dA, void* out, bool silu, const void* addend,
-                int film_off, float* film_bias = nullptr)
+    // db of a conv: from the GroupNorm backward's pairs where its output gradient came out of one, else launch_colsum on that gradient
+    bool bias_grad(const BiasPlan& b, const void* dy, float* gdst, const char* what)
     {
-        const int G = groups_for(x.C), cpg = x.C / G, HW = x.H * x.W;
-        const GnBwdGeom gg = gn_bwd_geom(tr->cfg.dtype, B, HW, x.C);
-        want(need.scr_gn, (size_t)B * gg.nblk * x.C * sizeof(float2));
-        want(need.scr_film, (size_t)B * gg.nblk * x.C * sizeof(float2));
-        const float* film_r = film_off >= 0 && film ? film + film_off : nullptr;
-        float* dfilm_r = film_off >= 0 && dfilm ? dfilm + film_off : nullptr;
-        g_sum_rows = film_off >= 0 ? 0 : B * gg.nblk;
-        float2* gstat = (float2*)take((size_t)B * G * sizeof(float2));
-        if (!launch) return true;
-        const int dt = tr->cfg.dtype;
-        // algorithmic HBM bytes: pass 1 reads x and dA, pass 2 reads them again (+ the residual gradient) and writes dx
-        mark(TF_GN_BWD, 0.0, (double)B * HW * x.C * tr->elem * (addend ? 6.0 : 5.0));
-        note(RN_GNBWD, 0, "", x.C, HW, gg.ppb / gg.pstep, gg.nblk, HW % gg.ppb);
+        mark(TF_BIAS);
+        note(RN_COLSUM, 0, b.pairs ? "pairs" : "dy", b.rows, colsum_finalize_ygrid(b.rows));
+        if (b.pairs) return ok(launch_colsum_from_pairs(at<float2>(pl.scr_film), b.rows, b.C, gdst, st), what);
+        return ok(launch_colsum(tr->cfg.dtype, dy, at<float>(pl.scr_col), gdst, B, b.HW, b.C, st), what);
+    }
+    bool conv_dgrad(const ConvPlan& c, const void* dy, void* dx, const void* res)
+    {
+        return run_conv(c, tr->zero_bias, dy, dx, nullptr, nullptr, nullptr, res, nullptr);
+    }
+    // GroupNorm(+SiLU) backward of the norm reading tensor `x`: dA -> out (may alias dA); film_off >= 0: the FiLM behind the norm
+    bool gn_bwd(const Tensor& x, const ArchNorm& an, const NormPlan& n, const GnBwdPlan& g, const void* dA, void* out, const void* addend, int film_off,
+                float* film_bias = nullptr)
+    {
+        const int dt = tr->cfg.dtype, HW = n.HW;
+        const float2 *ab = at<float2>(n.ab), *stats = at<float2>(n.st);
+        float2 *scr_gn = at<float2>(pl.scr_gn), *scr_film = at<float2>(pl.scr_film), *gstat = at<float2>(g.gstat);
+        const float* film_r = film_off >= 0 ? at<float>(pl.film) + film_off : nullptr;
+        mark(TF_GN_BWD, 0.0, g.bytes);
+        note(RN_GNBWD, 0, "", x.C, HW, g.gg.ppb / g.gg.pstep, g.gg.nblk, HW % g.gg.ppb);
         // (round 3: the three passes as ONE launch with one 1024-thread workgroup per (sample, group) for the levels below 256 px was
         // built, parity-green, and 0.95 ms SLOWER per step (2.47 vs 1.53 ms for the family): a group's channels are 32-128 contiguous
         // bytes per pixel, so 32 workgroups pull uncoalesced 32-byte segments at a few tens of GB/s each; docs/EXPERIMENTS.md R3.5)
-        if (!ok(launch_gn_bwd_reduce(dt, x.p, dA, ab, stats, scr_gn, B, HW, x.C, cpg, G, silu ? 1 : 0, st), "gn_bwd_reduce")) return false;
-        if (!ok(launch_gn_bwd_finalize(scr_gn, gg.nblk, B, x.C, cpg, G, (double)cpg * HW, par(n.pg), gstat, grad(n.pg), grad(n.pb), st), "gn_bwd_finalize")) return false;
-        if (!ok(launch_gn_bwd_apply(dt, x.p, dA, ab, stats, gstat, addend, out, film_r, tr->arch.F, scr_film, B, HW, x.C, cpg, G, silu ? 1 : 0, st), "gn_bwd_apply"))
+        if (!ok(launch_gn_bwd_reduce(dt, at(x.off), dA, ab, stats, scr_gn, B, HW, x.C, n.cpg, n.G, g.silu, st), "gn_bwd_reduce")) return false;
+        if (!ok(launch_gn_bwd_finalize(scr_gn, g.gg.nblk, B, x.C, n.cpg, n.G, n.count, par(an.pg), gstat, grad(an.pg), grad(an.pb), st), "gn_bwd_finalize")) return false;
+        if (!ok(launch_gn_bwd_apply(dt, at(x.off), dA, ab, stats, gstat, addend, out, film_r, tr->arch.F, scr_film, B, HW, x.C, n.cpg, n.G, g.silu, st), "gn_bwd_apply"))
             return false;
-        if (film_r) return ok(launch_film_bwd_finalize(scr_film, gg.nblk, film_r, tr->arch.F, dfilm_r, film_bias, B, x.C, st), "film_bwd");
+        if (film_r) return ok(launch_film_bwd_finalize(scr_film, g.gg.nblk, film_r, tr->arch.F, at<float>(pl.dfilm) + film_off, film_bias, B, x.C, st), "film_bwd");
         return true;
     }
     bool flush_bucket(long long lo, bool force)
     {
-        if (!bucket_cb || !launch) return true;
+        if (!bucket_cb) return true;
         if (!force && hi_pending - lo < bucket_floats) return true;
         if (lo >= hi_pending) return true;
         if (!join_side()) return false;
@@ -635,7 +796,6 @@ struct Walk {
     }
     bool lin_bwd(const ArchLin& l, const float* dy, int lddy, const float* x, int ldx, float* dx, int lddx, int accumulate)
     {
-        if (!launch) return true;
         if (!ok(launch_tlinear_dw(dy, lddy, x, ldx, grad(l.pw), grad(l.pb), B, l.K, l.N, st), "linear_dw")) return false;
         if (dx) return ok(launch_tlinear_dx(dy, lddy, par(l.pw), dx, lddx, B, l.K, l.N, accumulate, st), "linear_dx");
         return true;
@@ -644,67 +804,47 @@ struct Walk {
     bool backward(const float* x_t, const float* z, const float* d_eps)
     {
         const ccn_config_t& c = tr->cfg;
-        const int td = c.time_dim, dt = c.dtype;
-        dfilm = (float*)take((size_t)B * tr->arch.F * 4); dh = (float*)take((size_t)B * td * 4);
-        dt1 = (float*)take((size_t)B * td * 16); du0 = (float*)take((size_t)B * td * 16); duz = (float*)take((size_t)B * td * 4);
+        const int td = c.time_dim, dt = c.dtype, H = pl.H, W = pl.W;
+        float *dfilm = at<float>(pl.dfilm), *dh = at<float>(pl.dh), *dt1 = at<float>(pl.dt1), *du0 = at<float>(pl.du0), *duz = at<float>(pl.duz);
+        float* hv = at<float>(pl.hv);
+        tr->sync_used = 0;
         hi_pending = (long long)tr->arch.total;
-        if (launch && tr->pack_dg_pending) {                   // the data-gradient operands repacked beside the forward pass
+        if (tr->pack_dg_pending) {                              // the data-gradient operands repacked beside the forward pass
             if (hipStreamWaitEvent(st, tr->pack_dg_done, 0) != hipSuccess) { err = "stream wait failed"; return false; }
             tr->pack_dg_pending = false;
         }
-        if (launch && bucket_cb && hipMemsetAsync(dh, 0, (size_t)B * td * 4, st) != hipSuccess) { err = "hipMemsetAsync failed"; return false; }
-        TT g;                                                  // gradient w.r.t. the current tensor
-        std::vector<void*> dskip;                              // gradients waiting at the skip connections (pushed by the up path)
-        int ri = (int)rs.size() - 1, di = (int)down_in.size() - 1, ui = (int)up_in.size() - 1;
+        if (bucket_cb && hipMemsetAsync(dh, 0, pl.dh_bytes, st) != hipSuccess) { err = "hipMemsetAsync failed"; return false; }
         for (int li = (int)tr->arch.layers.size() - 1; li >= 0; --li) {
             const ArchLayer& L = tr->arch.layers[li];
+            const LayerPlan& lp = pl.layers[li];
             switch (L.type) {
                 case L_HEAD: {
                     const TConvW& w = tr->convs[L.idx];
-                    const TT& u = head_in;
                     // out.weight: the generic kernel on d eps as an NHWC tensor (channels padded to 8), A = out_norm(u) without SiLU
-                    void* de = take((size_t)B * H * W * 8 * tr->elem);
-                    if (launch) {
-                        mark(TF_SMALL);
-                        if (!ok(launch_nchw_to_nhwc_pad(dt, d_eps, de, B, c.img_ch, 8, (int64_t)H * W, st), "head_deps_layout")) return false;
-                        if (!ok(launch_nchw_chansum(d_eps, grad(w.pb), B, c.img_ch, (int64_t)H * W, st), "head_bias")) return false;
-                    }
-                    if (!wgrad_generic(KIND_C3S1, u.p, H, W, u.C, u.C, ab_o, 0, de, 8, c.img_ch, grad_or_null(w.pw))) return false;
-                    g = new_tensor(u.C, H, W);
-                    if (!conv_dgrad(w, d_eps, H, W, g.p, nullptr)) return false;
-                    if (!gn_bwd(u, tr->arch.out_norm, ab_o, st_o, g.p, g.p, false, nullptr, -1)) return false;
+                    mark(TF_SMALL);
+                    if (!ok(launch_nchw_to_nhwc_pad(dt, d_eps, at(lp.de), B, c.img_ch, 8, pl.HW, st), "head_deps_layout")) return false;
+                    if (!ok(launch_nchw_chansum(d_eps, grad(w.pb), B, c.img_ch, pl.HW, st), "head_bias")) return false;
+                    if (!wgrad(lp.w1, at(lp.x.off), at<float2>(lp.n1.ab), at(lp.de), grad_or_null(w.pw))) return false;
+                    if (!conv_dgrad(lp.d1, d_eps, at(lp.g2), nullptr)) return false;
+                    if (!gn_bwd(lp.x, tr->arch.out_norm, lp.n1, lp.gb1, at(lp.g2), at(lp.g2), nullptr, -1)) return false;
                     break;
                 }
-                case L_UP: {
+                case L_UP: case L_DOWN: {
                     const TConvW& w = tr->convs[L.idx];
-                    const TT& xin = up_in[ui]; --ui;
-                    dskip.push_back(g.p);                       // x = convT(xin) + skip
-                    if (!conv_wgrad(w, xin, nullptr, g.p, g.H, g.W)) return false;
-                    TT d = new_tensor(xin.C, xin.H, xin.W);
-                    if (!conv_dgrad(w, g.p, g.H, g.W, d.p, nullptr)) return false;
-                    g = d;
-                    break;
-                }
-                case L_DOWN: {
-                    const TConvW& w = tr->convs[L.idx];
-                    const TT& xin = down_in[di]; --di;
-                    if (!conv_wgrad(w, xin, nullptr, g.p, g.H, g.W)) return false;
-                    TT d = new_tensor(xin.C, xin.H, xin.W);
-                    const void* sk = dskip.back(); dskip.pop_back();
-                    if (!conv_dgrad(w, g.p, g.H, g.W, d.p, sk)) return false;
-                    g = d;
+                    if (!wgrad(lp.w1, at(lp.x.off), nullptr, at(lp.g), grad_or_null(w.pw))) return false;
+                    if (!bias_grad(lp.bias, at(lp.g), grad(w.pb), "bias_grad")) return false;
+                    if (!conv_dgrad(lp.d1, at(lp.g), at(lp.g2), L.type == L_DOWN ? at(lp.dskip) : nullptr)) return false;
                     break;
                 }
                 case L_RES: {
                     const ArchRes& r = tr->arch.res[L.idx];
                     const TConvW &c1 = tr->convs[r.c1], &c2 = tr->convs[r.c2];
-                    const ResSave& s = rs[ri]; --ri;
                     // out = x + conv2(A2), A2 = silu(gn2(F)), F = film(conv1(A1)), A1 = silu(gn1(x))
-                    if (!conv_wgrad(c2, s.pre ? s.ya : s.y, s.pre ? nullptr : s.ab2, g.p, g.H, g.W)) return false;
-                    TT g1 = new_tensor(r.C, g.H, g.W);
-                    if (!conv_dgrad(c2, g.p, g.H, g.W, g1.p, nullptr)) return false;
-                    if (!gn_bwd(s.y, r.n2, s.ab2, s.st2, g1.p, g1.p, true, nullptr, r.film_off, launch ? grad(c1.pb) : nullptr)) return false;
-                    if (launch && bucket_cb) {
+                    if (!wgrad(lp.w2, at(lp.pre ? lp.ya.off : lp.y.off), lp.pre ? nullptr : at<float2>(lp.n2.ab), at(lp.g), grad_or_null(c2.pw))) return false;
+                    if (!bias_grad(lp.bias, at(lp.g), grad(c2.pb), "bias_grad")) return false;
+                    if (!conv_dgrad(lp.d2, at(lp.g), at(lp.g1), nullptr)) return false;
+                    if (!gn_bwd(lp.y, r.n2, lp.n2, lp.gb2, at(lp.g1), at(lp.g1), nullptr, r.film_off, grad(c1.pb))) return false;
+                    if (bucket_cb) {
                         // bucketed mode: this block's FiLM linears now (side stream) instead of one grouped launch at the end, so that the
                         // block's whole parameter range is complete when its bucket is handed out
                         if (!fork_side()) return false;
@@ -712,28 +852,18 @@ struct Walk {
                         if (!ok(launch_film_group_dw(Gd, d2, 2, r.C, dfilm, hv, B, td, tr->arch.F, wg_stream), "film_dw")) return false;
                         if (!ok(launch_film_group_dx(P, d2, 2, dfilm, dh, B, td, tr->arch.F, wg_stream), "film_dx")) return false;
                     }
-                    if (!conv_wgrad(c1, s.pre ? s.xa : s.x, s.pre ? nullptr : s.ab1, g1.p, g.H, g.W, true)) return false;
-                    TT g2 = new_tensor(r.C, g.H, g.W);
-                    if (!conv_dgrad(c1, g1.p, g.H, g.W, g2.p, nullptr)) return false;
-                    if (!gn_bwd(s.x, r.n1, s.ab1, s.st1, g2.p, g2.p, true, g.p, -1)) return false;
-                    g = g2;
+                    if (!wgrad(lp.w1, at(lp.pre ? lp.xa.off : lp.x.off), lp.pre ? nullptr : at<float2>(lp.n1.ab), at(lp.g1), grad_or_null(c1.pw))) return false;
+                    if (!conv_dgrad(lp.d1, at(lp.g1), at(lp.g2), nullptr)) return false;
+                    if (!gn_bwd(lp.x, r.n1, lp.n1, lp.gb1, at(lp.g2), at(lp.g2), at(lp.g), -1)) return false;
                     break;
                 }
                 case L_STEM: {
                     const TConvW& w = tr->convs[L.idx];
                     // in_conv.weight: 1x1 weight gradient against the im2col of the image (27 of 32 columns)
-                    const GnBwdGeom gg = gn_bwd_geom(dt, B, H * W, w.Cout);
-                    want(need.scr_col, (size_t)B * gg.nblk * w.Cout * 4);
-                    void* col = take((size_t)B * H * W * 32 * tr->elem);
-                    if (launch) {
-                        mark(TF_SMALL);
-                        if (!ok(launch_im2col27(dt, x_t, col, B, c.img_ch, H, W, st), "stem_im2col")) return false;
-                        mark(TF_BIAS);
-                        note_colsum(gg);
-                        if (g_sum_rows > 0) { if (!ok(launch_colsum_from_pairs(scr_film, g_sum_rows, w.Cout, grad(w.pb), st), "stem_bias")) return false; }
-                        else if (!ok(launch_colsum(dt, g.p, scr_col, grad(w.pb), B, H * W, w.Cout, st), "stem_bias")) return false;
-                    }
-                    if (!wgrad_generic(KIND_STEM, col, H, W, 32, c.img_ch * 9, nullptr, 0, g.p, w.Cout, w.Cout, grad_or_null(w.pw))) return false;
+                    mark(TF_SMALL);
+                    if (!ok(launch_im2col27(dt, x_t, at(lp.col), B, c.img_ch, H, W, st), "stem_im2col")) return false;
+                    if (!bias_grad(lp.bias, at(lp.g), grad(w.pb), "stem_bias")) return false;
+                    if (!wgrad(lp.w1, at(lp.col), nullptr, at(lp.g), grad_or_null(w.pw))) return false;
                     break;
                 }
             }
@@ -744,21 +874,20 @@ struct Walk {
             }
         }
         // conditioning: film_r = h W_r^T + b_r for every block; h = time_proj(temb(t)) + z_proj(z)
-        if (!launch) return true;
         mark(TF_COND);
         if (bucket_cb) {
             if (!join_side()) return false;                      // dh was accumulated block by block on the side stream
         } else {
-            if (hipMemsetAsync(dh, 0, (size_t)B * td * 4, st) != hipSuccess) { err = "hipMemsetAsync failed"; return false; }
+            if (hipMemsetAsync(dh, 0, pl.dh_bytes, st) != hipSuccess) { err = "hipMemsetAsync failed"; return false; }
             if (!ok(launch_film_group_dw(Gd, tr->lin_descs, tr->n_lin, tr->max_lin_n, dfilm, hv, B, td, tr->arch.F, st), "film_dw")) return false;
             if (!ok(launch_film_group_dx(P, tr->lin_descs, tr->n_lin, dfilm, dh, B, td, tr->arch.F, st), "film_dx")) return false;
         }
-        if (!lin_bwd(tr->arch.tp2, dh, td, t1, 4 * td, dt1, 4 * td, 0)) return false;
-        if (!ok(launch_silu_bwd(du0, dt1, u0, (int64_t)B * 4 * td, st), "silu_bwd")) return false;
-        if (!lin_bwd(tr->arch.tp0, du0, 4 * td, temb, td, nullptr, 0, 0)) return false;
-        if (!ok(launch_silu_bwd(duz, dh, uz, (int64_t)B * td, st), "silu_bwd")) return false;
+        if (!lin_bwd(tr->arch.tp2, dh, td, at<float>(pl.t1), 4 * td, dt1, 4 * td, 0)) return false;
+        if (!ok(launch_silu_bwd(du0, dt1, at<float>(pl.u0), (int64_t)B * 4 * td, st), "silu_bwd")) return false;
+        if (!lin_bwd(tr->arch.tp0, du0, 4 * td, at<float>(pl.temb), td, nullptr, 0, 0)) return false;
+        if (!ok(launch_silu_bwd(duz, dh, at<float>(pl.uz), (int64_t)B * td, st), "silu_bwd")) return false;
         if (!lin_bwd(tr->arch.zp, duz, td, z, c.z_dim, nullptr, 0, 0)) return false;
-        return flush_bucket(0, true);
+        return flush_bucket(0, true) && join_side();
     }
 };
 
@@ -768,33 +897,38 @@ std::string shape_key(int B, int H, int W)
     return std::to_string(B) + "x" + std::to_string(H) + "x" + std::to_string(W) + (conv_pr_selected(1, KIND_C3S1, 128, 8) ? "p" : "n");
 }
 
-int shape_info(ccn_trainer_s* tr, int B, int H, int W, ShapeInfo* out)
+// the cached plan of a shape, built (and its repack list uploaded) on first use
+int step_plan(ccn_trainer_s* tr, int B, int H, int W, const StepPlan** out)
 {
     if (B <= 0 || H <= 0 || W <= 0) return tfail(CCN_EINVAL, "B, H, W must be positive");
     const int div = 1 << tr->cfg.n_mult;
     if (H % div || W % div) return tfail(CCN_EINVAL, "H and W must be divisible by 2^len(ch_mult)");
     const std::string key = shape_key(B, H, W);
     auto it = tr->shapes.find(key);
-    if (it != tr->shapes.end()) { *out = it->second; return CCN_OK; }
-    Walk w(tr, B, H, W, nullptr, false, nullptr, nullptr, nullptr);
-    if (!w.forward(nullptr, nullptr, nullptr, nullptr)) return tfail(CCN_EINVAL, w.err);
-    const int n_packs_fwd = (int)w.pack_list.size();            // the forward convs' operands come first in the list
-    if (!w.backward(nullptr, nullptr, nullptr)) return tfail(CCN_EINVAL, w.err);
-    ShapeInfo si = w.need;
-    si.n_packs_fwd = n_packs_fwd;
-    si.tensors = align_up(w.off, 256);
-    si.total = si.tensors + align_up(si.scr_wg, 256) + align_up(si.scr_gn, 256) + align_up(si.scr_film, 256) + align_up(si.scr_col, 256) +
-               5 * 256;
-    {
+    if (it == tr->shapes.end()) {
+        StepPlan pl;
+        pl.B = B; pl.H = H; pl.W = W;
+        Planner(tr, pl).run();
         std::string err;
         void* dev = nullptr;
-        if (!alloc_dev(tr, w.pack_list.size() * sizeof(PackDesc), &dev, err)) return tfail(CCN_EHIP, err);
-        if (hipMemcpy(dev, w.pack_list.data(), w.pack_list.size() * sizeof(PackDesc), hipMemcpyHostToDevice) != hipSuccess) return tfail(CCN_EHIP, "descriptor upload failed");
-        si.packs = (PackDesc*)dev; si.n_packs = (int)w.pack_list.size();
+        if (!alloc_dev(tr, pl.pack_list.size() * sizeof(PackDesc), &dev, err)) return tfail(CCN_EHIP, err);
+        if (hipMemcpy(dev, pl.pack_list.data(), pl.pack_list.size() * sizeof(PackDesc), hipMemcpyHostToDevice) != hipSuccess) return tfail(CCN_EHIP, "descriptor upload failed");
+        pl.packs = (PackDesc*)dev; pl.n_packs = (int)pl.pack_list.size();
+        it = tr->shapes.emplace(key, std::move(pl)).first;
     }
-    tr->shapes[key] = si;
-    *out = si;
+    *out = &it->second;
     return CCN_OK;
+}
+
+// snprintf-like end of the report hooks: at most cap bytes (NUL-terminated) into buf, returns the length of the whole text
+int copy_report(const std::string& text, char* buf, size_t cap)
+{
+    if (buf && cap) {
+        const size_t n = text.size() < cap - 1 ? text.size() : cap - 1;
+        std::memcpy(buf, text.data(), n);
+        buf[n] = 0;
+    }
+    return (int)text.size();
 }
 
 // replay the cached graph for `key`, or capture `body` (which enqueues on the capture stream) and replay it
@@ -916,13 +1050,14 @@ int ccn_train_param_info(ccn_trainer_t tr, int32_t i, const char** name, int64_t
     return CCN_OK;
 }
 
+
 int ccn_train_workspace_bytes(ccn_trainer_t tr, int32_t B, int32_t H, int32_t W, size_t* bytes)
 {
     if (!tr || !bytes) return tfail(CCN_EINVAL, "null argument");
-    ShapeInfo si;
-    const int rc = shape_info(tr, B, H, W, &si);
+    const StepPlan* pl;
+    const int rc = step_plan(tr, B, H, W, &pl);
     if (rc) return rc;
-    *bytes = si.total;
+    *bytes = pl->total;
     return CCN_OK;
 }
 
@@ -930,17 +1065,15 @@ int ccn_train_forward(ccn_trainer_t tr, const float* params_dev, const float* x_
                       int32_t B, int32_t H, int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream)
 {
     if (!tr || !params_dev || !x_t_dev || !z_dev || !t_dev || !eps_dev) return tfail(CCN_EINVAL, "null argument");
-    ShapeInfo si;
-    int rc = shape_info(tr, B, H, W, &si);
+    const StepPlan* pl;
+    int rc = step_plan(tr, B, H, W, &pl);
     if (rc) return rc;
     if (!workspace_dev || ((uintptr_t)workspace_dev & 255)) return tfail(CCN_EWORKSPACE, "workspace must be non-null and 256-byte aligned");
-    if (workspace_bytes < si.total) return tfail(CCN_EWORKSPACE, "workspace too small: need " + std::to_string(si.total));
+    if (workspace_bytes < pl->total) return tfail(CCN_EWORKSPACE, "workspace too small: need " + std::to_string(pl->total));
     auto body = [&](hipStream_t st, std::string& err) {
-        Walk w(tr, B, H, W, workspace_dev, true, st, params_dev, nullptr);
-        w.place_scratch(si);
-        w.shape_packs = si.packs; w.n_shape_packs = si.n_packs; w.n_shape_packs_fwd = si.n_packs_fwd;
-        if (!w.forward(x_t_dev, z_dev, t_dev, eps_dev)) { err = w.err; return false; }
-        w.mark(-1);
+        Step s(tr, *pl, workspace_dev, st, params_dev, nullptr);
+        if (!s.forward(x_t_dev, z_dev, t_dev, eps_dev)) { err = s.err; return false; }
+        s.mark(-1);
         return true;
     };
     if (tr->use_graph && !tr->profiling) {
@@ -956,27 +1089,28 @@ int ccn_train_forward(ccn_trainer_t tr, const float* params_dev, const float* x_
     return CCN_OK;
 }
 
-int ccn_train_backward(ccn_trainer_t tr, const float* params_dev, float* grads_dev, const float* x_t_dev, const float* z_dev, const float* d_eps_dev,
-                       int32_t B, int32_t H, int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream)
+}  // extern "C"
+
+namespace {
+
+// both backward entry points; cb: the bucketed form, which never runs under a graph
+int train_backward(const char* who, ccn_trainer_t tr, const float* params_dev, float* grads_dev, const float* x_t_dev, const float* z_dev, const float* d_eps_dev,
+                   int32_t B, int32_t H, int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream, int64_t bucket_floats, ccn_grad_ready_cb cb, void* user)
 {
-    if (!tr || !params_dev || !grads_dev || !x_t_dev || !z_dev || !d_eps_dev) return tfail(CCN_EINVAL, "null argument");
     if (tr->fB != B || tr->fH != H || tr->fW != W || tr->fws != workspace_dev)
-        return tfail(CCN_ESTATE, "ccn_train_backward must follow ccn_train_forward with the same shape and workspace");
-    ShapeInfo si;
-    int rc = shape_info(tr, B, H, W, &si);
+        return tfail(CCN_ESTATE, std::string(who) + " must follow ccn_train_forward with the same shape and workspace");
+    const StepPlan* pl;
+    const int rc = step_plan(tr, B, H, W, &pl);
     if (rc) return rc;
-    if (workspace_bytes < si.total) return tfail(CCN_EWORKSPACE, "workspace too small");
+    if (workspace_bytes < pl->total) return tfail(CCN_EWORKSPACE, "workspace too small");
     auto body = [&](hipStream_t st, std::string& err) {
-        Walk w(tr, B, H, W, workspace_dev, false, st, params_dev, grads_dev);
-        w.place_scratch(si);
-        if (!w.forward(x_t_dev, z_dev, nullptr, nullptr)) { err = w.err; return false; }
-        w.launch = true;
-        tr->sync_used = 0;
-        if (!w.backward(x_t_dev, z_dev, d_eps_dev) || !w.join_side()) { err = w.err; return false; }
-        w.mark(-1);
+        Step s(tr, *pl, workspace_dev, st, params_dev, grads_dev);
+        s.bucket_cb = cb; s.bucket_user = user; s.bucket_floats = bucket_floats > 0 ? bucket_floats : 1;
+        if (!s.backward(x_t_dev, z_dev, d_eps_dev)) { err = s.err; return false; }
+        if (!cb) s.mark(-1);
         return true;
     };
-    if (tr->use_graph && !tr->profiling) {
+    if (!cb && tr->use_graph && !tr->profiling) {
         const std::vector<const void*> key = {(const void*)2, params_dev, grads_dev, x_t_dev, z_dev, d_eps_dev, workspace_dev, (const void*)(uintptr_t)B,
                                               (const void*)(uintptr_t)H, (const void*)(uintptr_t)W};
         return run_graphed(tr, key, (hipStream_t)stream, body);
@@ -986,35 +1120,34 @@ int ccn_train_backward(ccn_trainer_t tr, const float* params_dev, float* grads_d
     return CCN_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int ccn_train_backward(ccn_trainer_t tr, const float* params_dev, float* grads_dev, const float* x_t_dev, const float* z_dev, const float* d_eps_dev,
+                       int32_t B, int32_t H, int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream)
+{
+    if (!tr || !params_dev || !grads_dev || !x_t_dev || !z_dev || !d_eps_dev) return tfail(CCN_EINVAL, "null argument");
+    return train_backward("ccn_train_backward", tr, params_dev, grads_dev, x_t_dev, z_dev, d_eps_dev, B, H, W, workspace_dev, workspace_bytes, stream, 0, nullptr, nullptr);
+}
+
 int ccn_train_backward_bucketed(ccn_trainer_t tr, const float* params_dev, float* grads_dev, const float* x_t_dev, const float* z_dev, const float* d_eps_dev,
                                 int32_t B, int32_t H, int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream, int64_t bucket_floats,
                                 ccn_grad_ready_cb cb, void* user)
 {
     if (!tr || !params_dev || !grads_dev || !x_t_dev || !z_dev || !d_eps_dev || !cb) return tfail(CCN_EINVAL, "null argument");
-    if (tr->fB != B || tr->fH != H || tr->fW != W || tr->fws != workspace_dev)
-        return tfail(CCN_ESTATE, "ccn_train_backward_bucketed must follow ccn_train_forward with the same shape and workspace");
-    ShapeInfo si;
-    int rc = shape_info(tr, B, H, W, &si);
-    if (rc) return rc;
-    if (workspace_bytes < si.total) return tfail(CCN_EWORKSPACE, "workspace too small");
-    Walk w(tr, B, H, W, workspace_dev, false, (hipStream_t)stream, params_dev, grads_dev);
-    w.place_scratch(si);
-    if (!w.forward(x_t_dev, z_dev, nullptr, nullptr)) return tfail(CCN_EHIP, w.err);
-    w.launch = true;
-    w.bucket_cb = cb; w.bucket_user = user; w.bucket_floats = bucket_floats > 0 ? bucket_floats : 1;
-    tr->sync_used = 0;
-    if (!w.backward(x_t_dev, z_dev, d_eps_dev) || !w.join_side()) return tfail(CCN_EHIP, w.err);
-    return CCN_OK;
+    return train_backward("ccn_train_backward_bucketed", tr, params_dev, grads_dev, x_t_dev, z_dev, d_eps_dev, B, H, W, workspace_dev, workspace_bytes, stream, bucket_floats,
+                          cb, user);
 }
 
 // Test hook, not part of include/ccn_hip.h (ccn_internal_plan_routes' counterpart for the training step): one line per launch decision
-// of the last launching forward walk and the backward walks since, in launch order, taken where the launch is made:
+// of the last forward call and the backward calls since, in launch order, taken where the launch is made:
 //   conv fwd|dgrad <KIND> <kernel> th= bn= n_nt= four=     (kernel: conv_kernel_name(conv_kernel_for(..)), or head2)
 //   norm fused|stats+act|prologue|side-fused|side-stats+act slots=
 //   gnbwd C= HW= iters= nblk= tail=                        (pixel passes per workgroup; pixels of the partial last block)
 //   wgrad <KIND> nsplit= tiles= cin= cout=
 //   colsum src=dy|pairs rows= ygrid=
-// A graph replay leaves the captured walk's lines.  snprintf-like: writes at most cap bytes (NUL-terminated) and returns the length of the
+// A graph replay leaves the captured call's lines.  snprintf-like: writes at most cap bytes (NUL-terminated) and returns the length of the
 // whole report, or -1.
 int ccn_internal_train_routes(ccn_trainer_t tr, char* buf, size_t cap)
 {
@@ -1033,12 +1166,21 @@ int ccn_internal_train_routes(ccn_trainer_t tr, char* buf, size_t cap)
         }
         text += line;
     }
-    if (buf && cap) {
-        const size_t n = text.size() < cap - 1 ? text.size() : cap - 1;
-        std::memcpy(buf, text.data(), n);
-        buf[n] = 0;
-    }
-    return (int)text.size();
+    return copy_report(text, buf, cap);
+}
+
+// Test hook, not part of include/ccn_hip.h: the planned workspace of a shape (built if absent, otherwise only read), one line per region
+// in planning order
+//   <name> off= bytes=
+// and a last line total=, the value of ccn_train_workspace_bytes.  snprintf-like, as ccn_internal_train_routes.
+int ccn_internal_train_layout(ccn_trainer_t tr, int32_t B, int32_t H, int32_t W, char* buf, size_t cap)
+{
+    const StepPlan* pl;
+    if (!tr || step_plan(tr, B, H, W, &pl)) return -1;
+    std::string text;
+    for (const Region& r : pl->regions) text += r.name + " off=" + std::to_string(r.off) + " bytes=" + std::to_string(r.bytes) + "\n";
+    text += "total=" + std::to_string(pl->total) + "\n";
+    return copy_report(text, buf, cap);
 }
 
 int ccn_train_profile_enable(ccn_trainer_t tr, int32_t on)
