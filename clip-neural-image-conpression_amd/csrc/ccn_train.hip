@@ -224,6 +224,23 @@ bool setup_conv(ccn_trainer_s* tr, TConvW& w, std::string& err)
     return true;
 }
 
+// geometry, taps and split counts of one weight-gradient launch: the planner's (Planner::wgrad) and the test hook's (ccn_internal_wgrad)
+WgPlan wgrad_plan(int dtype, int kind, int B, int Hin, int Win, int Cin, int Civ, int silu, int Cout, int Cov)
+{
+    const ConvGeom g = conv_geom(kind, false, Hin, Win, 4);
+    WgPlan w{};
+    WgArgs& a = w.a;
+    a.silu = silu;
+    a.B = B; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = g.Hout; a.Wout = g.Wout; a.Cout = Cout;
+    a.MH = g.MH; a.MW = g.MW; a.OS = g.OS; a.npar = g.npar; a.ntaps = g.ntaps; a.taps_w = kind == KIND_CT4 ? 16 : (kind == KIND_STEM ? 1 : 9);
+    a.n_ty = g.n_ty; a.n_tx = g.n_tx;
+    fill_taps(a.tapinfo, kind, false);
+    w.kind = kind; w.Cov = Cov; w.Civ = Civ; w.tiles = B * g.n_ty * g.n_tx;
+    w.nsplit[0] = wgrad_nsplit(dtype, kind, B, g.MH, g.MW, Cin, Cout, false);
+    w.nsplit[1] = wgrad_nsplit(dtype, kind, B, g.MH, g.MW, Cin, Cout, true);
+    w.flops = 2.0 * B * g.Hout * g.Wout * (double)Cov * (kind == KIND_CT4 ? 4 : (kind == KIND_STEM ? 1 : 9)) * Civ;
+    return w;
+}
 
 // ---- planner: one pass over the layer list, forward then backward, that places every region and fixes every launch's geometry ---------
 struct Planner {
@@ -304,19 +321,8 @@ struct Planner {
     // channels that exist in the parameter
     WgPlan wgrad(int kind, int Hin, int Win, int Cin, int Civ, int silu, int Cout, int Cov)
     {
-        const ConvGeom g = conv_geom(kind, false, Hin, Win, 4);
-        WgPlan w{};
-        WgArgs& a = w.a;
-        a.silu = silu;
-        a.B = B; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = g.Hout; a.Wout = g.Wout; a.Cout = Cout;
-        a.MH = g.MH; a.MW = g.MW; a.OS = g.OS; a.npar = g.npar; a.ntaps = g.ntaps; a.taps_w = kind == KIND_CT4 ? 16 : (kind == KIND_STEM ? 1 : 9);
-        a.n_ty = g.n_ty; a.n_tx = g.n_tx;
-        fill_taps(a.tapinfo, kind, false);
-        w.kind = kind; w.Cov = Cov; w.Civ = Civ; w.tiles = B * g.n_ty * g.n_tx;
-        w.nsplit[0] = wgrad_nsplit(tr->cfg.dtype, kind, B, g.MH, g.MW, Cin, Cout, false);
-        w.nsplit[1] = wgrad_nsplit(tr->cfg.dtype, kind, B, g.MH, g.MW, Cin, Cout, true);
-        want(pl.scr_wg, (size_t)(w.nsplit[0] > w.nsplit[1] ? w.nsplit[0] : w.nsplit[1]) * a.taps_w * Cout * Cin * 4);
-        w.flops = 2.0 * B * g.Hout * g.Wout * (double)Cov * (kind == KIND_CT4 ? 4 : (kind == KIND_STEM ? 1 : 9)) * Civ;
+        const WgPlan w = wgrad_plan(tr->cfg.dtype, kind, B, Hin, Win, Cin, Civ, silu, Cout, Cov);
+        want(pl.scr_wg, (size_t)(w.nsplit[0] > w.nsplit[1] ? w.nsplit[0] : w.nsplit[1]) * w.a.taps_w * Cout * Cin * 4);
         return w;
     }
     // > 0: scr_film holds per-block channel sums of the current gradient tensor (rows = B * blocks); a conv's output has none
@@ -1181,6 +1187,102 @@ int ccn_internal_train_layout(ccn_trainer_t tr, int32_t B, int32_t H, int32_t W,
     for (const Region& r : pl->regions) text += r.name + " off=" + std::to_string(r.off) + " bytes=" + std::to_string(r.bytes) + "\n";
     text += "total=" + std::to_string(pl->total) + "\n";
     return copy_report(text, buf, cap);
+}
+
+// Test hooks, not part of include/ccn_hip.h: one training-backward kernel family alone, on operands the caller supplies, through the same
+// launch_* functions and in the same order as Step::wgrad, Step::gn_bwd / bias_grad and launch_colsum.  Device pointers, the caller's
+// stream, CCN error codes; every argument is checked before anything is launched.  With scratch == NULL nothing is launched and *need
+// receives the scratch bytes of the call (the geometry outputs are filled too).  tests/test_gpu_train_kernels.py.
+
+// dW of one conv.  kind: KIND_C3S1 / C3S2 / CT4 / STEM (0..3); x [B][Hin][Win][Cin], dy [B][Hout][Wout][Cout] in `dtype`; gn_ab: the
+// pair-interleaved scale / shift table [B][Cin] or NULL; grad (fp32, parameter layout with Cov x Civ channels) is added to.
+// split: 0 the planner's count for a lone launch, -1 its count beside the main stream's kernels, n > 0 that many (at most the tile count).
+int ccn_internal_wgrad(int32_t dtype, int32_t kind, const void* x, const void* gn_ab, int32_t silu, const void* dy, int32_t B, int32_t Hin, int32_t Win,
+                       int32_t Cin, int32_t Civ, int32_t Cout, int32_t Cov, int32_t split, void* scratch, size_t scratch_bytes, float* grad, void* stream,
+                       int32_t* nsplit_out, int32_t* tiles_out, size_t* need)
+{
+    if (dtype != CCN_DTYPE_F32 && dtype != CCN_DTYPE_BF16) return tfail(CCN_EINVAL, "ccn_internal_wgrad: dtype must be fp32 or bf16");
+    if (kind != KIND_C3S1 && kind != KIND_C3S2 && kind != KIND_CT4 && kind != KIND_STEM) return tfail(CCN_EINVAL, "ccn_internal_wgrad: bad kind");
+    if (B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0) return tfail(CCN_EINVAL, "ccn_internal_wgrad: sizes must be positive");
+    const int epc = dtype == CCN_DTYPE_F32 ? 4 : 8;
+    if (Cin % epc || Cout % epc) return tfail(CCN_EINVAL, "ccn_internal_wgrad: Cin and Cout must be multiples of " + std::to_string(epc));
+    if (Civ <= 0 || Civ > Cin || Cov <= 0 || Cov > Cout) return tfail(CCN_EINVAL, "ccn_internal_wgrad: Civ / Cov must lie in 1..Cin / 1..Cout");
+    if (kind == KIND_C3S2 && (Hin % 2 || Win % 2)) return tfail(CCN_EINVAL, "ccn_internal_wgrad: the stride-2 conv needs even Hin and Win");
+    if (gn_ab && !silu && kind != KIND_C3S1) return tfail(CCN_EINVAL, "ccn_internal_wgrad: GroupNorm without SiLU only exists in front of a 3x3 s1 conv");
+    if (split < -1) return tfail(CCN_EINVAL, "ccn_internal_wgrad: split must be -1, 0 or a count");
+    const WgPlan w = wgrad_plan(dtype, kind, B, Hin, Win, Cin, Civ, silu ? 1 : 0, Cout, Cov);
+    const int nsplit = split == 0 ? w.nsplit[0] : (split < 0 ? w.nsplit[1] : (split > w.tiles ? w.tiles : split));
+    const size_t bytes = (size_t)nsplit * w.a.taps_w * Cout * Cin * 4;
+    if (nsplit_out) *nsplit_out = nsplit;
+    if (tiles_out) *tiles_out = w.tiles;
+    if (need) *need = bytes;
+    if (!scratch) return need ? CCN_OK : tfail(CCN_EINVAL, "ccn_internal_wgrad: null scratch and nowhere to report its size");
+    if (!x || !dy || !grad) return tfail(CCN_EINVAL, "ccn_internal_wgrad: null argument");
+    if (scratch_bytes < bytes) return tfail(CCN_EINVAL, "ccn_internal_wgrad: scratch too small: need " + std::to_string(bytes));
+    if (wgrad_prepare() != hipSuccess) return tfail(CCN_EHIP, "kernel attribute setup failed");
+    WgArgs a = w.a;
+    a.x = x; a.gn_ab = (const float2*)gn_ab; a.dy = dy; a.part = (float*)scratch; a.nsplit = nsplit;
+    hipError_t e = launch_wgrad(dtype, kind, a, (hipStream_t)stream);
+    if (e != hipSuccess) return tfail(CCN_EHIP, std::string("wgrad: ") + hipGetErrorString(e));
+    e = launch_wgrad_reduce(a.part, nsplit, a.taps_w, Cout, Cin, Cov, Civ, kind == KIND_CT4 ? 1 : 0, grad, (hipStream_t)stream);
+    if (e != hipSuccess) return tfail(CCN_EHIP, std::string("wgrad_reduce: ") + hipGetErrorString(e));
+    return CCN_OK;
+}
+
+// GroupNorm(+SiLU) backward of the norm reading x [B][HW][C]: reduce, finalize, apply, then the FiLM finalize (film != NULL: the
+// sample's row of `film_bstride` floats holds C scales then C shifts, `dfilm` has the same layout; dbias, when given, is added to) or,
+// without FiLM and with dbias, the column sum of `out` from the apply pass's pairs.  out may alias dA; dgamma / dbeta are added to.
+// geom: {nslb, pstep, ppb, nblk, zblocks} of gn_bwd_geom.
+int ccn_internal_gn_bwd(int32_t dtype, const void* x, const void* dA, const void* ab, const void* stats, const float* gamma, const void* addend,
+                        const float* film, int32_t film_bstride, int32_t silu, int32_t B, int32_t HW, int32_t C, int32_t G, void* out, void* gstat,
+                        float* dgamma, float* dbeta, float* dfilm, float* dbias, void* scratch, size_t scratch_bytes, void* stream, int32_t* geom,
+                        size_t* need)
+{
+    if (dtype != CCN_DTYPE_F32 && dtype != CCN_DTYPE_BF16) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: dtype must be fp32 or bf16");
+    if (B <= 0 || HW <= 0 || C <= 0 || G <= 0) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: sizes must be positive");
+    if (C % 8) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: C must be a multiple of 8");
+    if (C % G) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: C must be a multiple of G");
+    if (film && film_bstride < 2 * C) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: a FiLM row holds C scales and C shifts");
+    if (film && !dfilm) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: FiLM needs dfilm");
+    const GnBwdGeom gg = gn_bwd_geom(dtype, B, HW, C);
+    const size_t half = align_up((size_t)B * gg.nblk * C * sizeof(float2), 256), bytes = 2 * half;
+    if (geom) { geom[0] = gg.nslb; geom[1] = gg.pstep; geom[2] = gg.ppb; geom[3] = gg.nblk; geom[4] = gg.zblocks; }
+    if (need) *need = bytes;
+    if (!scratch) return need ? CCN_OK : tfail(CCN_EINVAL, "ccn_internal_gn_bwd: null scratch and nowhere to report its size");
+    if (!x || !dA || !ab || !stats || !gamma || !out || !gstat || !dgamma || !dbeta) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: null argument");
+    if (scratch_bytes < bytes) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: scratch too small: need " + std::to_string(bytes));
+    hipStream_t st = (hipStream_t)stream;
+    float2 *scr_gn = (float2*)scratch, *scr_film = (float2*)((char*)scratch + half);
+    const int cpg = C / G;
+    const double count = (double)cpg * HW;
+    const float2 *abt = (const float2*)ab, *stt = (const float2*)stats;
+    hipError_t e = launch_gn_bwd_reduce(dtype, x, dA, abt, stt, scr_gn, B, HW, C, cpg, G, silu ? 1 : 0, st);
+    if (e != hipSuccess) return tfail(CCN_EHIP, std::string("gn_bwd_reduce: ") + hipGetErrorString(e));
+    e = launch_gn_bwd_finalize(scr_gn, gg.nblk, B, C, cpg, G, count, gamma, (float2*)gstat, dgamma, dbeta, st);
+    if (e != hipSuccess) return tfail(CCN_EHIP, std::string("gn_bwd_finalize: ") + hipGetErrorString(e));
+    e = launch_gn_bwd_apply(dtype, x, dA, abt, stt, (const float2*)gstat, addend, out, film, film_bstride, scr_film, B, HW, C, cpg, G, silu ? 1 : 0, st);
+    if (e != hipSuccess) return tfail(CCN_EHIP, std::string("gn_bwd_apply: ") + hipGetErrorString(e));
+    if (film) e = launch_film_bwd_finalize(scr_film, gg.nblk, film, film_bstride, dfilm, dbias, B, C, st);
+    else if (dbias) e = launch_colsum_from_pairs(scr_film, B * gg.nblk, C, dbias, st);
+    if (e != hipSuccess) return tfail(CCN_EHIP, std::string(film ? "film_bwd: " : "colsum_from_pairs: ") + hipGetErrorString(e));
+    return CCN_OK;
+}
+
+// db += the per-channel sum over (B, HW) of dy [B][HW][C]
+int ccn_internal_colsum(int32_t dtype, const void* dy, int32_t B, int32_t HW, int32_t C, void* scratch, size_t scratch_bytes, float* db, void* stream,
+                        size_t* need)
+{
+    if (dtype != CCN_DTYPE_F32 && dtype != CCN_DTYPE_BF16) return tfail(CCN_EINVAL, "ccn_internal_colsum: dtype must be fp32 or bf16");
+    if (B <= 0 || HW <= 0 || C <= 0) return tfail(CCN_EINVAL, "ccn_internal_colsum: sizes must be positive");
+    if (C % 8) return tfail(CCN_EINVAL, "ccn_internal_colsum: C must be a multiple of 8");
+    const size_t bytes = (size_t)B * gn_bwd_geom(dtype, B, HW, C).nblk * C * 4;
+    if (need) *need = bytes;
+    if (!scratch) return need ? CCN_OK : tfail(CCN_EINVAL, "ccn_internal_colsum: null scratch and nowhere to report its size");
+    if (!dy || !db) return tfail(CCN_EINVAL, "ccn_internal_colsum: null argument");
+    if (scratch_bytes < bytes) return tfail(CCN_EINVAL, "ccn_internal_colsum: scratch too small: need " + std::to_string(bytes));
+    const hipError_t e = launch_colsum(dtype, dy, (float*)scratch, db, B, HW, C, (hipStream_t)stream);
+    if (e != hipSuccess) return tfail(CCN_EHIP, std::string("colsum: ") + hipGetErrorString(e));
+    return CCN_OK;
 }
 
 int ccn_train_profile_enable(ccn_trainer_t tr, int32_t on)
