@@ -2,9 +2,9 @@
 //
 // A handle owns the repacked weights of one CLIPCondUNet: build_arch's description of the network (ccn_arch.h, shared with the
 // training handle) plus, per conv, the committed operands in every weight version (ConvW).  ccn_commit_params walks the conv list
-// once, one weight version at a time.  ccn_forward / ccn_sample build (once per
-// shape and workspace address) a *plan*: the fixed list of kernel launches of one UNet evaluation with
-// every activation, GroupNorm partial-sum and scale/shift buffer placed in the caller's workspace.
+// once, one weight version at a time.  ccn_forward / ccn_sample plan (once per shape: ShapePlan) the fixed list
+// of kernel launches of one UNet evaluation, every activation, GroupNorm partial-sum and scale/shift buffer an
+// offset into the caller's workspace; a Binding ties a plan to one workspace address and owns what depends on it.
 // ccn_sample replays the plan `steps` times -- conditioning (timestep MLP, z projection, all FiLM
 // linears) is hoisted in front of the loop for all steps, because t is batch-uniform and known ahead
 // (diffusion/ddim.py:25,32) -- either launch by launch or as one captured hipGraph.
@@ -17,7 +17,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -72,15 +71,19 @@ struct ConvW : ArchConv {
 struct NormW { int C = 0; float* gamma = nullptr; float* beta = nullptr; };
 struct ResW { NormW n1, n2; };
 
+constexpr size_t kNone = ~(size_t)0;     // workspace offset of an operand the launch does not have
+// an NHWC activation of a plan: offsets into the workspace
 struct TensorRef {
-    void* p = nullptr;
+    std::string name;            // of its workspace region; the conv that writes it is reported under it (RouteRec)
+    size_t off = kNone;
     int C = 0, H = 0, W = 0;
-    float2* part = nullptr;      // GroupNorm partial sums written by the producer
+    size_t part = kNone;         // GroupNorm partial sums written by the producer
     int n_sp = 0, n_nt = 0, bn = 0;
     bool pr = false;             // partial sums laid out per consumer wave (persistent kernel)
-    std::shared_ptr<ConvArgs> prod;   // launch arguments of the producing conv (patched when its GroupNorm finalize is fused in)
+    int prod = -1;               // index in ShapePlan::ops of the producing conv (patched when its GroupNorm finalize is fused in)
 };
 
+// what a launch takes from the call instead of the plan
 struct StepCtx {
     int step = 0;
     const float* x_in = nullptr;   // NCHW fp32 image entering the stem
@@ -92,33 +95,27 @@ struct StepCtx {
     float sigma = 0.f;
 };
 
-struct Launch {
-    int family;
-    double flops, bytes;
-    std::function<hipError_t(hipStream_t, const StepCtx&)> fn;
-};
-
 const char* kFamilies[] = {"conv3x3_s1_igemm", "conv3x3_s2_igemm", "convT4x4_s2_igemm", "stem_conv_igemm",
                            "head_conv_ddim", "gn_finalize", "conditioning", "gn_silu_prepass"};
 enum { F_C3S1 = 0, F_C3S2, F_CT4, F_STEM, F_HEAD, F_GNF, F_COND, F_LAYOUT, F_COUNT };
 
-struct Bump {
-    char* base; size_t off = 0; bool measure;
-    Bump(void* b, bool m) : base((char*)b), measure(m) {}
-    void* take(size_t bytes) { off = align_up(off, 256); void* p = measure ? nullptr : base + off; off += bytes; return p; }
+// One launch of a plan, as plain data: the arguments that depend on the shape and the committed model, and the workspace offsets
+// of its operands.  launch() adds the workspace address, the stream and the StepCtx.
+enum Op { OP_CONV = 0, OP_HEAD2, OP_GN_FINALIZE, OP_GN_ACT, OP_GN_ACT_FUSED };
+struct Launch {
+    Op op = OP_CONV; int family = 0; double flops = 0, bytes = 0;     // (profiling family, algorithmic work)
+    int conv = -1;               // OP_CONV, OP_HEAD2: index in h->convs (weights: version step % nphase; stem and head by its kind)
+    bool frag = false;           // OP_CONV: the route reads the fragment-ordered weights
+    int film_off = -1;           // OP_CONV: offset of this conv's [scale | shift] in a FiLM row, or -1
+    ConvArgs a{};                // OP_CONV, OP_HEAD2: every field that is not a workspace address or a per-call value
+    size_t in = kNone, out = kNone, res = kNone, part = kNone, kpart = kNone, kflag = kNone, gs_part = kNone, gn_ab = kNone,
+           fin_ab = kNone, fin_counter = kNone, scratch = kNone;
+    // the GroupNorm kinds: finalize of `part` into `gn_ab`; GroupNorm + SiLU pass in -> out from `gn_ab`, or (fused) from `part`
+    int C = 0, HW = 0, G = 0, cpg = 0, n_sp = 0, n_nt = 0, bn = 0;
+    double count = 0; const float* gamma = nullptr; const float* beta = nullptr;
 };
 
 constexpr int kMaxNorms = 128;
-
-struct GraphEntry {
-    int steps = 0;
-    std::vector<int32_t> ts;
-    std::vector<float> coef;
-    std::vector<float> sigma;            // eta > 0 (empty: eta = 0)
-    const float* noise = nullptr;        // ... and the address of the caller's noise tensor the graph was captured with
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-};
 
 // one conv-family launch of a plan as decided at plan build (ccn_internal_plan_routes)
 struct RouteRec {
@@ -132,29 +129,41 @@ struct RouteRec {
     int ops = -1;              // f16x3 plans only: 1 = split fp16 operands, 0 = the fp32 kernel; -1: not reported
 };
 
-constexpr size_t kMaxGraphsPerPlan = 4;
-struct Plan {
+// The plan of one (B, H, W, steps) on the committed model: every buffer an offset, every launch a record.  No address, no stream.
+struct Region { std::string name; size_t off, bytes; };
+struct ShapePlan {
     int B = 0, H = 0, W = 0, steps = 0;
-    void* ws = nullptr;
-    size_t bytes = 0;
-    // conditioning buffers
-    int32_t* ts_dev = nullptr;
-    float *temb = nullptr, *t1 = nullptr, *tp = nullptr, *zp = nullptr, *film = nullptr;
-    float *zbuf = nullptr, *xstate = nullptr;
-    std::vector<std::pair<void*, size_t>> zero_once;   // regions zeroed when the plan is created (split-K hand-off flags)
-    unsigned* counters = nullptr;        // arrival counters of the fused GroupNorm finalizes, [kMaxNorms][B], zero at rest
-    int n_counters = 0;
-    std::vector<int32_t> ts_keep;        // the timestep table currently in ts_dev (uploaded synchronously, only when it changes)
+    std::vector<Region> regions; size_t total = 0;
+    std::vector<std::pair<size_t, size_t>> zero;        // (offset, bytes) zeroed when a workspace is bound: split-K hand-off flags, counters
+    size_t ts_dev = 0, temb = 0, t1 = 0, tp = 0, zp = 0, film = 0, zbuf = 0, xstate = 0;   // conditioning buffers, DDIM state
+    int film_stride = 0;                 // floats between consecutive samples' FiLM rows
+    size_t counters = 0;                 // arrival counters of the fused GroupNorm finalizes, [max_counters][B], zero at rest
+    int n_counters = 0, max_counters = 0;
     std::vector<Launch> ops;             // one UNet evaluation (+ DDIM update in the head)
     std::map<std::string, TensorRef> named;
     std::vector<RouteRec> routes;        // every conv-family launch of `ops`, in order
+};
+
+struct GraphEntry {
+    int steps = 0;
+    std::vector<int32_t> ts;
+    std::vector<float> coef;
+    std::vector<float> sigma;            // eta > 0 (empty: eta = 0)
+    const float* noise = nullptr;        // ... and the address of the caller's noise tensor the graph was captured with
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    void destroy() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); }   // (after draining the device)
+};
+
+// A plan bound to one workspace address: what lives IN that workspace (the uploaded timestep table, the zeroed flags) and the graphs
+// captured with its addresses.
+constexpr size_t kMaxGraphsPerBinding = 4;
+struct Binding {
+    const ShapePlan* plan = nullptr;
+    char* ws = nullptr;
+    std::vector<int32_t> ts_keep;        // the timestep table currently in ts_dev (uploaded synchronously, only when it changes)
     std::vector<GraphEntry> graphs;
-    ~Plan() {
-        for (auto& g : graphs) {
-            if (g.exec) (void)hipGraphExecDestroy(g.exec);
-            if (g.graph) (void)hipGraphDestroy(g.graph);
-        }
-    }
+    ~Binding() { for (auto& g : graphs) g.destroy(); }
 };
 
 }  // namespace
@@ -177,7 +186,8 @@ struct ccn_handle_s {
     int G = 8;
     int weight_rounding = CCN_ROUND_DIFFUSED_PHASES;   // how bf16 mode rounds the conv weights in ccn_commit_params (ccn_set_weight_rounding)
     int nphase = 1;                                     // versions per conv weight of the committed model (round_version)
-    std::vector<std::unique_ptr<Plan>> plans;
+    std::vector<std::unique_ptr<ShapePlan>> shape_plans;   // of the committed model, one per (B, H, W, steps)
+    std::vector<std::unique_ptr<Binding>> bindings;         // plan x workspace address, least recently used first
     hipStream_t cap_stream = nullptr;
     unsigned* err_host = nullptr;       // pinned, device-mapped error word the kernels OR into (ConvArgs::err)
     unsigned* err_dev = nullptr;
@@ -447,22 +457,36 @@ int pack_conv(ccn_handle_s* h, ConvW& cw, const float* w, const float* bias, voi
 }
 
 // ---- plan -------------------------------------------------------------------------------------------------
-struct PlanBuilder {
-    ccn_handle_s* h;
-    Plan* plan;
-    Bump bump;
-    int B;
-    int film_stride;     // floats between consecutive samples' FiLM rows
-    PlanBuilder(ccn_handle_s* h_, Plan* p, void* ws, bool measure) : h(h_), plan(p), bump(ws, measure), B(p->B), film_stride(h_->arch.F) {}
+struct ConvOpts {
+    int film_off = -1;                  // epilogue FiLM: offset of this conv's [scale | shift] in a FiLM row
+    const TensorRef* res = nullptr;     // epilogue residual / skip
+    bool want_part = false;             // also emit the partial sums of the output's GroupNorm
+    size_t gn_ab = kNone;               // prologue GroupNorm from this finalized scale/shift table, or
+    const NormW* in_norm = nullptr;     // the input goes through this GroupNorm (+ SiLU) first; its finalize either becomes part of the
+                                        // conv launch itself (persistent kernel, conv_in_kernel_stats) or a gn_finalize launch in front of it
+    const char* pre_pass = nullptr;     // the input was made by a GroupNorm + SiLU pass: its form, for the route report
+};
 
-    TensorRef new_tensor(int C, int H, int W)
+struct PlanBuilder {
+    ccn_handle_s* h; ShapePlan& pl; const int B;
+    size_t off = 0;
+    PlanBuilder(ccn_handle_s* h_, ShapePlan& p) : h(h_), pl(p), B(p.B) {}
+
+    size_t take(const std::string& name, size_t bytes)     // a named region of the workspace, 256-byte aligned: its offset
     {
-        TensorRef t; t.C = C; t.H = H; t.W = W;
-        t.p = bump.take((size_t)B * H * W * C * h->elem);
+        pl.regions.push_back({name, align_up(off, 256), bytes});
+        off = pl.regions.back().off + bytes;
+        return off - bytes;
+    }
+    TensorRef new_tensor(const std::string& name, int C, int H, int W)
+    {
+        TensorRef t; t.name = name; t.C = C; t.H = H; t.W = W;
+        t.off = take(name, (size_t)B * H * W * C * h->elem);
         return t;
     }
-    float2* new_ab(int C) { return (float2*)bump.take((size_t)B * C * sizeof(float2)); }
     int groups_for(int C) const { return C < h->G ? C : h->G; }
+    // arrival counters of the fused GroupNorm finalizes: they start (and are left) at zero
+    void take_counters(int n) { pl.max_counters = n; pl.counters = take("counters", (size_t)n * B * 4); pl.zero.push_back({pl.counters, (size_t)n * B * 4}); }
 
     // the inference plan's policy for conv_route: the stride-2 conv on the persistent kernel from 128 eight-row tiles (half the CUs),
     // the ConvTranspose only where conv_tile_rows gives 8 rows; split-K on the stride-2 layers (CCN_SPLITK_S1=1: the 3x3 s1 layers too)
@@ -473,151 +497,108 @@ struct PlanBuilder {
                            gn_ab, res, film}, policy);
     }
 
-    // conv launch; `want_part`: also emit the partial sums of the output's GroupNorm
-    // `in_norm` (instead of gn_ab): the input goes through this GroupNorm (+ SiLU) first; its finalize either becomes part of
-    // the conv launch itself (persistent kernel, conv_in_kernel_stats) or a gn_finalize launch in front of it
-    void conv(const ConvW& cw, int family, const TensorRef& in, TensorRef& out, const float2* gn_ab, int film_off,
-              const TensorRef* res, bool want_part, bool is_stem = false, bool is_head = false, const NormW* in_norm = nullptr)
+    // conv launch of h->convs[ci]; the stem reads the call's image and the head writes the call's outputs (by the conv's kind)
+    void conv(int ci, const TensorRef& in, TensorRef& out, const ConvOpts& o)
     {
-        const ConvRoute r = route(cw, in.H, in.W, gn_ab != nullptr, res != nullptr, film_off >= 0);
+        const ConvW& cw = h->convs[ci];
+        size_t gn_ab = o.gn_ab;
+        const ConvRoute r = route(cw, in.H, in.W, gn_ab != kNone, o.res != nullptr, o.film_off >= 0);
         const ConvGeom& g = r.g;
-        std::shared_ptr<ConvArgs> ap(new ConvArgs());
-        ConvArgs& a = *ap;
+        Launch L;
+        static_assert(F_C3S1 == KIND_C3S1 && F_C3S2 == KIND_C3S2 && F_CT4 == KIND_CT4 && F_STEM == KIND_STEM && F_HEAD == KIND_HEAD, "family = kind");
+        L.family = cw.kind; L.conv = ci; L.film_off = o.film_off; L.frag = r.uses_frag() && cw.wfrag;
+        L.in = in.off; L.out = out.off; L.res = o.res ? o.res->off : kNone;
+        ConvArgs& a = L.a;
         r.fill(a);
-        a.in = in.p; a.w = cw.w; a.wfrag = r.uses_frag() ? cw.wfrag : nullptr; a.bias = cw.bias; a.out = out.p;
-        a.film = nullptr; a.res = res ? res->p : nullptr;
-        a.ops = cw.split ? 1 : 0; a.wscale_inv = cw.inv_scale;
+        a.bias = cw.bias; a.ops = cw.split ? 1 : 0; a.wscale_inv = cw.inv_scale;
         RouteRec rec;
         if (h->split) rec.ops = a.ops;
-        rec.kind = cw.kind; rec.th = r.th; rec.ksplit = r.ksplit; rec.n_nt = r.n_nt; rec.film = film_off >= 0; rec.res = res != nullptr;
-        rec.gn = gn_ab ? "prologue" : "none";
+        rec.name = out.name; rec.kind = cw.kind; rec.th = r.th; rec.ksplit = r.ksplit; rec.n_nt = r.n_nt;
+        rec.film = o.film_off >= 0; rec.res = o.res != nullptr;
+        rec.gn = gn_ab != kNone ? "prologue" : "none";
         static const bool no_instat = diag_env("CCN_NO_INSTAT") != nullptr;       // diagnostics build only
-        if (in_norm) {
+        if (o.in_norm) {
             const int G_in = groups_for(cw.Cin), cpg_in = cw.Cin / G_in;
             if (r.gs_ok && !no_instat && in.C == cw.Cin && conv_in_kernel_stats(h->cfg.dtype, in.C, G_in, in.n_sp, in.bn)) {
-                a.gs_part = in.part; a.gs_gamma = in_norm->gamma; a.gs_beta = in_norm->beta;
+                L.gs_part = in.part; a.gs_gamma = o.in_norm->gamma; a.gs_beta = o.in_norm->beta;
                 a.gs_inv_count = 1.0 / ((double)cpg_in * in.H * in.W);
                 a.gs_nsp = in.n_sp; a.gs_nnt = in.n_nt; a.gs_bn = in.bn; a.gs_cpg = cpg_in;
                 rec.gn = "instat";
-            } else { gn_ab = gn(in, *in_norm); rec.gn = "prologue"; }     // (pushes the finalize launch in front of this conv)
+            } else { gn_ab = gn(in, *o.in_norm); rec.gn = "prologue"; }     // (pushes the finalize launch in front of this conv)
         }
-        a.gn_ab = gn_ab;
+        if (o.pre_pass) rec.gn = o.pre_pass;
+        L.gn_ab = gn_ab;
         rec.kernel = conv_kernel_name(conv_kernel_for(cw.kind, cw.BN, a));
-        plan->routes.push_back(rec);
+        pl.routes.push_back(rec);
         if (r.ksplit == 2) {
-            a.kpart = bump.take((size_t)B * g.Hout * g.Wout * cw.Cout * h->elem);
+            L.kpart = take(out.name + ".kpart", (size_t)B * g.Hout * g.Wout * cw.Cout * h->elem);
             const size_t fbytes = (size_t)B * r.fin_blocks * 4 * sizeof(unsigned);
-            a.kflag = (unsigned*)bump.take(fbytes);
-            if (a.kflag) plan->zero_once.push_back({a.kflag, fbytes});
+            L.kflag = take(out.name + ".kflag", fbytes);
+            pl.zero.push_back({L.kflag, fbytes});
         }
-        a.film_bstride = film_stride;
-        a.err = h->err_dev;
-        if (want_part) {
-            out.part = (float2*)bump.take((size_t)B * a.G * a.nslot * sizeof(float2));
+        a.film_bstride = pl.film_stride; a.err = h->err_dev;
+        if (o.want_part) {
+            out.part = take(out.name + ".part", (size_t)B * a.G * a.nslot * sizeof(float2));
             out.n_sp = r.part_nsp; out.n_nt = r.part_nnt; out.bn = r.part_bn;
             if (r.pr || r.stem2) out.pr = true;
-            out.prod = ap;
+            out.prod = (int)pl.ops.size();
         }
-        a.part = out.part;
+        L.part = out.part;
         const double macs = (double)B * g.Hout * g.Wout * cw.Cout * (double)(cw.kind == KIND_CT4 ? 4 : 9) * cw.Cin;
-        double bytes = ((double)B * in.H * in.W * cw.Cin + (double)B * g.Hout * g.Wout * cw.Cout + (res ? (double)B * g.Hout * g.Wout * cw.Cout : 0.0)
-                        + (double)(cw.kind == KIND_CT4 ? 16 : 9) * cw.Cin * cw.Cout) * h->elem;
-        if (is_stem) bytes = (double)B * in.H * in.W * cw.Cin * 4 + ((double)B * g.Hout * g.Wout * cw.Cout + 9.0 * cw.Cin * cw.Cout) * h->elem;
-        if (is_head) bytes = ((double)B * in.H * in.W * cw.Cin + 9.0 * cw.Cin * cw.Cout) * h->elem + 3.0 * (double)B * g.Hout * g.Wout * cw.Cout * 4;
-        const int dtype = h->cfg.dtype, kind = cw.kind, bn = cw.BN;
-        float* film_tab = plan->film;
-        const int F = film_stride;
-        const int Bc = B;
-        const ConvW cwv = cw;                                 // (device pointers of every weight version)
-        const bool frag_used = a.wfrag != nullptr;
-        Launch L{family, 2.0 * macs, bytes, nullptr};
-        L.fn = [=](hipStream_t s, const StepCtx& c) -> hipError_t {
-            ConvArgs k = *ap;                                 // read at launch time: gn() may have fused its finalize in
-            if (cwv.nphase > 1 && (c.step % cwv.nphase)) {    // DDIM step i runs on weight version i % nphase (round_version)
-                const int v = c.step % cwv.nphase - 1;
-                k.w = cwv.w_ph[v];
-                if (frag_used) k.wfrag = cwv.wfrag_ph[v];
-            }
-            if (film_off >= 0) k.film = film_tab + (size_t)c.step * Bc * F + film_off;
-            if (is_stem) k.in = c.x_in;
-            if (is_head) {
-                k.x_state = c.x_state; k.eps_out = c.eps_out; k.do_ddim = c.do_ddim;
-                k.c0 = c.c[0]; k.c1 = c.c[1]; k.c2 = c.c[2]; k.c3 = c.c[3];
-                k.noise = c.noise; k.sigma = c.sigma;
-            }
-            return launch_conv(dtype, kind, bn, k, s);
-        };
-        plan->ops.push_back(std::move(L));
+        L.flops = 2.0 * macs;
+        L.bytes = ((double)B * in.H * in.W * cw.Cin + (double)B * g.Hout * g.Wout * cw.Cout + (o.res ? (double)B * g.Hout * g.Wout * cw.Cout : 0.0)
+                   + (double)(cw.kind == KIND_CT4 ? 16 : 9) * cw.Cin * cw.Cout) * h->elem;
+        if (cw.kind == KIND_STEM) L.bytes = (double)B * in.H * in.W * cw.Cin * 4 + ((double)B * g.Hout * g.Wout * cw.Cout + 9.0 * cw.Cin * cw.Cout) * h->elem;
+        if (cw.kind == KIND_HEAD) L.bytes = ((double)B * in.H * in.W * cw.Cin + 9.0 * cw.Cin * cw.Cout) * h->elem + 3.0 * (double)B * g.Hout * g.Wout * cw.Cout * 4;
+        pl.ops.push_back(L);
     }
-    // the route record of the conv just added: the activation it writes and, for an operand made by a pre-pass, how
-    void label(const std::string& name, const char* gn_form = nullptr)
+    // a GroupNorm launch over tensor `t` for the norm (gamma, beta)
+    Launch norm_launch(Op op, int family, double bytes, const TensorRef& t, const NormW& n) const
     {
-        plan->routes.back().name = name;
-        if (gn_form) plan->routes.back().gn = gn_form;
+        Launch L;
+        L.op = op; L.family = family; L.bytes = bytes;
+        L.C = t.C; L.HW = t.H * t.W; L.G = groups_for(t.C); L.cpg = t.C / L.G; L.count = (double)L.cpg * t.H * t.W;
+        L.in = t.off; L.part = t.part; L.n_sp = t.n_sp; L.n_nt = t.n_nt; L.bn = t.bn; L.gamma = n.gamma; L.beta = n.beta;
+        return L;
     }
 
     // GroupNorm finalize of tensor `t` for the norm (gamma, beta): returns the scale/shift table
-    const float2* gn(const TensorRef& t, const NormW& n)
+    size_t gn(const TensorRef& t, const NormW& n)
     {
-        float2* ab = new_ab(t.C);
-        const int G = groups_for(t.C), cpg = t.C / G;
-        const double count = (double)cpg * t.H * t.W;
+        const size_t ab = take(t.name + ".ab", (size_t)B * t.C * sizeof(float2));
+        Launch L = norm_launch(OP_GN_FINALIZE, F_GNF, (double)B * groups_for(t.C) * t.n_sp * t.n_nt * 8.0 + (double)B * t.C * 8.0, t, n);
         // measured slower than the 5 us finalize launch it removes (every workgroup drains its stores and pays an atomic
         // round trip before exiting): 50.4 vs 52.1 img/s at C2, so opt-in only
         static const bool fuse = diag_env("CCN_FUSED_FINALIZE") != nullptr;
-        if (fuse && t.prod && !t.pr && plan->counters && plan->n_counters < kMaxNorms) {
+        if (fuse && t.prod >= 0 && !t.pr && pl.n_counters < pl.max_counters) {
             // the producing conv's last workgroup per sample does the finalize (no launch, no kernel boundary)
-            ConvArgs& pa = *t.prod;
-            pa.fin_counter = plan->counters + (size_t)plan->n_counters * B;
-            plan->n_counters++;
-            pa.fin_gamma = n.gamma; pa.fin_beta = n.beta; pa.fin_ab = ab; pa.fin_count = count;
+            Launch& p = pl.ops[t.prod];
+            p.fin_counter = pl.counters + (size_t)pl.n_counters * B * sizeof(unsigned);
+            pl.n_counters++;
+            p.a.fin_gamma = n.gamma; p.a.fin_beta = n.beta; p.fin_ab = ab; p.a.fin_count = L.count;
             return ab;
         }
-        const float2* part = t.part; const int n_sp = t.n_sp, n_nt = t.n_nt, bn = t.bn, C = t.C, Bc = B;
-        const float* gamma = n.gamma; const float* beta = n.beta;
-        Launch L{F_GNF, 0.0, (double)B * G * n_sp * n_nt * 8.0 + (double)B * C * 8.0, nullptr};
-        L.fn = [=](hipStream_t s, const StepCtx&) -> hipError_t {
-            return launch_gn_finalize(part, Bc, G, n_sp, n_nt, bn, cpg, C, count, gamma, beta, 1e-5f, ab, s);
-        };
-        plan->ops.push_back(std::move(L));
+        L.gn_ab = ab;
+        pl.ops.push_back(L);
         return ab;
     }
 
-    // GroupNorm-apply + SiLU as a separate pass when the consuming conv would redo it per N tile (C >= 256)
-    TensorRef preact(const TensorRef& t, const float2* ab)
+    // GroupNorm-apply + SiLU as a separate pass when the consuming conv would redo it per N tile (C >= 256): from the finalized table
+    // `ab`, or (kNone) with the finalize of `t`'s GroupNorm folded in (no gn() launch, no scale/shift table)
+    TensorRef preact(const TensorRef& t, const NormW& n, size_t ab)
     {
-        TensorRef o = new_tensor(t.C, t.H, t.W);
-        const int dtype = h->cfg.dtype, Bc = B, HW = t.H * t.W, C = t.C;
-        const void* src = t.p; void* dst = o.p;
-        Launch L{F_LAYOUT, 0.0, 2.0 * B * HW * (double)C * h->elem, nullptr};
-        L.fn = [=](hipStream_t s, const StepCtx&) -> hipError_t { return launch_gn_act(dtype, src, ab, dst, Bc, HW, C, s); };
-        plan->ops.push_back(std::move(L));
-        return o;
-    }
-
-    // the same pass with the finalize of `t`'s GroupNorm folded in (no gn() launch, no scale/shift table)
-    TensorRef preact_fused(const TensorRef& t, const NormW& n)
-    {
-        TensorRef o = new_tensor(t.C, t.H, t.W);
-        const int dtype = h->cfg.dtype, Bc = B, HW = t.H * t.W, C = t.C;
-        const int G = groups_for(t.C), cpg = t.C / G;
-        const double count = (double)cpg * t.H * t.W;
-        const float2* part = t.part; const int n_sp = t.n_sp, n_nt = t.n_nt, bn = t.bn;
-        const float* gamma = n.gamma; const float* beta = n.beta;
-        const void* src = t.p; void* dst = o.p;
-        Launch L{F_LAYOUT, 0.0, 2.0 * B * HW * (double)C * h->elem, nullptr};
-        L.fn = [=](hipStream_t s, const StepCtx&) -> hipError_t {
-            return launch_gn_act_fused(dtype, src, dst, Bc, HW, C, part, G, n_sp, n_nt, bn, cpg, count, gamma, beta, 1e-5f, s);
-        };
-        plan->ops.push_back(std::move(L));
+        TensorRef o = new_tensor(t.name + ".act", t.C, t.H, t.W);
+        Launch L = norm_launch(ab == kNone ? OP_GN_ACT_FUSED : OP_GN_ACT, F_LAYOUT, 2.0 * B * t.H * t.W * (double)t.C * h->elem, t, n);
+        L.out = o.off; L.gn_ab = ab;
+        pl.ops.push_back(L);
         return o;
     }
 
     // x + conv2(SiLU(GN2(FiLM(conv1(SiLU(GN1(x))))))) -- models/blocks.py:40-44
-    TensorRef resblock(int ri, const TensorRef& x, bool out_feeds_gn, int film_off = -2)
+    TensorRef resblock(int ri, const TensorRef& x, bool out_feeds_gn, int film_off)
     {
         const ArchRes& r = h->arch.res[ri];
-        const ConvW &c1 = h->convs[r.c1], &c2 = h->convs[r.c2];
+        const ConvW& c1 = h->convs[r.c1];
         const NormW &n1 = h->res[ri].n1, &n2 = h->res[ri].n2;
         // pre-pass only where the conv kernel would redo the transform per N tile AND has no idle VALU for it: the persistent
         // kernel's producers absorb it up to 4 N tiles (measured at the 512-channel level of C2, 4-row tiles: 69.5 vs 68.8
@@ -626,164 +607,175 @@ struct PlanBuilder {
         const bool pre = conv_wants_preact(c1.kind, c1.BN, c1.Cout_pad / c1.BN) && r.C / (h->elem == 2 ? 8 : 4) <= 256 &&
                          (preact_pr || c1.Cout_pad / c1.BN >= 6 || !route(c1, x.H, x.W, false, false, false).pr);
         static const bool fuse_act = !diag_env("CCN_NO_FUSED_GNACT");       // finalize folded into the pre-pass (A/B switch)
-        const bool f1 = pre && fuse_act && x.n_sp > 0, f2 = pre && fuse_act;     // (n_sp, not the pointer: null while measuring)
-        TensorRef y = new_tensor(r.C, x.H, x.W);
-        if (f1) { TensorRef xa = preact_fused(x, n1); conv(c1, F_C3S1, xa, y, nullptr, film_off == -2 ? r.film_off : film_off, nullptr, true); }
-        else if (pre) {
-            const float2* ab1 = gn(x, n1);
-            TensorRef xa = preact(x, ab1); conv(c1, F_C3S1, xa, y, nullptr, film_off == -2 ? r.film_off : film_off, nullptr, true);
-        } else conv(c1, F_C3S1, x, y, nullptr, film_off == -2 ? r.film_off : film_off, nullptr, true, false, false, &n1);
-        label(r.prefix + ".film", f1 ? "preact_fused" : (pre ? "preact" : nullptr));
-        plan->named[r.prefix + ".film"] = y;
-        TensorRef o = new_tensor(r.C, x.H, x.W);
-        if (f2) { TensorRef ya = preact_fused(y, n2); conv(c2, F_C3S1, ya, o, nullptr, -1, &x, out_feeds_gn); }
-        else if (pre) {
-            const float2* ab2 = gn(y, n2);
-            TensorRef ya = preact(y, ab2); conv(c2, F_C3S1, ya, o, nullptr, -1, &x, out_feeds_gn);
-        } else conv(c2, F_C3S1, y, o, nullptr, -1, &x, out_feeds_gn, false, false, &n2);
-        label(r.prefix, f2 ? "preact_fused" : (pre ? "preact" : nullptr));
-        plan->named[r.prefix] = o;
+        const bool f1 = pre && fuse_act && x.n_sp > 0, f2 = pre && fuse_act;     // (an input without partial sums: table first)
+        ConvOpts o1, o2;
+        o1.film_off = film_off; o1.want_part = true; o1.pre_pass = f1 ? "preact_fused" : (pre ? "preact" : nullptr);
+        o2.res = &x; o2.want_part = out_feeds_gn; o2.pre_pass = f2 ? "preact_fused" : (pre ? "preact" : nullptr);
+        TensorRef y = new_tensor(r.prefix + ".film", r.C, x.H, x.W);
+        if (pre) conv(r.c1, preact(x, n1, f1 ? kNone : gn(x, n1)), y, o1);
+        else { o1.in_norm = &n1; conv(r.c1, x, y, o1); }
+        pl.named[y.name] = y;
+        TensorRef o = new_tensor(r.prefix, r.C, x.H, x.W);
+        if (pre) conv(r.c2, preact(y, n2, f2 ? kNone : gn(y, n2)), o, o2);
+        else { o2.in_norm = &n2; conv(r.c2, y, o, o2); }
+        pl.named[o.name] = o;
         return o;
     }
 };
 
-int build_plan(ccn_handle_s* h, Plan* plan, void* ws, bool measure)
+int build_plan(ccn_handle_s* h, ShapePlan& pl)
 {
     const ccn_config_t& c = h->cfg;
-    PlanBuilder pb(h, plan, ws, measure);
-    const int B = plan->B, H = plan->H, W = plan->W, S = plan->steps;
+    PlanBuilder pb(h, pl);
+    const int B = pl.B, H = pl.H, W = pl.W, S = pl.steps;
     const int TR = B > S ? B : S, FR = S * B > B ? S * B : B;
-    plan->ts_dev = (int32_t*)pb.bump.take((size_t)S * 4);
-    plan->temb = (float*)pb.bump.take((size_t)TR * c.time_dim * 4);
-    plan->t1 = (float*)pb.bump.take((size_t)TR * c.time_dim * 4 * 4);
-    plan->tp = (float*)pb.bump.take((size_t)TR * c.time_dim * 4);
-    plan->zp = (float*)pb.bump.take((size_t)B * c.time_dim * 4);
-    plan->film = (float*)pb.bump.take((size_t)FR * h->arch.F * 4);
-    plan->zbuf = (float*)pb.bump.take((size_t)B * c.z_dim * 4);
-    plan->xstate = (float*)pb.bump.take((size_t)B * c.img_ch * H * W * 4);
-    plan->counters = (unsigned*)pb.bump.take((size_t)kMaxNorms * B * 4);
-    plan->n_counters = 0;
+    pl.film_stride = h->arch.F;
+    pl.ts_dev = pb.take("ts", (size_t)S * 4);
+    pl.temb = pb.take("temb", (size_t)TR * c.time_dim * 4);
+    pl.t1 = pb.take("t1", (size_t)TR * c.time_dim * 4 * 4);
+    pl.tp = pb.take("tp", (size_t)TR * c.time_dim * 4);
+    pl.zp = pb.take("zp", (size_t)B * c.time_dim * 4);
+    pl.film = pb.take("film", (size_t)FR * h->arch.F * 4);
+    pl.zbuf = pb.take("z", (size_t)B * c.z_dim * 4);
+    pl.xstate = pb.take("x_state", (size_t)B * c.img_ch * H * W * 4);
+    pb.take_counters(kMaxNorms);
 
-    plan->ops.clear(); plan->named.clear(); plan->routes.clear();
-    TensorRef img; img.C = c.img_ch; img.H = H; img.W = W;     // NCHW fp32, pointer supplied per call
-    TensorRef x;
+    TensorRef x, img; img.C = c.img_ch; img.H = H; img.W = W;     // img: NCHW fp32, pointer supplied per call
     std::vector<TensorRef> skips;
-    const std::vector<ArchLayer>& layers = h->arch.layers;
-    const size_t nl = layers.size();
+    const std::vector<ArchLayer>& layers = h->arch.layers; const size_t nl = layers.size();
     for (size_t li = 0; li < nl; ++li) {
         const ArchLayer& L = layers[li];
-        const bool next_is_gn = li + 1 < nl && (layers[li + 1].type == L_RES || layers[li + 1].type == L_HEAD);
-        switch (L.type) {
-            case L_STEM: {
-                const ConvW& cw = h->convs[L.idx];
-                x = pb.new_tensor(cw.Cout, H, W);
-                pb.conv(cw, F_STEM, img, x, nullptr, -1, nullptr, next_is_gn, true, false);
-                pb.label(L.name);
-                plan->named[L.name] = x;
-                break;
+        ConvOpts o;
+        o.want_part = li + 1 < nl && (layers[li + 1].type == L_RES || layers[li + 1].type == L_HEAD);   // a GroupNorm reads the output
+        if (L.type == L_RES) { x = pb.resblock(L.idx, x, o.want_part, h->arch.res[L.idx].film_off); continue; }
+        const ConvW& cw = h->convs[L.idx];
+        if (L.type == L_HEAD) {
+            o.gn_ab = pb.gn(x, h->out_norm); o.want_part = false;
+            static const bool no_head2 = diag_env("CCN_NO_HEAD2") != nullptr;
+            if (no_head2 || !head2_supported(c.dtype, cw.Cin, cw.Cout, h->G)) {
+                TensorRef none; none.name = L.name;
+                pb.conv(L.idx, x, none, o);
+                continue;
             }
-            case L_RES: {
-                x = pb.resblock(L.idx, x, next_is_gn);
-                break;
-            }
-            case L_DOWN: {
-                skips.push_back(x);
-                const ConvW& cw = h->convs[L.idx];
-                if ((x.H % 2) || (x.W % 2)) return fail(CCN_EINVAL, "H and W must be divisible by 2^len(ch_mult)");
-                TensorRef o = pb.new_tensor(cw.Cout, x.H / 2, x.W / 2);
-                pb.conv(cw, F_C3S2, x, o, nullptr, -1, nullptr, next_is_gn);
-                pb.label(L.name);
-                plan->named[L.name] = o;
-                x = o;
-                break;
-            }
-            case L_UP: {
-                const ConvW& cw = h->convs[L.idx];
-                TensorRef o = pb.new_tensor(cw.Cout, x.H * 2, x.W * 2);
-                TensorRef sk = skips.back(); skips.pop_back();
-                if (sk.C != cw.Cout || sk.H != o.H || sk.W != o.W) return fail(CCN_EINVAL, "skip shape mismatch");
-                pb.conv(cw, F_CT4, x, o, nullptr, -1, &sk, next_is_gn);
-                pb.label(L.name);
-                plan->named[L.name] = o;
-                x = o;
-                break;
-            }
-            case L_HEAD: {
-                const ConvW& hd = h->convs[L.idx];
-                static const bool no_head2 = diag_env("CCN_NO_HEAD2") != nullptr;
-                if (!no_head2 && head2_supported(c.dtype, hd.Cin, hd.Cout, h->G)) {
-                    // dedicated kernel pair: out_norm's finalize folded into per-sample head weights, taps in the N dimension
-                    std::shared_ptr<ConvArgs> ap(new ConvArgs());
-                    ConvArgs& a = *ap;
-                    a.in = x.p; a.bias = hd.bias; a.B = B; a.Hin = H; a.Win = W; a.Cin = hd.Cin; a.Cout = hd.Cout;
-                    a.Hout = H; a.Wout = W;
-                    const float2* ab = pb.gn(x, h->out_norm);
-                    void* scratch = pb.bump.take(head2_scratch_bytes(B, x.C));
-                    const float* wf = h->head_w_f32;
-                    const double macs = (double)B * H * W * hd.Cout * 9.0 * hd.Cin;
-                    Launch Lh{F_HEAD, 2.0 * macs, ((double)B * H * W * x.C + 9.0 * x.C * hd.Cout) * h->elem + 3.0 * (double)B * H * W * hd.Cout * 4, nullptr};
-                    Lh.fn = [=](hipStream_t s, const StepCtx& sc) -> hipError_t {
-                        ConvArgs k = *ap;
-                        k.x_state = sc.x_state; k.eps_out = sc.eps_out; k.do_ddim = sc.do_ddim;
-                        k.c0 = sc.c[0]; k.c1 = sc.c[1]; k.c2 = sc.c[2]; k.c3 = sc.c[3];
-                        k.noise = sc.noise; k.sigma = sc.sigma;
-                        return launch_head2(k, ab, wf, scratch, sc.step, s);
-                    };
-                    plan->ops.push_back(std::move(Lh));
-                    RouteRec rec;
-                    rec.name = L.name; rec.kind = KIND_HEAD; rec.kernel = "head2"; rec.th = 8; rec.gn = "weights";
-                    if (h->split) rec.ops = 0;
-                    plan->routes.push_back(rec);
-                    break;
-                }
-                const float2* ab = pb.gn(x, h->out_norm);
-                TensorRef none;
-                pb.conv(hd, F_HEAD, x, none, ab, -1, nullptr, false, false, true);
-                pb.label(L.name);
-                break;
-            }
+            // dedicated kernel pair: out_norm's finalize folded into per-sample head weights, taps in the N dimension
+            Launch Lh;
+            Lh.op = OP_HEAD2; Lh.family = F_HEAD; Lh.conv = L.idx; Lh.in = x.off; Lh.gn_ab = o.gn_ab;
+            ConvArgs& a = Lh.a;
+            a.bias = cw.bias; a.B = B; a.Hin = H; a.Win = W; a.Cin = cw.Cin; a.Cout = cw.Cout; a.Hout = H; a.Wout = W;
+            Lh.scratch = pb.take(L.name + ".scratch", head2_scratch_bytes(B, x.C));
+            const double macs = (double)B * H * W * cw.Cout * 9.0 * cw.Cin;
+            Lh.flops = 2.0 * macs;
+            Lh.bytes = ((double)B * H * W * x.C + 9.0 * x.C * cw.Cout) * h->elem + 3.0 * (double)B * H * W * cw.Cout * 4;
+            pl.ops.push_back(Lh);
+            RouteRec rec;
+            rec.name = L.name; rec.kind = KIND_HEAD; rec.kernel = "head2"; rec.th = 8; rec.gn = "weights";
+            if (h->split) rec.ops = 0;
+            pl.routes.push_back(rec);
+            continue;
         }
+        TensorRef sk;
+        if (L.type == L_DOWN) skips.push_back(x);                   // (check_shape: H and W halve evenly at every level)
+        if (L.type == L_UP) { sk = skips.back(); skips.pop_back(); o.res = &sk; }
+        const TensorRef& in = L.type == L_STEM ? img : x;
+        const int up = L.type == L_UP ? 2 : 1, down = L.type == L_DOWN ? 2 : 1;
+        TensorRef out = pb.new_tensor(L.name, cw.Cout, in.H * up / down, in.W * up / down);
+        if (o.res && (sk.C != cw.Cout || sk.H != out.H || sk.W != out.W)) return fail(CCN_EINVAL, "skip shape mismatch");
+        pb.conv(L.idx, in, out, o);
+        pl.named[L.name] = x = out;
     }
-    plan->bytes = align_up(pb.bump.off, 256);
+    pl.total = align_up(pb.off, 256);
     return CCN_OK;
 }
 
-// A Plan owns hipGraphExec objects whose replays may still be running on caller streams (two batches in flight in cli.eval /
-// bench.py): drain the device before destroying any of them.
-void drop_plans(ccn_handle_s* h, size_t keep_newest)
+// ---- launching --------------------------------------------------------------------------------------------
+// The one place where a record meets a workspace, a stream and a call: offsets become pointers, DDIM step i takes weight version
+// i % nphase (round_version) and its FiLM row, the stem the call's image, the head (both forms) the call's per-step fields.
+hipError_t launch(const ccn_handle_s* h, const ShapePlan& pl, const Launch& L, char* ws, hipStream_t s, const StepCtx& c)
 {
-    if (h->plans.size() <= keep_newest) return;
-    (void)hipDeviceSynchronize();
-    while (h->plans.size() > keep_newest) h->plans.erase(h->plans.begin());
+    auto at = [ws](size_t o) -> char* { return o == kNone ? nullptr : ws + o; };
+    const int dtype = h->cfg.dtype;
+    switch (L.op) {
+        case OP_GN_FINALIZE:
+            return launch_gn_finalize((const float2*)at(L.part), pl.B, L.G, L.n_sp, L.n_nt, L.bn, L.cpg, L.C, L.count, L.gamma, L.beta, 1e-5f,
+                                      (float2*)at(L.gn_ab), s);
+        case OP_GN_ACT: return launch_gn_act(dtype, at(L.in), (const float2*)at(L.gn_ab), at(L.out), pl.B, L.HW, L.C, s);
+        case OP_GN_ACT_FUSED:
+            return launch_gn_act_fused(dtype, at(L.in), at(L.out), pl.B, L.HW, L.C, (const float2*)at(L.part), L.G, L.n_sp, L.n_nt, L.bn, L.cpg,
+                                       L.count, L.gamma, L.beta, 1e-5f, s);
+        default: break;
+    }
+    const ConvW& cw = h->convs[L.conv];
+    ConvArgs k = L.a;
+    k.in = cw.kind == KIND_STEM ? (const void*)c.x_in : at(L.in);
+    if (cw.kind == KIND_HEAD) {
+        k.x_state = c.x_state; k.eps_out = c.eps_out; k.do_ddim = c.do_ddim;
+        k.c0 = c.c[0]; k.c1 = c.c[1]; k.c2 = c.c[2]; k.c3 = c.c[3]; k.noise = c.noise; k.sigma = c.sigma;
+    }
+    if (L.op == OP_HEAD2) return launch_head2(k, (const float2*)at(L.gn_ab), h->head_w_f32, at(L.scratch), c.step, s);
+    const int v = c.step % cw.nphase;
+    k.w = v ? cw.w_ph[v - 1] : cw.w;
+    k.wfrag = !L.frag ? nullptr : (v ? cw.wfrag_ph[v - 1] : cw.wfrag);
+    k.out = at(L.out); k.res = at(L.res); k.part = (float2*)at(L.part); k.gn_ab = (const float2*)at(L.gn_ab);
+    k.gs_part = (const float2*)at(L.gs_part); k.kpart = at(L.kpart); k.kflag = (unsigned*)at(L.kflag);
+    k.fin_ab = (float2*)at(L.fin_ab); k.fin_counter = (unsigned*)at(L.fin_counter);
+    if (L.film_off >= 0) k.film = (const float*)at(pl.film) + (size_t)c.step * pl.B * k.film_bstride + L.film_off;
+    return launch_conv(dtype, cw.kind, cw.BN, k, s);
 }
 
-
-int get_plan(ccn_handle_s* h, int B, int H, int W, int steps, void* ws, size_t ws_bytes, Plan** out)
+// ---- plan and binding caches ------------------------------------------------------------------------------
+int check_shape(const ccn_handle_s* h, int B, int H, int W, int steps)
 {
     if (B <= 0 || H <= 0 || W <= 0 || steps <= 0) return fail(CCN_EINVAL, "B, H, W, steps must be positive");
     const int div = 1 << h->cfg.n_mult;
     if (H % div || W % div) return fail(CCN_EINVAL, "H and W must be divisible by 2^len(ch_mult)");
+    return CCN_OK;
+}
+
+// A Binding owns hipGraphExec objects whose replays may still be running on caller streams (two batches in flight in cli.eval /
+// bench.py): drain the device before destroying any of them.
+void drop_bindings(ccn_handle_s* h, size_t keep_newest)
+{
+    if (h->bindings.size() <= keep_newest) return;
+    (void)hipDeviceSynchronize();
+    while (h->bindings.size() > keep_newest) h->bindings.erase(h->bindings.begin());
+}
+
+// the plan of a shape on the committed model, built on first use (ccn_commit_params drops them all)
+int shape_plan(ccn_handle_s* h, int B, int H, int W, int steps, const ShapePlan** out)
+{
+    if (int rc = check_shape(h, B, H, W, steps)) return rc;
+    for (auto& p : h->shape_plans)
+        if (p->B == B && p->H == H && p->W == W && p->steps == steps) { *out = p.get(); return CCN_OK; }
+    std::unique_ptr<ShapePlan> p(new ShapePlan);
+    p->B = B; p->H = H; p->W = W; p->steps = steps;
+    if (int rc = build_plan(h, *p)) return rc;
+    if (h->shape_plans.size() >= 64) { drop_bindings(h, 0); h->shape_plans.clear(); }    // a caller walking through shapes: start over
+    *out = p.get();
+    h->shape_plans.push_back(std::move(p));
+    return CCN_OK;
+}
+
+int get_binding(ccn_handle_s* h, int B, int H, int W, int steps, void* ws, size_t ws_bytes, Binding** out)
+{
+    const ShapePlan* pl = nullptr;
+    if (int rc = shape_plan(h, B, H, W, steps, &pl)) return rc;
     if (!ws || ((uintptr_t)ws & 255)) return fail(CCN_EWORKSPACE, "workspace must be non-null and 256-byte aligned");
-    for (size_t i = 0; i < h->plans.size(); ++i) {
-        Plan* p = h->plans[i].get();
-        if (p->B == B && p->H == H && p->W == W && p->steps == steps && p->ws == ws) {
-            if (ws_bytes < p->bytes) return fail(CCN_EWORKSPACE, "workspace too small");
-            // least recently used first: a hit moves the plan to the back, eviction (below) takes the front
-            std::rotate(h->plans.begin() + (long)i, h->plans.begin() + (long)i + 1, h->plans.end());
-            *out = p;
+    if (ws_bytes < pl->total) return fail(CCN_EWORKSPACE, "workspace too small: need " + std::to_string(pl->total));
+    for (size_t i = 0; i < h->bindings.size(); ++i) {
+        Binding* b = h->bindings[i].get();
+        if (b->plan == pl && b->ws == ws) {
+            // least recently used first: a hit moves the binding to the back, eviction (below) takes the front
+            std::rotate(h->bindings.begin() + (long)i, h->bindings.begin() + (long)i + 1, h->bindings.end());
+            *out = b;
             return CCN_OK;
         }
     }
-    std::unique_ptr<Plan> p(new Plan);
-    p->B = B; p->H = H; p->W = W; p->steps = steps; p->ws = ws;
-    int rc = build_plan(h, p.get(), ws, false);
-    if (rc) return rc;
-    if (ws_bytes < p->bytes) return fail(CCN_EWORKSPACE, "workspace too small: need " + std::to_string(p->bytes));
-    HIPCHK(hipMemset(p->counters, 0, (size_t)kMaxNorms * B * 4));          // arrival counters start (and are left) at zero
-    for (auto& z : p->zero_once) HIPCHK(hipMemset(z.first, 0, z.second));
-    if (h->plans.size() >= 8) drop_plans(h, 7);
-    *out = p.get();
-    h->plans.push_back(std::move(p));
+    std::unique_ptr<Binding> b(new Binding);
+    b->plan = pl; b->ws = (char*)ws;
+    for (auto& z : pl->zero) HIPCHK(hipMemset(b->ws + z.first, 0, z.second));
+    if (h->bindings.size() >= 8) drop_bindings(h, 7);
+    *out = b.get();
+    h->bindings.push_back(std::move(b));
     return CCN_OK;
 }
 
@@ -791,75 +783,66 @@ int get_plan(ccn_handle_s* h, int B, int H, int W, int steps, void* ws, size_t w
 int ccn_release_workspace(ccn_handle_t h, void* workspace_dev)
 {
     if (!h) return fail(CCN_EINVAL, "null handle");
-    bool any = false;
-    for (auto& p : h->plans) any = any || p->ws == workspace_dev;
-    if (!any) return CCN_OK;
+    auto lives_there = [&](const std::unique_ptr<Binding>& b) { return b->ws == workspace_dev; };
+    if (std::none_of(h->bindings.begin(), h->bindings.end(), lives_there)) return CCN_OK;
     HIPCHK(hipDeviceSynchronize());                                 // replays on caller streams may still be using it
-    h->plans.erase(std::remove_if(h->plans.begin(), h->plans.end(), [&](const std::unique_ptr<Plan>& p) { return p->ws == workspace_dev; }),
-                   h->plans.end());
+    h->bindings.erase(std::remove_if(h->bindings.begin(), h->bindings.end(), lives_there), h->bindings.end());
     return CCN_OK;
 }
 namespace {
 
 // ---- running a plan -------------------------------------------------------------------------------------------
-int ensure_events(ccn_handle_s* h, size_t n)
+// `go` enqueues one launch on `s`; while profiling it is bracketed by two events and booked under `family`
+template <typename F>
+int timed(ccn_handle_s* h, int family, double flops, double bytes, hipStream_t s, F&& go)
 {
-    while (h->ev_pool.size() < n) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        h->ev_pool.push_back(e);
-    }
+    if (!h->profiling) { HIPCHK(go()); return CCN_OK; }
+    for (hipEvent_t e; h->ev_pool.size() < h->ev_used + 2; h->ev_pool.push_back(e)) HIPCHK(hipEventCreate(&e));
+    const int e0 = (int)h->ev_used, e1 = e0 + 1;
+    h->ev_used += 2;
+    HIPCHK(hipEventRecord(h->ev_pool[e0], s));
+    HIPCHK(go());
+    HIPCHK(hipEventRecord(h->ev_pool[e1], s));
+    h->recs.push_back({family, flops, bytes, e0, e1});
     return CCN_OK;
 }
 
-int run_launch(ccn_handle_s* h, const Launch& L, hipStream_t s, const StepCtx& c)
+// one UNet evaluation (+ DDIM update in the head)
+int run_ops(ccn_handle_s* h, const Binding* b, hipStream_t s, const StepCtx& c)
 {
-    if (h->profiling) {
-        int rc = ensure_events(h, h->ev_used + 2);
-        if (rc) return rc;
-        const int e0 = (int)h->ev_used, e1 = e0 + 1;
-        h->ev_used += 2;
-        HIPCHK(hipEventRecord(h->ev_pool[e0], s));
-        HIPCHK(L.fn(s, c));
-        HIPCHK(hipEventRecord(h->ev_pool[e1], s));
-        h->recs.push_back({L.family, L.flops, L.bytes, e0, e1});
-        return CCN_OK;
+    for (const Launch& L : b->plan->ops) {
+        if (int rc = timed(h, L.family, L.flops, L.bytes, s, [&] { return launch(h, *b->plan, L, b->ws, s, c); })) return rc;
     }
-    HIPCHK(L.fn(s, c));
     return CCN_OK;
 }
 
 // conditioning for `TR` time rows and `FR` FiLM rows; sample: FR = S*B rows (s,b); forward: FR = B rows
-int run_conditioning(ccn_handle_s* h, Plan* p, hipStream_t s, const int64_t* t_i64, int TR, int FR, int a_div)
+int run_conditioning(ccn_handle_s* h, const Binding* b, hipStream_t s, const int64_t* t_i64, int TR, int FR, int a_div)
 {
-    const ccn_config_t& c = h->cfg;
-    const int td = c.time_dim, B = p->B;
-    std::vector<Launch> v;
-    const float* z = p->zbuf;
-    v.push_back({F_COND, 0, 0, [=](hipStream_t st, const StepCtx&) {
-        return t_i64 ? launch_temb_i64(t_i64, p->temb, TR, td, st) : launch_temb_i32(p->ts_dev, p->temb, TR, td, st); }});
-    v.push_back({F_COND, 2.0 * TR * td * 4.0 * td, 0, [=](hipStream_t st, const StepCtx&) {
-        return launch_linear(p->temb, nullptr, 1, TR, h->tp0_w, h->tp0_b, p->t1, TR, td, 4 * td, 1, st); }});
-    v.push_back({F_COND, 2.0 * TR * td * 4.0 * td, 0, [=](hipStream_t st, const StepCtx&) {
-        return launch_linear(p->t1, nullptr, 1, TR, h->tp2_w, h->tp2_b, p->tp, TR, 4 * td, td, 0, st); }});
-    v.push_back({F_COND, 2.0 * B * c.z_dim * td, 0, [=](hipStream_t st, const StepCtx&) {
-        return launch_linear(z, nullptr, 1, B, h->zp_w, h->zp_b, p->zp, B, c.z_dim, td, 1, st); }});
-    v.push_back({F_COND, 2.0 * FR * td * (double)h->arch.F, 0, [=](hipStream_t st, const StepCtx&) {
-        return launch_linear(p->tp, p->zp, a_div, B, h->film_w, h->film_b, p->film, FR, td, h->arch.F, 0, st); }});
-    StepCtx c0;
-    for (auto& L : v) { int rc = run_launch(h, L, s, c0); if (rc) return rc; }
-    return CCN_OK;
+    const ccn_config_t& c = h->cfg; const ShapePlan& p = *b->plan;
+    const int td = c.time_dim, B = p.B, F = h->arch.F;
+    auto f32 = [b](size_t off) { return (float*)(b->ws + off); };
+    float *temb = f32(p.temb), *t1 = f32(p.t1), *tp = f32(p.tp), *zp = f32(p.zp);
+    int rc;
+    if ((rc = timed(h, F_COND, 0, 0, s, [&] {
+            return t_i64 ? launch_temb_i64(t_i64, temb, TR, td, s) : launch_temb_i32((const int32_t*)(b->ws + p.ts_dev), temb, TR, td, s); }))) return rc;
+    if ((rc = timed(h, F_COND, 2.0 * TR * td * 4.0 * td, 0, s, [&] { return launch_linear(temb, nullptr, 1, TR, h->tp0_w, h->tp0_b, t1, TR, td, 4 * td, 1, s); }))) return rc;
+    if ((rc = timed(h, F_COND, 2.0 * TR * td * 4.0 * td, 0, s, [&] { return launch_linear(t1, nullptr, 1, TR, h->tp2_w, h->tp2_b, tp, TR, 4 * td, td, 0, s); }))) return rc;
+    if ((rc = timed(h, F_COND, 2.0 * B * c.z_dim * td, 0, s, [&] { return launch_linear(f32(p.zbuf), nullptr, 1, B, h->zp_w, h->zp_b, zp, B, c.z_dim, td, 1, s); }))) return rc;
+    return timed(h, F_COND, 2.0 * FR * td * (double)F, 0, s, [&] { return launch_linear(tp, zp, a_div, B, h->film_w, h->film_b, f32(p.film), FR, td, F, 0, s); });
 }
 
-int run_steps(ccn_handle_s* h, Plan* p, hipStream_t s, int steps, const float* coef, const float* sigma = nullptr, const float* noise = nullptr)
+int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, int steps, const float* coef, const float* sigma = nullptr, const float* noise = nullptr)
 {
-    const size_t img = (size_t)p->B * h->cfg.img_ch * p->H * p->W;
+    const ShapePlan& p = *b->plan;
+    const size_t img = (size_t)p.B * h->cfg.img_ch * p.H * p.W;
+    float* xstate = (float*)(b->ws + p.xstate);
     for (int i = 0; i < steps; ++i) {
         StepCtx c;
-        c.step = i; c.x_in = p->xstate; c.x_state = p->xstate; c.eps_out = nullptr; c.do_ddim = 1;
+        c.step = i; c.x_in = xstate; c.x_state = xstate; c.eps_out = nullptr; c.do_ddim = 1;
         for (int k = 0; k < 4; ++k) c.c[k] = coef[i * 4 + k];
         if (sigma && noise && sigma[i] > 0.f) { c.noise = noise + (size_t)i * img; c.sigma = sigma[i]; }
-        for (auto& L : p->ops) { int rc = run_launch(h, L, s, c); if (rc) return rc; }
+        if (int rc = run_ops(h, b, s, c)) return rc;
     }
     return CCN_OK;
 }
@@ -880,6 +863,30 @@ int check_device_errors(ccn_handle_s* h)
                               "launches enqueued since the last successful check are not fp32-grade: use dtype fp32 for this model");
     if (e) return fail(CCN_EHIP, "device-side error word " + std::to_string(e));
     return CCN_OK;
+}
+
+// a report of a test hook, snprintf-like: writes at most cap bytes (NUL-terminated) and returns the length of the whole text
+int copy_report(const std::string& text, char* buf, size_t cap)
+{
+    if (buf && cap) {
+        const size_t n = std::min(text.size(), cap - 1);
+        std::memcpy(buf, text.data(), n);
+        buf[n] = 0;
+    }
+    return (int)text.size();
+}
+
+std::string routes_text(const ShapePlan& pl)
+{
+    static const char* kinds[] = {"C3S1", "C3S2", "CT4", "STEM", "HEAD"};
+    std::string text;
+    for (const RouteRec& r : pl.routes) {
+        char line[256];
+        std::snprintf(line, sizeof(line), "%s %s %s th=%d ksplit=%d n_nt=%d gn=%s film=%d res=%d", r.name.c_str(), kinds[r.kind], r.kernel,
+                      r.th, r.ksplit, r.n_nt, r.gn, r.film ? 1 : 0, r.res ? 1 : 0);
+        text += std::string(line) + (r.ops < 0 ? "" : r.ops ? " ops=f16x3" : " ops=f32") + "\n";
+    }
+    return text;
 }
 
 int check_ready(ccn_handle_s* h)
@@ -945,7 +952,7 @@ int ccn_destroy(ccn_handle_t h)
 {
     if (!h) return CCN_OK;
     (void)hipDeviceSynchronize();
-    h->plans.clear();
+    h->bindings.clear();
     for (void* p : h->dev_allocs) (void)hipFree(p);
     for (auto e : h->ev_pool) (void)hipEventDestroy(e);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
@@ -1011,7 +1018,8 @@ int ccn_commit_params(ccn_handle_t h)
     for (auto& p : a.params)
         if (!h->host.count(p.name)) missing += (missing.empty() ? "" : ", ") + p.name;
     if (!missing.empty()) return fail(CCN_EWEIGHTS, "Missing key(s) in state_dict: " + missing);
-    drop_plans(h, 0);                                             // drains the device first: replays may still read the old weights
+    drop_bindings(h, 0);                                          // drains the device first: replays may still read the old weights
+    h->shape_plans.clear();                                       // they hold what this commit decides: BN, fragment operands, split rows
     for (void* p : h->dev_allocs) (void)hipFree(p);
     h->dev_allocs.clear();
     const ccn_config_t& c = h->cfg;
@@ -1078,13 +1086,9 @@ int ccn_workspace_bytes(ccn_handle_t h, int32_t B, int32_t H, int32_t W, int32_t
     int rc = check_ready(h);
     if (rc) return rc;
     if (!bytes) return fail(CCN_EINVAL, "null argument");
-    if (B <= 0 || H <= 0 || W <= 0 || steps <= 0) return fail(CCN_EINVAL, "B, H, W, steps must be positive");
-    const int div = 1 << h->cfg.n_mult;
-    if (H % div || W % div) return fail(CCN_EINVAL, "H and W must be divisible by 2^len(ch_mult)");
-    Plan p; p.B = B; p.H = H; p.W = W; p.steps = steps;
-    rc = build_plan(h, &p, nullptr, true);
-    if (rc) return rc;
-    *bytes = p.bytes;
+    const ShapePlan* pl = nullptr;
+    if ((rc = shape_plan(h, B, H, W, steps, &pl))) return rc;
+    *bytes = pl->total;
     return CCN_OK;
 }
 
@@ -1094,15 +1098,14 @@ int ccn_forward(ccn_handle_t h, const float* x_dev, const float* z_dev, const in
     int rc = check_ready(h);
     if (rc) return rc;
     if (!x_dev || !z_dev || !t_dev || !eps_dev) return fail(CCN_EINVAL, "null tensor pointer");
-    Plan* p = nullptr;
-    if ((rc = get_plan(h, B, H, W, 1, workspace_dev, workspace_bytes, &p))) return rc;
+    Binding* b = nullptr;
+    if ((rc = get_binding(h, B, H, W, 1, workspace_dev, workspace_bytes, &b))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(p->zbuf, z_dev, (size_t)B * h->cfg.z_dim * 4, hipMemcpyDeviceToDevice, s));
-    if ((rc = run_conditioning(h, p, s, t_dev, B, B, 1))) return rc;
+    HIPCHK(hipMemcpyAsync(b->ws + b->plan->zbuf, z_dev, (size_t)B * h->cfg.z_dim * 4, hipMemcpyDeviceToDevice, s));
+    if ((rc = run_conditioning(h, b, s, t_dev, B, B, 1))) return rc;
     StepCtx c;
     c.step = 0; c.x_in = x_dev; c.x_state = nullptr; c.eps_out = eps_dev; c.do_ddim = 0;
-    for (auto& L : p->ops) if ((rc = run_launch(h, L, s, c))) return rc;
-    return CCN_OK;
+    return run_ops(h, b, s, c);
 }
 
 static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H, int32_t W,
@@ -1112,19 +1115,20 @@ static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev,
     int rc = check_ready(h);
     if (rc) return rc;
     if (!z_dev || !x_T_dev || !x_out_dev || !ts_host || !coef_host) return fail(CCN_EINVAL, "null pointer");
-    Plan* p = nullptr;
-    if ((rc = get_plan(h, B, H, W, steps, workspace_dev, workspace_bytes, &p))) return rc;
+    Binding* p = nullptr;
+    if ((rc = get_binding(h, B, H, W, steps, workspace_dev, workspace_bytes, &p))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t img_bytes = (size_t)B * h->cfg.img_ch * H * W * 4;
-    HIPCHK(hipMemcpyAsync(p->zbuf, z_dev, (size_t)B * h->cfg.z_dim * 4, hipMemcpyDeviceToDevice, s));
-    if (x_T_dev != p->xstate) HIPCHK(hipMemcpyAsync(p->xstate, x_T_dev, img_bytes, hipMemcpyDeviceToDevice, s));
+    float* xstate = (float*)(p->ws + p->plan->xstate);
+    HIPCHK(hipMemcpyAsync(p->ws + p->plan->zbuf, z_dev, (size_t)B * h->cfg.z_dim * 4, hipMemcpyDeviceToDevice, s));
+    if (x_T_dev != xstate) HIPCHK(hipMemcpyAsync(xstate, x_T_dev, img_bytes, hipMemcpyDeviceToDevice, s));
 
-    // the timestep table of a plan almost never changes: upload it only when it does, and then synchronously after draining
+    // the timestep table of a binding almost never changes: upload it only when it does, and then synchronously after draining
     // the stream (an async copy out of a host vector that the next call rewrites could still be pending)
     if (p->ts_keep.size() != (size_t)steps || std::memcmp(p->ts_keep.data(), ts_host, (size_t)steps * 4)) {
         HIPCHK(hipStreamSynchronize(s));
         p->ts_keep.assign(ts_host, ts_host + steps);
-        HIPCHK(hipMemcpy(p->ts_dev, p->ts_keep.data(), (size_t)steps * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->ws + p->plan->ts_dev, p->ts_keep.data(), (size_t)steps * 4, hipMemcpyHostToDevice));
     }
     if (use_graph && !h->profiling) {
         GraphEntry* ge = nullptr;
@@ -1147,14 +1151,12 @@ static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev,
             if (ce != hipSuccess) return fail(CCN_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
             g.graph = graph;
             HIPCHK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-            // at most kMaxGraphsPerPlan captured graphs per plan, least recently used first (a caller that passes a fresh noise
+            // at most kMaxGraphsPerBinding captured graphs per binding, least recently used first (a caller that passes a fresh noise
             // tensor / coefficient table every call would otherwise grow the list without bound); an exec may still be replaying
             // on a caller stream, so the device is drained before one is destroyed
-            if (p->graphs.size() >= kMaxGraphsPerPlan) {
+            if (p->graphs.size() >= kMaxGraphsPerBinding) {
                 HIPCHK(hipDeviceSynchronize());
-                GraphEntry& old = p->graphs.front();
-                if (old.exec) (void)hipGraphExecDestroy(old.exec);
-                if (old.graph) (void)hipGraphDestroy(old.graph);
+                p->graphs.front().destroy();
                 p->graphs.erase(p->graphs.begin());
             }
             p->graphs.push_back(g);
@@ -1168,7 +1170,7 @@ static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev,
         if ((rc = run_conditioning(h, p, s, nullptr, steps, steps * B, B))) return rc;
         if ((rc = run_steps(h, p, s, steps, coef_host, sigma_host, noise_dev))) return rc;
     }
-    if (x_out_dev != p->xstate) HIPCHK(hipMemcpyAsync(x_out_dev, p->xstate, img_bytes, hipMemcpyDeviceToDevice, s));
+    if (x_out_dev != xstate) HIPCHK(hipMemcpyAsync(x_out_dev, xstate, img_bytes, hipMemcpyDeviceToDevice, s));
     return CCN_OK;
 }
 
@@ -1247,31 +1249,26 @@ int ccn_resblock_forward(ccn_handle_t h, const char* prefix, const float* x_dev,
     hipStream_t s = (hipStream_t)stream;
     const int G = (r->C < h->G ? r->C : h->G), cpg = r->C / G;
     int nslot = (H * W + 1023) / 1024; if (nslot < 1) nslot = 1;
-    Plan tmp; tmp.B = B; tmp.H = H; tmp.W = W; tmp.steps = 1;
-    TensorRef x, o;
-    // pass 0 measures (nothing is written before the size is known to fit), pass 1 places the buffers
-    for (int pass = 0; pass < 2; ++pass) {
-        tmp.ops.clear(); tmp.named.clear(); tmp.zero_once.clear();
-        PlanBuilder pb(h, &tmp, workspace_dev, pass == 0);
-        pb.film_stride = 2 * r->C;                                // dense (B, 2C) table: [scale | shift] of this block only
-        tmp.film = (float*)pb.bump.take((size_t)B * 2 * r->C * 4);
-        tmp.counters = (unsigned*)pb.bump.take((size_t)8 * B * 4);
-        tmp.n_counters = 0;
-        x = pb.new_tensor(r->C, H, W);
-        x.part = (float2*)pb.bump.take((size_t)B * G * nslot * sizeof(float2));
-        x.n_sp = nslot; x.n_nt = 1; x.bn = 1 << 30;
-        o = pb.resblock((int)(r - h->arch.res.data()), x, false, 0);
-        if (pb.bump.off > workspace_bytes) return fail(CCN_EWORKSPACE, "workspace too small: need " + std::to_string(pb.bump.off));
-    }
-    HIPCHK(hipMemsetAsync(tmp.counters, 0, (size_t)8 * B * 4, s));
-    for (auto& z : tmp.zero_once) HIPCHK(hipMemsetAsync(z.first, 0, z.second, s));   // split-K hand-off flags of a fresh workspace
-    HIPCHK(launch_nchw_to_nhwc(h->cfg.dtype, x_dev, x.p, B, r->C, H, W, s));
-    HIPCHK(launch_gn_partials(h->cfg.dtype, x.p, x.part, B, H * W, r->C, cpg, G, nslot, s));
+    // the block's own plan (not cached): offsets first, nothing is written before the size is known to fit
+    ShapePlan pl; pl.B = B; pl.H = H; pl.W = W; pl.steps = 1;
+    PlanBuilder pb(h, pl);
+    pl.film_stride = 2 * r->C;                                    // dense (B, 2C) table: [scale | shift] of this block only
+    pl.film = pb.take("film", (size_t)B * 2 * r->C * 4);
+    pb.take_counters(8);
+    TensorRef x = pb.new_tensor("x", r->C, H, W);
+    x.part = pb.take("x.part", (size_t)B * G * nslot * sizeof(float2));
+    x.n_sp = nslot; x.n_nt = 1; x.bn = 1 << 30;
+    const TensorRef o = pb.resblock((int)(r - h->arch.res.data()), x, false, 0);
+    if (pb.off > workspace_bytes) return fail(CCN_EWORKSPACE, "workspace too small: need " + std::to_string(pb.off));
+    char* ws = (char*)workspace_dev;
+    for (auto& z : pl.zero) HIPCHK(hipMemsetAsync(ws + z.first, 0, z.second, s));   // counters, split-K hand-off flags of a fresh workspace
+    HIPCHK(launch_nchw_to_nhwc(h->cfg.dtype, x_dev, ws + x.off, B, r->C, H, W, s));
+    HIPCHK(launch_gn_partials(h->cfg.dtype, ws + x.off, (float2*)(ws + x.part), B, H * W, r->C, cpg, G, nslot, s));
     HIPCHK(launch_linear(cond_dev, nullptr, 1, B, h->film_w + (size_t)r->film_off * h->cfg.time_dim, h->film_b + r->film_off,
-                         tmp.film, B, h->cfg.time_dim, 2 * r->C, 0, s));
+                         (float*)(ws + pl.film), B, h->cfg.time_dim, 2 * r->C, 0, s));
     StepCtx c;
-    for (auto& L : tmp.ops) HIPCHK(L.fn(s, c));
-    HIPCHK(launch_nhwc_to_nchw(h->cfg.dtype, o.p, y_dev, B, r->C, H, W, s));
+    for (const Launch& L : pl.ops) HIPCHK(launch(h, pl, L, ws, s, c));
+    HIPCHK(launch_nhwc_to_nchw(h->cfg.dtype, ws + o.off, y_dev, B, r->C, H, W, s));
     return CCN_OK;
 }
 
@@ -1280,14 +1277,14 @@ int ccn_read_activation(ccn_handle_t h, const char* name, float* out_dev, size_t
     int rc = check_ready(h);
     if (rc) return rc;
     if (!name || !out_dev) return fail(CCN_EINVAL, "null pointer");
-    if (h->plans.empty()) return fail(CCN_ESTATE, "no forward has run yet");
-    Plan* p = h->plans.back().get();
-    auto it = p->named.find(name);
-    if (it == p->named.end()) return fail(CCN_EINVAL, std::string("unknown activation ") + name);
+    if (h->bindings.empty()) return fail(CCN_ESTATE, "no forward has run yet");
+    const Binding* b = h->bindings.back().get();                    // the most recently used one
+    auto it = b->plan->named.find(name);
+    if (it == b->plan->named.end()) return fail(CCN_EINVAL, std::string("unknown activation ") + name);
     const TensorRef& t = it->second;
-    if (out_elems < (size_t)p->B * t.C * t.H * t.W) return fail(CCN_EINVAL, "output buffer too small");
+    if (out_elems < (size_t)b->plan->B * t.C * t.H * t.W) return fail(CCN_EINVAL, "output buffer too small");
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(launch_nhwc_to_nchw(h->cfg.dtype, t.p, out_dev, p->B, t.C, t.H, t.W, s));
+    HIPCHK(launch_nhwc_to_nchw(h->cfg.dtype, b->ws + t.off, out_dev, b->plan->B, t.C, t.H, t.W, s));
     HIPCHK(hipStreamSynchronize(s));
     return CCN_OK;
 }
@@ -1297,23 +1294,25 @@ int ccn_read_activation(ccn_handle_t h, const char* name, float* out_dev, size_t
 // that plan was built; lines of an f16x3 plan end in " ops=f16x3" (split fp16 operands) or " ops=f32".  snprintf-like: writes at most cap bytes (NUL-terminated) and returns the length of the whole report, or -1.
 extern "C" int ccn_internal_plan_routes(ccn_handle_t h, char* buf, size_t cap)
 {
-    if (!h || h->plans.empty()) return -1;
-    static const char* kinds[] = {"C3S1", "C3S2", "CT4", "STEM", "HEAD"};
+    if (!h || h->bindings.empty()) return -1;
+    return copy_report(routes_text(*h->bindings.back()->plan), buf, cap);
+}
+// Test hooks, not part of include/ccn_hip.h, on the cached plan of a shape (built if need be; nothing is bound to a workspace, launched,
+// or made "the last used"): the same report, and the workspace layout -- "<name> off=<bytes> bytes=<bytes>" per region, "total=<bytes>".
+extern "C" int ccn_internal_plan_routes_of(ccn_handle_t h, int32_t B, int32_t H, int32_t W, int32_t steps, char* buf, size_t cap)
+{
+    const ShapePlan* pl;
+    if (!h || !h->committed || shape_plan(h, B, H, W, steps, &pl)) return -1;
+    return copy_report(routes_text(*pl), buf, cap);
+}
+extern "C" int ccn_internal_plan_layout(ccn_handle_t h, int32_t B, int32_t H, int32_t W, int32_t steps, char* buf, size_t cap)
+{
+    const ShapePlan* pl;
+    if (!h || !h->committed || shape_plan(h, B, H, W, steps, &pl)) return -1;
     std::string text;
-    for (const RouteRec& r : h->plans.back()->routes) {
-        char line[256];
-        std::snprintf(line, sizeof(line), "%s %s %s th=%d ksplit=%d n_nt=%d gn=%s film=%d res=%d", r.name.c_str(), kinds[r.kind], r.kernel,
-                      r.th, r.ksplit, r.n_nt, r.gn, r.film ? 1 : 0, r.res ? 1 : 0);
-        text += line;
-        if (r.ops >= 0) text += r.ops ? " ops=f16x3" : " ops=f32";
-        text += "\n";
-    }
-    if (buf && cap) {
-        const size_t n = std::min(text.size(), cap - 1);
-        std::memcpy(buf, text.data(), n);
-        buf[n] = 0;
-    }
-    return (int)text.size();
+    for (const Region& r : pl->regions) text += r.name + " off=" + std::to_string(r.off) + " bytes=" + std::to_string(r.bytes) + "\n";
+    text += "total=" + std::to_string(pl->total) + "\n";
+    return copy_report(text, buf, cap);
 }
 
 int ccn_poll_errors(ccn_handle_t h)
@@ -1360,10 +1359,10 @@ int ccn_algorithmic_work(ccn_handle_t h, int32_t B, int32_t H, int32_t W, double
     int rc = check_ready(h);
     if (rc) return rc;
     if (!flops || !bytes) return fail(CCN_EINVAL, "null pointer");
-    Plan p; p.B = B; p.H = H; p.W = W; p.steps = 1;
-    if ((rc = build_plan(h, &p, nullptr, true))) return rc;
+    const ShapePlan* pl = nullptr;
+    if ((rc = shape_plan(h, B, H, W, 1, &pl))) return rc;
     double f = 0, b = 0;
-    for (auto& L : p.ops) if (L.family <= F_HEAD) { f += L.flops; b += L.bytes; }
+    for (auto& L : pl->ops) if (L.family <= F_HEAD) { f += L.flops; b += L.bytes; }
     const ccn_config_t& c = h->cfg;
     f += 2.0 * B * ((double)c.time_dim * 4 * c.time_dim * 2 + (double)c.z_dim * c.time_dim + (double)c.time_dim * h->arch.F);
     *flops = f; *bytes = b;

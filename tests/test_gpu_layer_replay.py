@@ -23,6 +23,8 @@ the input shifted by one pixel inside the last column tile, GroupNorm statistics
 violate the bound on a clear majority of the outputs it changes, i.e. the bound tells those bug classes apart from rounding.
 """
 import ctypes
+import sys
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -30,6 +32,11 @@ import torch
 import torch.nn.functional as F
 
 from oracle import ref_unet
+
+HERE = Path(__file__).resolve().parent
+if str(HERE) not in sys.path:
+    sys.path.insert(0, str(HERE))
+from infer_plan_cases import plan_routes  # noqa: E402
 
 DEV = "cuda:0"
 U32 = 2.0 ** -24          # fp32 unit roundoff
@@ -88,30 +95,11 @@ GN_FORMS_BF16 = {"none", "prologue", "instat", "preact_fused", "weights"}
 def _lib():
     from clip_feature_codec import _native
     lib = _native.load_library()
-    lib.ccn_internal_plan_routes.restype = ctypes.c_int
-    lib.ccn_internal_plan_routes.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
     lib.ccn_internal_round_weights.restype = ctypes.c_int
     lib.ccn_internal_round_weights.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_void_p]
     lib.ccn_internal_set_conv_variant.restype = ctypes.c_int
     return lib
-
-
-def plan_routes(nat):
-    """{activation name: route dict} of the plan the handle's last forward / sample used."""
-    lib = _lib()
-    n = lib.ccn_internal_plan_routes(nat.h, None, 0)
-    assert n > 0
-    buf = ctypes.create_string_buffer(n + 1)
-    assert lib.ccn_internal_plan_routes(nat.h, buf, n + 1) == n
-    out = {}
-    for line in buf.value.decode().splitlines():
-        f = line.split()
-        r = dict(name=f[0], kind=f[1], kernel=f[2], **{k: v for k, v in (x.split("=") for x in f[3:])})
-        for k in ("th", "ksplit", "n_nt", "film", "res"):
-            r[k] = int(r[k])
-        out[r["name"]] = r
-    return out
 
 
 def round_weights(w, convT, version):

@@ -3,7 +3,6 @@ three v_mfma_f32_32x32x16_f16 per product).  It is held to the fp32 parity mode'
 emulation of the arithmetic (tests/split_emulation.py) meets each of them with >= 6x headroom -- C1 taps worst 2.9e-6, eps 1.6e-7 at C2,
 C2 50 steps 3.2e-5 -- and the GPU's own fp32 summation order is what those constants already carry for the fp32 mode.  The route and
 exact-operand tests at the end are what an alias of the fp32 mode, or a kernel that dropped a cross term, cannot pass."""
-import ctypes
 import sys
 from pathlib import Path
 
@@ -22,6 +21,7 @@ from oracle import ref_unet
 HERE = Path(__file__).resolve().parent
 if str(HERE) not in sys.path:
     sys.path.insert(0, str(HERE))
+import infer_plan_cases  # noqa: E402
 import split_emulation  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -58,14 +58,7 @@ def check_packed(name, got, g, tol):
 
 
 def route_lines(nat):
-    lib = _native.load_library()
-    lib.ccn_internal_plan_routes.restype = ctypes.c_int
-    lib.ccn_internal_plan_routes.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
-    n = lib.ccn_internal_plan_routes(nat.h, None, 0)
-    assert n > 0
-    buf = ctypes.create_string_buffer(n + 1)
-    assert lib.ccn_internal_plan_routes(nat.h, buf, n + 1) == n
-    return buf.value.decode().splitlines()
+    return infer_plan_cases.route_text(nat).splitlines()
 
 
 @pytest.fixture(scope="module")
