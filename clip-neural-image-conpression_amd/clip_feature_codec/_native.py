@@ -43,6 +43,9 @@ SIGNATURES = {
     "ccn_sample": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp, c_i32]),
     "ccn_sample_eta": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_i32]),
     "ccn_ddim_step": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_vp]),
+    "ccn_sample_guided": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_sz,
+                                  c_vp, c_i32]),
+    "ccn_cfg_ddim_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_vp]),
     "ccn_q_sample": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp]),
     "ccn_predict_x0": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp]),
     "ccn_film_forward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -149,6 +152,7 @@ class Workspace:
         base = self.buf.data_ptr()
         self.ptr = (base + 255) // 256 * 256
         self.nbytes = nbytes
+        self.eps: Optional[torch.Tensor] = None     # NativeUNet.sample_guided: the eps of both halves, kept with the workspace
 
 
 class NativeUNet:
@@ -273,6 +277,46 @@ class NativeUNet:
                 check(self.lib.ccn_sample(self.h, z.data_ptr(), x_T.data_ptr(), out.data_ptr(), B, H, W, steps,
                                           ts.ctypes.data, coef.ctypes.data, ws.ptr, ws.nbytes,
                                           current_stream(x_T.device), 1 if use_graph else 0))
+        return out
+
+    def sample_guided(self, z: torch.Tensor, x_T: torch.Tensor, ts, coef, w: float, z_null: Optional[torch.Tensor] = None,
+                      use_graph: bool = True, slot: int = 0, sigma=None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The DDIM loop under classifier-free guidance of scale ``w`` (ccn_sample_guided): the plan and the workspace of batch 2B,
+        ``z`` in the first half, ``z_null`` (``(z_dim,)``; None: zeros) in the second.  ``sigma`` / ``noise`` as for ``sample``,
+        ``noise`` of ``(steps, B, C, H, W)``: one set of draws for both halves.  The eps scratch of the 2B rows is kept with the
+        workspace, so that a later call replays the graph captured with its address."""
+        import math
+        import numpy as np
+        z = require_dev(z, "z_clip"); x_T = require_dev(x_T, "x_T")
+        B, C, H, W = x_T.shape
+        ts = np.ascontiguousarray(ts, dtype=np.int32)
+        coef = np.ascontiguousarray(coef, dtype=np.float32)
+        steps = int(ts.shape[0])
+        if coef.shape != (steps, 4):
+            raise ValueError("coef must be (steps, 4)")
+        if C != self.img_ch or z.shape != (B, self.z_dim):
+            raise ValueError(f"shape mismatch: x_T {tuple(x_T.shape)}, z {tuple(z.shape)}")
+        if not math.isfinite(float(w)):
+            raise ValueError(f"the guidance scale must be finite, got {w}")
+        if z_null is not None:
+            z_null = require_dev(z_null, "null_z")
+            if tuple(z_null.shape) != (self.z_dim,):
+                raise ValueError(f"null_z must be ({self.z_dim},), got {tuple(z_null.shape)}")
+        sig_p = None
+        if sigma is not None:
+            sigma = np.ascontiguousarray(sigma, dtype=np.float32)
+            noise = require_dev(noise, "noise")
+            if sigma.shape != (steps,) or tuple(noise.shape) != (steps, B, C, H, W):
+                raise ValueError(f"sigma must be ({steps},) and noise ({steps}, {B}, {C}, {H}, {W})")
+            sig_p = sigma.ctypes.data
+        ws = self.workspace(2 * B, H, W, steps, slot)
+        if ws.eps is None:
+            ws.eps = torch.empty((2 * B, C, H, W), dtype=torch.float32, device=self.device)
+        out = torch.empty_like(x_T)
+        with torch.cuda.device(x_T.device):
+            check(self.lib.ccn_sample_guided(self.h, z.data_ptr(), ptr(z_null), x_T.data_ptr(), out.data_ptr(), B, H, W, steps,
+                                             ts.ctypes.data, coef.ctypes.data, sig_p, ptr(noise) if sigma is not None else None, float(w),
+                                             ws.eps.data_ptr(), ws.ptr, ws.nbytes, current_stream(x_T.device), 1 if use_graph else 0))
         return out
 
     def resblock(self, prefix: str, x: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
@@ -587,6 +631,23 @@ def ddim_step(x: torch.Tensor, eps: torch.Tensor, coef: Sequence[float], sigma: 
     with torch.cuda.device(x.device):
         check(lib.ccn_ddim_step(x.data_ptr(), eps.data_ptr(), ptr(nz), float(coef[0]), float(coef[1]), float(coef[2]),
                                 float(coef[3]), float(sigma), x.numel(), current_stream(x.device)))
+    return x
+
+
+def cfg_ddim_step(x: torch.Tensor, eps_c: torch.Tensor, eps_u: torch.Tensor, w: float, coef: Sequence[float], sigma: float = 0.0,
+                  noise: Optional[torch.Tensor] = None, x_dup: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In-place DDIM update of ``x`` on the guided prediction ``eps_u + w * (eps_c - eps_u)``, one pass (ccn_cfg_ddim_step);
+    ``x_dup``, if given, receives a copy of the new ``x``."""
+    lib = load_library()
+    x = require_dev(x, "x"); eps_c = require_dev(eps_c, "eps_c"); eps_u = require_dev(eps_u, "eps_u")
+    nz = require_dev(noise, "noise") if noise is not None else None
+    if eps_c.numel() != x.numel() or eps_u.numel() != x.numel() or (nz is not None and nz.numel() != x.numel()):
+        raise ValueError("x, eps_c, eps_u and noise must hold the same number of elements")
+    if x_dup is not None and not (x_dup.is_cuda and x_dup.dtype == torch.float32 and x_dup.is_contiguous() and x_dup.numel() == x.numel()):
+        raise ValueError("x_dup must be a contiguous fp32 HIP tensor of x's size")
+    with torch.cuda.device(x.device):
+        check(lib.ccn_cfg_ddim_step(x.data_ptr(), ptr(x_dup), eps_c.data_ptr(), eps_u.data_ptr(), ptr(nz), float(w), float(coef[0]),
+                                    float(coef[1]), float(coef[2]), float(coef[3]), float(sigma), x.numel(), current_stream(x.device)))
     return x
 
 

@@ -47,8 +47,9 @@ def build_model(weights: str, device: str, z_dim: int, dtype: str = "fp32") -> C
     return net
 
 
-def build_sampler(eta: float, device: str) -> DDIMSampler:
-    return DDIMSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), eta=eta)
+def build_sampler(eta: float, device: str, guided: bool = False) -> DDIMSampler:
+    """``guided``: the sampler gives ``cfg_scale`` its meaning (classifier-free guidance against the zero embedding)."""
+    return DDIMSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), eta=eta, guided=guided)
 
 
 def start_noise(indices: Sequence[int], size: int, seed: int | None, img_ch: int = 3) -> torch.Tensor | None:

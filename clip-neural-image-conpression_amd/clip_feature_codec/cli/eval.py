@@ -11,7 +11,8 @@ at a time on one device:
   per-record metric rows at the end; rank 0 prints / writes;
 * ``--seed`` makes start noise reproducible and independent of the sharding (record i always gets
   the CPU-generator stream ``seed+i``); without it noise is unseeded like the reference;
-* originals are decoded / resized on host threads while the GPU samples.
+* originals are decoded / resized on host threads while the GPU samples;
+* ``--cfg_scale`` other than 1.0 samples under classifier-free guidance (the fused loop at twice the batch).
 """
 from __future__ import annotations
 
@@ -173,6 +174,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch", type=int, default=8, help="records per fused DDIM launch per GPU")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--dtype", choices=["fp32", "bf16", "f16x3"], default="fp32")
+    ap.add_argument("--cfg_scale", type=float, default=1.0,
+                    help="classifier-free guidance scale w: eps = eps_u + w * (eps_c - eps_u), eps_u predicted from the zero embedding "
+                         "(a checkpoint trained with z_drop); 1.0 (default): unguided, the reference's behaviour")
     ap.add_argument("--timing", action="store_true", help="print set-up and loop wall time (records/s of the loop) to stderr")
     ap.add_argument("--workers", type=int, default=None, help="host threads for decode / metrics (default: this rank's share of the CPUs, 2..16)")
     ap.add_argument("--force-process-group", action="store_true",
@@ -215,12 +219,12 @@ def main(argv=None) -> None:
     manifest = json.loads((store_dir / "manifest.json").read_text(encoding="utf-8"))
     scale, zero = load_codec_meta(store_dir)
     net = build_model(args.weights, device, scale.shape[0], args.dtype)
-    sampler = build_sampler(args.eta, device)
+    sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0)
 
     def reconstruct(z: np.ndarray, x_T: Optional[torch.Tensor]) -> np.ndarray:
         zt = torch.from_numpy(z).to(device)
         with torch.no_grad():
-            x = sampler.sample(net, zt, shape=(zt.shape[0], 3, args.size, args.size), steps=args.steps,
+            x = sampler.sample(net, zt, shape=(zt.shape[0], 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale,
                                x_T=None if x_T is None else x_T.to(device))
         return x.clamp(-1, 1).cpu().numpy()
 
@@ -239,7 +243,7 @@ def main(argv=None) -> None:
         st = streams[slot]
         st.wait_stream(torch.cuda.current_stream(device))
         with torch.no_grad(), torch.cuda.stream(st):
-            x = sampler.sample(net, zt, shape=(zt.shape[0], 3, args.size, args.size), steps=args.steps, x_T=xt, slot=slot).clamp(-1, 1)
+            x = sampler.sample(net, zt, shape=(zt.shape[0], 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale, x_T=xt, slot=slot).clamp(-1, 1)
             if u8:
                 # _to_uint8 (eval/metrics.py:16-19) on the device: the same two separately rounded fp32 ops, clip, truncation
                 x = ((x + 1.0) * 127.5).clamp(0, 255).to(torch.uint8)

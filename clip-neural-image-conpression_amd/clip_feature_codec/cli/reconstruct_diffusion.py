@@ -4,7 +4,8 @@ Same flags, defaults and output as the reference CLI (cli/reconstruct_diffusion.
 ``--store_dir --bitstream --weights --out --steps --eta --size --device``; prints ``Saved to <out>``;
 the PNG is written from ``((clamp(x,-1,1)+1)*127.5).astype(uint8)`` (truncation).  Additions that
 default to the reference behaviour: ``--seed`` (reproducible CPU-generated start noise; the reference
-never seeds), ``--dtype {fp32,bf16,f16x3}`` and the architecture is read from the checkpoint's shapes.
+never seeds), ``--dtype {fp32,bf16,f16x3}``, ``--cfg_scale`` (classifier-free guidance; 1.0 = off) and the architecture is read
+from the checkpoint's shapes.
 """
 from __future__ import annotations
 
@@ -30,6 +31,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--device", type=str, default=None)
     ap.add_argument("--seed", type=int, default=None, help="seed of the CPU-generated start noise (default: unseeded, like the reference)")
     ap.add_argument("--dtype", choices=["fp32", "bf16", "f16x3"], default="fp32")
+    ap.add_argument("--cfg_scale", type=float, default=1.0,
+                    help="classifier-free guidance scale w: eps = eps_u + w * (eps_c - eps_u), eps_u predicted from the zero embedding "
+                         "(a checkpoint trained with z_drop); 1.0 (default): unguided, the reference's behaviour")
     return ap
 
 
@@ -40,10 +44,10 @@ def main(argv=None) -> None:
     scale, zero = load_codec_meta(Path(args.store_dir))
     z = torch.from_numpy(load_embedding(Path(args.bitstream), scale, zero)).to(device)
     net = build_model(args.weights, device, z.shape[1], args.dtype)
-    sampler = build_sampler(args.eta, device)
+    sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0)
     x_T = start_noise([0], args.size, args.seed)
     with torch.no_grad():
-        x = sampler.sample(net, z, shape=(1, 3, args.size, args.size), steps=args.steps,
+        x = sampler.sample(net, z, shape=(1, 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale,
                            x_T=None if x_T is None else x_T.to(device))
     img = x[0].clamp(-1, 1).cpu().numpy().transpose(1, 2, 0)
     Image.fromarray(((img + 1.0) * 127.5).astype(np.uint8)).save(args.out)

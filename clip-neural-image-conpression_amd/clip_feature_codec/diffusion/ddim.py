@@ -12,11 +12,20 @@ Interface of ``diffusion/ddim.py:14-45`` of the reference.  Two execution routes
 
 Reference behaviours kept on purpose: ``ts = linspace(T-1, 0, steps).long()``; ``alpha_bar_prev`` is
 ``alphas_cumprod_prev[t]`` (not the next sampled step) and 1.0 on the last step; the direction term is
-``sqrt(alpha_bar_s - sigma^2) * eps``; ``x0`` is clamped to [-1, 1]; ``cfg_scale`` is accepted and unused;
-the result is NOT clamped; the output lives on ``z_clip.device``.
+``sqrt(alpha_bar_s - sigma^2) * eps``; ``x0`` is clamped to [-1, 1]; with the default ``guided=False``, ``cfg_scale`` is
+accepted and unused; the result is NOT clamped; the output lives on ``z_clip.device``.
+
+``DDIMSampler(scheduler, eta, guided=True, null_z=None)`` gives ``cfg_scale`` its meaning (no reference counterpart): every step
+uses ``eps = eps_u + cfg_scale * (eps_c - eps_u)``, ``eps_c`` the prediction with ``z_clip`` and ``eps_u`` the one with the null
+embedding ``null_z`` (``(z_dim,)``; None: zeros, what ``train_step(..., z_drop=p)`` trains).  ``cfg_scale == 1.0`` takes the
+unguided route, same bits.  Otherwise the fused route is ``ccn_sample_guided`` -- the same captured loop at batch 2B, the state
+held twice, one combine-and-update launch per step; ``slot``, ``use_graph`` and the ``eta > 0`` draws (one set, shared by both
+halves) as above -- and the stepwise route calls ``model(x, z, t)`` and ``model(x, z_null, t)`` per step, then
+``ccn_cfg_ddim_step``.  A non-finite ``cfg_scale`` or a ``null_z`` of another shape is a ``ValueError``.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -25,15 +34,31 @@ from .. import _native
 
 
 class DDIMSampler:
-    """Deterministic (eta = 0) / stochastic DDIM sampler."""
+    """Deterministic (eta = 0) / stochastic DDIM sampler; ``guided=True``: classifier-free guidance of scale ``cfg_scale``."""
 
     MAX_NOISE_BUFFERS = 4
 
-    def __init__(self, scheduler, eta: float = 0.0) -> None:
+    def __init__(self, scheduler, eta: float = 0.0, guided: bool = False, null_z: Optional[torch.Tensor] = None) -> None:
         self.sch = scheduler
         self.eta = eta
+        self.guided = bool(guided)
+        self.null_z = null_z                 # (z_dim,), the embedding of the unconditional branch; None: zeros (train_step's z_drop)
         self.use_graph = True
         self._noise: dict = {}
+
+    def _guidance(self, z_clip: torch.Tensor, cfg_scale: float):
+        """(scale, null row on z_clip's device) of a guided call, or (None, None): unguided, or the scale is 1.0."""
+        if not self.guided:
+            return None, None
+        w = float(cfg_scale)
+        if not math.isfinite(w):
+            raise ValueError(f"cfg_scale must be finite, got {cfg_scale}")
+        null_z = self.null_z
+        if null_z is not None:
+            if not isinstance(null_z, torch.Tensor) or tuple(null_z.shape) != (z_clip.shape[-1],):
+                raise ValueError(f"null_z must be a tensor of shape ({z_clip.shape[-1]},), got {tuple(getattr(null_z, 'shape', ()))}")
+            null_z = null_z.to(z_clip.device, torch.float32)
+        return (None, None) if w == 1.0 else (w, null_z)
 
     @torch.no_grad()
     def sample(self, model, z_clip: torch.Tensor, shape: tuple, steps: int = 50, cfg_scale: float = 1.0,
@@ -41,12 +66,14 @@ class DDIMSampler:
         device = z_clip.device
         if device.type != "cuda":
             raise RuntimeError(f"z_clip is on {device}: DDIMSampler (MI355X build) needs a HIP device; no CPU fallback")
+        w, null_z = self._guidance(z_clip, cfg_scale)
         ts = self.sch.ddim_timesteps(steps)
         coef = self.sch.ddim_coefficients(steps, self.eta)
         x = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
         if hasattr(model, "sample_ddim"):
+            guide = {} if w is None else dict(guidance=w, null_z=null_z)
             if self.eta == 0:
-                return model.sample_ddim(z_clip, x, ts, coef[:, :4], use_graph=self.use_graph, slot=slot)
+                return model.sample_ddim(z_clip, x, ts, coef[:, :4], use_graph=self.use_graph, slot=slot, **guide)
             # eta > 0: every noisy step's draw up front, into a buffer kept per (shape, steps, slot) so that the captured graph
             # (keyed by the buffer's address) is replayed by later calls
             # Memory: steps x batch x C x H x W fp32 per key (314 MB at C2: 50 steps, batch 8, 256 px; 1.26 GB at C4) -- at most
@@ -62,12 +89,19 @@ class DDIMSampler:
             for i in range(steps):
                 if float(coef[i, 4]) > 0:
                     buf[i].normal_()                                  # == torch.randn_like(x): same generator, same order
-            return model.sample_ddim(z_clip, x, ts, coef[:, :4], use_graph=self.use_graph, slot=slot, sigma=coef[:, 4], noise=buf)
+            return model.sample_ddim(z_clip, x, ts, coef[:, :4], use_graph=self.use_graph, slot=slot, sigma=coef[:, 4], noise=buf, **guide)
         x = _native.require_dev(x, "x_T").clone()
+        z_u = None
+        if w is not None:
+            z_u = (torch.zeros_like(z_clip[0]) if null_z is None else null_z).expand(shape[0], -1).contiguous()
         for i in range(steps):
             t_b = torch.full((shape[0],), int(ts[i]), device=device, dtype=torch.long)
             eps = model(x, z_clip, t_b)
+            eps_u = model(x, z_u, t_b) if w is not None else None
             sigma = float(coef[i, 4])
             noise = torch.randn_like(x) if (self.eta > 0 and sigma > 0) else None
-            _native.ddim_step(x, eps, coef[i, :4], sigma, noise)
+            if w is None:
+                _native.ddim_step(x, eps, coef[i, :4], sigma, noise)
+            else:
+                _native.cfg_ddim_step(x, eps, eps_u, w, coef[i, :4], sigma, noise)
         return x

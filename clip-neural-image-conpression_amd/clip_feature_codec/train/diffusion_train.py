@@ -511,11 +511,30 @@ def average_gradients(flat_grad: torch.Tensor) -> torch.Tensor:
     return flat_grad
 
 
+def z_dropout(z: torch.Tensor, p: float, generator: Optional[torch.Generator] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Embedding dropout, the training half of classifier-free guidance: every row of ``z`` (B, ...) is replaced by zeros with
+    probability ``p`` -- the null embedding ``DDIMSampler(guided=True)`` samples the unconditional branch with.  Returns
+    ``(z_dropped, keep_mask)``, ``keep_mask`` a (B,) bool tensor on ``z``'s device.  One ``torch.rand(B)`` draw on that device, from
+    its default generator unless ``generator`` is given; ``p == 0`` draws nothing and returns ``z`` itself.  Any device."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"the dropout probability must be in [0, 1], not {p}")
+    b = z.shape[0]
+    if p == 0.0:
+        return z, torch.ones(b, dtype=torch.bool, device=z.device)
+    keep = torch.rand(b, device=z.device, generator=generator) >= p        # rand is in [0, 1): p = 1 drops every row
+    return torch.where(keep.view((b,) + (1,) * (z.dim() - 1)), z, torch.zeros((), dtype=z.dtype, device=z.device)), keep
+
+
 def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[torch.Tensor] = None,
                noise: Optional[torch.Tensor] = None, ddp=False, graph: bool = False, recon_w: float = 0.0,
                tv_w: float = 0.0, scaler: Optional[GradScaler] = None, max_grad_norm: Optional[float] = None,
-               ema_decay: Optional[float] = None) -> torch.Tensor:
+               ema_decay: Optional[float] = None, z_drop: float = 0.0) -> torch.Tensor:
     """One optimisation step; returns the (detached) loss.  ``t`` / ``noise`` default to the reference's draws.
+
+    ``z_drop`` (usually 0.1): ``z_dropout`` zeroes whole rows of ``z`` with that probability before the copy into the static buffer,
+    which trains the unconditional branch that guided sampling needs.  Under data parallelism each rank draws its own mask.  With 0
+    (the default) nothing is drawn and the step is what it was, launch for launch.
 
     The weight EMA belongs to the optimiser (``FusedAdamW(net, ema_decay=)``) and needs no argument here; ``ema_decay`` is only
     checked: a ``TypeError`` with any other optimiser, a ``ValueError`` if it is not the optimiser's own.
@@ -550,7 +569,12 @@ def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[tor
     clip = max_grad_norm is not None and max_grad_norm > 0
     if (guard is not None or clip) and not isinstance(opt, FusedAdamW):
         raise TypeError("scaler= / max_grad_norm= need a FusedAdamW: drive a torch.optim optimiser with torch.amp.GradScaler")
-    sb = state.static_buffers(_native.require_dev(x0, "x0"), _native.require_dev(z, "z"))
+    if not 0.0 <= z_drop <= 1.0:
+        raise ValueError(f"z_drop must be in [0, 1], not {z_drop}")
+    z_dev = _native.require_dev(z, "z")
+    if z_drop > 0:
+        z = z_dev = z_dropout(z_dev, z_drop)[0]
+    sb = state.static_buffers(_native.require_dev(x0, "x0"), z_dev)
     sb["x0"].copy_(x0); sb["z"].copy_(z)
     if t is None:
         sb["t"].random_(0, sch.timesteps)
@@ -687,7 +711,7 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
                     schedule: str = "cosine", recon_w: float = 0.05, clip_w: float = 0.1, tv_w: float = 1e-4, device: str = "cuda",
                     save_dir=None, base: int = 128, ch_mult=(1, 2, 2), dtype: str = "bf16", num_workers: int = 2, log=print,
                     fused_objective: bool = True, grad_scaler: bool = False, max_grad_norm: Optional[float] = None,
-                    ema_decay: Optional[float] = None, ema_warmup: bool = False, resume=None):
+                    ema_decay: Optional[float] = None, ema_warmup: bool = False, resume=None, z_drop: float = 0.0):
     """The reference's ``train_diffusion`` (same arguments, defaults, checkpoint names and log line) on the MI355X kernels.
 
     Per batch (train/diffusion_train.py:115-140): t ~ U{0..T-1}, noise ~ N, then ``train_step`` with the ``t`` / ``noise`` drawn here:
@@ -708,12 +732,18 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
     Every epoch rank 0 also writes ``train_state.pt`` (to a temporary name, then ``os.replace``): epoch, weights, optimiser and scaler
     state, torch's CPU and device RNG states.  ``resume=<that file>`` restores all of it on every rank and continues with the next
     epoch (same ``[train] epoch k/N`` numbering); a file of another architecture or parameter count is refused.
+
+    ``z_drop`` (usually 0.1): every batch's embeddings go through ``z_dropout`` -- whole rows zeroed with that probability, one
+    ``torch.rand`` draw per batch on the device, each rank its own -- which trains the unconditional branch that
+    ``DDIMSampler(guided=True)`` needs.  ``train_state.pt`` already carries the RNG states, so a resumed run continues the masks.
     """
     import os
     from pathlib import Path
     import torch.distributed as dist
     from ..models.unet import CLIPCondUNet
     from ..diffusion.scheduler import NoiseScheduler
+    if not 0.0 <= z_drop <= 1.0:
+        raise ValueError(f"z_drop must be in [0, 1], not {z_drop}")
     save_dir = Path(save_dir or store_dir)
     save_dir.mkdir(parents=True, exist_ok=True)
     ds = StoreDataset(store_dir, out_size=out_size)
@@ -771,9 +801,11 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
             noise = torch.randn_like(x0)
             if fused_objective:
                 loss = train_step(net, sch, opt, x0, z, t=t, noise=noise, ddp=ddp, recon_w=max(recon_w, 0.0), tv_w=max(tv_w, 0.0),
-                                  scaler=scaler, max_grad_norm=max_grad_norm)
+                                  scaler=scaler, max_grad_norm=max_grad_norm, z_drop=z_drop)
                 running_dev += loss.double() * b          # the loss is a view of a static buffer: consumed here, in stream order
             else:
+                if z_drop > 0:
+                    z = z_dropout(z, z_drop)[0]
                 running += float(autograd_objective_step(net, sch, opt, x0, z, t, noise, recon_w, tv_w, scaler=scaler,
                                                                  max_grad_norm=max_grad_norm)) * b
             seen += b

@@ -150,6 +150,9 @@ struct GraphEntry {
     std::vector<float> coef;
     std::vector<float> sigma;            // eta > 0 (empty: eta = 0)
     const float* noise = nullptr;        // ... and the address of the caller's noise tensor the graph was captured with
+    bool guided = false;                 // ccn_sample_guided: the plan's batch is two halves, and each step ends in the combine launch
+    float w = 0.f;                       // ... whose by-value guidance scale
+    const float* eps = nullptr;          // ... and eps scratch address the graph was captured with
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     void destroy() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); }   // (after draining the device)
@@ -832,17 +835,34 @@ int run_conditioning(ccn_handle_s* h, const Binding* b, hipStream_t s, const int
     return timed(h, F_COND, 2.0 * FR * td * (double)F, 0, s, [&] { return launch_linear(tp, zp, a_div, B, h->film_w, h->film_b, f32(p.film), FR, td, F, 0, s); });
 }
 
-int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, int steps, const float* coef, const float* sigma = nullptr, const float* noise = nullptr)
+// Classifier-free guidance (ccn_sample_guided): the plan's batch is 2B rows -- [0, B) carry z, [B, 2B) the null embedding, both the
+// same state -- the head writes eps of all 2B rows into `eps`, and one combine launch per step updates both halves of the state.
+struct Guide { const float* z_null; float w; float* eps; };
+
+int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, int steps, const float* coef, const float* sigma = nullptr, const float* noise = nullptr,
+              const Guide* gd = nullptr)
 {
     const ShapePlan& p = *b->plan;
-    const size_t img = (size_t)p.B * h->cfg.img_ch * p.H * p.W;
+    const size_t img = (size_t)(gd ? p.B / 2 : p.B) * h->cfg.img_ch * p.H * p.W;     // one state (and one step's draws)
     float* xstate = (float*)(b->ws + p.xstate);
     for (int i = 0; i < steps; ++i) {
+        const bool noisy = sigma && noise && sigma[i] > 0.f;
         StepCtx c;
-        c.step = i; c.x_in = xstate; c.x_state = xstate; c.eps_out = nullptr; c.do_ddim = 1;
-        for (int k = 0; k < 4; ++k) c.c[k] = coef[i * 4 + k];
-        if (sigma && noise && sigma[i] > 0.f) { c.noise = noise + (size_t)i * img; c.sigma = sigma[i]; }
+        c.step = i; c.x_in = xstate;
+        if (gd) { c.x_state = nullptr; c.eps_out = gd->eps; c.do_ddim = 0; }
+        else {
+            c.x_state = xstate; c.eps_out = nullptr; c.do_ddim = 1;
+            for (int k = 0; k < 4; ++k) c.c[k] = coef[i * 4 + k];
+            if (noisy) { c.noise = noise + (size_t)i * img; c.sigma = sigma[i]; }
+        }
         if (int rc = run_ops(h, b, s, c)) return rc;
+        if (gd) {
+            const float* cf = coef + i * 4;
+            const float* nz = noisy ? noise + (size_t)i * img : nullptr;
+            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * (nz ? 6 : 5), s, [&] {
+                    return launch_cfg_ddim_step(xstate, xstate + img, gd->eps, gd->eps + img, nz, gd->w, cf[0], cf[1], cf[2], cf[3],
+                                                noisy ? sigma[i] : 0.f, (int64_t)img, s); })) return rc;
+        }
     }
     return CCN_OK;
 }
@@ -1110,18 +1130,30 @@ int ccn_forward(ccn_handle_t h, const float* x_dev, const float* z_dev, const in
 
 static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H, int32_t W,
                        int32_t steps, const int32_t* ts_host, const float* coef_host, const float* sigma_host, const float* noise_dev,
-                       void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph)
+                       void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph, const Guide* gd = nullptr)
 {
     int rc = check_ready(h);
     if (rc) return rc;
     if (!z_dev || !x_T_dev || !x_out_dev || !ts_host || !coef_host) return fail(CCN_EINVAL, "null pointer");
+    if (gd && (B <= 0 || B > INT32_MAX / 2)) return fail(CCN_EINVAL, "B, H, W, steps must be positive");
+    const int PB = gd ? 2 * B : B;                                  // the plan's batch: guided, the two halves
     Binding* p = nullptr;
-    if ((rc = get_binding(h, B, H, W, steps, workspace_dev, workspace_bytes, &p))) return rc;
+    if ((rc = get_binding(h, PB, H, W, steps, workspace_dev, workspace_bytes, &p))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const size_t img_bytes = (size_t)B * h->cfg.img_ch * H * W * 4;
+    const size_t img_bytes = (size_t)B * h->cfg.img_ch * H * W * 4, z_row = (size_t)h->cfg.z_dim * 4;
     float* xstate = (float*)(p->ws + p->plan->xstate);
-    HIPCHK(hipMemcpyAsync(p->ws + p->plan->zbuf, z_dev, (size_t)B * h->cfg.z_dim * 4, hipMemcpyDeviceToDevice, s));
+    char* zbuf = p->ws + p->plan->zbuf;
+    HIPCHK(hipMemcpyAsync(zbuf, z_dev, (size_t)B * z_row, hipMemcpyDeviceToDevice, s));
+    if (gd && !gd->z_null) HIPCHK(hipMemsetAsync(zbuf + (size_t)B * z_row, 0, (size_t)B * z_row, s));
+    if (gd && gd->z_null) {
+        // the null row B times: once from the caller, then doubling from the rows already there
+        char* zn = zbuf + (size_t)B * z_row;
+        HIPCHK(hipMemcpyAsync(zn, gd->z_null, z_row, hipMemcpyDeviceToDevice, s));
+        for (int have = 1; have < B; have *= 2)
+            HIPCHK(hipMemcpyAsync(zn + (size_t)have * z_row, zn, (size_t)std::min(have, B - have) * z_row, hipMemcpyDeviceToDevice, s));
+    }
     if (x_T_dev != xstate) HIPCHK(hipMemcpyAsync(xstate, x_T_dev, img_bytes, hipMemcpyDeviceToDevice, s));
+    if (gd) HIPCHK(hipMemcpyAsync((char*)xstate + img_bytes, xstate, img_bytes, hipMemcpyDeviceToDevice, s));
 
     // the timestep table of a binding almost never changes: upload it only when it does, and then synchronously after draining
     // the stream (an async copy out of a host vector that the next call rewrites could still be pending)
@@ -1136,15 +1168,17 @@ static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev,
             if (g.steps == steps && !std::memcmp(g.ts.data(), ts_host, (size_t)steps * 4) &&
                 !std::memcmp(g.coef.data(), coef_host, (size_t)steps * 16) && g.noise == noise_dev &&
                 g.sigma.size() == (sigma_host ? (size_t)steps : 0) &&
-                (!sigma_host || !std::memcmp(g.sigma.data(), sigma_host, (size_t)steps * 4))) { ge = &g; break; }
+                (!sigma_host || !std::memcmp(g.sigma.data(), sigma_host, (size_t)steps * 4)) &&
+                g.guided == (gd != nullptr) && (!gd || (g.w == gd->w && g.eps == gd->eps))) { ge = &g; break; }
         if (!ge) {
             GraphEntry g;
             g.steps = steps; g.ts.assign(ts_host, ts_host + steps); g.coef.assign(coef_host, coef_host + steps * 4);
             if (sigma_host) g.sigma.assign(sigma_host, sigma_host + steps);
             g.noise = noise_dev;
+            if (gd) { g.guided = true; g.w = gd->w; g.eps = gd->eps; }
             HIPCHK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeRelaxed));
-            rc = run_conditioning(h, p, h->cap_stream, nullptr, steps, steps * B, B);
-            if (!rc) rc = run_steps(h, p, h->cap_stream, steps, coef_host, sigma_host, noise_dev);
+            rc = run_conditioning(h, p, h->cap_stream, nullptr, steps, steps * PB, PB);
+            if (!rc) rc = run_steps(h, p, h->cap_stream, steps, coef_host, sigma_host, noise_dev, gd);
             hipGraph_t graph = nullptr;
             const hipError_t ce = hipStreamEndCapture(h->cap_stream, &graph);
             if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -1167,8 +1201,8 @@ static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev,
         }
         HIPCHK(hipGraphLaunch(ge->exec, s));
     } else {
-        if ((rc = run_conditioning(h, p, s, nullptr, steps, steps * B, B))) return rc;
-        if ((rc = run_steps(h, p, s, steps, coef_host, sigma_host, noise_dev))) return rc;
+        if ((rc = run_conditioning(h, p, s, nullptr, steps, steps * PB, PB))) return rc;
+        if ((rc = run_steps(h, p, s, steps, coef_host, sigma_host, noise_dev, gd))) return rc;
     }
     if (x_out_dev != xstate) HIPCHK(hipMemcpyAsync(x_out_dev, xstate, img_bytes, hipMemcpyDeviceToDevice, s));
     return CCN_OK;
@@ -1187,6 +1221,28 @@ int ccn_sample_eta(ccn_handle_t h, const float* z_dev, const float* x_T_dev, flo
 {
     if (!sigma_host || !noise_dev) return fail(CCN_EINVAL, "null sigma / noise");
     return sample_impl(h, z_dev, x_T_dev, x_out_dev, B, H, W, steps, ts_host, coef_host, sigma_host, noise_dev, workspace_dev, workspace_bytes, stream, use_graph);
+}
+
+int ccn_sample_guided(ccn_handle_t h, const float* z_dev, const float* z_null_dev, const float* x_T_dev, float* x_out_dev, int32_t B,
+                      int32_t H, int32_t W, int32_t steps, const int32_t* ts_host, const float* coef_host, const float* sigma_host,
+                      const float* noise_dev, float w, float* eps_scratch_dev, void* workspace_dev, size_t workspace_bytes, void* stream,
+                      int32_t use_graph)
+{
+    if (!sigma_host != !noise_dev) return fail(CCN_EINVAL, "sigma and noise must be given together");
+    if (!std::isfinite(w)) return fail(CCN_EINVAL, "the guidance scale must be finite");
+    if (!eps_scratch_dev || ((uintptr_t)eps_scratch_dev & 15)) return fail(CCN_EINVAL, "the eps scratch must be non-null and 16-byte aligned");
+    const Guide gd{z_null_dev, w, eps_scratch_dev};
+    return sample_impl(h, z_dev, x_T_dev, x_out_dev, B, H, W, steps, ts_host, coef_host, sigma_host, noise_dev, workspace_dev, workspace_bytes, stream,
+                       use_graph, &gd);
+}
+
+int ccn_cfg_ddim_step(float* x_dev, float* x_dup_dev, const float* eps_c_dev, const float* eps_u_dev, const float* noise_dev, float w,
+                      float c0, float c1, float c2, float c3, float sigma, int64_t n, void* stream)
+{
+    if (!x_dev || !eps_c_dev || !eps_u_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
+    if (n == 0) return CCN_OK;
+    HIPCHK(launch_cfg_ddim_step(x_dev, x_dup_dev, eps_c_dev, eps_u_dev, noise_dev, w, c0, c1, c2, c3, sigma, n, (hipStream_t)stream));
+    return CCN_OK;
 }
 
 int ccn_ddim_step(float* x_dev, const float* eps_dev, const float* noise_dev, float c0, float c1, float c2, float c3,

@@ -260,6 +260,9 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
 // ---- elementwise ---------------------------------------------------------------------------------
 hipError_t launch_ddim_step(float* x, const float* eps, const float* noise, float c0, float c1, float c2, float c3,
                             float sigma, int64_t n, hipStream_t s);
+// the guided update: e = eps_u + w*(eps_c - eps_u), launch_ddim_step's update on e; x_dup (nullable) receives a copy of the new x
+hipError_t launch_cfg_ddim_step(float* x, float* x_dup, const float* eps_c, const float* eps_u, const float* noise, float w,
+                                float c0, float c1, float c2, float c3, float sigma, int64_t n, hipStream_t s);
 hipError_t launch_q_sample(float* out, const float* x0, const float* noise, const float* a, const float* sg,
                            int B, int64_t per, hipStream_t s);
 hipError_t launch_predict_x0(float* out, const float* xt, const float* eps, const float* a, const float* sg,

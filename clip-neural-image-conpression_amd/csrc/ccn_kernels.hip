@@ -827,6 +827,56 @@ hipError_t launch_ddim_step(float* x, const float* eps, const float* noise, floa
     return hipGetLastError();
 }
 
+// Classifier-free guidance and the DDIM update in one pass: e = eps_u + w*(eps_c - eps_u), then ddim_step_kernel's sequence on e, every
+// op rounded to fp32 on its own.  x is updated in place; x_dup (nullable) receives the same values: the unconditional half of the
+// guided loop's state.  VEC: every pointer is 16-byte aligned, four elements per lane and access; the n % 4 tail goes one by one.
+__device__ __forceinline__ float cfg_ddim_one(float x, float ec, float eu, float w, float c0, float c1, float c2, float c3)
+{
+    const float e = __fadd_rn(eu, __fmul_rn(w, __fsub_rn(ec, eu)));
+    float x0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(c0, e)), c1);
+    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    return __fadd_rn(__fmul_rn(c2, x0), __fmul_rn(c3, e));
+}
+template <bool VEC>
+__global__ void cfg_ddim_step_kernel(float* __restrict__ x, float* __restrict__ x_dup, const float* __restrict__ eps_c,
+                                     const float* __restrict__ eps_u, const float* __restrict__ noise, float w, float c0, float c1,
+                                     float c2, float c3, float sigma, int64_t n)
+{
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n4 = VEC ? n / 4 : 0;
+    for (int64_t q = tid; q < n4; q += nthr) {
+        const float4 xv = ((const float4*)x)[q], cv = ((const float4*)eps_c)[q], uv = ((const float4*)eps_u)[q];
+        float4 o;
+        o.x = cfg_ddim_one(xv.x, cv.x, uv.x, w, c0, c1, c2, c3);
+        o.y = cfg_ddim_one(xv.y, cv.y, uv.y, w, c0, c1, c2, c3);
+        o.z = cfg_ddim_one(xv.z, cv.z, uv.z, w, c0, c1, c2, c3);
+        o.w = cfg_ddim_one(xv.w, cv.w, uv.w, w, c0, c1, c2, c3);
+        if (noise) {
+            const float4 nv = ((const float4*)noise)[q];
+            o.x = __fadd_rn(o.x, __fmul_rn(sigma, nv.x)); o.y = __fadd_rn(o.y, __fmul_rn(sigma, nv.y));
+            o.z = __fadd_rn(o.z, __fmul_rn(sigma, nv.z)); o.w = __fadd_rn(o.w, __fmul_rn(sigma, nv.w));
+        }
+        ((float4*)x)[q] = o;
+        if (x_dup) ((float4*)x_dup)[q] = o;
+    }
+    for (int64_t i = n4 * 4 + tid; i < n; i += nthr) {
+        float xn = cfg_ddim_one(x[i], eps_c[i], eps_u[i], w, c0, c1, c2, c3);
+        if (noise) xn = __fadd_rn(xn, __fmul_rn(sigma, noise[i]));
+        x[i] = xn;
+        if (x_dup) x_dup[i] = xn;
+    }
+}
+hipError_t launch_cfg_ddim_step(float* x, float* x_dup, const float* eps_c, const float* eps_u, const float* noise, float w, float c0,
+                                float c1, float c2, float c3, float sigma, int64_t n, hipStream_t s)
+{
+    const bool vec = !(((uintptr_t)x | (uintptr_t)x_dup | (uintptr_t)eps_c | (uintptr_t)eps_u | (uintptr_t)noise) & 15);
+    const int64_t work = vec ? (n + 3) / 4 : n, blocks = (work + 255) / 256;
+    const int grid = (int)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);      // 256 CUs x 8 blocks, grid-stride beyond
+    if (vec) hipLaunchKernelGGL(cfg_ddim_step_kernel<true>, dim3(grid), dim3(256), 0, s, x, x_dup, eps_c, eps_u, noise, w, c0, c1, c2, c3, sigma, n);
+    else hipLaunchKernelGGL(cfg_ddim_step_kernel<false>, dim3(grid), dim3(256), 0, s, x, x_dup, eps_c, eps_u, noise, w, c0, c1, c2, c3, sigma, n);
+    return hipGetLastError();
+}
+
 __global__ void q_sample_kernel(float* __restrict__ out, const float* __restrict__ x0, const float* __restrict__ noise,
                                 const float* __restrict__ a, const float* __restrict__ sg, int64_t per)
 {

@@ -142,6 +142,31 @@ int ccn_sample_eta(ccn_handle_t h, const float* z_dev, const float* x_T_dev, flo
 int ccn_ddim_step(float* x_dev, const float* eps_dev, const float* noise_dev,
                   float c0, float c1, float c2, float c3, float sigma, int64_t n, void* stream);
 
+/* The DDIM loop under classifier-free guidance: per step eps = eps_u + w*(eps_c - eps_u), eps_c the prediction with z, eps_u the one
+ * with the null embedding, then the update of ccn_sample / ccn_sample_eta on that eps.  (No reference counterpart: the reference's
+ * sampler accepts cfg_scale and never reads it, diffusion/ddim.py:22.)
+ * The loop is the plan of batch 2B: rows [0, B) carry z_dev (B,z_dim), rows [B, 2B) carry z_null_dev (z_dim,) (NULL: zeros), both
+ * halves the same state.  Each step evaluates the UNet on the 2B rows, the head writing eps, and one ccn_cfg_ddim_step launch
+ * writes the new state into both halves.  Conditioning of all steps is hoisted in front of the loop as in ccn_sample.
+ * workspace_dev: the one of ccn_workspace_bytes(h, 2*B, H, W, steps).  eps_scratch_dev: 2*B*img_ch*H*W floats, 16-byte aligned,
+ * owned by the caller like the workspace, and to be kept at the same address while a captured graph for it is cached.
+ * sigma_host / noise_dev: both NULL (eta = 0) or both given as for ccn_sample_eta, noise_dev (steps,B,img_ch,H,W): one set of draws,
+ * shared by the two halves.  w must be finite.  x_T_dev -> x_out_dev (may alias), (B,img_ch,H,W).
+ * The captured graph is cached with those of ccn_sample at batch 2B on the same workspace, per (table, sigma, noise address, w,
+ * eps scratch address): w is a by-value kernel argument, so a new w is a new capture. */
+int ccn_sample_guided(ccn_handle_t h, const float* z_dev, const float* z_null_dev, const float* x_T_dev, float* x_out_dev,
+                      int32_t B, int32_t H, int32_t W, int32_t steps,
+                      const int32_t* ts_host, const float* coef_host, const float* sigma_host, const float* noise_dev,
+                      float w, float* eps_scratch_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph);
+
+/* One guided DDIM update, combine and update in one pass, every op rounded to fp32 on its own like the torch ops:
+ *     e = eps_u + w*(eps_c - eps_u);  x0 = clamp((x - c0*e)/c1, -1, 1);  x = c2*x0 + c3*e [+ sigma*noise]
+ * In place on x_dev; x_dup_dev (may be NULL) receives the same values (the second half of ccn_sample_guided's state); noise_dev may
+ * be NULL.  n elements each.  Four elements per lane when every pointer is 16-byte aligned, one otherwise. */
+int ccn_cfg_ddim_step(float* x_dev, float* x_dup_dev, const float* eps_c_dev, const float* eps_u_dev, const float* noise_dev,
+                      float w, float c0, float c1, float c2, float c3, float sigma, int64_t n, void* stream);
+
 /* NoiseScheduler.q_sample (diffusion/scheduler.py:46-49): out[b] = a[b]*x0[b] + s[b]*noise[b];
  * a_dev/s_dev are the gathered per-sample coefficients, (B,) fp32; per_sample = C*H*W. */
 int ccn_q_sample(float* out_dev, const float* x0_dev, const float* noise_dev,
