@@ -46,6 +46,11 @@ SIGNATURES = {
     "ccn_sample_guided": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_sz,
                                   c_vp, c_i32]),
     "ccn_cfg_ddim_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_vp]),
+    "ccn_sample_ms": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_i32]),
+    "ccn_sample_guided_ms": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_sz,
+                                     c_vp, c_i32]),
+    "ccn_ms_step": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_vp]),
+    "ccn_cfg_ms_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_vp]),
     "ccn_q_sample": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp]),
     "ccn_predict_x0": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp]),
     "ccn_film_forward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -153,6 +158,17 @@ class Workspace:
         self.ptr = (base + 255) // 256 * 256
         self.nbytes = nbytes
         self.eps: Optional[torch.Tensor] = None     # NativeUNet.sample_guided: the eps of both halves, kept with the workspace
+        # NativeUNet.sample_ms / sample_guided_ms: the x0 history of one state, likewise -- by element count, because the slot is keyed
+        # by the PLAN's batch: a guided call of batch B (history of B rows) and an unguided one of batch 2B (2B rows) share it
+        self.hist: Dict[int, torch.Tensor] = {}
+
+    def history(self, like: torch.Tensor) -> torch.Tensor:
+        """The kept x0 history of ``like``'s size (allocated on first use; never freed before the workspace, so that a captured
+        graph keyed by its address stays valid)."""
+        h = self.hist.get(like.numel())
+        if h is None:
+            h = self.hist[like.numel()] = torch.empty(like.shape, dtype=torch.float32, device=like.device)
+        return h
 
 
 class NativeUNet:
@@ -317,6 +333,64 @@ class NativeUNet:
             check(self.lib.ccn_sample_guided(self.h, z.data_ptr(), ptr(z_null), x_T.data_ptr(), out.data_ptr(), B, H, W, steps,
                                              ts.ctypes.data, coef.ctypes.data, sig_p, ptr(noise) if sigma is not None else None, float(w),
                                              ws.eps.data_ptr(), ws.ptr, ws.nbytes, current_stream(x_T.device), 1 if use_graph else 0))
+        return out
+
+    def _ms_args(self, z, x_T, ts, coef, hist):
+        import numpy as np
+        z = require_dev(z, "z_clip"); x_T = require_dev(x_T, "x_T")
+        B, C, H, W = x_T.shape
+        ts = np.ascontiguousarray(ts, dtype=np.int32)
+        coef = np.ascontiguousarray(coef, dtype=np.float32)
+        steps = int(ts.shape[0])
+        if coef.shape != (steps, 5):
+            raise ValueError("coef must be (steps, 5)")
+        if C != self.img_ch or z.shape != (B, self.z_dim):
+            raise ValueError(f"shape mismatch: x_T {tuple(x_T.shape)}, z {tuple(z.shape)}")
+        if hist is not None and not (isinstance(hist, torch.Tensor) and hist.is_cuda and hist.dtype == torch.float32 and hist.is_contiguous()
+                                     and hist.numel() == x_T.numel() and hist.data_ptr() % 16 == 0):
+            raise ValueError(f"hist must be a contiguous, 16-byte aligned fp32 HIP tensor of {x_T.numel()} elements")
+        return z, x_T, ts, coef, steps
+
+    def sample_ms(self, z: torch.Tensor, x_T: torch.Tensor, ts, coef, use_graph: bool = True, slot: int = 0,
+                  hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The multistep loop (ccn_sample_ms): ``coef`` of ``(steps, 5)``, see ``NoiseScheduler.solver_coefficients``.  ``hist``: the
+        x0 history, fp32 of ``x_T``'s size; None: one kept with the workspace, so that a later call replays the graph captured with
+        its address."""
+        z, x_T, ts, coef, steps = self._ms_args(z, x_T, ts, coef, hist)
+        B, C, H, W = x_T.shape
+        ws = self.workspace(B, H, W, steps, slot)
+        if hist is None:
+            hist = ws.history(x_T)
+        out = torch.empty_like(x_T)
+        with torch.cuda.device(x_T.device):
+            check(self.lib.ccn_sample_ms(self.h, z.data_ptr(), x_T.data_ptr(), out.data_ptr(), B, H, W, steps, ts.ctypes.data,
+                                         coef.ctypes.data, hist.data_ptr(), ws.ptr, ws.nbytes, current_stream(x_T.device),
+                                         1 if use_graph else 0))
+        return out
+
+    def sample_guided_ms(self, z: torch.Tensor, x_T: torch.Tensor, ts, coef, w: float, z_null: Optional[torch.Tensor] = None,
+                         use_graph: bool = True, slot: int = 0, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The multistep loop under classifier-free guidance of scale ``w`` (ccn_sample_guided_ms): ``sample_guided``'s plan and
+        workspace of batch 2B, ``coef`` and ``hist`` (of ONE state, ``x_T``'s size) as for ``sample_ms``."""
+        import math
+        z, x_T, ts, coef, steps = self._ms_args(z, x_T, ts, coef, hist)
+        B, C, H, W = x_T.shape
+        if not math.isfinite(float(w)):
+            raise ValueError(f"the guidance scale must be finite, got {w}")
+        if z_null is not None:
+            z_null = require_dev(z_null, "null_z")
+            if tuple(z_null.shape) != (self.z_dim,):
+                raise ValueError(f"null_z must be ({self.z_dim},), got {tuple(z_null.shape)}")
+        ws = self.workspace(2 * B, H, W, steps, slot)
+        if ws.eps is None:
+            ws.eps = torch.empty((2 * B, C, H, W), dtype=torch.float32, device=self.device)
+        if hist is None:
+            hist = ws.history(x_T)
+        out = torch.empty_like(x_T)
+        with torch.cuda.device(x_T.device):
+            check(self.lib.ccn_sample_guided_ms(self.h, z.data_ptr(), ptr(z_null), x_T.data_ptr(), out.data_ptr(), B, H, W, steps,
+                                                ts.ctypes.data, coef.ctypes.data, float(w), ws.eps.data_ptr(), hist.data_ptr(), ws.ptr,
+                                                ws.nbytes, current_stream(x_T.device), 1 if use_graph else 0))
         return out
 
     def resblock(self, prefix: str, x: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
@@ -648,6 +722,41 @@ def cfg_ddim_step(x: torch.Tensor, eps_c: torch.Tensor, eps_u: torch.Tensor, w: 
     with torch.cuda.device(x.device):
         check(lib.ccn_cfg_ddim_step(x.data_ptr(), ptr(x_dup), eps_c.data_ptr(), eps_u.data_ptr(), ptr(nz), float(w), float(coef[0]),
                                     float(coef[1]), float(coef[2]), float(coef[3]), float(sigma), x.numel(), current_stream(x.device)))
+    return x
+
+
+def _ms_check(x, hist, *eps):
+    x = require_dev(x, "x")
+    eps = [require_dev(e, "eps") for e in eps]
+    if not (isinstance(hist, torch.Tensor) and hist.is_cuda and hist.dtype == torch.float32 and hist.is_contiguous()):
+        raise ValueError("hist must be a contiguous fp32 HIP tensor (it is written in place)")
+    if hist.numel() != x.numel() or any(e.numel() != x.numel() for e in eps):
+        raise ValueError("x, hist and eps must hold the same number of elements")
+    return [x, hist] + eps
+
+
+def ms_step(x: torch.Tensor, hist: torch.Tensor, eps: torch.Tensor, coef: Sequence[float]) -> torch.Tensor:
+    """In-place multistep update of ``x`` (ccn_ms_step): ``coef`` = (c0, c1, c2, c3, c4); ``hist`` is read only when ``c4 != 0``
+    and then receives this step's clamped x0."""
+    lib = load_library()
+    x, hist, eps = _ms_check(x, hist, eps)
+    with torch.cuda.device(x.device):
+        check(lib.ccn_ms_step(x.data_ptr(), hist.data_ptr(), eps.data_ptr(), float(coef[0]), float(coef[1]), float(coef[2]),
+                              float(coef[3]), float(coef[4]), x.numel(), current_stream(x.device)))
+    return x
+
+
+def cfg_ms_step(x: torch.Tensor, hist: torch.Tensor, eps_c: torch.Tensor, eps_u: torch.Tensor, w: float, coef: Sequence[float],
+                x_dup: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``ms_step`` on the guided prediction ``eps_u + w * (eps_c - eps_u)``, one pass (ccn_cfg_ms_step); ``x_dup``, if given,
+    receives a copy of the new ``x``."""
+    lib = load_library()
+    x, hist, eps_c, eps_u = _ms_check(x, hist, eps_c, eps_u)
+    if x_dup is not None and not (x_dup.is_cuda and x_dup.dtype == torch.float32 and x_dup.is_contiguous() and x_dup.numel() == x.numel()):
+        raise ValueError("x_dup must be a contiguous fp32 HIP tensor of x's size")
+    with torch.cuda.device(x.device):
+        check(lib.ccn_cfg_ms_step(x.data_ptr(), ptr(x_dup), hist.data_ptr(), eps_c.data_ptr(), eps_u.data_ptr(), float(w), float(coef[0]),
+                                  float(coef[1]), float(coef[2]), float(coef[3]), float(coef[4]), x.numel(), current_stream(x.device)))
     return x
 
 

@@ -12,6 +12,7 @@ from ..io.bitstream import read_bitstream, decode_embedding
 from ..models.unet import CLIPCondUNet, infer_arch
 from ..diffusion.scheduler import NoiseScheduler
 from ..diffusion.ddim import DDIMSampler
+from ..diffusion.dpm_solver import DPMSolverSampler
 
 
 def pick_device(requested: str | None) -> str:
@@ -47,8 +48,20 @@ def build_model(weights: str, device: str, z_dim: int, dtype: str = "fp32") -> C
     return net
 
 
-def build_sampler(eta: float, device: str, guided: bool = False) -> DDIMSampler:
-    """``guided``: the sampler gives ``cfg_scale`` its meaning (classifier-free guidance against the zero embedding)."""
+def check_sampler_flags(sampler: str, eta: float) -> None:
+    """``--sampler dpmpp2m`` is deterministic: ``--eta > 0`` with it is an error (both CLIs call this right after parsing)."""
+    if sampler == "dpmpp2m" and eta > 0:
+        raise SystemExit("--sampler dpmpp2m is deterministic: --eta must be 0")
+
+
+def build_sampler(eta: float, device: str, guided: bool = False, sampler: str = "ddim", spacing: str = "logsnr"):
+    """``guided``: the sampler gives ``cfg_scale`` its meaning (classifier-free guidance against the zero embedding).
+    ``sampler="dpmpp2m"``: the second-order multistep solver on the ``spacing`` timestep table (deterministic: no ``eta``)."""
+    check_sampler_flags(sampler, eta)
+    if sampler == "dpmpp2m":
+        return DPMSolverSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), order=2, spacing=spacing, guided=guided)
+    if sampler != "ddim":
+        raise SystemExit(f"unknown sampler {sampler}")
     return DDIMSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), eta=eta, guided=guided)
 
 

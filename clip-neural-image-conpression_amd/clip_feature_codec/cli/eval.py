@@ -13,6 +13,8 @@ at a time on one device:
   the CPU-generator stream ``seed+i``); without it noise is unseeded like the reference;
 * originals are decoded / resized on host threads while the GPU samples;
 * ``--cfg_scale`` other than 1.0 samples under classifier-free guidance (the fused loop at twice the batch).
+* ``--sampler dpmpp2m`` samples with the second-order multistep solver (``diffusion/dpm_solver.py``) on the ``--spacing`` timestep
+  table; the default ``ddim`` is the reference's sampler, bit for bit.  ``--eta > 0`` with ``dpmpp2m`` is an error.
 """
 from __future__ import annotations
 
@@ -177,6 +179,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--cfg_scale", type=float, default=1.0,
                     help="classifier-free guidance scale w: eps = eps_u + w * (eps_c - eps_u), eps_u predicted from the zero embedding "
                          "(a checkpoint trained with z_drop); 1.0 (default): unguided, the reference's behaviour")
+    ap.add_argument("--sampler", choices=["ddim", "dpmpp2m"], default="ddim",
+                    help="ddim (default): the reference's first-order sampler; dpmpp2m: DPM-Solver++ 2M, second-order multistep, "
+                         "deterministic (an error with --eta > 0), the same one UNet evaluation per step")
+    ap.add_argument("--spacing", choices=["linspace", "logsnr"], default="logsnr",
+                    help="timestep table of --sampler dpmpp2m (read only then): uniform in log-SNR (may merge into fewer than "
+                         "--steps entries) or the reference's linspace")
     ap.add_argument("--timing", action="store_true", help="print set-up and loop wall time (records/s of the loop) to stderr")
     ap.add_argument("--workers", type=int, default=None, help="host threads for decode / metrics (default: this rank's share of the CPUs, 2..16)")
     ap.add_argument("--force-process-group", action="store_true",
@@ -190,6 +198,8 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
+    from ._common import check_sampler_flags
+    check_sampler_flags(args.sampler, args.eta)                    # (before any rank is started)
 
     from ..utils.launch import ensure_ranks, init_process_group, rank_env, single_rank_env
     if args.gpus is not None:
@@ -219,7 +229,7 @@ def main(argv=None) -> None:
     manifest = json.loads((store_dir / "manifest.json").read_text(encoding="utf-8"))
     scale, zero = load_codec_meta(store_dir)
     net = build_model(args.weights, device, scale.shape[0], args.dtype)
-    sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0)
+    sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0, sampler=args.sampler, spacing=args.spacing)
 
     def reconstruct(z: np.ndarray, x_T: Optional[torch.Tensor]) -> np.ndarray:
         zt = torch.from_numpy(z).to(device)

@@ -4,7 +4,8 @@ Same flags, defaults and output as the reference CLI (cli/reconstruct_diffusion.
 ``--store_dir --bitstream --weights --out --steps --eta --size --device``; prints ``Saved to <out>``;
 the PNG is written from ``((clamp(x,-1,1)+1)*127.5).astype(uint8)`` (truncation).  Additions that
 default to the reference behaviour: ``--seed`` (reproducible CPU-generated start noise; the reference
-never seeds), ``--dtype {fp32,bf16,f16x3}``, ``--cfg_scale`` (classifier-free guidance; 1.0 = off) and the architecture is read
+never seeds), ``--dtype {fp32,bf16,f16x3}``, ``--cfg_scale`` (classifier-free guidance; 1.0 = off), ``--sampler {ddim,dpmpp2m}`` with ``--spacing {linspace,logsnr}``
+(the second-order multistep solver of ``diffusion/dpm_solver.py``; default ``ddim``) and the architecture is read
 from the checkpoint's shapes.
 """
 from __future__ import annotations
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ._common import pick_device, load_codec_meta, load_embedding, build_model, build_sampler, start_noise
+from ._common import check_sampler_flags, pick_device, load_codec_meta, load_embedding, build_model, build_sampler, start_noise
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -34,17 +35,24 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--cfg_scale", type=float, default=1.0,
                     help="classifier-free guidance scale w: eps = eps_u + w * (eps_c - eps_u), eps_u predicted from the zero embedding "
                          "(a checkpoint trained with z_drop); 1.0 (default): unguided, the reference's behaviour")
+    ap.add_argument("--sampler", choices=["ddim", "dpmpp2m"], default="ddim",
+                    help="ddim (default): the reference's first-order sampler; dpmpp2m: DPM-Solver++ 2M, second-order multistep, "
+                         "deterministic (an error with --eta > 0), the same one UNet evaluation per step")
+    ap.add_argument("--spacing", choices=["linspace", "logsnr"], default="logsnr",
+                    help="timestep table of --sampler dpmpp2m (read only then): uniform in log-SNR (may merge into fewer than "
+                         "--steps entries) or the reference's linspace")
     return ap
 
 
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
+    check_sampler_flags(args.sampler, args.eta)
 
     device = pick_device(args.device)
     scale, zero = load_codec_meta(Path(args.store_dir))
     z = torch.from_numpy(load_embedding(Path(args.bitstream), scale, zero)).to(device)
     net = build_model(args.weights, device, z.shape[1], args.dtype)
-    sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0)
+    sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0, sampler=args.sampler, spacing=args.spacing)
     x_T = start_noise([0], args.size, args.seed)
     with torch.no_grad():
         x = sampler.sample(net, z, shape=(1, 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale,

@@ -1,0 +1,98 @@
+"""DPMSolverSampler: a second-order multistep sampler (DPM-Solver++ 2M, data-prediction form) on the MI355X path.
+
+No reference counterpart: the reference ships first-order DDIM only (``diffusion/ddim.py``).  The solver integrates the same
+probability-flow ODE as ``DDIMSampler(eta=0)`` and costs the same one UNet evaluation per step; it keeps the previous step's ``x0``
+prediction and adds one multiply-add per element, which lives in the head kernel's epilogue next to the DDIM update.
+
+Per step from ``t = ts[i]`` to ``u = ts[i+1]``, with ``a = sqrt(alpha_bar)``, ``s = sqrt(1 - alpha_bar)``, ``lambda = log(a/s)``,
+``h_i = lambda_u - lambda_t`` and ``r_i = h_(i-1) / h_i`` (``NoiseScheduler.solver_coefficients``)::
+
+    x0 = clamp((x - s_t e) / a_t, -1, 1)
+    x  = a_u x0 + s_u e                                  # == (s_u/s_t) x + a_u (1 - exp(-h)) x0 without the clamp
+    x += a_u (1 - exp(-h_i)) / (2 r_i) * (x0 - x0_prev)  # order 2, steps 0 < i < n-1
+
+Differences from ``DDIMSampler``, on purpose: the noise level after a step is that of the NEXT table entry (``alphas_cumprod[ts[i+1]]``,
+1.0 after the last step), not the reference's ``alphas_cumprod_prev[t]`` -- a multistep solver extrapolates across steps and needs the
+state at the noise level the model is told; and the default timestep table is uniform in ``lambda`` (``spacing="logsnr"``), the
+spacing the method is designed for.  Targets that snap to the same table timestep are merged, so the table may hold fewer than
+``steps`` entries (``NoiseScheduler.solver_timesteps``).  The first step and the last one (``h`` is infinite there) are first order.
+``order=1`` is the same loop without the correction term.  The sampler is deterministic: no ``eta``.
+
+Two routes as in ``DDIMSampler``: fused (``model.sample_ddim`` -> ``ccn_sample_ms`` / ``ccn_sample_guided_ms``, one captured graph)
+and stepwise for any callable ``model(x, z, t)`` (one model call per step, two when guided, then ``ccn_ms_step`` /
+``ccn_cfg_ms_step``).  ``guided=True`` with ``cfg_scale == 1.0`` takes the unguided route.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+
+from .. import _native
+
+_SPACINGS = ("logsnr", "linspace")
+
+
+class DPMSolverSampler:
+    """Deterministic DPM-Solver++ 2M (``order=2``) / its first-order form (``order=1``); ``guided=True``: classifier-free guidance."""
+
+    def __init__(self, scheduler, order: int = 2, spacing: str = "logsnr", guided: bool = False,
+                 null_z: Optional[torch.Tensor] = None) -> None:
+        if order not in (1, 2):
+            raise ValueError(f"order must be 1 or 2, got {order}")
+        if spacing not in _SPACINGS:
+            raise ValueError(f"Unknown spacing {spacing}")
+        self.sch = scheduler
+        self.order = order
+        self.spacing = spacing
+        self.guided = bool(guided)
+        self.null_z = null_z                 # (z_dim,), the embedding of the unconditional branch; None: zeros
+        self.use_graph = True
+
+    def tables(self, steps: int):
+        """(timesteps int32 (n,), coefficients fp32 (n, 5)) of a ``steps``-step run; ``n <= steps``."""
+        if steps < 2:
+            raise ValueError(f"a multistep sampler needs steps >= 2, got {steps}")
+        ts = self.sch.solver_timesteps(steps, self.spacing)
+        return ts, self.sch.solver_coefficients(ts, self.order)
+
+    def _guidance(self, z_clip: torch.Tensor, cfg_scale: float):
+        """(scale, null row on z_clip's device) of a guided call, or (None, None): unguided, or the scale is 1.0."""
+        if not self.guided:
+            return None, None
+        w = float(cfg_scale)
+        if not math.isfinite(w):
+            raise ValueError(f"cfg_scale must be finite, got {cfg_scale}")
+        null_z = self.null_z
+        if null_z is not None:
+            if not isinstance(null_z, torch.Tensor) or tuple(null_z.shape) != (z_clip.shape[-1],):
+                raise ValueError(f"null_z must be a tensor of shape ({z_clip.shape[-1]},), got {tuple(getattr(null_z, 'shape', ()))}")
+            null_z = null_z.to(z_clip.device, torch.float32)
+        return (None, None) if w == 1.0 else (w, null_z)
+
+    @torch.no_grad()
+    def sample(self, model, z_clip: torch.Tensor, shape: tuple, steps: int = 20, cfg_scale: float = 1.0,
+               x_T: Optional[torch.Tensor] = None, slot: int = 0) -> torch.Tensor:
+        ts, coef = self.tables(steps)
+        w, null_z = self._guidance(z_clip, cfg_scale)
+        device = z_clip.device
+        if device.type != "cuda":
+            raise RuntimeError(f"z_clip is on {device}: DPMSolverSampler (MI355X build) needs a HIP device; no CPU fallback")
+        x = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
+        if hasattr(model, "sample_ddim"):
+            guide = {} if w is None else dict(guidance=w, null_z=null_z)
+            return model.sample_ddim(z_clip, x, ts, coef[:, :4], use_graph=self.use_graph, slot=slot, c4=coef[:, 4], **guide)
+        x = _native.require_dev(x, "x_T").clone()
+        hist = torch.empty_like(x)
+        z_u = None
+        if w is not None:
+            z_u = (torch.zeros_like(z_clip[0]) if null_z is None else null_z).expand(shape[0], -1).contiguous()
+        for i in range(len(ts)):
+            t_b = torch.full((shape[0],), int(ts[i]), device=device, dtype=torch.long)
+            eps = model(x, z_clip, t_b)
+            if w is None:
+                _native.ms_step(x, hist, eps, coef[i])
+            else:
+                _native.cfg_ms_step(x, hist, eps, model(x, z_u, t_b), w, coef[i])
+        return x

@@ -83,6 +83,64 @@ class NoiseScheduler:
                        float(torch.sqrt(ab_s - sigma ** 2)), float(sigma))
         return rows
 
+    # -- multistep solver host-side tables (diffusion/dpm_solver.py; no reference counterpart) ----
+    def _log_snr(self) -> np.ndarray:
+        """lambda_t = log(sqrt(ab_t) / sqrt(1 - ab_t)) of every table timestep, float64 from the fp32 host tables."""
+        a = self.host["sqrt_alphas_cumprod"].numpy().astype(np.float64)
+        s = self.host["sqrt_one_minus_alphas_cumprod"].numpy().astype(np.float64)
+        return np.log(a) - np.log(s)
+
+    def solver_timesteps(self, steps: int, spacing: str = "logsnr") -> np.ndarray:
+        """The timestep table of ``DPMSolverSampler``, int32, strictly decreasing from ``T-1`` to ``0``.
+
+        ``spacing="linspace"``: the reference's table, ``ddim_timesteps(steps)``.  ``spacing="logsnr"``: ``steps`` targets uniform
+        in ``lambda = log(alpha/sigma)`` between ``lambda(T-1)`` and ``lambda(0)``, each snapped to the nearest table timestep;
+        targets that snap to the same timestep are merged, so the table may hold FEWER than ``steps`` entries (cosine schedule,
+        T = 1000: 40 requested give 29, 50 give 35 -- the cosine schedule's lambda is steep at both ends, where many targets fall
+        between two neighbouring timesteps)."""
+        if steps < 2:
+            raise ValueError(f"a multistep sampler needs steps >= 2, got {steps}")
+        if spacing == "linspace":
+            return self.ddim_timesteps(steps)
+        if spacing != "logsnr":
+            raise ValueError(f"Unknown spacing {spacing}")
+        lam = self._log_snr()                                   # strictly decreasing in t
+        targets = np.linspace(lam[-1], lam[0], steps)
+        inc = lam[::-1]                                         # increasing, index j <-> t = T-1-j
+        j = np.clip(np.searchsorted(inc, targets), 1, len(inc) - 1)
+        j = np.where(np.abs(inc[j - 1] - targets) <= np.abs(inc[j] - targets), j - 1, j)
+        ts = (len(lam) - 1 - j).astype(np.int64)
+        ts[0], ts[-1] = len(lam) - 1, 0
+        keep = np.concatenate([[True], ts[1:] < np.minimum.accumulate(ts)[:-1]])
+        return ts[keep].astype(np.int32)
+
+    def solver_coefficients(self, ts, order: int = 2) -> np.ndarray:
+        """(len(ts), 5) fp32 for ``ccn_sample_ms``: per step from ``t = ts[i]`` to ``u = ts[i+1]``, ``c0 = s_t, c1 = a_t, c2 = a_u,
+        c3 = s_u`` (``a = sqrt(ab)``, ``s = sqrt(1 - ab)``; 1, 0 on the last step) and, for ``order=2`` on the steps
+        ``0 < i < n-1``, ``c4 = a_u (1 - exp(-h_i)) / (2 r_i)`` with ``h_i = lambda_u - lambda_t``, ``r_i = h_(i-1) / h_i``; else 0.
+        Computed in float64 from the fp32 host tables, then rounded to fp32.  Unlike ``ddim_coefficients``, the noise level after
+        a step is that of the next table entry, not of ``t - 1``."""
+        if order not in (1, 2):
+            raise ValueError(f"order must be 1 or 2, got {order}")
+        ts = np.asarray(ts, dtype=np.int64)
+        n = int(ts.shape[0])
+        if ts.ndim != 1 or n < 2 or np.any(np.diff(ts) >= 0) or ts[0] >= self.timesteps or ts[-1] < 0:
+            raise ValueError("ts must be a strictly decreasing table of at least two timesteps")
+        a = self.host["sqrt_alphas_cumprod"].numpy().astype(np.float64)
+        s = self.host["sqrt_one_minus_alphas_cumprod"].numpy().astype(np.float64)
+        lam = self._log_snr()
+        rows = np.zeros((n, 5), np.float64)
+        for i in range(n):
+            t = ts[i]
+            last = i == n - 1
+            a_u, s_u = (1.0, 0.0) if last else (a[ts[i + 1]], s[ts[i + 1]])
+            rows[i, :4] = (s[t], a[t], a_u, s_u)
+            if order == 2 and 0 < i < n - 1:
+                h = lam[ts[i + 1]] - lam[t]
+                r = (lam[t] - lam[ts[i - 1]]) / h
+                rows[i, 4] = a_u * (-np.expm1(-h)) / (2.0 * r)
+        return rows.astype(np.float32)
+
     # -- per-element helpers --------------------------------------------------------------------
     def _gather(self, table: torch.Tensor, t: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
         return table.to(like.device)[t.to(like.device)].to(torch.float32).contiguous()

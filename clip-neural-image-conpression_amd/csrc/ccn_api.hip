@@ -93,6 +93,8 @@ struct StepCtx {
     float c[4] = {0, 0, 0, 0};
     const float* noise = nullptr;  // eta > 0: this step's noise tensor (sigma > 0), else null
     float sigma = 0.f;
+    float* x0_hist = nullptr;      // multistep sampler: the previous step's x0 (caller-owned, outside the workspace), else null
+    float c4 = 0.f;                // ... and its coefficient in this step's update
 };
 
 const char* kFamilies[] = {"conv3x3_s1_igemm", "conv3x3_s2_igemm", "convT4x4_s2_igemm", "stem_conv_igemm",
@@ -153,6 +155,8 @@ struct GraphEntry {
     bool guided = false;                 // ccn_sample_guided: the plan's batch is two halves, and each step ends in the combine launch
     float w = 0.f;                       // ... whose by-value guidance scale
     const float* eps = nullptr;          // ... and eps scratch address the graph was captured with
+    std::vector<float> c4;               // multistep sampler (empty: none): the fifth coefficient column
+    const float* hist = nullptr;         // ... and the x0 history address the graph was captured with
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     void destroy() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); }   // (after draining the device)
@@ -713,6 +717,7 @@ hipError_t launch(const ccn_handle_s* h, const ShapePlan& pl, const Launch& L, c
     if (cw.kind == KIND_HEAD) {
         k.x_state = c.x_state; k.eps_out = c.eps_out; k.do_ddim = c.do_ddim;
         k.c0 = c.c[0]; k.c1 = c.c[1]; k.c2 = c.c[2]; k.c3 = c.c[3]; k.noise = c.noise; k.sigma = c.sigma;
+        k.x0_hist = c.x0_hist; k.c4 = c.c4;
     }
     if (L.op == OP_HEAD2) return launch_head2(k, (const float2*)at(L.gn_ab), h->head_w_f32, at(L.scratch), c.step, s);
     const int v = c.step % cw.nphase;
@@ -838,9 +843,12 @@ int run_conditioning(ccn_handle_s* h, const Binding* b, hipStream_t s, const int
 // Classifier-free guidance (ccn_sample_guided): the plan's batch is 2B rows -- [0, B) carry z, [B, 2B) the null embedding, both the
 // same state -- the head writes eps of all 2B rows into `eps`, and one combine launch per step updates both halves of the state.
 struct Guide { const float* z_null; float w; float* eps; };
+// The multistep sampler (ccn_sample_ms, ccn_sample_guided_ms): per step the coefficient c4 of (x0 - previous x0), and the caller's
+// history tensor of one state (B rows, also when guided), which the updating launch of every step reads (c4 != 0) and rewrites.
+struct MultiStep { const float* c4; float* hist; };
 
 int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, int steps, const float* coef, const float* sigma = nullptr, const float* noise = nullptr,
-              const Guide* gd = nullptr)
+              const Guide* gd = nullptr, const MultiStep* ms = nullptr)
 {
     const ShapePlan& p = *b->plan;
     const size_t img = (size_t)(gd ? p.B / 2 : p.B) * h->cfg.img_ch * p.H * p.W;     // one state (and one step's draws)
@@ -854,9 +862,16 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, int steps, const
             c.x_state = xstate; c.eps_out = nullptr; c.do_ddim = 1;
             for (int k = 0; k < 4; ++k) c.c[k] = coef[i * 4 + k];
             if (noisy) { c.noise = noise + (size_t)i * img; c.sigma = sigma[i]; }
+            if (ms) { c.x0_hist = ms->hist; c.c4 = ms->c4[i]; }
         }
         if (int rc = run_ops(h, b, s, c)) return rc;
-        if (gd) {
+        if (gd && ms) {
+            const float* cf = coef + i * 4;
+            const float c4 = ms->c4[i];
+            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * (c4 != 0.f ? 7 : 6), s, [&] {
+                    return launch_cfg_ms_step(xstate, xstate + img, ms->hist, gd->eps, gd->eps + img, gd->w, cf[0], cf[1], cf[2], cf[3], c4,
+                                              (int64_t)img, s); })) return rc;
+        } else if (gd) {
             const float* cf = coef + i * 4;
             const float* nz = noisy ? noise + (size_t)i * img : nullptr;
             if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * (nz ? 6 : 5), s, [&] {
@@ -1130,7 +1145,8 @@ int ccn_forward(ccn_handle_t h, const float* x_dev, const float* z_dev, const in
 
 static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H, int32_t W,
                        int32_t steps, const int32_t* ts_host, const float* coef_host, const float* sigma_host, const float* noise_dev,
-                       void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph, const Guide* gd = nullptr)
+                       void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph, const Guide* gd = nullptr,
+                       const MultiStep* ms = nullptr)
 {
     int rc = check_ready(h);
     if (rc) return rc;
@@ -1169,16 +1185,19 @@ static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev,
                 !std::memcmp(g.coef.data(), coef_host, (size_t)steps * 16) && g.noise == noise_dev &&
                 g.sigma.size() == (sigma_host ? (size_t)steps : 0) &&
                 (!sigma_host || !std::memcmp(g.sigma.data(), sigma_host, (size_t)steps * 4)) &&
-                g.guided == (gd != nullptr) && (!gd || (g.w == gd->w && g.eps == gd->eps))) { ge = &g; break; }
+                g.guided == (gd != nullptr) && (!gd || (g.w == gd->w && g.eps == gd->eps)) &&
+                g.hist == (ms ? ms->hist : nullptr) && g.c4.size() == (ms ? (size_t)steps : 0) &&
+                (!ms || !std::memcmp(g.c4.data(), ms->c4, (size_t)steps * 4))) { ge = &g; break; }
         if (!ge) {
             GraphEntry g;
             g.steps = steps; g.ts.assign(ts_host, ts_host + steps); g.coef.assign(coef_host, coef_host + steps * 4);
             if (sigma_host) g.sigma.assign(sigma_host, sigma_host + steps);
             g.noise = noise_dev;
             if (gd) { g.guided = true; g.w = gd->w; g.eps = gd->eps; }
+            if (ms) { g.c4.assign(ms->c4, ms->c4 + steps); g.hist = ms->hist; }
             HIPCHK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeRelaxed));
             rc = run_conditioning(h, p, h->cap_stream, nullptr, steps, steps * PB, PB);
-            if (!rc) rc = run_steps(h, p, h->cap_stream, steps, coef_host, sigma_host, noise_dev, gd);
+            if (!rc) rc = run_steps(h, p, h->cap_stream, steps, coef_host, sigma_host, noise_dev, gd, ms);
             hipGraph_t graph = nullptr;
             const hipError_t ce = hipStreamEndCapture(h->cap_stream, &graph);
             if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -1202,7 +1221,7 @@ static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev,
         HIPCHK(hipGraphLaunch(ge->exec, s));
     } else {
         if ((rc = run_conditioning(h, p, s, nullptr, steps, steps * PB, PB))) return rc;
-        if ((rc = run_steps(h, p, s, steps, coef_host, sigma_host, noise_dev, gd))) return rc;
+        if ((rc = run_steps(h, p, s, steps, coef_host, sigma_host, noise_dev, gd, ms))) return rc;
     }
     if (x_out_dev != xstate) HIPCHK(hipMemcpyAsync(x_out_dev, xstate, img_bytes, hipMemcpyDeviceToDevice, s));
     return CCN_OK;
@@ -1234,6 +1253,64 @@ int ccn_sample_guided(ccn_handle_t h, const float* z_dev, const float* z_null_de
     const Guide gd{z_null_dev, w, eps_scratch_dev};
     return sample_impl(h, z_dev, x_T_dev, x_out_dev, B, H, W, steps, ts_host, coef_host, sigma_host, noise_dev, workspace_dev, workspace_bytes, stream,
                        use_graph, &gd);
+}
+
+// the [steps][5] table of the multistep entries -> the [steps][4] one of sample_impl and the c4 column, checked
+static int split_ms_table(int32_t steps, const float* coef_host, const float* x0_hist_dev, std::vector<float>& coef4, std::vector<float>& c4)
+{
+    if (!coef_host || steps <= 0) return fail(CCN_EINVAL, "null pointer");
+    if (!x0_hist_dev || ((uintptr_t)x0_hist_dev & 15)) return fail(CCN_EINVAL, "the x0 history must be non-null and 16-byte aligned");
+    coef4.resize((size_t)steps * 4); c4.resize((size_t)steps);
+    for (int i = 0; i < steps; ++i) {
+        for (int k = 0; k < 5; ++k)
+            if (!std::isfinite(coef_host[i * 5 + k])) return fail(CCN_EINVAL, "non-finite sampler coefficient");
+        for (int k = 0; k < 4; ++k) coef4[(size_t)i * 4 + k] = coef_host[i * 5 + k];
+        c4[i] = coef_host[i * 5 + 4];
+    }
+    if (c4[0] != 0.f) return fail(CCN_EINVAL, "c4 must be 0 on step 0: there is no x0 history yet");
+    return CCN_OK;
+}
+
+int ccn_sample_ms(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H, int32_t W, int32_t steps,
+                  const int32_t* ts_host, const float* coef_host, float* x0_hist_dev, void* workspace_dev, size_t workspace_bytes,
+                  void* stream, int32_t use_graph)
+{
+    std::vector<float> coef4, c4;
+    if (int rc = split_ms_table(steps, coef_host, x0_hist_dev, coef4, c4)) return rc;
+    const MultiStep ms{c4.data(), x0_hist_dev};
+    return sample_impl(h, z_dev, x_T_dev, x_out_dev, B, H, W, steps, ts_host, coef4.data(), nullptr, nullptr, workspace_dev, workspace_bytes, stream,
+                       use_graph, nullptr, &ms);
+}
+
+int ccn_sample_guided_ms(ccn_handle_t h, const float* z_dev, const float* z_null_dev, const float* x_T_dev, float* x_out_dev, int32_t B,
+                         int32_t H, int32_t W, int32_t steps, const int32_t* ts_host, const float* coef_host, float w, float* eps_scratch_dev,
+                         float* x0_hist_dev, void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph)
+{
+    if (!std::isfinite(w)) return fail(CCN_EINVAL, "the guidance scale must be finite");
+    if (!eps_scratch_dev || ((uintptr_t)eps_scratch_dev & 15)) return fail(CCN_EINVAL, "the eps scratch must be non-null and 16-byte aligned");
+    std::vector<float> coef4, c4;
+    if (int rc = split_ms_table(steps, coef_host, x0_hist_dev, coef4, c4)) return rc;
+    const Guide gd{z_null_dev, w, eps_scratch_dev};
+    const MultiStep ms{c4.data(), x0_hist_dev};
+    return sample_impl(h, z_dev, x_T_dev, x_out_dev, B, H, W, steps, ts_host, coef4.data(), nullptr, nullptr, workspace_dev, workspace_bytes, stream,
+                       use_graph, &gd, &ms);
+}
+
+int ccn_ms_step(float* x_dev, float* x0_hist_dev, const float* eps_dev, float c0, float c1, float c2, float c3, float c4, int64_t n, void* stream)
+{
+    if (!x_dev || !x0_hist_dev || !eps_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
+    if (n == 0) return CCN_OK;
+    HIPCHK(launch_ms_step(x_dev, x0_hist_dev, eps_dev, c0, c1, c2, c3, c4, n, (hipStream_t)stream));
+    return CCN_OK;
+}
+
+int ccn_cfg_ms_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* eps_c_dev, const float* eps_u_dev, float w,
+                    float c0, float c1, float c2, float c3, float c4, int64_t n, void* stream)
+{
+    if (!x_dev || !x0_hist_dev || !eps_c_dev || !eps_u_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
+    if (n == 0) return CCN_OK;
+    HIPCHK(launch_cfg_ms_step(x_dev, x_dup_dev, x0_hist_dev, eps_c_dev, eps_u_dev, w, c0, c1, c2, c3, c4, n, (hipStream_t)stream));
+    return CCN_OK;
 }
 
 int ccn_cfg_ddim_step(float* x_dev, float* x_dup_dev, const float* eps_c_dev, const float* eps_u_dev, const float* noise_dev, float w,

@@ -22,6 +22,21 @@ __device__ __forceinline__ unsigned pack_bf2(float a, float b) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));   // v_cvt_pk_bf16_f32, RNE
 }
 
+// ---- the sampler update of one element (DDIM, and DPM-Solver++ 2M on top of it) ---------------------------------------------------
+// Every op rounds to fp32 on its own, like the torch op sequence (diffusion/ddim.py:38-43):
+//     x0 = clamp((x - c0*e)/c1, -1, 1);  xn = c2*x0 + c3*e;  c4 != 0:  xn = xn + c4*(x0 - hist)
+// `hist` is the previous step's x0 and only enters when c4 != 0 (the caller does not read it otherwise: on step 0 it holds nothing);
+// the clamped x0 comes back through `x0_out`, the next step's history.  With c4 == 0 this is the DDIM update, bit for bit.
+__device__ __forceinline__ float sampler_update(float x, float e, float c0, float c1, float c2, float c3, float c4, float hist, float& x0_out)
+{
+    float x0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(c0, e)), c1);
+    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    float xn = __fadd_rn(__fmul_rn(c2, x0), __fmul_rn(c3, e));
+    if (c4 != 0.f) xn = __fadd_rn(xn, __fmul_rn(c4, __fsub_rn(x0, hist)));
+    x0_out = x0;
+    return xn;
+}
+
 template <typename T> __device__ __forceinline__ float silu_f(float v);
 template <> __device__ __forceinline__ float silu_f<float>(float v) { return v / (1.0f + expf(-v)); }
 template <> __device__ __forceinline__ float silu_f<__bf16>(float v) { return __fdividef(v, 1.0f + __expf(-v)); }

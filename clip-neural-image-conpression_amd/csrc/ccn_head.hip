@@ -177,12 +177,15 @@ __global__ __launch_bounds__(256, 4) void head_kernel(const ConvArgs a, const un
         const size_t idx = ((size_t)(b * Cout + co) * H + y) * W + x;
         if (a.eps_out) a.eps_out[idx] = e;
         if (a.do_ddim) {
-            // diffusion/ddim.py:38-43 -- every op rounds to fp32 separately, like the torch ops
+            // diffusion/ddim.py:38-43 -- every op rounds to fp32 separately, like the torch ops; x0_hist (multistep sampler): the
+            // previous step's x0 enters with c4 and this step's replaces it
             const float xs = a.x_state[idx];
-            float x0v = __fdiv_rn(__fsub_rn(xs, __fmul_rn(a.c0, e)), a.c1);
-            x0v = fminf(fmaxf(x0v, -1.0f), 1.0f);
-            float xn = __fadd_rn(__fmul_rn(a.c2, x0v), __fmul_rn(a.c3, e));
+            const float c4 = a.x0_hist ? a.c4 : 0.f;
+            const float hv = c4 != 0.f ? a.x0_hist[idx] : 0.f;
+            float x0v;
+            float xn = sampler_update(xs, e, a.c0, a.c1, a.c2, a.c3, c4, hv, x0v);
             if (a.noise) xn = __fadd_rn(xn, __fmul_rn(a.sigma, a.noise[idx]));      // eta > 0 (diffusion/ddim.py:44-45)
+            if (a.x0_hist) a.x0_hist[idx] = x0v;
             a.x_state[idx] = xn;
         }
     }

@@ -149,6 +149,9 @@ struct ConvArgs {
     // (last, so that no other field moves)
     int ops;                // operand form of the ws / fr kernels: 0 = the storage type's, 1 = f16x3 (fp32 storage, `w` in split rows)
     float wscale_inv;       // f16x3: 1 / (power-of-two scale of the packed weights), applied to the accumulator before the bias
+    float* x0_hist;         // head, multistep sampler: the previous step's clamped x0, NCHW fp32 like x_state; read when c4 != 0, then
+                            // overwritten with this step's; null = the plain DDIM update
+    float c4;               // head: coefficient of (x0 - x0_hist) in the update (sampler_update in ccn_device.h)
     __host__ __device__ int tapinfo_dy(int i) const { return (tapinfo[i] & 3) - 1; }
     __host__ __device__ int tapinfo_dx(int i) const { return ((tapinfo[i] >> 2) & 3) - 1; }
     __host__ __device__ int tapinfo_w(int i) const { return tapinfo[i] >> 4; }
@@ -263,6 +266,11 @@ hipError_t launch_ddim_step(float* x, const float* eps, const float* noise, floa
 // the guided update: e = eps_u + w*(eps_c - eps_u), launch_ddim_step's update on e; x_dup (nullable) receives a copy of the new x
 hipError_t launch_cfg_ddim_step(float* x, float* x_dup, const float* eps_c, const float* eps_u, const float* noise, float w,
                                 float c0, float c1, float c2, float c3, float sigma, int64_t n, hipStream_t s);
+// the multistep update (sampler_update in ccn_device.h) as its own pass: x in place, hist <- the clamped x0 (read only when c4 != 0);
+// the guided form combines e = eps_u + w*(eps_c - eps_u) first and copies the new x into x_dup (nullable)
+hipError_t launch_ms_step(float* x, float* hist, const float* eps, float c0, float c1, float c2, float c3, float c4, int64_t n, hipStream_t s);
+hipError_t launch_cfg_ms_step(float* x, float* x_dup, float* hist, const float* eps_c, const float* eps_u, float w, float c0, float c1,
+                              float c2, float c3, float c4, int64_t n, hipStream_t s);
 hipError_t launch_q_sample(float* out, const float* x0, const float* noise, const float* a, const float* sg,
                            int B, int64_t per, hipStream_t s);
 hipError_t launch_predict_x0(float* out, const float* xt, const float* eps, const float* a, const float* sg,

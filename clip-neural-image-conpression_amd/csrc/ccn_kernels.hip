@@ -226,12 +226,15 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a)
                     const size_t idx = ((size_t)(b * a.Cout + c) * a.Hout + my) * a.Wout + mx;
                     if (a.eps_out) a.eps_out[idx] = e;
                     if (a.do_ddim) {
-                        // diffusion/ddim.py:38-43 -- every op rounds to fp32 separately, like the torch ops
+                        // diffusion/ddim.py:38-43 -- every op rounds to fp32 separately, like the torch ops; x0_hist (multistep
+                        // sampler): the previous step's x0 enters with c4 and this step's replaces it
                         const float x = a.x_state[idx];
-                        float x0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(a.c0, e)), a.c1);
-                        x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-                        float xn = __fadd_rn(__fmul_rn(a.c2, x0), __fmul_rn(a.c3, e));
+                        const float c4 = a.x0_hist ? a.c4 : 0.f;
+                        const float hv = c4 != 0.f ? a.x0_hist[idx] : 0.f;
+                        float x0;
+                        float xn = sampler_update(x, e, a.c0, a.c1, a.c2, a.c3, c4, hv, x0);
                         if (a.noise) xn = __fadd_rn(xn, __fmul_rn(a.sigma, a.noise[idx]));      // eta > 0 (diffusion/ddim.py:44-45)
+                        if (a.x0_hist) a.x0_hist[idx] = x0;
                         a.x_state[idx] = xn;
                     }
                 }
@@ -875,6 +878,65 @@ hipError_t launch_cfg_ddim_step(float* x, float* x_dup, const float* eps_c, cons
     if (vec) hipLaunchKernelGGL(cfg_ddim_step_kernel<true>, dim3(grid), dim3(256), 0, s, x, x_dup, eps_c, eps_u, noise, w, c0, c1, c2, c3, sigma, n);
     else hipLaunchKernelGGL(cfg_ddim_step_kernel<false>, dim3(grid), dim3(256), 0, s, x, x_dup, eps_c, eps_u, noise, w, c0, c1, c2, c3, sigma, n);
     return hipGetLastError();
+}
+
+// The multistep update as its own pass (DPM-Solver++ 2M, data prediction; sampler_update in ccn_device.h): x in place, hist <- this
+// step's clamped x0; hist is read only when c4 != 0.  GUIDED: e = eps_u + w*(eps_c - eps_u) first (eps = eps_c), and x_dup (nullable)
+// receives a copy of the new x.  VEC as in cfg_ddim_step_kernel.
+template <bool VEC, bool GUIDED>
+__global__ void ms_step_kernel(float* __restrict__ x, float* __restrict__ x_dup, float* __restrict__ hist, const float* __restrict__ eps,
+                               const float* __restrict__ eps_u, float w, float c0, float c1, float c2, float c3, float c4, int64_t n)
+{
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n4 = VEC ? n / 4 : 0;
+    for (int64_t q = tid; q < n4; q += nthr) {
+        const float4 xv = ((const float4*)x)[q];
+        float4 ev = ((const float4*)eps)[q];
+        if (GUIDED) {
+            const float4 uv = ((const float4*)eps_u)[q];
+            ev.x = __fadd_rn(uv.x, __fmul_rn(w, __fsub_rn(ev.x, uv.x))); ev.y = __fadd_rn(uv.y, __fmul_rn(w, __fsub_rn(ev.y, uv.y)));
+            ev.z = __fadd_rn(uv.z, __fmul_rn(w, __fsub_rn(ev.z, uv.z))); ev.w = __fadd_rn(uv.w, __fmul_rn(w, __fsub_rn(ev.w, uv.w)));
+        }
+        float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), o, p;
+        if (c4 != 0.f) hv = ((const float4*)hist)[q];
+        o.x = sampler_update(xv.x, ev.x, c0, c1, c2, c3, c4, hv.x, p.x);
+        o.y = sampler_update(xv.y, ev.y, c0, c1, c2, c3, c4, hv.y, p.y);
+        o.z = sampler_update(xv.z, ev.z, c0, c1, c2, c3, c4, hv.z, p.z);
+        o.w = sampler_update(xv.w, ev.w, c0, c1, c2, c3, c4, hv.w, p.w);
+        ((float4*)hist)[q] = p;
+        ((float4*)x)[q] = o;
+        if (GUIDED && x_dup) ((float4*)x_dup)[q] = o;
+    }
+    for (int64_t i = n4 * 4 + tid; i < n; i += nthr) {
+        float e = eps[i];
+        if (GUIDED) { const float u = eps_u[i]; e = __fadd_rn(u, __fmul_rn(w, __fsub_rn(e, u))); }
+        const float hv = c4 != 0.f ? hist[i] : 0.f;
+        float p;
+        const float xn = sampler_update(x[i], e, c0, c1, c2, c3, c4, hv, p);
+        hist[i] = p;
+        x[i] = xn;
+        if (GUIDED && x_dup) x_dup[i] = xn;
+    }
+}
+template <bool GUIDED>
+static hipError_t launch_ms(float* x, float* x_dup, float* hist, const float* eps, const float* eps_u, float w, float c0, float c1, float c2,
+                            float c3, float c4, int64_t n, hipStream_t s)
+{
+    const bool vec = !(((uintptr_t)x | (uintptr_t)x_dup | (uintptr_t)hist | (uintptr_t)eps | (uintptr_t)eps_u) & 15);
+    const int64_t work = vec ? (n + 3) / 4 : n, blocks = (work + 255) / 256;
+    const int grid = (int)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);      // 256 CUs x 8 blocks, grid-stride beyond
+    if (vec) hipLaunchKernelGGL((ms_step_kernel<true, GUIDED>), dim3(grid), dim3(256), 0, s, x, x_dup, hist, eps, eps_u, w, c0, c1, c2, c3, c4, n);
+    else hipLaunchKernelGGL((ms_step_kernel<false, GUIDED>), dim3(grid), dim3(256), 0, s, x, x_dup, hist, eps, eps_u, w, c0, c1, c2, c3, c4, n);
+    return hipGetLastError();
+}
+hipError_t launch_ms_step(float* x, float* hist, const float* eps, float c0, float c1, float c2, float c3, float c4, int64_t n, hipStream_t s)
+{
+    return launch_ms<false>(x, nullptr, hist, eps, nullptr, 0.f, c0, c1, c2, c3, c4, n, s);
+}
+hipError_t launch_cfg_ms_step(float* x, float* x_dup, float* hist, const float* eps_c, const float* eps_u, float w, float c0, float c1,
+                              float c2, float c3, float c4, int64_t n, hipStream_t s)
+{
+    return launch_ms<true>(x, x_dup, hist, eps_c, eps_u, w, c0, c1, c2, c3, c4, n, s);
 }
 
 __global__ void q_sample_kernel(float* __restrict__ out, const float* __restrict__ x0, const float* __restrict__ noise,

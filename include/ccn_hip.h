@@ -167,6 +167,44 @@ int ccn_sample_guided(ccn_handle_t h, const float* z_dev, const float* z_null_de
 int ccn_cfg_ddim_step(float* x_dev, float* x_dup_dev, const float* eps_c_dev, const float* eps_u_dev, const float* noise_dev,
                       float w, float c0, float c1, float c2, float c3, float sigma, int64_t n, void* stream);
 
+/* A second-order multistep sampler, DPM-Solver++ 2M in its data-prediction form, deterministic, on the loop of ccn_sample.  (No
+ * reference counterpart: the reference ships first-order DDIM only.)
+ * coef_host[steps][5]: fp32 (c0..c3 as for ccn_sample, c4) per step; the head's update becomes
+ *     x0 = clamp((x - c0*eps)/c1, -1, 1);  x = c2*x0 + c3*eps;  c4 != 0:  x = x + c4*(x0 - hist);  hist = x0    -- every op rounded to fp32
+ * With a = sqrt(ab), s = sqrt(1 - ab), lambda = log(a/s), a step from t = ts[i] to u = ts[i+1], h_i = lambda_u - lambda_t and
+ * r_i = h_(i-1)/h_i:  c0 = s_t, c1 = a_t, c2 = a_u, c3 = s_u (1, 0 on the last step), c4 = a_u (1 - exp(-h_i)) / (2 r_i) on the
+ * steps 0 < i < steps-1, else 0.  Unlike DDIMSampler's table, ab_u is the noise level of the NEXT table entry.  With c4 == 0 on every
+ * step the loop computes what ccn_sample computes on coef_host[:, :4], bit for bit.
+ * x0_hist_dev: B*img_ch*H*W floats, 16-byte aligned, owned by the caller like the workspace (and outside it: ccn_workspace_bytes is
+ * unchanged), to be kept at the same address while a captured graph for it is cached; its contents on entry do not matter (it is
+ * not read while c4 == 0, and every step rewrites it).
+ * CCN_EINVAL: x0_hist_dev NULL or misaligned, a non-finite coefficient, c4 != 0 on step 0 (there is no history yet).
+ * The captured graph is cached with those of ccn_sample on the same workspace, per (table, c4 column, history address). */
+int ccn_sample_ms(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev,
+                  int32_t B, int32_t H, int32_t W, int32_t steps,
+                  const int32_t* ts_host, const float* coef_host, float* x0_hist_dev,
+                  void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph);
+
+/* The same sampler under classifier-free guidance: ccn_sample_guided's loop at batch 2B (eta = 0 only: no sigma, no noise), each step
+ * ending in one ccn_cfg_ms_step launch that writes the new state into both halves.  coef_host[steps][5] and the CCN_EINVAL cases as for
+ * ccn_sample_ms; x0_hist_dev holds ONE state, B*img_ch*H*W floats; workspace_dev and eps_scratch_dev as for ccn_sample_guided.
+ * The captured graph is cached per (table, c4 column, w, eps scratch address, history address). */
+int ccn_sample_guided_ms(ccn_handle_t h, const float* z_dev, const float* z_null_dev, const float* x_T_dev, float* x_out_dev,
+                         int32_t B, int32_t H, int32_t W, int32_t steps,
+                         const int32_t* ts_host, const float* coef_host,
+                         float w, float* eps_scratch_dev, float* x0_hist_dev,
+                         void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph);
+
+/* One multistep update outside the fused loop, the sequence above: in place on x_dev; x0_hist_dev is read only when c4 != 0 and
+ * then receives this step's clamped x0.  n elements each.  Four elements per lane when every pointer is 16-byte aligned, one otherwise. */
+int ccn_ms_step(float* x_dev, float* x0_hist_dev, const float* eps_dev,
+                float c0, float c1, float c2, float c3, float c4, int64_t n, void* stream);
+
+/* ... and its guided form: e = eps_u + w*(eps_c - eps_u), then the update on e; x_dup_dev (may be NULL) receives a copy of the new x
+ * (the second half of ccn_sample_guided_ms's state).  The eps inputs are not written. */
+int ccn_cfg_ms_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* eps_c_dev, const float* eps_u_dev,
+                    float w, float c0, float c1, float c2, float c3, float c4, int64_t n, void* stream);
+
 /* NoiseScheduler.q_sample (diffusion/scheduler.py:46-49): out[b] = a[b]*x0[b] + s[b]*noise[b];
  * a_dev/s_dev are the gathered per-sample coefficients, (B,) fp32; per_sample = C*H*W. */
 int ccn_q_sample(float* out_dev, const float* x0_dev, const float* noise_dev,
