@@ -53,6 +53,9 @@ SIGNATURES = {
     "ccn_cfg_ms_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_vp]),
     "ccn_q_sample": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp]),
     "ccn_predict_x0": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp]),
+    "ccn_score_scratch_bytes": (c_i32, [c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
+    "ccn_psnr_ssim_f32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "ccn_psnr_ssim_u8": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
     "ccn_film_forward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "ccn_resblock_forward": (c_i32, [c_vp, ctypes.c_char_p, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
     "ccn_timestep_embedding": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp]),
@@ -579,6 +582,51 @@ def diffusion_loss_grad(eps: torch.Tensor, noise: torch.Tensor, x_t: torch.Tenso
                                           B, C, H, W, float(recon_w), float(tv_w), terms.data_ptr(), ptr(d), scratch.data_ptr(),
                                           current_stream(eps.device)))
     return terms, d
+
+
+def score_scratch_bytes(B: int, C: int, H: int, W: int) -> int:
+    """Bytes of scratch ``psnr_ssim`` needs for the shape (host arithmetic only)."""
+    n = c_sz(0)
+    check(load_library().ccn_score_scratch_bytes(B, C, H, W, ctypes.byref(n)))
+    return int(n.value)
+
+
+def psnr_ssim(recon: torch.Tensor, orig_u8: torch.Tensor, recon_u8_out: Optional[torch.Tensor] = None, bufs=None) -> torch.Tensor:
+    """Per record the squared error of the two uint8 images and their SSIM (eval/metrics.py: ``psnr_u8``'s sum, ``_ssim_plane``
+    averaged over channels) as a (B,2) float64 device tensor ``[sse, ssim]``; never synchronises.  ``recon``: (B,C,H,W) fp32 in
+    [-1,1] (converted as ``_to_uint8`` does; ``recon_u8_out``, a uint8 tensor of that shape, receives the bytes) or uint8.
+    ``bufs``: optional preallocated ``(out, scratch)`` -- out (>= B,2) float64, scratch a uint8 tensor of at least
+    ``score_scratch_bytes`` bytes; with it no allocator is touched."""
+    lib = load_library()
+    if not isinstance(recon, torch.Tensor) or recon.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("recon must be a float32 or uint8 torch.Tensor")
+    recon = require_dev(recon, "recon", recon.dtype); orig_u8 = require_dev(orig_u8, "orig_u8", torch.uint8)
+    if recon.dim() != 4 or recon.shape != orig_u8.shape:
+        raise ValueError("recon and orig_u8 must be (B, C, H, W) tensors of one shape")
+    B, C, H, W = recon.shape
+    if recon_u8_out is not None:
+        if recon.dtype != torch.float32:
+            raise ValueError("recon_u8_out goes with an fp32 reconstruction")
+        if not (recon_u8_out.is_cuda and recon_u8_out.dtype == torch.uint8 and recon_u8_out.is_contiguous() and recon_u8_out.shape == recon.shape):
+            raise ValueError("recon_u8_out must be a contiguous uint8 HIP tensor of recon's shape")
+    if bufs is not None:
+        out, scratch = bufs
+        if not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 2 and out.shape[0] >= B):
+            raise ValueError("bufs[0] must be a contiguous (>= B, 2) float64 HIP tensor")
+        if not (scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous()):
+            raise ValueError("bufs[1] must be a contiguous uint8 HIP tensor")
+        out = out[:B]
+    else:
+        out = torch.empty((B, 2), dtype=torch.float64, device=recon.device)
+        scratch = torch.empty(score_scratch_bytes(B, C, H, W), dtype=torch.uint8, device=recon.device)
+    with torch.cuda.device(recon.device):
+        if recon.dtype == torch.float32:
+            check(lib.ccn_psnr_ssim_f32(recon.data_ptr(), orig_u8.data_ptr(), ptr(recon_u8_out), out.data_ptr(), B, C, H, W,
+                                        scratch.data_ptr(), scratch.numel(), current_stream(recon.device)))
+        else:
+            check(lib.ccn_psnr_ssim_u8(recon.data_ptr(), orig_u8.data_ptr(), out.data_ptr(), B, C, H, W, scratch.data_ptr(), scratch.numel(),
+                                       current_stream(recon.device)))
+    return out
 
 
 def _flat_buffers(p: torch.Tensor, typed: bool = False, **named: torch.Tensor) -> None:

@@ -15,6 +15,8 @@ at a time on one device:
 * ``--cfg_scale`` other than 1.0 samples under classifier-free guidance (the fused loop at twice the batch).
 * ``--sampler dpmpp2m`` samples with the second-order multistep solver (``diffusion/dpm_solver.py``) on the ``--spacing`` timestep
   table; the default ``ddim`` is the reference's sampler, bit for bit.  ``--eta > 0`` with ``dpmpp2m`` is an error.
+* ``--device_metrics`` (off by default) scores PSNR and SSIM on the GPU (``ccn_psnr_ssim_f32``): the originals go up as uint8, 16 bytes
+  per record come back, and no host thread scores anything.  Without the flag nothing differs from a build that lacks it.
 """
 from __future__ import annotations
 
@@ -103,9 +105,46 @@ def metric_row_u8(orig_u8: np.ndarray, recon_u8: np.ndarray) -> List[float]:
     return [psnr_u8(orig_u8, recon_u8), ssim_u8(orig_u8, recon_u8), float("nan"), float("nan")]
 
 
+class DeviceScorer:
+    """PSNR / SSIM of a batch on the GPU, for both routes of ``evaluate``.  Per slot (a batch in flight) it owns a pinned and a device
+    buffer for the uint8 originals, the kernel's output block and scratch, and a pinned block for the (b,2) float64 result, all sized
+    for a full batch once: a call allocates nothing.  ``enqueue`` puts upload, ``_native.psnr_ssim`` and the 16 bytes per record of
+    download on the CURRENT stream, behind the sampler's work; ``collect`` reads the block after the caller has waited for that
+    stream and turns the exact squared error into PSNR."""
+
+    def __init__(self, device: str, batch: int, channels: int, size: int, slots: int = 2) -> None:
+        from .. import _native
+        self._score = _native.psnr_ssim
+        shape = (batch, channels, size, size)
+        self.per_record = channels * size * size
+        nbytes = _native.score_scratch_bytes(*shape)
+        self.pin_orig = [torch.empty(shape, dtype=torch.uint8, pin_memory=True) for _ in range(slots)]
+        self.dev_orig = [torch.empty(shape, dtype=torch.uint8, device=device) for _ in range(slots)]
+        self.out = [torch.empty((batch, 2), dtype=torch.float64, device=device) for _ in range(slots)]
+        self.scratch = [torch.empty(nbytes, dtype=torch.uint8, device=device) for _ in range(slots)]
+        self.pin_out = [torch.empty((batch, 2), dtype=torch.float64, pin_memory=True) for _ in range(slots)]
+
+    def enqueue(self, x: torch.Tensor, orig_u8: np.ndarray, slot: int):
+        """``x``: the sampler's (b,3,S,S) fp32 output on the device (unclamped is fine: the conversion clips)."""
+        b = x.shape[0]
+        self.pin_orig[slot][:b].copy_(torch.from_numpy(orig_u8))
+        self.dev_orig[slot][:b].copy_(self.pin_orig[slot][:b], non_blocking=True)
+        out = self._score(x, self.dev_orig[slot][:b], bufs=(self.out[slot], self.scratch[slot]))
+        self.pin_out[slot][:b].copy_(out, non_blocking=True)
+        return slot, b
+
+    def collect(self, ticket) -> np.ndarray:
+        """(b,2) float64 ``[psnr, ssim]``; the stream ``enqueue`` ran on must have been waited for."""
+        from ..eval.metrics import psnr_from_sse
+        slot, b = ticket
+        block = self.pin_out[slot][:b].numpy().copy()              # the pinned block of this slot is reused two batches later
+        return np.stack([psnr_from_sse(block[:, 0], self.per_record), block[:, 1]], axis=1)
+
+
 def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstruct: Callable, size: int, batch: int,
              seed: Optional[int], rank: int, world: int, device: str, start_noise_fn: Callable, submit: Optional[Callable] = None,
-             fetch: Optional[Callable] = None, workers: Optional[int] = None, u8: bool = False, marks: Optional[list] = None) -> np.ndarray:
+             fetch: Optional[Callable] = None, workers: Optional[int] = None, u8: bool = False, marks: Optional[list] = None,
+             device_metrics: bool = False, learned: bool = False) -> np.ndarray:
     """Shard, reconstruct in batches, score on the host, gather.  ``reconstruct(z, x_T) -> (b,3,S,S)`` numpy in [-1,1].
 
     With ``submit(z, x_T, slot) -> handle`` / ``fetch(handle) -> numpy`` (the GPU path) two batches are kept in flight: batch k+1 is
@@ -114,7 +153,12 @@ def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstru
     decode, the per-record start noise, PSNR / SSIM -- runs on a pool of ``workers`` threads (numpy / scipy / PIL / torch release the
     GIL in their kernels), inputs prepared one batch AHEAD of the GPU and metrics collected only at the end, so the submitting
     thread never waits for host work.  ``u8``: ``fetch`` returns the reconstruction already converted to uint8 on the device
-    (a quarter of the D2H bytes; same arithmetic as ``_to_uint8``) and the originals are converted once."""
+    (a quarter of the D2H bytes; same arithmetic as ``_to_uint8``) and the originals are converted once.
+
+    ``device_metrics``: PSNR / SSIM come from the GPU (``DeviceScorer``).  ``submit`` / ``reconstruct`` then take the batch's uint8
+    originals, (b,3,S,S), as one more argument, and ``fetch`` / ``reconstruct`` return ``(scores, recon)``: the (b,2) float64
+    ``[psnr, ssim]`` block and, with ``learned`` (LPIPS / CLIP similarity can produce numbers here), the float reconstruction for
+    those two columns -- else ``None``, and no worker thread scores anything."""
     mine = shard_indices(len(manifest), rank, world)
     nw = workers or default_workers(world)
     batches = [mine[lo:lo + batch] for lo in range(0, len(mine), batch)]
@@ -123,8 +167,9 @@ def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstru
     with ThreadPoolExecutor(max_workers=nw) as pool:
         def prepare(idx):
             """Futures of one batch's inputs: originals (float or uint8), z rows, start-noise rows (None when unseeded)."""
-            load = original_u8 if u8 else load_original
+            load = original_u8 if u8 or device_metrics else load_original
             return dict(idx=idx,
+                        origf=[pool.submit(load_original, manifest[i]["image"], size) for i in idx] if device_metrics and learned else None,
                         orig=[pool.submit(load, manifest[i]["image"], size) for i in idx],
                         z=[pool.submit(z_of, manifest[i]) for i in idx],
                         noise=None if seed is None else [pool.submit(start_noise_fn, [i], size, seed) for i in idx])
@@ -134,7 +179,18 @@ def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstru
             x_T = None if p["noise"] is None else torch.cat([f.result() for f in p["noise"]], 0)
             return z, x_T
 
+        def learned_row(ps, of, r):
+            return [ps[0], ps[1], lpips_distance(of.result(), r, device=device), clip_similarity(of.result(), r, device=device)]
+
         def score(p, recon):
+            if device_metrics:
+                scores, recon = recon
+                for k in range(len(p["idx"])):
+                    if learned:
+                        rows_f.append(pool.submit(learned_row, scores[k], p["origf"][k], recon[k]))
+                    else:
+                        rows_f.append([scores[k, 0], scores[k, 1], float("nan"), float("nan")])
+                return
             for k, o in enumerate(p["orig"]):
                 if u8:
                     rows_f.append(pool.submit(lambda of, r: metric_row_u8(of.result(), r), o, recon[k]))
@@ -150,16 +206,18 @@ def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstru
             if marks is not None:
                 import time
                 marks.append((time.perf_counter(), sum(len(b) for b in batches[:bi])))   # (when batch bi is handed over, records before it)
+            # (device_metrics: the originals were decoded while the previous batch was sampled)
+            extra = (np.stack([f.result() for f in cur["orig"]], 0),) if device_metrics else ()
             if submit is not None and fetch is not None:
-                handle = submit(z, x_T, bi & 1)
+                handle = submit(z, x_T, bi & 1, *extra)
                 if pending is not None:
                     score(pending[1], fetch(pending[0]))
                 pending = (handle, cur)
             else:
-                score(cur, reconstruct(z, x_T))
+                score(cur, reconstruct(z, x_T, *extra))
         if pending is not None:
             score(pending[1], fetch(pending[0]))
-        rows = [f.result() for f in rows_f]
+        rows = [f.result() if hasattr(f, "result") else f for f in rows_f]
     local = np.asarray(rows, dtype=np.float64).reshape(len(mine), len(METRIC_KEYS))
     return gather_metric_rows(mine, local, len(manifest), device)
 
@@ -185,6 +243,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--spacing", choices=["linspace", "logsnr"], default="logsnr",
                     help="timestep table of --sampler dpmpp2m (read only then): uniform in log-SNR (may merge into fewer than "
                          "--steps entries) or the reference's linspace")
+    ap.add_argument("--device_metrics", action="store_true",
+                    help="score PSNR and SSIM on the GPU (one kernel on the sampler's output; the originals go up as uint8, 16 bytes per "
+                         "record come back) instead of on host threads; off by default")
     ap.add_argument("--timing", action="store_true", help="print set-up and loop wall time (records/s of the loop) to stderr")
     ap.add_argument("--workers", type=int, default=None, help="host threads for decode / metrics (default: this rank's share of the CPUs, 2..16)")
     ap.add_argument("--force-process-group", action="store_true",
@@ -231,11 +292,16 @@ def main(argv=None) -> None:
     net = build_model(args.weights, device, scale.shape[0], args.dtype)
     sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0, sampler=args.sampler, spacing=args.spacing)
 
-    def reconstruct(z: np.ndarray, x_T: Optional[torch.Tensor]) -> np.ndarray:
+    def reconstruct(z: np.ndarray, x_T: Optional[torch.Tensor], orig_u8: Optional[np.ndarray] = None):
         zt = torch.from_numpy(z).to(device)
         with torch.no_grad():
             x = sampler.sample(net, zt, shape=(zt.shape[0], 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale,
                                x_T=None if x_T is None else x_T.to(device))
+            if orig_u8 is not None:                                # --device_metrics on the sequential route
+                ticket = scorer.enqueue(x, orig_u8, 0)
+                recon = None if u8 else x.clamp(-1, 1).cpu().numpy()
+                torch.cuda.current_stream(device).synchronize()
+                return scorer.collect(ticket), recon
         return x.clamp(-1, 1).cpu().numpy()
 
     streams = [torch.cuda.Stream(device=device), torch.cuda.Stream(device=device)]
@@ -246,14 +312,27 @@ def main(argv=None) -> None:
     from ..eval.metrics import learned_metrics_available
     # LPIPS / CLIP similarity need the float images (and packages that are absent offline); without them only uint8 leaves the GPU
     u8 = not learned_metrics_available()
+    scorer = DeviceScorer(device, args.batch, 3, args.size) if args.device_metrics else None
 
-    def submit(z: np.ndarray, x_T: Optional[torch.Tensor], slot: int):
+    def submit(z: np.ndarray, x_T: Optional[torch.Tensor], slot: int, orig_u8: Optional[np.ndarray] = None):
         zt = torch.from_numpy(z).to(device)
         xt = None if x_T is None else x_T.to(device)
         st = streams[slot]
         st.wait_stream(torch.cuda.current_stream(device))
         with torch.no_grad(), torch.cuda.stream(st):
-            x = sampler.sample(net, zt, shape=(zt.shape[0], 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale, x_T=xt, slot=slot).clamp(-1, 1)
+            x = sampler.sample(net, zt, shape=(zt.shape[0], 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale, x_T=xt, slot=slot)
+            if orig_u8 is not None:                                # --device_metrics: only the (b,2) block returns, unless LPIPS / CLIP need floats
+                ticket = scorer.enqueue(x, orig_u8, slot)
+                host = None
+                if not u8:
+                    x = x.clamp(-1, 1)
+                    host = pinned.get((slot, tuple(x.shape), x.dtype))
+                    if host is None:
+                        host = pinned[(slot, tuple(x.shape), x.dtype)] = torch.empty(x.shape, dtype=x.dtype, pin_memory=True)
+                    host.copy_(x, non_blocking=True)
+                ev = torch.cuda.Event(); ev.record(st)
+                return host, ev, zt, xt, x, ticket
+            x = x.clamp(-1, 1)
             if u8:
                 # _to_uint8 (eval/metrics.py:16-19) on the device: the same two separately rounded fp32 ops, clip, truncation
                 x = ((x + 1.0) * 127.5).clamp(0, 255).to(torch.uint8)
@@ -268,6 +347,8 @@ def main(argv=None) -> None:
     def fetch(handle) -> np.ndarray:
         handle[1].synchronize()
         net.native().poll_errors()                                 # a device-side failure flagged during this batch raises here
+        if len(handle) > 5:                                        # --device_metrics
+            return scorer.collect(handle[5]), None if handle[0] is None else handle[0].numpy().copy()
         return handle[0].numpy().copy()                            # the pinned buffer of this slot is reused two batches later
 
     pipelined = args.eta == 0                                      # the fused sampler; eta > 0 draws noise step by step
@@ -276,7 +357,7 @@ def main(argv=None) -> None:
     rows = evaluate(manifest, lambda rec: load_embedding(Path(rec["bitstream"]), scale, zero), reconstruct,
                     args.size, args.batch, args.seed, rank, world, device, start_noise,
                     submit if pipelined else None, fetch if pipelined else None, workers=args.workers, u8=u8 and pipelined,
-                    marks=marks)
+                    marks=marks, device_metrics=args.device_metrics, learned=args.device_metrics and not u8)
     if args.timing and rank == 0:
         t_end = time.perf_counter()
         print(f"[eval] set-up {t_loop - t_start:.2f} s (checkpoint load + weight repack), loop {t_end - t_loop:.2f} s for {len(manifest)} records = "

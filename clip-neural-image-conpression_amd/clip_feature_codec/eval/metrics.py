@@ -28,6 +28,27 @@ def psnr_u8(x1: np.ndarray, x2: np.ndarray) -> float:
     return 20.0 * np.log10(255.0 / np.sqrt(mse))
 
 
+def psnr_from_sse(sse, n):
+    """PSNR (float64) from the sum of squared uint8 differences over ``n`` values: ``inf`` at 0, else 20 log10(255 / sqrt(sse / n)).
+    ``sse``: a number or an array."""
+    sse = np.asarray(sse, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        out = np.where(sse == 0, np.inf, 20.0 * np.log10(255.0 / np.sqrt(sse / float(n))))
+    return out if out.ndim else float(out)
+
+
+def psnr_ssim_device(recon, orig_u8):
+    """``(psnr, ssim)`` of a batch scored on the GPU (``_native.psnr_ssim``): numpy float64 (B,) arrays.  ``recon``: (B,C,H,W) fp32
+    in [-1, 1] or uint8, ``orig_u8``: (B,C,H,W) uint8; torch tensors (host ones are uploaded) or numpy arrays.  PSNR is ``psnr_u8``'s
+    with the mean taken exactly; SSIM is ``_ssim_plane`` averaged over the channels.  The one place that synchronises."""
+    import torch
+    from .. import _native
+    recon, orig_u8 = (torch.as_tensor(t) for t in (recon, orig_u8))
+    dev = recon.device if recon.is_cuda else (orig_u8.device if orig_u8.is_cuda else torch.device("cuda"))
+    block = _native.psnr_ssim(recon.to(dev), orig_u8.to(dev)).cpu().numpy()
+    return psnr_from_sse(block[:, 0], recon[0].numel()), block[:, 1].copy()
+
+
 def psnr(img1: np.ndarray, img2: np.ndarray) -> float:
     return psnr_u8(_to_uint8(img1), _to_uint8(img2))
 

@@ -214,6 +214,35 @@ int ccn_q_sample(float* out_dev, const float* x0_dev, const float* noise_dev,
 int ccn_predict_x0(float* out_dev, const float* x_t_dev, const float* eps_dev,
                    const float* a_dev, const float* s_dev, int32_t B, int64_t per_sample, void* stream);
 
+/* ---- reconstruction scores on the device (eval/metrics.py: _to_uint8, psnr_u8, _ssim_plane) ---- */
+
+/* Stateless like the optimiser tail: raw buffers, no handle, no allocation, never synchronises, capturable.
+ * Per record b the two launches (partials per workgroup, then one wave per record that adds them in index order) write
+ *     out_dev[b][0] = sum over C*H*W of (a - b)^2 on the two uint8 images, an exact integer (PSNR = 20 log10(255 / sqrt(sse / n)))
+ *     out_dev[b][1] = SSIM with skimage's defaults: 7 x 7 uniform window, sample covariance (49/48), K1 = 0.01, K2 = 0.03,
+ *                     data_range = 255, mean over the channels and over the (H-6) x (W-6) window positions inside the image
+ * as float64.  The window sums are exact integers, the quotient and the sums over positions are fp64 in a fixed order without
+ * atomics: results are bit-reproducible, do not depend on pointer alignment (16-byte accesses are used when W % 16 == 0 and the
+ * image pointers are 16-byte aligned, single-pixel accesses otherwise) nor on what else is in the batch.  Identical images give
+ * exactly 0 and 1.0.  H < 7 or W < 7: there is no window position, SSIM is NaN and the SSE is still produced.
+ * The fp32 reconstruction (NCHW, nominally in [-1, 1]; the sampler's unclamped output is fine) is converted as _to_uint8 does:
+ * (x + 1.0f) * 127.5f as two separately rounded fp32 operations, clipped to [0, 255], truncated -- byte for byte numpy's and
+ * torch's result on finite input.  Non-finite input is this build's choice: +inf gives 255, -inf gives 0, NaN gives 0.
+ * scratch_dev: at least ccn_score_scratch_bytes bytes (16 per workgroup; it depends on the tiling, hence the query), 8-byte aligned.
+ * CCN_EINVAL: a NULL buffer (recon_u8_out_dev may be NULL), a non-positive dimension, scratch too small or not 8-byte aligned,
+ * recon_dev not 4-byte aligned. */
+int ccn_score_scratch_bytes(int32_t B, int32_t C, int32_t H, int32_t W, size_t* bytes);
+
+/* recon_dev (B,C,H,W) fp32; orig_u8_dev (B,C,H,W) uint8; recon_u8_out_dev: NULL, or (B,C,H,W) uint8 that receives the converted
+ * reconstruction; out_dev (B,2) float64, 8-byte aligned. */
+int ccn_psnr_ssim_f32(const float* recon_dev, const uint8_t* orig_u8_dev, uint8_t* recon_u8_out_dev, double* out_dev,
+                      int32_t B, int32_t C, int32_t H, int32_t W, void* scratch_dev, size_t scratch_bytes, void* stream);
+
+/* The same for a reconstruction that is already uint8 (two stored images, or the bytes ccn_psnr_ssim_f32 wrote): the same kernel
+ * without the conversion, the same bits in out_dev. */
+int ccn_psnr_ssim_u8(const uint8_t* recon_u8_dev, const uint8_t* orig_u8_dev, double* out_dev,
+                     int32_t B, int32_t C, int32_t H, int32_t W, void* scratch_dev, size_t scratch_bytes, void* stream);
+
 /* ---- operator-level entry points (what the reference's unit tests exercise) ------------------ */
 
 /* FiLM.forward (models/blocks.py:22-25) with explicit parameters: y = x*(1 + Ws h + bs) + (Wh h + bh).
