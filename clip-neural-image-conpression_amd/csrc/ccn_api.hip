@@ -124,6 +124,7 @@ struct RouteRec {
     std::string name;          // the activation it writes: <block>.film (conv1), <block> (conv2), down.N, up.N, in_conv; out = head
     int kind = 0;
     const char* kernel = "";   // conv_kernel_name(conv_kernel_for(...)), or head2
+    const char* geom = nullptr; // persistent kernel: the fixed-geometry instantiation launch_conv_pr picks (conv_pr_geom_name), or null
     int th = 0, ksplit = 1, n_nt = 1;
     const char* gn = "none";   // input GroupNorm: none, prologue (finalize launch + conv prologue), instat (in-kernel statistics),
                                // preact / preact_fused (GroupNorm + SiLU pass in front), weights (head2: folded into the weights)
@@ -551,6 +552,8 @@ struct PlanBuilder {
             out.prod = (int)pl.ops.size();
         }
         L.part = out.part;
+        if (conv_kernel_for(cw.kind, cw.BN, a) == CK_PR)
+            pl.routes.back().geom = conv_pr_geom_name(a, o.res != nullptr, o.film_off >= 0, L.gs_part != kNone ? 1 : (gn_ab != kNone ? 0 : 2));
         const double macs = (double)B * g.Hout * g.Wout * cw.Cout * (double)(cw.kind == KIND_CT4 ? 4 : 9) * cw.Cin;
         L.flops = 2.0 * macs;
         L.bytes = ((double)B * in.H * in.W * cw.Cin + (double)B * g.Hout * g.Wout * cw.Cout + (o.res ? (double)B * g.Hout * g.Wout * cw.Cout : 0.0)
@@ -911,13 +914,14 @@ int copy_report(const std::string& text, char* buf, size_t cap)
     return (int)text.size();
 }
 
-std::string routes_text(const ShapePlan& pl)
+// instantiations = true: the kernel word of a launch that runs a fixed-geometry instantiation is that instantiation's name ("pr:...")
+std::string routes_text(const ShapePlan& pl, bool instantiations = false)
 {
     static const char* kinds[] = {"C3S1", "C3S2", "CT4", "STEM", "HEAD"};
     std::string text;
     for (const RouteRec& r : pl.routes) {
         char line[256];
-        std::snprintf(line, sizeof(line), "%s %s %s th=%d ksplit=%d n_nt=%d gn=%s film=%d res=%d", r.name.c_str(), kinds[r.kind], r.kernel,
+        std::snprintf(line, sizeof(line), "%s %s %s th=%d ksplit=%d n_nt=%d gn=%s film=%d res=%d", r.name.c_str(), kinds[r.kind], instantiations && r.geom ? r.geom : r.kernel,
                       r.th, r.ksplit, r.n_nt, r.gn, r.film ? 1 : 0, r.res ? 1 : 0);
         text += std::string(line) + (r.ops < 0 ? "" : r.ops ? " ops=f16x3" : " ops=f32") + "\n";
     }
@@ -1437,6 +1441,20 @@ extern "C" int ccn_internal_plan_routes_of(ccn_handle_t h, int32_t B, int32_t H,
     const ShapePlan* pl;
     if (!h || !h->committed || shape_plan(h, B, H, W, steps, &pl)) return -1;
     return copy_report(routes_text(*pl), buf, cap);
+}
+// The route report with the kernel word of every launch that runs a fixed-geometry instantiation of the persistent kernel replaced by
+// that instantiation's name ("pr:c3.128x128.film", ...; plain "pr" = the run-time instantiation).  A report of its own: the lines of
+// ccn_internal_plan_routes are compared with the parent commit's (tests/golden/infer_plan_parent.json) and stay what they were.
+extern "C" int ccn_internal_plan_kernels(ccn_handle_t h, char* buf, size_t cap)
+{
+    if (!h || h->bindings.empty()) return -1;
+    return copy_report(routes_text(*h->bindings.back()->plan, true), buf, cap);
+}
+extern "C" int ccn_internal_plan_kernels_of(ccn_handle_t h, int32_t B, int32_t H, int32_t W, int32_t steps, char* buf, size_t cap)
+{
+    const ShapePlan* pl;
+    if (!h || !h->committed || shape_plan(h, B, H, W, steps, &pl)) return -1;
+    return copy_report(routes_text(*pl, true), buf, cap);
 }
 extern "C" int ccn_internal_plan_layout(ccn_handle_t h, int32_t B, int32_t H, int32_t W, int32_t steps, char* buf, size_t cap)
 {

@@ -59,6 +59,51 @@ template <int TH_> struct PrLdsT {
 typedef PrLdsT<8> PrLds;
 static_assert(PrLds::TOTAL <= 160 * 1024, "LDS budget");
 
+// ---- launch geometry as a compile-time parameter (conv_pr_kernel's GEO) ------------------------------------------------
+// The kernel reads every geometry value of its launch through PrGeo<GEO>: GEO = void is the run-time form (the value comes from
+// ConvArgs, exactly as before), GEO = PrGeom<..> one fixed layer shape whose values are constants -- address arithmetic and tile
+// decodes fold, the magic-number divisions become shifts, and the SGPRs that carried the values (and their spills) go away.
+// Batch, pointers, the contents of bias / FiLM, the error word and the split-K fields stay run-time in both forms; so do "the output
+// feeds a GroupNorm" (a.part) and the producers' priority (a.prod_first): as constants neither measured faster (docs/EXPERIMENTS.md R18).
+#define CCN_PR_GEOM_INTS(X) \
+    X(Hin) X(Win) X(Cin) X(Hout) X(Wout) X(Cout) X(Cout_pad) X(MH) X(MW) X(nchunk) X(n_nt) X(n_tx) X(n_ty) X(cpg) X(G) X(nslot) \
+    X(gs_nsp) X(gs_nnt) X(gs_bn) X(gs_cpg) X(film_bstride)
+template <class GEO> struct PrGeo {
+    static constexpr bool FIXED = true;
+#define X(f) static __host__ __device__ __forceinline__ constexpr int f(const ConvArgs&) { return GEO::f; }
+    CCN_PR_GEOM_INTS(X)
+#undef X
+    static __device__ __forceinline__ constexpr bool film(const ConvArgs&) { return GEO::HAS_FILM; }
+};
+template <> struct PrGeo<void> {
+    static constexpr bool FIXED = false;
+#define X(f) static __host__ __device__ __forceinline__ int f(const ConvArgs& a) { return a.f; }
+    CCN_PR_GEOM_INTS(X)
+#undef X
+    static __device__ __forceinline__ bool film(const ConvArgs& a) { return a.film != nullptr; }
+};
+// One layer shape.  FORM: 9 = 3x3 stride 1, 2 = 3x3 stride 2 (five plane passes per channel chunk), 4 = ConvTranspose (four parities);
+// TH the tile rows; H, W, CIN the input, COUT the output channels (both multiples of the chunk / N tile: no padding); GSNSP x GSNNT the
+// partial-sum layout of the input's GroupNorm (in-kernel statistics only); FBS the batch stride of the FiLM rows (FiLM only).
+// Everything else follows as conv_geom / ConvRoute::fill derive it (launch_conv_pr compares every value before it picks one).
+template <int FORM, int TH_, int H, int W, int CIN, int COUT, bool FILM, int GSNSP = 1, int GSNNT = 1, int FBS = 0>
+struct PrGeom {
+    static constexpr int Hin = H, Win = W, Cin = CIN, Cout = COUT, Cout_pad = COUT;
+    static constexpr int Hout = FORM == 2 ? H / 2 : (FORM == 4 ? H * 2 : H), Wout = FORM == 2 ? W / 2 : (FORM == 4 ? W * 2 : W);
+    static constexpr int MH = FORM == 4 ? H : Hout, MW = FORM == 4 ? W : Wout, npar = FORM == 4 ? 4 : 1;
+    static constexpr int nchunk = CIN / 64 * (FORM == 2 ? 5 : 1);
+    static constexpr int n_nt = COUT / 128, n_tx = (MW + 31) / 32, n_ty = (MH + TH_ - 1) / TH_;
+    static constexpr int G = 8, cpg = COUT / 8, nslot = n_ty * n_tx * npar * n_nt;
+    static constexpr int gs_nsp = GSNSP, gs_nnt = GSNNT, gs_bn = 128, gs_cpg = CIN / 8;
+    static constexpr int film_bstride = FBS;
+    static constexpr bool HAS_FILM = FILM;
+    static_assert(H % 2 == 0 && W % 2 == 0 && CIN % 64 == 0 && COUT % 128 == 0 && (COUT / 8) % 8 == 0, "unpadded shapes only");
+};
+// x / d for a launch-constant divisor: the magic multiply of CCN_FDIV (magic number `m` of ConvArgs), or a plain division by the constant
+#define CCN_GDIV(x, m, d) (PrGeo<GEO>::FIXED ? (int)((unsigned)(x) / (unsigned)(d)) : CCN_FDIV(x, a.m, d))
+// geometry value `f` of this launch
+#define CCN_GV(f) (PrGeo<GEO>::f(a))
+
 }  // namespace
 
 // MODE 1 (RES): the epilogue adds the residual tensor and ignores FiLM (ResBlock conv2, ConvTranspose + skip); MODE 0: bias /
@@ -80,7 +125,7 @@ static_assert(PrLds::TOTAL <= 160 * 1024, "LDS budget");
 // kernel's partial sums (a.gs_part), 2 none (the input is already activated, or the form has no GroupNorm: ConvTranspose, stride 2).
 // P4 (NTAPS == 4 only): the 4x4 stride-2 pad-1 convolution (the data gradient of the ConvTranspose, training) as FOUR plane passes per
 // channel chunk with 2x2 taps each -- the ConvTranspose form's consumers on the stride-2 form's staging; see the pass table below.
-template <int NTAPS, int D, int MODE, int TH = 8, int GS = 0, bool P4 = false>
+template <int NTAPS, int D, int MODE, int TH = 8, int GS = 0, bool P4 = false, class GEO = void>
 __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const int grid_tiles)
 {
     static_assert(TH == 8 || (TH == 4 && NTAPS == 9), "4-row tiles: 3x3 stride-1 form only");
@@ -132,7 +177,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
     const int ks = (MODE == 2 && a.ksplit == 2) ? 2 : 1;
     // XCD this workgroup runs on: HW_REG_XCC_ID (id 20), bits [3:0] -- only the split-K hand-off uses it
     const unsigned xcc_id = MODE == 2 ? (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20) : 0u;
-    const int nck = a.nchunk / ks;                             // chunks per virtual tile
+    const int nck = CCN_GV(nchunk) / ks;                         // chunks per virtual tile
     const int ktotal = my_tiles * nck;
     auto vt_tile = [&](int v) __attribute__((always_inline)) { return ks == 2 ? (v >> 1) : v; };
     auto vt_kh = [&](int v) __attribute__((always_inline)) { return ks == 2 ? (v & 1) : 0; };
@@ -177,7 +222,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
     const int o16 = etid & 15, pr = etid >> 4;
     unsigned char* const outb = (unsigned char*)a.out;
     const unsigned char* const resb = (const unsigned char*)a.res;
-    const unsigned out_bytes = (unsigned)((size_t)a.B * a.Hout * a.Wout * a.Cout * sizeof(T));
+    const unsigned out_bytes = (unsigned)((size_t)a.B * CCN_GV(Hout) * CCN_GV(Wout) * CCN_GV(Cout) * sizeof(T));
     // per-wave channel sums of an epilogue, behind the staging tile
     float* const chs = (float*)(stg + L::STG_BYTES) + ew * 256;
     constexpr int NQ = TH / 2;               // epilogue batches of 4 items (two tile rows each)
@@ -194,30 +239,30 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
     // laundered copy of e_base: otherwise the 16 offsets are computed once per tile and kept live across dump() and the barrier
     auto item_off = [&](unsigned eb, int it) __attribute__((always_inline)) -> unsigned {
         const unsigned rmask = (it >> 1) < e_rows ? 0u : OOB;                 // wave-uniform
-        return (eb + (unsigned)(it >> 1) * (unsigned)(OSC * a.Wout * a.Cout * (int)sizeof(T)) + (unsigned)((it & 1) * 16) * (unsigned)(OSC * a.Cout * (int)sizeof(T)))
+        return (eb + (unsigned)(it >> 1) * (unsigned)(OSC * CCN_GV(Wout) * CCN_GV(Cout) * (int)sizeof(T)) + (unsigned)((it & 1) * 16) * (unsigned)(OSC * CCN_GV(Cout) * (int)sizeof(T)))
                | ((it & 1) ? e_m1 : e_m0) | rmask;
     };
     // during the tile's last chunk: decode the tile
     auto epi_setup = [&](int v) __attribute__((always_inline)) {
         const int tile = vt_tile(v);
         e_kh = vt_kh(v); e_tile = tile;
-        const int t2 = CCN_FDIV(tile, a.fd_nt, a.n_nt);
-        e_nt = tile - t2 * a.n_nt;
+        const int t2 = CCN_GDIV(tile, fd_nt, CCN_GV(n_nt));
+        e_nt = tile - t2 * CCN_GV(n_nt);
         e_par = t2 % NPARC;
         const int sp = t2 / NPARC;
         {
-            const int row = CCN_FDIV(sp, a.fd_tx, a.n_tx);                    // (b, ty) row of tiles
-            e_tx = sp - row * a.n_tx;
-            e_b = CCN_FDIV(sp, a.fd_sp, a.n_tx * a.n_ty);
-            e_ty = row - e_b * a.n_ty;
+            const int row = CCN_GDIV(sp, fd_tx, CCN_GV(n_tx));                    // (b, ty) row of tiles
+            e_tx = sp - row * CCN_GV(n_tx);
+            e_b = CCN_GDIV(sp, fd_sp, CCN_GV(n_tx) * CCN_GV(n_ty));
+            e_ty = row - e_b * CCN_GV(n_ty);
         }
         const int nb = e_nt * BN + o16 * 8;
-        const bool nvalid = nb < a.Cout;
+        const bool nvalid = nb < CCN_GV(Cout);
         // output pixel of M-space pixel (my, mx): (my*OS + py, mx*OS + px) -- OS = 2 and 4 parities for the ConvTranspose
-        e_base = (unsigned)(((e_b * a.Hout + e_ty * TH * OSC + (e_par >> 1)) * a.Wout + (e_tx * 32 + pr) * OSC + (e_par & 1)) * a.Cout + nb) * (unsigned)sizeof(T);
-        e_rows = a.MH - e_ty * TH;
-        e_m0 = (nvalid && e_tx * 32 + pr < a.MW) ? 0u : OOB;
-        e_m1 = (nvalid && e_tx * 32 + pr + 16 < a.MW) ? 0u : OOB;
+        e_base = (unsigned)(((e_b * CCN_GV(Hout) + e_ty * TH * OSC + (e_par >> 1)) * CCN_GV(Wout) + (e_tx * 32 + pr) * OSC + (e_par & 1)) * CCN_GV(Cout) + nb) * (unsigned)sizeof(T);
+        e_rows = CCN_GV(MH) - e_ty * TH;
+        e_m0 = (nvalid && e_tx * 32 + pr < CCN_GV(MW)) ? 0u : OOB;
+        e_m1 = (nvalid && e_tx * 32 + pr + 16 < CCN_GV(MW)) ? 0u : OOB;
     };
     // residual source of the current epilogue: the residual tensor, or (second K half) the first half's partial tile
     auto res_on = [&]() __attribute__((always_inline)) -> bool { return RES || (MODE == 2 && ks == 2 && e_kh == 1); };
@@ -272,13 +317,13 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
             asm volatile("" ::: "memory");
         }
         const int nb = e_nt * BN + o16 * 8;
-        const int nbs = nb < a.Cout ? nb : 0;
+        const int nbs = nb < CCN_GV(Cout) ? nb : 0;
         fb[0] = *(const f32x4*)(a.bias + nbs); fb[1] = *(const f32x4*)(a.bias + nbs + 4);
         if constexpr (!RES) {
-            if (a.film) {
-                const float* fp = a.film + (size_t)e_b * a.film_bstride;
+            if (PrGeo<GEO>::film(a)) {
+                const float* fp = a.film + (size_t)e_b * CCN_GV(film_bstride);
                 fs[0] = *(const f32x4*)(fp + nbs); fs[1] = *(const f32x4*)(fp + nbs + 4);
-                ft[0] = *(const f32x4*)(fp + a.Cout + nbs); ft[1] = *(const f32x4*)(fp + a.Cout + nbs + 4);
+                ft[0] = *(const f32x4*)(fp + CCN_GV(Cout) + nbs); ft[1] = *(const f32x4*)(fp + CCN_GV(Cout) + nbs + 4);
             }
         }
         res_batch(q0, rr[q0 & 1]);
@@ -298,7 +343,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
             f2[e] = second ? 0.f : fb[e >> 2][e & 3];
             if constexpr (!RES) {
                 f1[e] = 1.f;
-                if (a.film) { f1[e] = 1.0f + fs[e >> 2][e & 3]; f2[e] = second ? 0.f : fmaf(f2[e], f1[e], ft[e >> 2][e & 3]); }
+                if (PrGeo<GEO>::film(a)) { f1[e] = 1.0f + fs[e >> 2][e & 3]; f2[e] = second ? 0.f : fmaf(f2[e], f1[e], ft[e >> 2][e & 3]); }
             }
         }
         const auto osrd_c = __builtin_amdgcn_make_buffer_rsrc((void*)(first ? kpartb : outb), 0, out_bytes, 0x00020000);
@@ -367,7 +412,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
             }
             // the four waves' per-channel sums are combined into ONE slot per tile after the next workgroup barrier (combine())
             pd_on = true; pd_b = e_b; pd_n0 = e_nt * BN;
-            pd_slot = ((e_ty * a.n_tx + e_tx) * NPARC + e_par) * a.n_nt + e_nt;
+            pd_slot = ((e_ty * CCN_GV(n_tx) + e_tx) * NPARC + e_par) * CCN_GV(n_nt) + e_nt;
         }
     };
     // After the barrier that follows an epilogue: group sums over the four producer waves' per-channel sums, one slot per
@@ -379,11 +424,11 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
         pd_on = false;
         const float* const all = (const float*)(stg + L::STG_BYTES);
         const int n0 = pd_n0;
-        if (n0 >= a.Cout) return;
-        const int nend = min(n0 + BN, a.Cout);
-        const int g1 = CCN_FDIV(nend - 1, a.fd_cpg, a.cpg);
-        for (int g = CCN_FDIV(n0, a.fd_cpg, a.cpg) + ew; g <= g1; g += 4) {
-            const int clo = max(g * a.cpg, n0), chi = min((g + 1) * a.cpg, nend);
+        if (n0 >= CCN_GV(Cout)) return;
+        const int nend = min(n0 + BN, CCN_GV(Cout));
+        const int g1 = CCN_GDIV(nend - 1, fd_cpg, CCN_GV(cpg));
+        for (int g = CCN_GDIV(n0, fd_cpg, CCN_GV(cpg)) + ew; g <= g1; g += 4) {
+            const int clo = max(g * CCN_GV(cpg), n0), chi = min((g + 1) * CCN_GV(cpg), nend);
             float t1 = 0.f, t2 = 0.f;
             const float* const wa = all + (lane >> 4) * 256;
             for (int c = clo + (lane & 15); c < chi; c += 16) {
@@ -391,7 +436,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
             }
 #pragma unroll
             for (int m = 32; m >= 1; m >>= 1) { t1 += __shfl_xor(t1, m); t2 += __shfl_xor(t2, m); }
-            if (lane == 0) part_store(a.part + (size_t)(pd_b * a.G + g) * a.nslot + pd_slot, t1, t2);
+            if (lane == 0) part_store(a.part + (size_t)(pd_b * CCN_GV(G) + g) * CCN_GV(nslot) + pd_slot, t1, t2);
         }
     };
 
@@ -428,15 +473,15 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
         // branch-free: the eight loads leave back to back (a per-slot `if` made the compiler wait for each load in its own block,
         // eight serial round trips on the cold-start path); slots past the group's count read slot 0 and are masked in stats_reduce
         const int g = lane >> 3, sub = lane & 7;
-        const int cpg = a.gs_cpg, pnt = a.gs_nnt, nsp = a.gs_nsp;
-        const int jlo = CCN_FDIV(g * cpg, a.fd_gsbn, a.gs_bn), jhi = CCN_FDIV((g + 1) * cpg - 1, a.fd_gsbn, a.gs_bn), nj = jhi - jlo + 1;
+        const int cpg = CCN_GV(gs_cpg), pnt = CCN_GV(gs_nnt), nsp = CCN_GV(gs_nsp);
+        const int jlo = CCN_GDIV(g * cpg, fd_gsbn, CCN_GV(gs_bn)), jhi = CCN_GDIV((g + 1) * cpg - 1, fd_gsbn, CCN_GV(gs_bn)), nj = jhi - jlo + 1;
         const float2* const base = a.gs_part + (size_t)(b * 8 + g) * ((size_t)nsp * pnt) + jlo;   // nsp * nj <= 64 (host: conv_in_kernel_stats)
         int off[8];
         svmask = 0u;
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int e = sub + 8 * u;                                 // slot e = jj * nsp + sp
-            const int jj = CCN_FDIV(e, a.fd_gsnsp, nsp), sp = e - jj * nsp;
+            const int jj = CCN_GDIV(e, fd_gsnsp, nsp), sp = e - jj * nsp;
             const bool ok = jj < nj;
             off[u] = ok ? sp * pnt + jj : 0;
             svmask |= ok ? (1u << u) : 0u;
@@ -464,16 +509,16 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
         if (rq_c == 0) {                                       // new tile: decode it once, not once per chunk (the divisions are ~100 SALU ops)
             q_tv = rq_ti < my_tiles;
             const int tile = vt_tile(q_tv ? v : vt(0));
-            const int sp = CCN_FDIV(tile, a.fd_ntp, a.n_nt * NPARC);   // tile = ((spatial tile) * npar + parity) * n_nt + N tile
-            const int row = CCN_FDIV(sp, a.fd_tx, a.n_tx);
-            const int tx = sp - row * a.n_tx;
-            q_b = CCN_FDIV(sp, a.fd_sp, a.n_tx * a.n_ty);
-            const int ty = row - q_b * a.n_ty;
+            const int sp = CCN_GDIV(tile, fd_ntp, CCN_GV(n_nt) * NPARC);   // tile = ((spatial tile) * npar + parity) * n_nt + N tile
+            const int row = CCN_GDIV(sp, fd_tx, CCN_GV(n_tx));
+            const int tx = sp - row * CCN_GV(n_tx);
+            q_b = CCN_GDIV(sp, fd_sp, CCN_GV(n_tx) * CCN_GV(n_ty));
+            const int ty = row - q_b * CCN_GV(n_ty);
             q_iy0 = ty * TH - 1; q_ix0 = tx * 32 - 1;
         }
         q_c = vt_kh(v) * nck + rq_c;
         const int cb = (q_c / NPASS) * CKE + ck * EPC;
-        q_cv = q_tv && cb < a.Cin;
+        q_cv = q_tv && cb < CCN_GV(Cin);
         q_cbs = q_cv ? cb : 0;
         const bool fresh = gstat && rq_c == 0 && q_tv && q_b != st_b;  // wave-uniform: statistics of another sample needed
         if (++rq_c == nck) { rq_c = 0; ++rq_ti; }
@@ -483,11 +528,11 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
         if (gstat) {
             qn_g[0] = *(const f32x4*)(a.gs_gamma + q_cbs); qn_g[1] = *(const f32x4*)(a.gs_gamma + q_cbs + 4);
             qn_bt[0] = *(const f32x4*)(a.gs_beta + q_cbs); qn_bt[1] = *(const f32x4*)(a.gs_beta + q_cbs + 4);
-        } else gkn.load(a.gn_ab + (size_t)q_b * a.Cin + q_cbs, gn && q_cv);
+        } else gkn.load(a.gn_ab + (size_t)q_b * CCN_GV(Cin) + q_cbs, gn && q_cv);
     };
     auto coef_sel = [&]() __attribute__((always_inline)) {
         if (gstat) {
-            const int src = CCN_FDIV(q_cbs, a.fd_gscpg, a.gs_cpg) * 8; // a lane that holds the statistics of the channels' group
+            const int src = CCN_GDIV(q_cbs, fd_gscpg, CCN_GV(gs_cpg)) * 8; // a lane that holds the statistics of the channels' group
             qn_mean = __shfl(st_mean, src); qn_rstd = __shfl(st_rstd, src);
         }
     };
@@ -510,24 +555,24 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
         const int py = S2 ? (pass <= 2 ? 1 : 0) : (P4 ? (pass < 2 ? 1 : 0) : 0);                          // plane of this pass
         const int px = S2 ? ((pass <= 1 || pass == 3) ? 1 : 0) : (P4 ? ((pass & 1) ? 0 : 1) : 0);
         const int cb = cc * CKE + ck * EPC;
-        const bool cv = q_tv && cb < a.Cin;
+        const bool cv = q_tv && cb < CCN_GV(Cin);
         q_cv_i = cv;
         // The descriptor is WAVE-UNIFORM (a lane-dependent base makes the compiler wrap every load in a readfirstlane waterfall
         // loop) and covers exactly sample b from this chunk's channels on: halo rows above the image give negative = huge
         // unsigned offsets, rows below it run past num_records, so the hardware range check zero-fills both with no
         // per-row compare; only the column validity (and the channel tail) is per lane, ORed in as an out-of-range constant.
-        const unsigned img_bytes = (unsigned)(a.Hin * a.Win * a.Cin) * (unsigned)sizeof(T);
-        const unsigned coff = (unsigned)(((q_tv && cc * CKE < a.Cin) ? cc : 0) * CKE) * (unsigned)sizeof(T);
+        const unsigned img_bytes = (unsigned)(CCN_GV(Hin) * CCN_GV(Win) * CCN_GV(Cin)) * (unsigned)sizeof(T);
+        const unsigned coff = (unsigned)(((q_tv && cc * CKE < CCN_GV(Cin)) ? cc : 0) * CKE) * (unsigned)sizeof(T);
         const auto srd = __builtin_amdgcn_make_buffer_rsrc((void*)(inb + (size_t)b * img_bytes + coff), 0, img_bytes - coff, 0x00020000);
-        const int rs = IS * a.Win * a.Cin * (int)sizeof(T);                   // row stride of the staged plane in bytes
+        const int rs = IS * CCN_GV(Win) * CCN_GV(Cin) * (int)sizeof(T);                   // row stride of the staged plane in bytes
         const int ixr = IS * (ix0 + pcol) + px;                               // input column of this thread's halo column
-        colv = cv && ixr >= 0 && ixr < a.Win;
+        colv = cv && ixr >= 0 && ixr < CCN_GV(Win);
         const unsigned cmask = colv ? 0u : OOB;
-        const int base = ((IS * iy0 + py) * a.Win + ixr) * a.Cin * (int)sizeof(T) + ck * 16;
+        const int base = ((IS * iy0 + py) * CCN_GV(Win) + ixr) * CCN_GV(Cin) * (int)sizeof(T) + ck * 16;
         // halo rows inside the image: [r_lo, r_hi) (wave-uniform), as a bit mask for the padding-stays-zero select in dump()
         const int first = IS * iy0 + py;                                      // input row of halo row 0
         const int r_lo = first < 0 ? (-first + IS - 1) / IS : 0;
-        int r_hi = (a.Hin - first + IS - 1) / IS; r_hi = r_hi > HROWS ? HROWS : (r_hi < 0 ? 0 : r_hi);
+        int r_hi = (CCN_GV(Hin) - first + IS - 1) / IS; r_hi = r_hi > HROWS ? HROWS : (r_hi < 0 ? 0 : r_hi);
         rowm = q_tv ? (((1u << r_hi) - 1u) & ~((1u << r_lo) - 1u)) : 0u;
 #pragma unroll
         for (int i = 0; i < HROWS; ++i) {
@@ -536,8 +581,8 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
         }
         {
             const int iyr = IS * (iy0 + xrow) + py, ixx = IS * (ix0 + xcol) + px;
-            xv = xthr && cv && iyr >= 0 && iyr < a.Hin && ixx >= 0 && ixx < a.Win;
-            const int off = (iyr * a.Win + ixx) * a.Cin * (int)sizeof(T) + ck * 16;
+            xv = xthr && cv && iyr >= 0 && iyr < CCN_GV(Hin) && ixx >= 0 && ixx < CCN_GV(Win);
+            const int off = (iyr * CCN_GV(Win) + ixx) * CCN_GV(Cin) * (int)sizeof(T) + ck * 16;
             if (with_x) areg[HROWS] = __builtin_amdgcn_raw_buffer_load_b128(srd, (unsigned)off | (xv ? 0u : OOB), 0, 0);
         }
     };
@@ -655,13 +700,13 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
         constexpr int WIN = 6, PF = 4;                             // row-fragment window / prefetch distance (steps of <= 96 cycles)
         static_assert((NG * NSG) % WIN == 0, "static window indexing");
         f32x16 acc[TH];
-        const int n32 = a.Cout_pad / 32;
+        const int n32 = CCN_GV(Cout_pad) / 32;
         constexpr unsigned COLB = 36 * 1024;
-        const unsigned wtotal = (unsigned)((size_t)a.nchunk * n32 * COLB);
+        const unsigned wtotal = (unsigned)((size_t)CCN_GV(nchunk) * n32 * COLB);
         const auto wsrd = __builtin_amdgcn_make_buffer_rsrc((void*)a.wfrag, 0, wtotal, 0x00020000);
         const unsigned lane16 = (unsigned)lane * 16u;
         auto wbase_of = [&](int tile, int chunk) __attribute__((always_inline)) -> unsigned {
-            const int nt = tile - CCN_FDIV(tile, a.fd_nt, a.n_nt) * a.n_nt;
+            const int nt = tile - CCN_GDIV(tile, fd_nt, CCN_GV(n_nt)) * CCN_GV(n_nt);
             return (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(chunk * n32 + nt * 4 + wave) * COLB));
         };
         const int px16 = lane & 15, g4 = lane >> 4;
@@ -693,8 +738,8 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
         // Cout not a multiple of 128 (C4's 192-wide level): the last N tile is part padding.  Every tile of a workgroup has the same N
         // tile when the grid is a multiple of n_nt (tiles are visited with stride `grid`), so a consumer wave whose 32 channels are ALL
         // padding has nothing to compute in this launch: it only keeps the barrier protocol (the epilogue masks those channels anyway).
-        const bool idle_w = ks == 1 && grid % a.n_nt == 0 &&
-                            (vt_tile(vt(0)) - CCN_FDIV(vt_tile(vt(0)), a.fd_nt, a.n_nt) * a.n_nt) * BN + wave * 32 >= a.Cout;
+        const bool idle_w = ks == 1 && grid % CCN_GV(n_nt) == 0 &&
+                            (vt_tile(vt(0)) - CCN_GDIV(vt_tile(vt(0)), fd_nt, CCN_GV(n_nt)) * CCN_GV(n_nt)) * BN + wave * 32 >= CCN_GV(Cout);
         if (idle_w) { for (int kk = 0; kk < ktotal; ++kk) timed_barrier(); }
         else
         for (int ti = 0; ti < my_tiles; ++ti) {
@@ -783,15 +828,15 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
 #pragma unroll
     for (int i = 0; i < MF; ++i) prow[i] = ((wm * MF + i) + 1) * HPITCH + r + 1;
     // weight fragments: [chunk][Cout_pad/32][tap][kk][lane] x 16 B (host-packed); this wave owns columns nt*4 + wn*2 + {0,1}
-    const int n32 = a.Cout_pad / 32;
+    const int n32 = CCN_GV(Cout_pad) / 32;
     constexpr unsigned COLB = NSTEP * 1024;                        // bytes of one 32-channel column of one chunk
-    const unsigned wtotal = (unsigned)((size_t)NPARC * a.nchunk * n32 * COLB);
+    const unsigned wtotal = (unsigned)((size_t)NPARC * CCN_GV(nchunk) * n32 * COLB);
     const auto wsrd = __builtin_amdgcn_make_buffer_rsrc((void*)a.wfrag, 0, wtotal, 0x00020000);
     const unsigned lane16 = (unsigned)lane * 16u;
     auto wbase_of = [&](int tile, int chunk) __attribute__((always_inline)) -> unsigned {
-        const int t2 = CCN_FDIV(tile, a.fd_nt, a.n_nt);
-        const int nt = tile - t2 * a.n_nt, par = t2 % NPARC;               // ConvTranspose: [parity][chunk][column][tap][kk][lane]
-        return (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)((par * a.nchunk + chunk) * n32 + nt * 4 + wn * NF) * COLB));
+        const int t2 = CCN_GDIV(tile, fd_nt, CCN_GV(n_nt));
+        const int nt = tile - t2 * CCN_GV(n_nt), par = t2 % NPARC;               // ConvTranspose: [parity][chunk][column][tap][kk][lane]
+        return (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)((par * CCN_GV(nchunk) + chunk) * n32 + nt * 4 + wn * NF) * COLB));
     };
     u32x4 bq[D][NF];
     {
@@ -816,7 +861,7 @@ __global__ __launch_bounds__(512) void conv_pr_kernel(const ConvArgs a, const in
         const int tile = vt_tile(v), c0 = vt_kh(v) * nck;        // first chunk of this virtual tile
         int toffs[NTAPS], tdxs[NTAPS];                            // ConvTranspose: the parity's 2x2 taps (wave-uniform)
         if constexpr (NTAPS == 4 && !P4) {
-            const int par = CCN_FDIV(tile, a.fd_nt, a.n_nt) % NPARC;
+            const int par = CCN_GDIV(tile, fd_nt, CCN_GV(n_nt)) % NPARC;
 #pragma unroll
             for (int t = 0; t < NTAPS; ++t) { tdxs[t] = a.tapinfo_dx(par * 4 + t); toffs[t] = a.tapinfo_dy(par * 4 + t) * HPITCH + tdxs[t]; }
         }
@@ -931,6 +976,82 @@ static pr_fn_t pick_pr(int ntaps, int mode, int th = 8, int gs = 0)
     return mode == 1 ? (pr_fn_t)conv_pr_kernel<4, 8, 1> : (mode == 2 ? (pr_fn_t)conv_pr_kernel<4, 8, 2> : (pr_fn_t)conv_pr_kernel<4, 8, 0>);
 }
 
+// ---- fixed-geometry instantiations: the conv layers of the headline model (base 128, ch_mult (1,2,2), 256 px) ------------------
+// One row per (layer shape, launch form): the kernel with its geometry as constants, picked by EXACT match of every value the
+// instantiation fixes (pr_geom_match); any other launch runs the run-time instantiations of pick_pr.  The training step's
+// launches of the same shapes match the same rows.
+struct PrGeomRow {
+    const char* name; pr_fn_t fn;
+    int ntaps, mode, th, gs, npar;
+    bool film;
+#define X(f) int f;
+    CCN_PR_GEOM_INTS(X)
+#undef X
+};
+template <int FORM, int MODE, int TH, int GS, class GEO> static PrGeomRow pr_geom_row(const char* name)
+{
+    PrGeomRow r{};
+    r.name = name; r.fn = (pr_fn_t)conv_pr_kernel<FORM, FORM == 9 ? PR_D : 8, MODE, TH, GS, false, GEO>;
+    r.ntaps = FORM; r.mode = MODE; r.th = TH; r.gs = GS; r.npar = GEO::npar;
+    r.film = GEO::HAS_FILM;
+#define X(f) r.f = GEO::f;
+    CCN_PR_GEOM_INTS(X)
+#undef X
+    return r;
+}
+constexpr int PR_FBS = 7680;                                     // FiLM row of that model: 2 C per ResBlock (6 x 128, 4 x 256, 4 x 512 channels)
+static const std::vector<PrGeomRow>& pr_geom_rows()
+{
+    // 3x3 stride 1, per level: conv1 (FiLM), conv2 (residual)
+#define CCN_PR_C3(tag, TH, GS, HW, C, NSP, NNT) \
+    pr_geom_row<9, 0, TH, GS, PrGeom<9, TH, HW, HW, C, C, true, NSP, NNT, PR_FBS>>("pr:c3." tag ".film"), \
+    pr_geom_row<9, 1, TH, GS, PrGeom<9, TH, HW, HW, C, C, false, NSP, NNT>>("pr:c3." tag ".res")
+    static const std::vector<PrGeomRow> rows = {
+        CCN_PR_C3("128x256", 8, 0, 256, 128, 1, 1),              // scale / shift table (too many slots for in-kernel statistics)
+        CCN_PR_C3("128x128", 8, 1, 128, 128, 64, 1),
+        CCN_PR_C3("256x64", 8, 1, 64, 256, 16, 2),
+        CCN_PR_C3("512x32", 4, 1, 32, 512, 8, 4),
+        // the first conv of the 32-pixel level reads the sums of the split-K stride-2 conv (8-row tiles: 4 slots per N tile)
+        pr_geom_row<9, 0, 4, 1, PrGeom<9, 4, 32, 32, 512, 512, true, 4, 4, PR_FBS>>("pr:c3.512x32.film.s4"),
+#ifndef CCN_PR_NO_GEOM_S2CT
+        // stride 2 (the last one split-K) and ConvTranspose + skip (`make ab EXTRA=-DCCN_PR_NO_GEOM_S2CT`: without them, for A/B runs)
+        pr_geom_row<2, 0, 8, 2, PrGeom<2, 8, 256, 256, 128, 128, false>>("pr:s2.128x256"),
+        pr_geom_row<2, 0, 8, 2, PrGeom<2, 8, 128, 128, 128, 256, false>>("pr:s2.128x128"),
+        pr_geom_row<2, 2, 8, 2, PrGeom<2, 8, 64, 64, 256, 512, false>>("pr:s2.256x64.k2"),
+        pr_geom_row<4, 1, 8, 2, PrGeom<4, 8, 32, 32, 512, 256, false>>("pr:ct.512x32"),
+        pr_geom_row<4, 1, 8, 2, PrGeom<4, 8, 64, 64, 256, 128, false>>("pr:ct.256x64"),
+        pr_geom_row<4, 1, 8, 2, PrGeom<4, 8, 128, 128, 128, 128, false>>("pr:ct.128x128"),
+#endif
+    };
+#undef CCN_PR_C3
+    return rows;
+}
+
+// values an instantiation never reads: the partial-sum layout without in-kernel statistics, the FiLM stride without FiLM
+static bool pr_geom_unused(const char* f, int gs, bool film) { return (!strncmp(f, "gs_", 3) && gs != 1) || (!strcmp(f, "film_bstride") && !film); }
+
+// the fixed-geometry row of a launch, or null: a.ntaps / a.th as launch_conv_pr sees them, mode / gs as it derives them
+static const PrGeomRow* pr_geom_match(const ConvArgs& a, int mode, int gs, bool film)
+{
+    if (!conv_pr_geom_enabled()) return nullptr;
+    for (const PrGeomRow& r : pr_geom_rows()) {
+        if (r.ntaps != a.ntaps || r.mode != mode || r.th != a.th || r.gs != gs || r.npar != a.npar || r.film != film) continue;
+        if (a.Cin_pad != r.Cin || (mode == 2) != (a.ksplit == 2)) continue;
+        bool same = true;
+#define X(f) same = same && (r.f == a.f || pr_geom_unused(#f, gs, film));
+        CCN_PR_GEOM_INTS(X)
+#undef X
+        if (same) return &r;
+    }
+    return nullptr;
+}
+
+const char* conv_pr_geom_name(const ConvArgs& a, bool res, bool film, int gs)
+{
+    const PrGeomRow* r = pr_geom_match(a, res ? 1 : (a.ksplit == 2 ? 2 : 0), gs, film);
+    return r ? r->name : nullptr;
+}
+
 bool conv_pr_supported(int kind, int bn, int th)
 {
     return bn == 128 && (((kind == KIND_C3S1 || kind == KIND_CT4 || kind == KIND_C3S2) && th == 8) || (kind == KIND_C3S1 && th == 4));
@@ -958,6 +1079,10 @@ hipError_t conv_pr_prepare()
             e = hipFuncSetAttribute((const void*)pick_pr(9, mode, 4, gs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PrLdsT<4>::TOTAL);
             if (e != hipSuccess) return e;
         }
+    for (const PrGeomRow& r : pr_geom_rows()) {
+        e = hipFuncSetAttribute((const void*)r.fn, hipFuncAttributeMaxDynamicSharedMemorySize, r.th == 4 ? (int)PrLdsT<4>::TOTAL : (int)PrLds::TOTAL);
+        if (e != hipSuccess) return e;
+    }
     int dev = 0;
     e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -1022,7 +1147,9 @@ hipError_t launch_conv_pr(int dtype, const ConvArgs& a, hipStream_t s)
         d.stamps = g_stamps;
     } else d.stamps = nullptr;
     if (a.gs_part && !(c3 && ks == 1)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pick_pr(a.ntaps, a.res ? 1 : (ks == 2 ? 2 : 0), a.th, a.gs_part ? 1 : (a.gn_ab ? 0 : 2)), dim3((unsigned)grid), dim3(512),
+    const int mode = a.res ? 1 : (ks == 2 ? 2 : 0), gs = a.gs_part ? 1 : (a.gn_ab ? 0 : 2);
+    const PrGeomRow* const geom = d.stamps || d.dbg ? nullptr : pr_geom_match(a, mode, gs, a.film != nullptr);
+    hipLaunchKernelGGL(geom ? geom->fn : pick_pr(a.ntaps, mode, a.th, gs), dim3((unsigned)grid), dim3(512),
                        a.th == 4 ? PrLdsT<4>::TOTAL : PrLds::TOTAL, s, d, ntiles);
     return hipGetLastError();
 }

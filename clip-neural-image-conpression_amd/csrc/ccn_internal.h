@@ -181,6 +181,10 @@ hipError_t launch_conv_fr(int dtype, int bn, const ConvArgs& a, hipStream_t s);
 // epilogue; GroupNorm partial slots are per consumer wave: n_sp*2 spatial x n_nt*2 channel columns of 64
 bool conv_pr_supported(int kind, int bn, int th);
 bool conv_pr_selected(int dtype, int kind, int bn, int th);   // supported and chosen by the variant switch
+bool conv_pr_geom_enabled();                               // variant switch: fixed-geometry instantiations of the persistent kernel allowed
+// name of the fixed-geometry instantiation launch_conv_pr runs for these arguments (res / film: the pointers it will get;
+// gs: 0 scale / shift table, 1 in-kernel statistics, 2 no input GroupNorm), or null: the run-time instantiation
+const char* conv_pr_geom_name(const ConvArgs& a, bool res, bool film, int gs);
 hipError_t conv_pr_prepare();
 hipError_t launch_conv_pr(int dtype, const ConvArgs& a, hipStream_t s);
 

@@ -388,7 +388,8 @@ int conv_tile_rows(int kind, int bn, int B, int MH, int MW, int npar, int n_nt)
 }
 
 // 0 (or 1) ws everywhere, 2 free-running everywhere, 3 free-running on 8-row tiles, 4 (default) persistent
-// register-weight kernel where it applies, else as 3.  CCN_CONV_DMA overrides; tests switch it between handles.
+// register-weight kernel where it applies, else as 3; 5 = 4 without the fixed-geometry instantiations of that kernel (every launch
+// takes the run-time form).  CCN_CONV_DMA overrides; tests switch it between handles.
 static int g_conv_variant = -1;
 static int conv_variant()
 {
@@ -399,8 +400,9 @@ extern "C" int ccn_internal_set_conv_variant(int v) { const int old = conv_varia
 
 bool conv_pr_selected(int dtype, int kind, int bn, int th)
 {
-    return dtype == 1 && conv_ws_enabled() && conv_variant() == 4 && conv_pr_supported(kind, bn, th);
+    return dtype == 1 && conv_ws_enabled() && (conv_variant() == 4 || conv_variant() == 5) && conv_pr_supported(kind, bn, th);
 }
+bool conv_pr_geom_enabled() { return conv_variant() == 4; }
 
 ConvGeom conv_geom(int kind, bool four, int Hin, int Win, int th)
 {
