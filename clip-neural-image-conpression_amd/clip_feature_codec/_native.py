@@ -20,6 +20,9 @@ DTYPE_F32, DTYPE_BF16, DTYPE_F16X3 = 0, 1, 2
 _DTYPES = {"fp32": DTYPE_F32, "f32": DTYPE_F32, "float32": DTYPE_F32, "bf16": DTYPE_BF16, "bfloat16": DTYPE_BF16,
            "f16x3": DTYPE_F16X3}
 
+PRED_EPS, PRED_V = 0, 1
+_PREDICTIONS = {"eps": PRED_EPS, "v": PRED_V}
+
 c_i32, c_i64, c_f32, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
 
@@ -37,6 +40,8 @@ SIGNATURES = {
     "ccn_load_param": (c_i32, [c_vp, ctypes.c_char_p, c_vp, ctypes.POINTER(c_i64), c_i32]),
     "ccn_commit_params": (c_i32, [c_vp]),
     "ccn_set_weight_rounding": (c_i32, [c_vp, c_i32]),
+    "ccn_set_prediction": (c_i32, [c_vp, c_i32]),
+    "ccn_sampler_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, ctypes.POINTER(c_f32), c_f32, c_i64, c_vp]),
     "ccn_workspace_bytes": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
     "ccn_release_workspace": (c_i32, [c_vp, c_vp]),
     "ccn_forward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
@@ -80,6 +85,7 @@ SIGNATURES = {
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_i32, ctypes.POINTER(c_i32)]),
     "ccn_mse_loss_grad": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "ccn_diffusion_loss_grad": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "ccn_diffusion_loss_grad_v": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "ccn_adamw_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp]),
     "ccn_adamw_step_zero_grad": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp]),
     "ccn_step_guard_init": (c_i32, [c_vp, c_f32, c_i32, c_i32, c_i32, c_vp]),
@@ -122,6 +128,13 @@ def dtype_code(dtype) -> int:
     if isinstance(dtype, torch.dtype):
         dtype = {torch.float32: "fp32", torch.bfloat16: "bf16"}[dtype]
     return _DTYPES[str(dtype).lower()]
+
+
+def prediction_code(prediction) -> int:
+    """``"eps"`` / ``"v"`` -> CCN_PRED_EPS / CCN_PRED_V; anything else is a ``ValueError``."""
+    if not isinstance(prediction, str) or prediction not in _PREDICTIONS:
+        raise ValueError(f"Unknown prediction {prediction!r}: expected one of {sorted(_PREDICTIONS)}")
+    return _PREDICTIONS[prediction]
 
 
 def check(rc: int) -> None:
@@ -232,6 +245,11 @@ class NativeUNet:
                 check(self.lib.ccn_load_param(self.h, name.encode(), t.data_ptr(), shape, t.dim()))
             check(self.lib.ccn_commit_params(self.h))
         self._ws.clear()
+
+    def set_prediction(self, prediction: str) -> None:
+        """What the network output is to the ``sample*`` loops, ``"eps"`` (default) or ``"v"`` (ccn_set_prediction): handle state,
+        part of every captured graph's key.  ``forward`` is unaffected."""
+        check(self.lib.ccn_set_prediction(self.h, prediction_code(prediction)))
 
     # -- scratch -----------------------------------------------------------------------------
     def workspace(self, B: int, H: int, W: int, steps: int, slot: int = 0) -> Workspace:
@@ -584,6 +602,31 @@ def diffusion_loss_grad(eps: torch.Tensor, noise: torch.Tensor, x_t: torch.Tenso
     return terms, d
 
 
+def diffusion_loss_grad_v(v: torch.Tensor, noise: torch.Tensor, x_t: torch.Tensor, x0: torch.Tensor, a: torch.Tensor, s: torch.Tensor,
+                          recon_w: float, tv_w: float, want_grad: bool = True, bufs=None):
+    """The objective of a network that predicts ``v`` (ccn_diffusion_loss_grad_v): mse(v, a noise - s x0) + recon_w * l1(x0_pred, x0)
+    + tv_w * TV(x0_pred) with x0_pred = clamp(a x_t - s v, -1, 1), and its gradient with respect to ``v``.  Arguments, result and
+    ``bufs`` as for ``diffusion_loss_grad``; with both weights zero it is the v-MSE and ``x_t`` is not read."""
+    lib = load_library()
+    v = require_dev(v, "v"); noise = require_dev(noise, "noise"); x_t = require_dev(x_t, "x_t"); x0 = require_dev(x0, "x0")
+    a = require_dev(a, "a"); s = require_dev(s, "s")
+    if v.dim() != 4 or not (v.shape == noise.shape == x_t.shape == x0.shape):
+        raise ValueError("v, noise, x_t and x0 must be (B, C, H, W) tensors of one shape")
+    B, C, H, W = v.shape
+    if a.numel() != B or s.numel() != B:
+        raise ValueError("a and s must hold one coefficient per sample")
+    terms, d, scratch = (bufs if bufs is not None else (None, None, None))
+    if terms is None:
+        terms = torch.empty(4, dtype=torch.float32, device=v.device)
+        d = torch.empty_like(v) if want_grad else None
+        scratch = torch.empty(OBJECTIVE_SCRATCH_FLOATS, dtype=torch.float32, device=v.device)
+    with torch.cuda.device(v.device):
+        check(lib.ccn_diffusion_loss_grad_v(v.data_ptr(), noise.data_ptr(), x_t.data_ptr(), x0.data_ptr(), a.data_ptr(), s.data_ptr(),
+                                            B, C, H, W, float(recon_w), float(tv_w), terms.data_ptr(), ptr(d), scratch.data_ptr(),
+                                            current_stream(v.device)))
+    return terms, d
+
+
 def score_scratch_bytes(B: int, C: int, H: int, W: int) -> int:
     """Bytes of scratch ``psnr_ssim`` needs for the shape (host arithmetic only)."""
     n = c_sz(0)
@@ -805,6 +848,33 @@ def cfg_ms_step(x: torch.Tensor, hist: torch.Tensor, eps_c: torch.Tensor, eps_u:
     with torch.cuda.device(x.device):
         check(lib.ccn_cfg_ms_step(x.data_ptr(), ptr(x_dup), hist.data_ptr(), eps_c.data_ptr(), eps_u.data_ptr(), float(w), float(coef[0]),
                                   float(coef[1]), float(coef[2]), float(coef[3]), float(coef[4]), x.numel(), current_stream(x.device)))
+    return x
+
+
+def sampler_step(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], prediction: str = "eps", out_u: Optional[torch.Tensor] = None,
+                 w: float = 0.0, hist: Optional[torch.Tensor] = None, sigma: float = 0.0, noise: Optional[torch.Tensor] = None,
+                 x_dup: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One in-place sampler update of ``x`` for either parameterisation (ccn_sampler_step): ``out_c`` is the network output
+    (``prediction`` says whether it is eps or v), ``out_u`` the unconditional one of a guided step (the update then acts on
+    ``out_u + w * (out_c - out_u)``), ``coef`` = (c0, c1, c2, c3[, c4]), ``hist`` the multistep sampler's x0 history (read when
+    ``c4 != 0``, then rewritten), ``noise`` the eta > 0 draw added as ``sigma * noise``, ``x_dup`` a copy of the new ``x``."""
+    lib = load_library()
+    pred = prediction_code(prediction)
+    x = require_dev(x, "x"); out_c = require_dev(out_c, "out_c")
+    out_u = require_dev(out_u, "out_u") if out_u is not None else None
+    nz = require_dev(noise, "noise") if noise is not None else None
+    for name, tns in (("hist", hist), ("x_dup", x_dup)):
+        if tns is not None and not (isinstance(tns, torch.Tensor) and tns.is_cuda and tns.dtype == torch.float32 and tns.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous fp32 HIP tensor (it is written in place)")
+    if any(tns is not None and tns.numel() != x.numel() for tns in (out_c, out_u, nz, hist, x_dup)):
+        raise ValueError("x, the outputs, hist, noise and x_dup must hold the same number of elements")
+    c = [float(v) for v in coef]
+    if len(c) not in (4, 5) or (hist is not None and len(c) != 5):
+        raise ValueError("coef must be (c0, c1, c2, c3) or, with hist, (c0, c1, c2, c3, c4)")
+    c5 = (c_f32 * 5)(*(c + [0.0] * (5 - len(c))))
+    with torch.cuda.device(x.device):
+        check(lib.ccn_sampler_step(x.data_ptr(), ptr(x_dup), ptr(hist), out_c.data_ptr(), ptr(out_u), ptr(nz), pred, float(w), c5,
+                                   float(sigma), x.numel(), current_stream(x.device)))
     return x
 
 

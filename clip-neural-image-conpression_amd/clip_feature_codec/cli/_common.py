@@ -54,15 +54,17 @@ def check_sampler_flags(sampler: str, eta: float) -> None:
         raise SystemExit("--sampler dpmpp2m is deterministic: --eta must be 0")
 
 
-def build_sampler(eta: float, device: str, guided: bool = False, sampler: str = "ddim", spacing: str = "logsnr"):
+def build_sampler(eta: float, device: str, guided: bool = False, sampler: str = "ddim", spacing: str = "logsnr", prediction: str = "eps"):
     """``guided``: the sampler gives ``cfg_scale`` its meaning (classifier-free guidance against the zero embedding).
-    ``sampler="dpmpp2m"``: the second-order multistep solver on the ``spacing`` timestep table (deterministic: no ``eta``)."""
+    ``sampler="dpmpp2m"``: the second-order multistep solver on the ``spacing`` timestep table (deterministic: no ``eta``).
+    ``prediction``: ``"eps"`` or ``"v"``, how the checkpoint was trained."""
     check_sampler_flags(sampler, eta)
     if sampler == "dpmpp2m":
-        return DPMSolverSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), order=2, spacing=spacing, guided=guided)
+        return DPMSolverSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), order=2, spacing=spacing, guided=guided,
+                                prediction=prediction)
     if sampler != "ddim":
         raise SystemExit(f"unknown sampler {sampler}")
-    return DDIMSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), eta=eta, guided=guided)
+    return DDIMSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), eta=eta, guided=guided, prediction=prediction)
 
 
 def start_noise(indices: Sequence[int], size: int, seed: int | None, img_ch: int = 3) -> torch.Tensor | None:

@@ -243,6 +243,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--spacing", choices=["linspace", "logsnr"], default="logsnr",
                     help="timestep table of --sampler dpmpp2m (read only then): uniform in log-SNR (may merge into fewer than "
                          "--steps entries) or the reference's linspace")
+    ap.add_argument("--prediction", choices=["eps", "v"], default="eps",
+                    help="what the network predicts: eps (default, the reference's) or v = sqrt(ab) noise - sqrt(1-ab) x0; it must match how "
+                         "the checkpoint was trained (train_diffusion(prediction=)): the checkpoint itself does not say")
     ap.add_argument("--device_metrics", action="store_true",
                     help="score PSNR and SSIM on the GPU (one kernel on the sampler's output; the originals go up as uint8, 16 bytes per "
                          "record come back) instead of on host threads; off by default")
@@ -290,7 +293,8 @@ def main(argv=None) -> None:
     manifest = json.loads((store_dir / "manifest.json").read_text(encoding="utf-8"))
     scale, zero = load_codec_meta(store_dir)
     net = build_model(args.weights, device, scale.shape[0], args.dtype)
-    sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0, sampler=args.sampler, spacing=args.spacing)
+    sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0, sampler=args.sampler, spacing=args.spacing,
+                            prediction=args.prediction)
 
     def reconstruct(z: np.ndarray, x_T: Optional[torch.Tensor], orig_u8: Optional[np.ndarray] = None):
         zt = torch.from_numpy(z).to(device)

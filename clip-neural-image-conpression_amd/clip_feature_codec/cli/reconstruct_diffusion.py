@@ -38,6 +38,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sampler", choices=["ddim", "dpmpp2m"], default="ddim",
                     help="ddim (default): the reference's first-order sampler; dpmpp2m: DPM-Solver++ 2M, second-order multistep, "
                          "deterministic (an error with --eta > 0), the same one UNet evaluation per step")
+    ap.add_argument("--prediction", choices=["eps", "v"], default="eps",
+                    help="what the network predicts: eps (default, the reference's) or v = sqrt(ab) noise - sqrt(1-ab) x0; it must match how "
+                         "the checkpoint was trained (train_diffusion(prediction=)): the checkpoint itself does not say")
     ap.add_argument("--spacing", choices=["linspace", "logsnr"], default="logsnr",
                     help="timestep table of --sampler dpmpp2m (read only then): uniform in log-SNR (may merge into fewer than "
                          "--steps entries) or the reference's linspace")
@@ -52,7 +55,8 @@ def main(argv=None) -> None:
     scale, zero = load_codec_meta(Path(args.store_dir))
     z = torch.from_numpy(load_embedding(Path(args.bitstream), scale, zero)).to(device)
     net = build_model(args.weights, device, z.shape[1], args.dtype)
-    sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0, sampler=args.sampler, spacing=args.spacing)
+    sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0, sampler=args.sampler, spacing=args.spacing,
+                            prediction=args.prediction)
     x_T = start_noise([0], args.size, args.seed)
     with torch.no_grad():
         x = sampler.sample(net, z, shape=(1, 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale,

@@ -22,6 +22,12 @@ unguided route, same bits.  Otherwise the fused route is ``ccn_sample_guided`` -
 held twice, one combine-and-update launch per step; ``slot``, ``use_graph`` and the ``eta > 0`` draws (one set, shared by both
 halves) as above -- and the stepwise route calls ``model(x, z, t)`` and ``model(x, z_null, t)`` per step, then
 ``ccn_cfg_ddim_step``.  A non-finite ``cfg_scale`` or a ``null_z`` of another shape is a ``ValueError``.
+
+``DDIMSampler(..., prediction="v")`` (no reference counterpart; default ``"eps"``) is for a network trained to predict
+``v = sqrt(ab_t) noise - sqrt(1-ab_t) x0`` (``train_step(..., prediction="v")``): everything above that says ``eps`` then holds for the
+``eps`` derived from the output, ``x0 = clamp(a_t x - s_t v)``, ``eps = s_t x + a_t v``, on the SAME tables -- the fused route through
+``ccn_set_prediction``, the stepwise one through ``ccn_sampler_step``; guidance combines the two ``v`` outputs first.  It must match
+how the weights were trained; an unknown string is a ``ValueError``.
 """
 from __future__ import annotations
 
@@ -38,7 +44,10 @@ class DDIMSampler:
 
     MAX_NOISE_BUFFERS = 4
 
-    def __init__(self, scheduler, eta: float = 0.0, guided: bool = False, null_z: Optional[torch.Tensor] = None) -> None:
+    def __init__(self, scheduler, eta: float = 0.0, guided: bool = False, null_z: Optional[torch.Tensor] = None,
+                 prediction: str = "eps") -> None:
+        _native.prediction_code(prediction)  # ValueError for an unknown parameterisation
+        self.prediction = prediction
         self.sch = scheduler
         self.eta = eta
         self.guided = bool(guided)
@@ -72,6 +81,8 @@ class DDIMSampler:
         x = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
         if hasattr(model, "sample_ddim"):
             guide = {} if w is None else dict(guidance=w, null_z=null_z)
+            if self.prediction != "eps":
+                guide["prediction"] = self.prediction
             if self.eta == 0:
                 return model.sample_ddim(z_clip, x, ts, coef[:, :4], use_graph=self.use_graph, slot=slot, **guide)
             # eta > 0: every noisy step's draw up front, into a buffer kept per (shape, steps, slot) so that the captured graph
@@ -100,7 +111,9 @@ class DDIMSampler:
             eps_u = model(x, z_u, t_b) if w is not None else None
             sigma = float(coef[i, 4])
             noise = torch.randn_like(x) if (self.eta > 0 and sigma > 0) else None
-            if w is None:
+            if self.prediction != "eps":
+                _native.sampler_step(x, eps, coef[i, :4], self.prediction, out_u=eps_u, w=w or 0.0, sigma=sigma, noise=noise)
+            elif w is None:
                 _native.ddim_step(x, eps, coef[i, :4], sigma, noise)
             else:
                 _native.cfg_ddim_step(x, eps, eps_u, w, coef[i, :4], sigma, noise)

@@ -21,6 +21,10 @@ spacing the method is designed for.  Targets that snap to the same table timeste
 Two routes as in ``DDIMSampler``: fused (``model.sample_ddim`` -> ``ccn_sample_ms`` / ``ccn_sample_guided_ms``, one captured graph)
 and stepwise for any callable ``model(x, z, t)`` (one model call per step, two when guided, then ``ccn_ms_step`` /
 ``ccn_cfg_ms_step``).  ``guided=True`` with ``cfg_scale == 1.0`` takes the unguided route.
+
+``prediction="v"`` (default ``"eps"``): the network output is ``v = a_t noise - s_t x0``; the first line of the step becomes
+``x0 = clamp(a_t x - s_t v, -1, 1)``, ``e = s_t x + a_t v`` on the same tables, the rest is unchanged (``ccn_set_prediction`` on the
+fused route, ``ccn_sampler_step`` on the stepwise one).  It must match how the weights were trained.
 """
 from __future__ import annotations
 
@@ -38,7 +42,9 @@ class DPMSolverSampler:
     """Deterministic DPM-Solver++ 2M (``order=2``) / its first-order form (``order=1``); ``guided=True``: classifier-free guidance."""
 
     def __init__(self, scheduler, order: int = 2, spacing: str = "logsnr", guided: bool = False,
-                 null_z: Optional[torch.Tensor] = None) -> None:
+                 null_z: Optional[torch.Tensor] = None, prediction: str = "eps") -> None:
+        _native.prediction_code(prediction)  # ValueError for an unknown parameterisation
+        self.prediction = prediction
         if order not in (1, 2):
             raise ValueError(f"order must be 1 or 2, got {order}")
         if spacing not in _SPACINGS:
@@ -82,6 +88,8 @@ class DPMSolverSampler:
         x = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
         if hasattr(model, "sample_ddim"):
             guide = {} if w is None else dict(guidance=w, null_z=null_z)
+            if self.prediction != "eps":
+                guide["prediction"] = self.prediction
             return model.sample_ddim(z_clip, x, ts, coef[:, :4], use_graph=self.use_graph, slot=slot, c4=coef[:, 4], **guide)
         x = _native.require_dev(x, "x_T").clone()
         hist = torch.empty_like(x)
@@ -91,7 +99,9 @@ class DPMSolverSampler:
         for i in range(len(ts)):
             t_b = torch.full((shape[0],), int(ts[i]), device=device, dtype=torch.long)
             eps = model(x, z_clip, t_b)
-            if w is None:
+            if self.prediction != "eps":
+                _native.sampler_step(x, eps, coef[i], self.prediction, out_u=None if w is None else model(x, z_u, t_b), w=w or 0.0, hist=hist)
+            elif w is None:
                 _native.ms_step(x, hist, eps, coef[i])
             else:
                 _native.cfg_ms_step(x, hist, eps, model(x, z_u, t_b), w, coef[i])

@@ -154,3 +154,26 @@ class NoiseScheduler:
         """(x_t - sqrt(1-ab_t) eps) / sqrt(ab_t) (scheduler.py:51-55)."""
         return _native.predict_x0(x_t, eps_hat, self._gather(self.sqrt_alphas_cumprod, t, x_t),
                                   self._gather(self.sqrt_one_minus_alphas_cumprod, t, x_t))
+
+    # -- the v-parameterisation (no reference counterpart) --------------------------------------------
+    # Helpers for callers and tests, written in torch ops so that each of the three operations rounds to fp32 on its own, on
+    # whatever device the tensors live (the training step never calls them: ccn_diffusion_loss_grad_v forms the target in registers).
+    def _coef(self, t: torch.Tensor, like: torch.Tensor):
+        shape = (-1,) + (1,) * (like.dim() - 1)
+        return (self._gather(self.sqrt_alphas_cumprod, t, like).view(shape),
+                self._gather(self.sqrt_one_minus_alphas_cumprod, t, like).view(shape))
+
+    def v_target(self, x0: torch.Tensor, t: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+        """``v = sqrt(ab_t) noise - sqrt(1-ab_t) x0`` (Salimans & Ho 2022): two fp32 products and one subtraction."""
+        a, s = self._coef(t, x0)
+        return a * noise - s * x0
+
+    def predict_x0_from_v(self, x_t: torch.Tensor, t: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """``sqrt(ab_t) x_t - sqrt(1-ab_t) v``: no division, so it stays accurate where ``predict_x0_from_eps`` divides by 1.6e-5."""
+        a, s = self._coef(t, x_t)
+        return a * x_t - s * v
+
+    def predict_eps_from_v(self, x_t: torch.Tensor, t: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """``sqrt(1-ab_t) x_t + sqrt(ab_t) v``."""
+        a, s = self._coef(t, x_t)
+        return s * x_t + a * v

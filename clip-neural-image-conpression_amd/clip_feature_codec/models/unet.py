@@ -164,13 +164,16 @@ class CLIPCondUNet(nn.Module):
     @torch.no_grad()
     def sample_ddim(self, z_clip: torch.Tensor, x_T: torch.Tensor, ts: Sequence[int], coef: np.ndarray,
                     use_graph: bool = True, slot: int = 0, sigma=None, noise: Optional[torch.Tensor] = None,
-                    guidance: Optional[float] = None, null_z: Optional[torch.Tensor] = None, c4=None) -> torch.Tensor:
+                    guidance: Optional[float] = None, null_z: Optional[torch.Tensor] = None, c4=None,
+                    prediction: str = "eps") -> torch.Tensor:
         """All DDIM steps (eta = 0) inside the library; see ``ccn_sample`` in include/ccn_hip.h.  ``slot`` selects an independent
         workspace / captured graph, so that consecutive batches can be in flight on different streams.  ``guidance``: a
         classifier-free guidance scale; the loop then runs at batch 2B, the second half on ``null_z`` (``(z_dim,)``; None: zeros),
         see ``ccn_sample_guided``.  ``c4``: a fifth coefficient column ``(steps,)`` -- the loop is then the multistep sampler's
-        (``ccn_sample_ms`` / ``ccn_sample_guided_ms``, eta = 0 only; ``NoiseScheduler.solver_coefficients``)."""
+        (``ccn_sample_ms`` / ``ccn_sample_guided_ms``, eta = 0 only; ``NoiseScheduler.solver_coefficients``).  ``prediction``: what
+        this network's output is, ``"eps"`` or ``"v"`` (``ccn_set_prediction``; the tables are the same)."""
         nat = self.native(x_T.device)
+        nat.set_prediction(prediction)
         if c4 is not None:
             if sigma is not None or noise is not None:
                 raise ValueError("the multistep sampler is deterministic: no sigma / noise")

@@ -529,8 +529,15 @@ def z_dropout(z: torch.Tensor, p: float, generator: Optional[torch.Generator] = 
 def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[torch.Tensor] = None,
                noise: Optional[torch.Tensor] = None, ddp=False, graph: bool = False, recon_w: float = 0.0,
                tv_w: float = 0.0, scaler: Optional[GradScaler] = None, max_grad_norm: Optional[float] = None,
-               ema_decay: Optional[float] = None, z_drop: float = 0.0) -> torch.Tensor:
+               ema_decay: Optional[float] = None, z_drop: float = 0.0, prediction: str = "eps") -> torch.Tensor:
     """One optimisation step; returns the (detached) loss.  ``t`` / ``noise`` default to the reference's draws.
+
+    ``prediction="v"`` (default ``"eps"``, the reference's; anything else is a ``ValueError``): the network is trained to predict
+    ``v = a noise - s x0`` (``NoiseScheduler.v_target``).  The loss and its gradient always come from ``ccn_diffusion_loss_grad_v``:
+    ``mse(v_hat, v) + recon_w * l1(x0_pred, x0) + tv_w * TV(x0_pred)`` with ``x0_pred = clamp(a x_t - s v_hat, -1, 1)``, whose
+    auxiliary gradient carries the factor ``s <= 1`` where the eps form has ``s/a`` (up to 6.4e4 on the cosine schedule); with both
+    weights 0 it is the v-MSE step.  ``q_sample``, forward, backward, buckets, guard, EMA and ``z_drop`` are the same, and
+    ``last_loss_terms`` is always filled (l1 and tv read 0 when their weights are 0).Sample such weights with ``DDIMSampler(..., prediction="v")``.
 
     ``z_drop`` (usually 0.1): ``z_dropout`` zeroes whole rows of ``z`` with that probability before the copy into the static buffer,
     which trains the unconditional branch that guided sampling needs.  Under data parallelism each rank draws its own mask.  With 0
@@ -556,6 +563,7 @@ def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[tor
     the backward are replayed as captured hipGraphs after the first step of a shape -- measured SLOWER than plain stream launches
     for this step (7.98 vs 7.33 ms; 7.53 without the side-stream branch), hence off by default.  The returned loss is a view of a
     static buffer: read it before the next step."""
+    v_pred = _native.prediction_code(prediction) == _native.PRED_V
     state: TrainState = net.train_state()
     fp = state.fp
     fp.rebind_grads()
@@ -587,15 +595,16 @@ def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[tor
     state.trainer.set_graph(graph)
     if recon_w < 0 or tv_w < 0:
         raise ValueError("recon_w and tv_w must be non-negative")
-    if recon_w > 0 or tv_w > 0:
+    if recon_w > 0 or tv_w > 0 or v_pred:
         state.objective_buffers(sb)
         dev = sb["x0"].device
         torch.index_select(sch.sqrt_alphas_cumprod.to(dev), 0, sb["t"], out=sb["a"])
         torch.index_select(sch.sqrt_one_minus_alphas_cumprod.to(dev), 0, sb["t"], out=sb["s"])
         _native.q_sample(sb["x0"], sb["noise"], sb["a"], sb["s"], sb["x_t"])
         state.trainer.forward(fp.flat, sb["x_t"], sb["z"], sb["t"], out=sb["eps"])
-        terms, d_eps = _native.diffusion_loss_grad(sb["eps"], sb["noise"], sb["x_t"], sb["x0"], sb["a"], sb["s"], recon_w, tv_w,
-                                                   bufs=(sb["terms"], sb["d_eps"], sb["scratch_obj"]))
+        objective = _native.diffusion_loss_grad_v if v_pred else _native.diffusion_loss_grad
+        terms, d_eps = objective(sb["eps"], sb["noise"], sb["x_t"], sb["x0"], sb["a"], sb["s"], recon_w, tv_w,
+                                 bufs=(sb["terms"], sb["d_eps"], sb["scratch_obj"]))
         loss = terms[0]
         state.last_loss_terms = terms
     else:
@@ -673,21 +682,23 @@ def total_variation(x: torch.Tensor) -> torch.Tensor:
 
 def autograd_objective_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: torch.Tensor, noise: torch.Tensor,
                             recon_w: float = 0.0, tv_w: float = 0.0, scaler: Optional[GradScaler] = None,
-                            max_grad_norm: Optional[float] = None) -> torch.Tensor:
+                            max_grad_norm: Optional[float] = None, prediction: str = "eps") -> torch.Tensor:
     """The loop body of train/diffusion_train.py:119-128,137-140 through autograd: the objective from torch ops on (B, 3, S, S), the
     library's forward and backward behind ``UNetFunction``, ``opt.step()`` and ``opt.zero_grad()`` as two passes.  What
     ``train_step(recon_w=, tv_w=)`` fuses; kept as ``train_diffusion(fused_objective=False)`` and for A/B (tools/objective_ab.py).
-    With ``scaler`` the last lines are the reference's ``scaler.scale(loss).backward(); scaler.step(opt); scaler.update()``."""
+    With ``scaler`` the last lines are the reference's ``scaler.scale(loss).backward(); scaler.step(opt); scaler.update()``.
+    ``prediction="v"``: the target is ``sch.v_target`` and ``x0_pred = clamp(a x_t - s v_hat)``, as in ``train_step``."""
     import torch.nn.functional as F
+    v_pred = _native.prediction_code(prediction) == _native.PRED_V
     state: TrainState = net.train_state()
     state.fp.rebind_grads()
     x_t = sch.q_sample(x0, t, noise)
     eps_hat = net(x_t, z, t)
-    loss = F.mse_loss(eps_hat, noise)
+    loss = F.mse_loss(eps_hat, sch.v_target(x0, t, noise) if v_pred else noise)
     if recon_w > 0 or tv_w > 0:
         # predict_x0_from_eps (diffusion/scheduler.py:51-55) written with torch ops: its gradient must reach eps_hat
         sg = sch.sqrt_one_minus_alphas_cumprod[t].view(-1, 1, 1, 1); ac = sch.sqrt_alphas_cumprod[t].view(-1, 1, 1, 1)
-        x0_pred = ((x_t - sg * eps_hat) / ac).clamp(-1, 1)
+        x0_pred = (ac * x_t - sg * eps_hat if v_pred else (x_t - sg * eps_hat) / ac).clamp(-1, 1)
         if recon_w > 0:
             loss = loss + recon_w * F.l1_loss(x0_pred, x0)
         if tv_w > 0:
@@ -707,11 +718,21 @@ def autograd_objective_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t:
     return loss.detach()
 
 
+def check_resume_prediction(ck, prediction: str, resume="the resumed state") -> None:
+    """``train_state.pt`` records the parameterisation its weights were trained with (a file from before the option: ``"eps"``);
+    continuing it with another one is a ``ValueError`` naming both."""
+    _native.prediction_code(prediction)
+    had = ck.get("prediction", "eps")
+    if had != prediction:
+        raise ValueError(f"{resume} was trained with prediction={had!r}, this run asks for prediction={prediction!r}")
+
+
 def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size: int = 8, lr: float = 2e-4, timesteps: int = 1000,
                     schedule: str = "cosine", recon_w: float = 0.05, clip_w: float = 0.1, tv_w: float = 1e-4, device: str = "cuda",
                     save_dir=None, base: int = 128, ch_mult=(1, 2, 2), dtype: str = "bf16", num_workers: int = 2, log=print,
                     fused_objective: bool = True, grad_scaler: bool = False, max_grad_norm: Optional[float] = None,
-                    ema_decay: Optional[float] = None, ema_warmup: bool = False, resume=None, z_drop: float = 0.0):
+                    ema_decay: Optional[float] = None, ema_warmup: bool = False, resume=None, z_drop: float = 0.0,
+                    prediction: str = "eps"):
     """The reference's ``train_diffusion`` (same arguments, defaults, checkpoint names and log line) on the MI355X kernels.
 
     Per batch (train/diffusion_train.py:115-140): t ~ U{0..T-1}, noise ~ N, then ``train_step`` with the ``t`` / ``noise`` drawn here:
@@ -736,6 +757,10 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
     ``z_drop`` (usually 0.1): every batch's embeddings go through ``z_dropout`` -- whole rows zeroed with that probability, one
     ``torch.rand`` draw per batch on the device, each rank its own -- which trains the unconditional branch that
     ``DDIMSampler(guided=True)`` needs.  ``train_state.pt`` already carries the RNG states, so a resumed run continues the masks.
+
+    ``prediction="v"`` trains the v-parameterisation (``train_step``).  The checkpoints keep the reference's key set, so they do NOT
+    say how they were trained: pass the same ``prediction`` to the samplers and the CLIs.  ``train_state.pt`` does record it, and
+    ``resume=`` with another one is a ``ValueError`` naming both.
     """
     import os
     from pathlib import Path
@@ -744,6 +769,7 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
     from ..diffusion.scheduler import NoiseScheduler
     if not 0.0 <= z_drop <= 1.0:
         raise ValueError(f"z_drop must be in [0, 1], not {z_drop}")
+    _native.prediction_code(prediction)
     save_dir = Path(save_dir or store_dir)
     save_dir.mkdir(parents=True, exist_ok=True)
     ds = StoreDataset(store_dir, out_size=out_size)
@@ -757,6 +783,7 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
     if resume is not None:
         from ..models.unet import infer_arch
         ck = torch.load(resume, map_location="cpu", weights_only=True)
+        check_resume_prediction(ck, prediction, resume)
         if infer_arch(ck["net"]) != net.arch:
             raise ValueError(f"{resume} holds a model of architecture {infer_arch(ck['net'])}, this run builds {net.arch}")
         net.load_state_dict(ck["net"], strict=True)        # the optimiser's load_state_dict below refuses another parameter count
@@ -801,13 +828,13 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
             noise = torch.randn_like(x0)
             if fused_objective:
                 loss = train_step(net, sch, opt, x0, z, t=t, noise=noise, ddp=ddp, recon_w=max(recon_w, 0.0), tv_w=max(tv_w, 0.0),
-                                  scaler=scaler, max_grad_norm=max_grad_norm, z_drop=z_drop)
+                                  scaler=scaler, max_grad_norm=max_grad_norm, z_drop=z_drop, prediction=prediction)
                 running_dev += loss.double() * b          # the loss is a view of a static buffer: consumed here, in stream order
             else:
                 if z_drop > 0:
                     z = z_dropout(z, z_drop)[0]
                 running += float(autograd_objective_step(net, sch, opt, x0, z, t, noise, recon_w, tv_w, scaler=scaler,
-                                                                 max_grad_norm=max_grad_norm)) * b
+                                                                 max_grad_norm=max_grad_norm, prediction=prediction)) * b
             seen += b
         skipped, loss_scale = 0, 1.0
         if opt._guard is not None:                        # the one host read of the epoch carries the guard's counters too
@@ -825,7 +852,7 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
                 torch.save(opt.ema_state_dict(), save_dir / f"diffusion_unet_ep{ep + 1}_ema.pt")
             tmp_path = save_dir / "train_state.pt.tmp"
             torch.save(dict(epoch=ep + 1, net=net.state_dict(), opt=opt.state_dict(), scaler=None if scaler is None else scaler.state_dict(),
-                            rng_cpu=torch.get_rng_state(), rng_device=torch.cuda.get_rng_state(device)), tmp_path)
+                            rng_cpu=torch.get_rng_state(), rng_device=torch.cuda.get_rng_state(device), prediction=prediction), tmp_path)
             os.replace(tmp_path, save_dir / "train_state.pt")
             log(f"[train] epoch {ep + 1}/{epochs} loss={running / max(seen, 1):.4f}")
             if skipped:

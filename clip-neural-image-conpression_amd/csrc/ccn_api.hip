@@ -158,6 +158,7 @@ struct GraphEntry {
     const float* eps = nullptr;          // ... and eps scratch address the graph was captured with
     std::vector<float> c4;               // multistep sampler (empty: none): the fifth coefficient column
     const float* hist = nullptr;         // ... and the x0 history address the graph was captured with
+    int pred = CCN_PRED_EPS;             // ccn_set_prediction at capture time: the update form is baked into the captured launches
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     void destroy() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); }   // (after draining the device)
@@ -194,6 +195,7 @@ struct ccn_handle_s {
     int G = 8;
     int weight_rounding = CCN_ROUND_DIFFUSED_PHASES;   // how bf16 mode rounds the conv weights in ccn_commit_params (ccn_set_weight_rounding)
     int nphase = 1;                                     // versions per conv weight of the committed model (round_version)
+    int pred = CCN_PRED_EPS;                            // what the network output is to the ccn_sample* loops (ccn_set_prediction)
     std::vector<std::unique_ptr<ShapePlan>> shape_plans;   // of the committed model, one per (B, H, W, steps)
     std::vector<std::unique_ptr<Binding>> bindings;         // plan x workspace address, least recently used first
     hipStream_t cap_stream = nullptr;
@@ -720,7 +722,7 @@ hipError_t launch(const ccn_handle_s* h, const ShapePlan& pl, const Launch& L, c
     if (cw.kind == KIND_HEAD) {
         k.x_state = c.x_state; k.eps_out = c.eps_out; k.do_ddim = c.do_ddim;
         k.c0 = c.c[0]; k.c1 = c.c[1]; k.c2 = c.c[2]; k.c3 = c.c[3]; k.noise = c.noise; k.sigma = c.sigma;
-        k.x0_hist = c.x0_hist; k.c4 = c.c4;
+        k.x0_hist = c.x0_hist; k.c4 = c.c4; k.pred = h->pred;
     }
     if (L.op == OP_HEAD2) return launch_head2(k, (const float2*)at(L.gn_ab), h->head_w_f32, at(L.scratch), c.step, s);
     const int v = c.step % cw.nphase;
@@ -845,6 +847,7 @@ int run_conditioning(ccn_handle_s* h, const Binding* b, hipStream_t s, const int
 
 // Classifier-free guidance (ccn_sample_guided): the plan's batch is 2B rows -- [0, B) carry z, [B, 2B) the null embedding, both the
 // same state -- the head writes eps of all 2B rows into `eps`, and one combine launch per step updates both halves of the state.
+// (`eps` holds the raw network output of the 2B rows whatever it predicts: the combine launch applies the handle's parameterisation.)
 struct Guide { const float* z_null; float w; float* eps; };
 // The multistep sampler (ccn_sample_ms, ccn_sample_guided_ms): per step the coefficient c4 of (x0 - previous x0), and the caller's
 // history tensor of one state (B rows, also when guided), which the updating launch of every step reads (c4 != 0) and rewrites.
@@ -868,7 +871,15 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, int steps, const
             if (ms) { c.x0_hist = ms->hist; c.c4 = ms->c4[i]; }
         }
         if (int rc = run_ops(h, b, s, c)) return rc;
-        if (gd && ms) {
+        if (gd && h->pred != CCN_PRED_EPS) {
+            // the v form: one kernel for the plain and the multistep combine (the eps forms below keep their own launches)
+            const float* cf = coef + i * 4;
+            const float c4 = ms ? ms->c4[i] : 0.f;
+            const float* nz = noisy ? noise + (size_t)i * img : nullptr;
+            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * (5 + (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0)), s, [&] {
+                    return launch_sampler_step(xstate, xstate + img, ms ? ms->hist : nullptr, gd->eps, gd->eps + img, nz, h->pred, gd->w, cf[0],
+                                               cf[1], cf[2], cf[3], c4, noisy ? sigma[i] : 0.f, (int64_t)img, s); })) return rc;
+        } else if (gd && ms) {
             const float* cf = coef + i * 4;
             const float c4 = ms->c4[i];
             if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * (c4 != 0.f ? 7 : 6), s, [&] {
@@ -1049,6 +1060,14 @@ int ccn_set_weight_rounding(ccn_handle_t h, int32_t mode)
     return CCN_OK;
 }
 
+int ccn_set_prediction(ccn_handle_t h, int32_t pred)
+{
+    if (!h) return fail(CCN_EINVAL, "null handle");
+    if (pred != CCN_PRED_EPS && pred != CCN_PRED_V) return fail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
+    h->pred = pred;
+    return CCN_OK;
+}
+
 int ccn_commit_params(ccn_handle_t h)
 {
     if (!h) return fail(CCN_EINVAL, "null handle");
@@ -1191,12 +1210,12 @@ static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev,
                 (!sigma_host || !std::memcmp(g.sigma.data(), sigma_host, (size_t)steps * 4)) &&
                 g.guided == (gd != nullptr) && (!gd || (g.w == gd->w && g.eps == gd->eps)) &&
                 g.hist == (ms ? ms->hist : nullptr) && g.c4.size() == (ms ? (size_t)steps : 0) &&
-                (!ms || !std::memcmp(g.c4.data(), ms->c4, (size_t)steps * 4))) { ge = &g; break; }
+                (!ms || !std::memcmp(g.c4.data(), ms->c4, (size_t)steps * 4)) && g.pred == h->pred) { ge = &g; break; }
         if (!ge) {
             GraphEntry g;
             g.steps = steps; g.ts.assign(ts_host, ts_host + steps); g.coef.assign(coef_host, coef_host + steps * 4);
             if (sigma_host) g.sigma.assign(sigma_host, sigma_host + steps);
-            g.noise = noise_dev;
+            g.noise = noise_dev; g.pred = h->pred;
             if (gd) { g.guided = true; g.w = gd->w; g.eps = gd->eps; }
             if (ms) { g.c4.assign(ms->c4, ms->c4 + steps); g.hist = ms->hist; }
             HIPCHK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeRelaxed));
@@ -1332,6 +1351,17 @@ int ccn_ddim_step(float* x_dev, const float* eps_dev, const float* noise_dev, fl
     if (!x_dev || !eps_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
     if (n == 0) return CCN_OK;
     HIPCHK(launch_ddim_step(x_dev, eps_dev, noise_dev, c0, c1, c2, c3, sigma, n, (hipStream_t)stream));
+    return CCN_OK;
+}
+
+int ccn_sampler_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,
+                     const float* noise_dev, int32_t pred, float w, const float* coef_host, float sigma, int64_t n, void* stream)
+{
+    if (!x_dev || !out_c_dev || !coef_host || n < 0) return fail(CCN_EINVAL, "bad argument");
+    if (pred != CCN_PRED_EPS && pred != CCN_PRED_V) return fail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
+    if (n == 0) return CCN_OK;
+    HIPCHK(launch_sampler_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, noise_dev, pred, w, coef_host[0], coef_host[1], coef_host[2],
+                               coef_host[3], x0_hist_dev ? coef_host[4] : 0.f, sigma, n, (hipStream_t)stream));
     return CCN_OK;
 }
 

@@ -27,14 +27,37 @@ __device__ __forceinline__ unsigned pack_bf2(float a, float b) {
 //     x0 = clamp((x - c0*e)/c1, -1, 1);  xn = c2*x0 + c3*e;  c4 != 0:  xn = xn + c4*(x0 - hist)
 // `hist` is the previous step's x0 and only enters when c4 != 0 (the caller does not read it otherwise: on step 0 it holds nothing);
 // the clamped x0 comes back through `x0_out`, the next step's history.  With c4 == 0 this is the DDIM update, bit for bit.
-__device__ __forceinline__ float sampler_update(float x, float e, float c0, float c1, float c2, float c3, float c4, float hist, float& x0_out)
+// sampler_tail is everything after (x0, e): shared by the two parameterisations below.
+__device__ __forceinline__ float sampler_tail(float x0, float e, float c2, float c3, float c4, float hist, float& x0_out)
 {
-    float x0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(c0, e)), c1);
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
     float xn = __fadd_rn(__fmul_rn(c2, x0), __fmul_rn(c3, e));
     if (c4 != 0.f) xn = __fadd_rn(xn, __fmul_rn(c4, __fsub_rn(x0, hist)));
     x0_out = x0;
     return xn;
+}
+__device__ __forceinline__ float sampler_update(float x, float e, float c0, float c1, float c2, float c3, float c4, float hist, float& x0_out)
+{
+    float x0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(c0, e)), c1);
+    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    return sampler_tail(x0, e, c2, c3, c4, hist, x0_out);
+}
+// The v-parameterisation (CCN_PRED_V): the network output is y = v = a*noise - s*x0, and with the SAME table (c0 = s_t, c1 = a_t)
+//     x0 = clamp(c1*x - c0*y, -1, 1);  e = c0*x + c1*y;  then the tail above.
+// x0 is formed directly, not as the eps form applied to e: at the noisy end of the cosine table 1/c1 = 6.4e4 and s rounds to 1.0f,
+// so (x - c0*e)/c1 cancels to nothing, while c1*x - c0*y has no division and no cancellation (Parameterisation).
+__device__ __forceinline__ float sampler_update_v(float x, float y, float c0, float c1, float c2, float c3, float c4, float hist, float& x0_out)
+{
+    float x0 = __fsub_rn(__fmul_rn(c1, x), __fmul_rn(c0, y));
+    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    const float e = __fadd_rn(__fmul_rn(c0, x), __fmul_rn(c1, y));
+    return sampler_tail(x0, e, c2, c3, c4, hist, x0_out);
+}
+// `pred` is wave-uniform (a kernel argument): PRED_EPS / PRED_V have the values of CCN_PRED_EPS / CCN_PRED_V
+enum { PRED_EPS = 0, PRED_V = 1 };
+__device__ __forceinline__ float sampler_update_p(int pred, float x, float y, float c0, float c1, float c2, float c3, float c4, float hist,
+                                                  float& x0_out)
+{
+    return pred == PRED_V ? sampler_update_v(x, y, c0, c1, c2, c3, c4, hist, x0_out) : sampler_update(x, y, c0, c1, c2, c3, c4, hist, x0_out);
 }
 
 template <typename T> __device__ __forceinline__ float silu_f(float v);

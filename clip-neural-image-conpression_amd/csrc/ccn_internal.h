@@ -152,6 +152,7 @@ struct ConvArgs {
     float* x0_hist;         // head, multistep sampler: the previous step's clamped x0, NCHW fp32 like x_state; read when c4 != 0, then
                             // overwritten with this step's; null = the plain DDIM update
     float c4;               // head: coefficient of (x0 - x0_hist) in the update (sampler_update in ccn_device.h)
+    int pred;               // head: what the network output is, 0 = eps, 1 = v (CCN_PRED_*): selects sampler_update / sampler_update_v
     __host__ __device__ int tapinfo_dy(int i) const { return (tapinfo[i] & 3) - 1; }
     __host__ __device__ int tapinfo_dx(int i) const { return ((tapinfo[i] >> 2) & 3) - 1; }
     __host__ __device__ int tapinfo_w(int i) const { return tapinfo[i] >> 4; }
@@ -275,6 +276,11 @@ hipError_t launch_cfg_ddim_step(float* x, float* x_dup, const float* eps_c, cons
 hipError_t launch_ms_step(float* x, float* hist, const float* eps, float c0, float c1, float c2, float c3, float c4, int64_t n, hipStream_t s);
 hipError_t launch_cfg_ms_step(float* x, float* x_dup, float* hist, const float* eps_c, const float* eps_u, float w, float c0, float c1,
                               float c2, float c3, float c4, int64_t n, hipStream_t s);
+// every stand-alone update in one kernel, either parameterisation (pred = CCN_PRED_*): x_dup, hist, out_u and noise are nullable --
+// no out_u: out_c is the prediction itself; no hist: c4 is not applied and no history is written.  With pred = 0 it computes what
+// the four launchers above compute, bit for bit.
+hipError_t launch_sampler_step(float* x, float* x_dup, float* hist, const float* out_c, const float* out_u, const float* noise, int pred,
+                               float w, float c0, float c1, float c2, float c3, float c4, float sigma, int64_t n, hipStream_t s);
 hipError_t launch_q_sample(float* out, const float* x0, const float* noise, const float* a, const float* sg,
                            int B, int64_t per, hipStream_t s);
 hipError_t launch_predict_x0(float* out, const float* xt, const float* eps, const float* a, const float* sg,

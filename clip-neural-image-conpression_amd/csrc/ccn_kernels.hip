@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a)
                         const float c4 = a.x0_hist ? a.c4 : 0.f;
                         const float hv = c4 != 0.f ? a.x0_hist[idx] : 0.f;
                         float x0;
-                        float xn = sampler_update(x, e, a.c0, a.c1, a.c2, a.c3, c4, hv, x0);
+                        float xn = sampler_update_p(a.pred, x, e, a.c0, a.c1, a.c2, a.c3, c4, hv, x0);
                         if (a.noise) xn = __fadd_rn(xn, __fmul_rn(a.sigma, a.noise[idx]));      // eta > 0 (diffusion/ddim.py:44-45)
                         if (a.x0_hist) a.x0_hist[idx] = x0;
                         a.x_state[idx] = xn;
@@ -939,6 +939,63 @@ hipError_t launch_cfg_ms_step(float* x, float* x_dup, float* hist, const float* 
                               float c2, float c3, float c4, int64_t n, hipStream_t s)
 {
     return launch_ms<true>(x, x_dup, hist, eps_c, eps_u, w, c0, c1, c2, c3, c4, n, s);
+}
+
+// Every stand-alone update above in one kernel, for either parameterisation (`pred`, wave-uniform: sampler_update_p in ccn_device.h).
+// y = out_c, or out_u + w*(out_c - out_u) when out_u is given; hist (nullable) is read when c4 != 0 and receives the clamped x0; the
+// noise term and x_dup as in cfg_ddim_step_kernel.  VEC as there.  With pred == PRED_EPS the op sequence is that of the kernels above.
+template <bool VEC>
+__global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x_dup, float* __restrict__ hist, const float* __restrict__ out_c,
+                                    const float* __restrict__ out_u, const float* __restrict__ noise, int pred, float w, float c0, float c1,
+                                    float c2, float c3, float c4, float sigma, int64_t n)
+{
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n4 = VEC ? n / 4 : 0;
+    if (!hist) c4 = 0.f;
+    for (int64_t q = tid; q < n4; q += nthr) {
+        const float4 xv = ((const float4*)x)[q];
+        float4 yv = ((const float4*)out_c)[q];
+        if (out_u) {
+            const float4 uv = ((const float4*)out_u)[q];
+            yv.x = __fadd_rn(uv.x, __fmul_rn(w, __fsub_rn(yv.x, uv.x))); yv.y = __fadd_rn(uv.y, __fmul_rn(w, __fsub_rn(yv.y, uv.y)));
+            yv.z = __fadd_rn(uv.z, __fmul_rn(w, __fsub_rn(yv.z, uv.z))); yv.w = __fadd_rn(uv.w, __fmul_rn(w, __fsub_rn(yv.w, uv.w)));
+        }
+        float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), o, p;
+        if (c4 != 0.f) hv = ((const float4*)hist)[q];
+        o.x = sampler_update_p(pred, xv.x, yv.x, c0, c1, c2, c3, c4, hv.x, p.x);
+        o.y = sampler_update_p(pred, xv.y, yv.y, c0, c1, c2, c3, c4, hv.y, p.y);
+        o.z = sampler_update_p(pred, xv.z, yv.z, c0, c1, c2, c3, c4, hv.z, p.z);
+        o.w = sampler_update_p(pred, xv.w, yv.w, c0, c1, c2, c3, c4, hv.w, p.w);
+        if (noise) {
+            const float4 nv = ((const float4*)noise)[q];
+            o.x = __fadd_rn(o.x, __fmul_rn(sigma, nv.x)); o.y = __fadd_rn(o.y, __fmul_rn(sigma, nv.y));
+            o.z = __fadd_rn(o.z, __fmul_rn(sigma, nv.z)); o.w = __fadd_rn(o.w, __fmul_rn(sigma, nv.w));
+        }
+        if (hist) ((float4*)hist)[q] = p;
+        ((float4*)x)[q] = o;
+        if (x_dup) ((float4*)x_dup)[q] = o;
+    }
+    for (int64_t i = n4 * 4 + tid; i < n; i += nthr) {
+        float y = out_c[i];
+        if (out_u) { const float u = out_u[i]; y = __fadd_rn(u, __fmul_rn(w, __fsub_rn(y, u))); }
+        const float hv = c4 != 0.f ? hist[i] : 0.f;
+        float p;
+        float xn = sampler_update_p(pred, x[i], y, c0, c1, c2, c3, c4, hv, p);
+        if (noise) xn = __fadd_rn(xn, __fmul_rn(sigma, noise[i]));
+        if (hist) hist[i] = p;
+        x[i] = xn;
+        if (x_dup) x_dup[i] = xn;
+    }
+}
+hipError_t launch_sampler_step(float* x, float* x_dup, float* hist, const float* out_c, const float* out_u, const float* noise, int pred,
+                               float w, float c0, float c1, float c2, float c3, float c4, float sigma, int64_t n, hipStream_t s)
+{
+    const bool vec = !(((uintptr_t)x | (uintptr_t)x_dup | (uintptr_t)hist | (uintptr_t)out_c | (uintptr_t)out_u | (uintptr_t)noise) & 15);
+    const int64_t work = vec ? (n + 3) / 4 : n, blocks = (work + 255) / 256;
+    const int grid = (int)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);      // 256 CUs x 8 blocks, grid-stride beyond
+    if (vec) hipLaunchKernelGGL(sampler_step_kernel<true>, dim3(grid), dim3(256), 0, s, x, x_dup, hist, out_c, out_u, noise, pred, w, c0, c1, c2, c3, c4, sigma, n);
+    else hipLaunchKernelGGL(sampler_step_kernel<false>, dim3(grid), dim3(256), 0, s, x, x_dup, hist, out_c, out_u, noise, pred, w, c0, c1, c2, c3, c4, sigma, n);
+    return hipGetLastError();
 }
 
 __global__ void q_sample_kernel(float* __restrict__ out, const float* __restrict__ x0, const float* __restrict__ noise,

@@ -2,6 +2,7 @@
 // AdamW and the weight EMA.  Kernels, their launchers and the extern "C" entry points of include/ccn_hip.h in one file: none of it
 // touches a ccn_trainer_t, and nothing outside this file calls into it.
 //   mse_*, objective_*   mean((eps - target)^2), and the reference's default objective MSE + L1 + TV in one pass, with d loss / d eps
+//                        (objective_partial_kernel<VEC, VP>: VP = the same objective for a network that predicts v)
 //   grad_guard_*         GradScaler's skipped step and scale update, clip_grad_norm_, decided on the device (ccn_step_guard_t)
 //   ema_tick_kernel      the EMA's weight and count of updates for this step (ccn_ema_state_t)
 //   adamw_kernel         torch.optim.AdamW over the flat buffers, <GUARDED, EMA, ZERO, VEC>: under the guard's decision, with the
@@ -83,7 +84,14 @@ template <bool VEC> __device__ __forceinline__ void obj_load4(const float* __res
     }
 }
 
-template <bool VEC>
+// VP: the v-parameterisation (ccn_diffusion_loss_grad_v): `eps` holds v_hat, raw x0_pred = a x_t - s v_hat, the MSE target is
+// a noise - s x0 (three fp32 ops, formed in registers), and d raw / d v_hat = -s.  Everything else is shared.
+template <bool VP> __device__ __forceinline__ float obj_raw_x0(float xt, float e, float ca, float cs)
+{
+    if (VP) return __fsub_rn(__fmul_rn(ca, xt), __fmul_rn(cs, e));
+    return __fdiv_rn(__fsub_rn(xt, __fmul_rn(cs, e)), ca);
+}
+template <bool VEC, bool VP>
 __global__ __launch_bounds__(256) void objective_partial_kernel(const float* __restrict__ eps, const float* __restrict__ noise,
                                                                  const float* __restrict__ xt, const float* __restrict__ x0,
                                                                  const float* __restrict__ a, const float* __restrict__ sg, int C, int H, int W,
@@ -114,7 +122,7 @@ __global__ __launch_bounds__(256) void objective_partial_kernel(const float* __r
                 f32x4 p;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float raw = __fdiv_rn(__fsub_rn(v[j], __fmul_rn(cs, e[k][j])), ca);
+                    const float raw = obj_raw_x0<VP>(v[j], e[k][j], ca, cs);
                     inside[k] |= (raw >= -1.0f && raw <= 1.0f) ? (1u << j) : 0u;
                     p[j] = fminf(fmaxf(raw, -1.0f), 1.0f);
                 }
@@ -129,7 +137,7 @@ __global__ __launch_bounds__(256) void objective_partial_kernel(const float* __r
                 obj_load4<VEC>(eps + o, cw, ev); obj_load4<VEC>(xt + o, cw, v);
                 f32x4 p;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) p[j] = fminf(fmaxf(__fdiv_rn(__fsub_rn(v[j], __fmul_rn(cs, ev[j])), ca), -1.0f), 1.0f);
+                for (int j = 0; j < 4; ++j) p[j] = fminf(fmaxf(obj_raw_x0<VP>(v[j], ev[j], ca, cs), -1.0f), 1.0f);
                 *(f32x4*)&tile[rr ? OBJ_TY + 1 : 0][4 + 4 * q] = p;
             }
         } else if (tid < 64 + 2 * OBJ_TY) {                                      // wave 1: the column left and right of the tile
@@ -137,12 +145,12 @@ __global__ __launch_bounds__(256) void objective_partial_kernel(const float* __r
             const int gy = ys + r, hx = right ? xs + OBJ_TX : xs - 1;
             if (gy < H && hx >= 0 && hx < W) {
                 const size_t o = pbase + (size_t)gy * W + hx;
-                tile[r + 1][right ? OBJ_TX + 4 : 3] = fminf(fmaxf(__fdiv_rn(__fsub_rn(xt[o], __fmul_rn(cs, eps[o])), ca), -1.0f), 1.0f);
+                tile[r + 1][right ? OBJ_TX + 4 : 3] = fminf(fmaxf(obj_raw_x0<VP>(xt[o], eps[o], ca, cs), -1.0f), 1.0f);
             }
         }
         __syncthreads();
         // ---- stencil from LDS --------------------------------------------------------------------------------------------------
-        const float coef = -__fdiv_rn(cs, ca);                                   // d raw / d eps
+        const float coef = VP ? -cs : -__fdiv_rn(cs, ca);                        // d raw / d eps (VP: d raw / d v_hat)
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int r = rr + 8 * k, gy = ys + r;
@@ -157,6 +165,7 @@ __global__ __launch_bounds__(256) void objective_partial_kernel(const float* __r
                 f32x4 out;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
+                    if (VP) nz[j] = __fsub_rn(__fmul_rn(ca, nz[j]), __fmul_rn(cs, xv[j]));   // the target: nz is only the MSE's from here on
                     const float d = e[k][j] - nz[j];
                     float g = 2.0f * d * inv_n;                                  // the op order of mse_partial_kernel
                     if (j < cw) {
@@ -219,13 +228,42 @@ __global__ void objective_mse_only_terms_kernel(float* __restrict__ loss)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) { loss[1] = loss[0]; loss[2] = 0.f; loss[3] = 0.f; }
 }
-hipError_t launch_diffusion_loss_grad(const float* eps, const float* noise, const float* xt, const float* x0, const float* a, const float* sg,
-                                      int B, int C, int H, int W, float recon_w, float tv_w, float* loss, float* d_eps, float* scratch,
-                                      hipStream_t s)
+// the v-MSE alone: mse_partial_kernel with the target a noise - s x0 formed in registers (the same three fp32 ops a caller would
+// materialise it with), same grid, same sums: bit-identical to launch_mse_loss_grad on that target
+__global__ __launch_bounds__(256) void mse_v_partial_kernel(const float* __restrict__ v, const float* __restrict__ noise, const float* __restrict__ x0,
+                                                             const float* __restrict__ a, const float* __restrict__ sg, int64_t per, int64_t n,
+                                                             float inv_n, float* __restrict__ d_v, float* __restrict__ scratch)
+{
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / per;
+        const float target = __fsub_rn(__fmul_rn(a[b], noise[i]), __fmul_rn(sg[b], x0[i]));
+        const float d = v[i] - target;
+        s += (double)d * (double)d;
+        if (d_v) d_v[i] = 2.0f * d * inv_n;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) scratch[blockIdx.x] = (float)((red[0] + red[1]) + (red[2] + red[3]));
+}
+template <bool VP>
+hipError_t launch_objective(const float* eps, const float* noise, const float* xt, const float* x0, const float* a, const float* sg,
+                            int B, int C, int H, int W, float recon_w, float tv_w, float* loss, float* d_eps, float* scratch,
+                            hipStream_t s)
 {
     const int64_t n = (int64_t)B * C * H * W;
     if (recon_w == 0.f && tv_w == 0.f) {
-        const hipError_t e = launch_mse_loss_grad(eps, noise, n, loss, d_eps, scratch, s);
+        hipError_t e = hipSuccess;
+        if (VP) {
+            const int nb = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);     // launch_mse_loss_grad's grid
+            hipLaunchKernelGGL(mse_v_partial_kernel, dim3(nb), dim3(256), 0, s, eps, noise, x0, a, sg, (int64_t)C * H * W, n,
+                               (float)(1.0 / (double)n), d_eps, scratch);
+            hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(64), 0, s, scratch, nb, 1.0 / (double)n, loss);
+            e = hipGetLastError();
+        } else e = launch_mse_loss_grad(eps, noise, n, loss, d_eps, scratch, s);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(objective_mse_only_terms_kernel, dim3(1), dim3(64), 0, s, loss);
         return hipGetLastError();
@@ -239,10 +277,10 @@ hipError_t launch_diffusion_loss_grad(const float* eps, const float* noise, cons
     const float c_l1 = (float)((double)recon_w / (double)n), c_tvh = (float)((double)tv_w / nh), c_tvw = (float)((double)tv_w / nw);
     const uintptr_t bits = (uintptr_t)eps | (uintptr_t)noise | (uintptr_t)xt | (uintptr_t)x0 | (uintptr_t)d_eps;
     if (W % 4 == 0 && (bits & 15) == 0)
-        hipLaunchKernelGGL(objective_partial_kernel<true>, dim3(nb), dim3(256), 0, s, eps, noise, xt, x0, a, sg, C, H, W, nby, nbx, (int)tiles,
+        hipLaunchKernelGGL((objective_partial_kernel<true, VP>), dim3(nb), dim3(256), 0, s, eps, noise, xt, x0, a, sg, C, H, W, nby, nbx, (int)tiles,
                            inv_n, c_l1, c_tvh, c_tvw, d_eps, (double*)scratch);
     else
-        hipLaunchKernelGGL(objective_partial_kernel<false>, dim3(nb), dim3(256), 0, s, eps, noise, xt, x0, a, sg, C, H, W, nby, nbx, (int)tiles,
+        hipLaunchKernelGGL((objective_partial_kernel<false, VP>), dim3(nb), dim3(256), 0, s, eps, noise, xt, x0, a, sg, C, H, W, nby, nbx, (int)tiles,
                            inv_n, c_l1, c_tvh, c_tvw, d_eps, (double*)scratch);
     hipLaunchKernelGGL(objective_final_kernel, dim3(1), dim3(64), 0, s, (const double*)scratch, nb, 1.0 / (double)n, 1.0 / nh, 1.0 / nw,
                        (double)recon_w, (double)tv_w, loss);
@@ -501,6 +539,25 @@ hipError_t launch_adamw(float* p, float* g, float* m, float* v, float* ema, int6
 
 using namespace ccn;
 
+// the two objectives share their argument checks; VP: x_t is not read when both weights are zero
+template <bool VP>
+static int objective_entry(const float* eps_dev, const float* noise_dev, const float* x_t_dev, const float* x0_dev, const float* a_dev,
+                           const float* s_dev, int32_t B, int32_t C, int32_t H, int32_t W, float recon_w, float tv_w, float* loss_dev,
+                           float* d_eps_dev, float* scratch_dev, void* stream)
+{
+    const bool need_xt = !VP || recon_w != 0.f || tv_w != 0.f;
+    if (!eps_dev || !noise_dev || (need_xt && !x_t_dev) || !x0_dev || !a_dev || !s_dev || !loss_dev || !scratch_dev || B <= 0 || C <= 0)
+        return tfail(CCN_EINVAL, "bad argument");
+    if (H < 2 || W < 2) return tfail(CCN_EINVAL, "H and W must be at least 2 (the total variation of a one-pixel-wide image is a mean over nothing)");
+    if (!(recon_w >= 0.f) || !(tv_w >= 0.f)) return tfail(CCN_EINVAL, "recon_w and tv_w must be non-negative");
+    if (((uintptr_t)scratch_dev & 7) != 0) return tfail(CCN_EINVAL, "scratch_dev must be 8-byte aligned");
+    if ((int64_t)B * C * H * W > (int64_t)1 << 40) return tfail(CCN_EINVAL, "tensor too large");
+    if (launch_objective<VP>(eps_dev, noise_dev, x_t_dev, x0_dev, a_dev, s_dev, B, C, H, W, recon_w, tv_w, loss_dev, d_eps_dev, scratch_dev,
+                             (hipStream_t)stream) != hipSuccess)
+        return tfail(CCN_EHIP, "objective launch failed");
+    return CCN_OK;
+}
+
 extern "C" {
 
 int ccn_mse_loss_grad(const float* eps_dev, const float* target_dev, int64_t n, float* loss_dev, float* d_eps_dev, float* scratch_dev, void* stream)
@@ -514,16 +571,14 @@ int ccn_diffusion_loss_grad(const float* eps_dev, const float* noise_dev, const 
                             const float* s_dev, int32_t B, int32_t C, int32_t H, int32_t W, float recon_w, float tv_w, float* loss_dev,
                             float* d_eps_dev, float* scratch_dev, void* stream)
 {
-    if (!eps_dev || !noise_dev || !x_t_dev || !x0_dev || !a_dev || !s_dev || !loss_dev || !scratch_dev || B <= 0 || C <= 0)
-        return tfail(CCN_EINVAL, "bad argument");
-    if (H < 2 || W < 2) return tfail(CCN_EINVAL, "H and W must be at least 2 (the total variation of a one-pixel-wide image is a mean over nothing)");
-    if (!(recon_w >= 0.f) || !(tv_w >= 0.f)) return tfail(CCN_EINVAL, "recon_w and tv_w must be non-negative");
-    if (((uintptr_t)scratch_dev & 7) != 0) return tfail(CCN_EINVAL, "scratch_dev must be 8-byte aligned");
-    if ((int64_t)B * C * H * W > (int64_t)1 << 40) return tfail(CCN_EINVAL, "tensor too large");
-    if (launch_diffusion_loss_grad(eps_dev, noise_dev, x_t_dev, x0_dev, a_dev, s_dev, B, C, H, W, recon_w, tv_w, loss_dev, d_eps_dev, scratch_dev,
-                                   (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "objective launch failed");
-    return CCN_OK;
+    return objective_entry<false>(eps_dev, noise_dev, x_t_dev, x0_dev, a_dev, s_dev, B, C, H, W, recon_w, tv_w, loss_dev, d_eps_dev, scratch_dev, stream);
+}
+
+int ccn_diffusion_loss_grad_v(const float* v_dev, const float* noise_dev, const float* x_t_dev, const float* x0_dev, const float* a_dev,
+                              const float* s_dev, int32_t B, int32_t C, int32_t H, int32_t W, float recon_w, float tv_w, float* loss_dev,
+                              float* d_v_dev, float* scratch_dev, void* stream)
+{
+    return objective_entry<true>(v_dev, noise_dev, x_t_dev, x0_dev, a_dev, s_dev, B, C, H, W, recon_w, tv_w, loss_dev, d_v_dev, scratch_dev, stream);
 }
 
 int ccn_adamw_step(float* params_dev, const float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n, float lr, float beta1, float beta2,

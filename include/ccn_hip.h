@@ -205,6 +205,35 @@ int ccn_ms_step(float* x_dev, float* x0_hist_dev, const float* eps_dev,
 int ccn_cfg_ms_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* eps_c_dev, const float* eps_u_dev,
                     float w, float c0, float c1, float c2, float c3, float c4, int64_t n, void* stream);
 
+/* ---- parameterisation: what the network output is ------------------------------------------------------------------------------ *
+ * (No reference counterpart: the reference trains and samples eps only.)  With a = sqrt(ab_t), s = sqrt(1 - ab_t):
+ *   CCN_PRED_EPS  (default) the network predicts the noise, every formula above as written;
+ *   CCN_PRED_V    the network predicts v = a*noise - s*x0 (Salimans & Ho 2022).  On the SAME coefficient tables (c0 = s_t, c1 = a_t)
+ *                 the first line of every update becomes
+ *                     x0 = clamp(c1*x - c0*y, -1, 1);  e = c0*x + c1*y        -- every op rounded to fp32, y the network output
+ *                 and the rest (c2*x0 + c3*e, the c4 term, sigma*noise, x_dup) is unchanged.  Under guidance y = y_u + w*(y_c - y_u)
+ *                 is combined first.  x0 is formed directly and not through e: at t = 999 of the cosine table 1/a = 6.4e4 and s
+ *                 rounds to 1.0f, so the eps form applied to e returns x0 = 0 whatever the network said. */
+enum { CCN_PRED_EPS = 0, CCN_PRED_V = 1 };
+
+/* Handle state read by ccn_sample, ccn_sample_eta, ccn_sample_guided, ccn_sample_ms and ccn_sample_guided_ms when they enqueue or
+ * capture; part of every captured graph's cache key, so toggling finds each mode's own graph on a shared workspace.  ccn_forward
+ * is unaffected (it returns the raw network output).  Any other value: CCN_EINVAL, the state is unchanged. */
+int ccn_set_prediction(ccn_handle_t h, int32_t pred);
+
+/* One sampler update outside the fused loop, for either parameterisation: the general form of ccn_ddim_step, ccn_cfg_ddim_step,
+ * ccn_ms_step and ccn_cfg_ms_step.  In place on x_dev; coef_host[5] = c0..c4 (a HOST pointer, read before the call returns).
+ *   out_c_dev   the network output (eps or v, by `pred`);
+ *   out_u_dev   NULL, or the unconditional output: y = out_u + w*(out_c - out_u) is used (w is ignored when NULL);
+ *   x0_hist_dev NULL (c4 is not applied, nothing is stored), or the x0 history: read only when c4 != 0, then receives this step's x0;
+ *   noise_dev   NULL, or N(0,1) draws added as sigma*noise;   x_dup_dev  NULL, or receives a copy of the new x.
+ * With pred = CCN_PRED_EPS the result equals that of the four older entry points bit for bit.  The output tensors are not written.
+ * n elements each.  Four elements per lane when every non-NULL pointer is 16-byte aligned, one otherwise.
+ * CCN_EINVAL: x_dev, out_c_dev or coef_host NULL, n < 0, an unknown pred. */
+int ccn_sampler_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,
+                     const float* noise_dev, int32_t pred, float w, const float* coef_host /* [5] */, float sigma, int64_t n,
+                     void* stream);
+
 /* NoiseScheduler.q_sample (diffusion/scheduler.py:46-49): out[b] = a[b]*x0[b] + s[b]*noise[b];
  * a_dev/s_dev are the gathered per-sample coefficients, (B,) fp32; per_sample = C*H*W. */
 int ccn_q_sample(float* out_dev, const float* x0_dev, const float* noise_dev,
@@ -370,6 +399,20 @@ int ccn_diffusion_loss_grad(const float* eps_dev, const float* noise_dev, const 
                             const float* a_dev, const float* s_dev, int32_t B, int32_t C, int32_t H, int32_t W,
                             float recon_w, float tv_w, float* loss_dev /* [4]: total, mse, l1, tv */,
                             float* d_eps_dev /* may be NULL */, float* scratch_dev, void* stream);
+
+/* The same objective for a network that predicts v (CCN_PRED_V; no reference counterpart).  Arguments, layout of loss_dev, the fixed
+ * order fp64 sums, bit-reproducibility, the H, W >= 2 rule and the scratch contract are ccn_diffusion_loss_grad's; what differs:
+ *     target  = a*noise - s*x0                       -- fp32: two products and one subtraction, each rounded
+ *     mse     = mean((v_hat - target)^2)
+ *     x0_pred = clamp(a*x_t - s*v_hat, -1, 1)        -- fp32, each op rounded; l1 and tv act on it as above
+ *     d total / d v_hat = 2 (v_hat - target) / n + [-1 <= raw <= 1] dL/dx0_pred * (-s)
+ * so the auxiliary gradient carries the factor s <= 1 where the eps form has s/a (up to 6.4e4).  With recon_w == tv_w == 0 d_v and
+ * mse are bit-identical to ccn_mse_loss_grad(v_hat, target) on a target materialised by those three fp32 ops, and x_t_dev is not
+ * read (it may then be NULL). */
+int ccn_diffusion_loss_grad_v(const float* v_dev, const float* noise_dev, const float* x_t_dev, const float* x0_dev,
+                              const float* a_dev, const float* s_dev, int32_t B, int32_t C, int32_t H, int32_t W,
+                              float recon_w, float tv_w, float* loss_dev /* [4]: total, mse, l1, tv */,
+                              float* d_v_dev /* may be NULL */, float* scratch_dev, void* stream);
 
 /* One torch.optim.AdamW step over a flat buffer (train/diffusion_train.py:105,138): p *= 1 - lr*wd;
  * m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr/(1-b1^step) * m / (sqrt(v)/sqrt(1-b2^step) + eps). step >= 1. */
