@@ -1126,6 +1126,22 @@ int train_backward(const char* who, ccn_trainer_t tr, const float* params_dev, f
     return CCN_OK;
 }
 
+// one launch decision as its report line (ccn_internal_train_routes; ccn_internal_conv_dgrad for the launch it made)
+std::string route_line(const RouteNote& r)
+{
+    static const char* kinds[] = {"C3S1", "C3S2", "CT4", "STEM", "HEAD"};
+    char line[192];
+    const char* kind = r.kind >= 0 && r.kind < 5 ? kinds[r.kind] : "?";
+    switch (r.what) {
+        case RN_CONV: std::snprintf(line, sizeof(line), "conv %s %s %s th=%d bn=%d n_nt=%d four=%d\n", r.v[0] ? "fwd" : "dgrad", kind, r.name, r.v[1], r.v[2], r.v[3], r.v[4]); break;
+        case RN_NORM: std::snprintf(line, sizeof(line), "norm %s slots=%d\n", r.name, r.v[0]); break;
+        case RN_GNBWD: std::snprintf(line, sizeof(line), "gnbwd C=%d HW=%d iters=%d nblk=%d tail=%d\n", r.v[0], r.v[1], r.v[2], r.v[3], r.v[4]); break;
+        case RN_WGRAD: std::snprintf(line, sizeof(line), "wgrad %s nsplit=%d tiles=%d cin=%d cout=%d\n", kind, r.v[0], r.v[1], r.v[2], r.v[3]); break;
+        default: std::snprintf(line, sizeof(line), "colsum src=%s rows=%d ygrid=%d\n", r.name, r.v[0], r.v[1]); break;
+    }
+    return line;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1158,20 +1174,8 @@ int ccn_train_backward_bucketed(ccn_trainer_t tr, const float* params_dev, float
 int ccn_internal_train_routes(ccn_trainer_t tr, char* buf, size_t cap)
 {
     if (!tr) return -1;
-    static const char* kinds[] = {"C3S1", "C3S2", "CT4", "STEM", "HEAD"};
     std::string text;
-    for (const RouteNote& r : tr->route_log) {
-        char line[192];
-        const char* kind = r.kind >= 0 && r.kind < 5 ? kinds[r.kind] : "?";
-        switch (r.what) {
-            case RN_CONV: std::snprintf(line, sizeof(line), "conv %s %s %s th=%d bn=%d n_nt=%d four=%d\n", r.v[0] ? "fwd" : "dgrad", kind, r.name, r.v[1], r.v[2], r.v[3], r.v[4]); break;
-            case RN_NORM: std::snprintf(line, sizeof(line), "norm %s slots=%d\n", r.name, r.v[0]); break;
-            case RN_GNBWD: std::snprintf(line, sizeof(line), "gnbwd C=%d HW=%d iters=%d nblk=%d tail=%d\n", r.v[0], r.v[1], r.v[2], r.v[3], r.v[4]); break;
-            case RN_WGRAD: std::snprintf(line, sizeof(line), "wgrad %s nsplit=%d tiles=%d cin=%d cout=%d\n", kind, r.v[0], r.v[1], r.v[2], r.v[3]); break;
-            default: std::snprintf(line, sizeof(line), "colsum src=%s rows=%d ygrid=%d\n", r.name, r.v[0], r.v[1]); break;
-        }
-        text += line;
-    }
+    for (const RouteNote& r : tr->route_log) text += route_line(r);
     return copy_report(text, buf, cap);
 }
 
@@ -1282,6 +1286,58 @@ int ccn_internal_colsum(int32_t dtype, const void* dy, int32_t B, int32_t HW, in
     if (scratch_bytes < bytes) return tfail(CCN_EINVAL, "ccn_internal_colsum: scratch too small: need " + std::to_string(bytes));
     const hipError_t e = launch_colsum(dtype, dy, (float*)scratch, db, B, HW, C, (hipStream_t)stream);
     if (e != hipSuccess) return tfail(CCN_EHIP, std::string("colsum: ") + hipGetErrorString(e));
+    return CCN_OK;
+}
+
+// Test hook, not part of include/ccn_hip.h: the data-gradient conv of one conv weight alone, as the step launches it.  weight_name: a conv
+// weight as ccn_train_param_info names it (the stem's is CCN_EINVAL: the image needs no gradient).  The conv's data-gradient operand is
+// repacked from params_dev by launch_pack_group on the descriptor the route consumes (the one Planner::conv puts on the step's pack
+// list), the route and the ConvArgs are Planner::conv_dgrad's and the launch is Step::conv_dgrad's, so no launch comes out of here that
+// a step could not make.  dy [B][Hdy][Wdy][Cout] NHWC in the trainer's type (the head: fp32 NCHW [B][img_ch][Hdy][Wdy], as d eps);
+// res: NULL, or -- the stride-2 conv only, whose launch adds dskip in the step -- a tensor like dx that the epilogue adds; dx
+// [B][Hdx][Wdx][Cin] NHWC is overwritten (3x3 / head: Hdy x Wdy; stride-2 conv: 2 Hdy x 2 Wdy; ConvTranspose: Hdy / 2 x Wdy / 2, both
+// even).  route: the launch's line of ccn_internal_train_routes, without the newline (snprintf-like truncation); the handle's own route
+// log is left as it was.  Every argument is checked before anything is launched; returns after the stream has drained.
+// tests/test_gpu_dgrad.py.
+int ccn_internal_conv_dgrad(ccn_trainer_t tr, const char* weight_name, const float* params_dev, const void* dy, const void* res, void* dx, int32_t B,
+                            int32_t Hdy, int32_t Wdy, void* stream, char* route, size_t route_cap)
+{
+    if (!tr || !weight_name || !params_dev || !dy || !dx) return tfail(CCN_EINVAL, "ccn_internal_conv_dgrad: null argument");
+    if (B <= 0 || Hdy <= 0 || Wdy <= 0) return tfail(CCN_EINVAL, "ccn_internal_conv_dgrad: sizes must be positive");
+    const TConvW* w = nullptr;
+    for (const TConvW& c : tr->convs)
+        if (tr->arch.params[c.pw].name == weight_name) w = &c;
+    if (!w) return tfail(CCN_EINVAL, std::string("ccn_internal_conv_dgrad: no conv weight named ") + weight_name);
+    if (w->kind == KIND_STEM) return tfail(CCN_EINVAL, "ccn_internal_conv_dgrad: the stem has no data gradient");
+    if (w->kind == KIND_CT4 && (Hdy % 2 || Wdy % 2)) return tfail(CCN_EINVAL, "ccn_internal_conv_dgrad: the ConvTranspose's gradient needs even Hdy and Wdy");
+    if (res && w->kind != KIND_C3S2) return tfail(CCN_EINVAL, "ccn_internal_conv_dgrad: only the stride-2 conv's gradient adds a residual in the step");
+    StepPlan pl;
+    pl.B = B; pl.H = Hdy; pl.W = Wdy;
+    const ConvPlan c = Planner(tr, pl).conv_dgrad(*w, Hdy, Wdy, res != nullptr);   // (leaves the operand's descriptor on pl.pack_list)
+    hipStream_t st = (hipStream_t)stream;
+    PackDesc* desc = nullptr;
+    if (hipMalloc((void**)&desc, sizeof(PackDesc)) != hipSuccess) return tfail(CCN_EHIP, "ccn_internal_conv_dgrad: hipMalloc failed");
+    std::string err;
+    if (hipMemcpy(desc, &pl.pack_list.back(), sizeof(PackDesc), hipMemcpyHostToDevice) != hipSuccess) err = "descriptor upload failed";
+    if (err.empty()) {
+        const hipError_t e = launch_pack_group(tr->cfg.dtype, params_dev, desc, 1, st);
+        if (e != hipSuccess) err = std::string("pack: ") + hipGetErrorString(e);
+    }
+    if (err.empty()) {
+        Step s(tr, pl, nullptr, st, params_dev, nullptr);
+        const size_t logged = tr->route_log.size();
+        if (!s.conv_dgrad(c, dy, dx, res)) err = s.err;
+        if (tr->route_log.size() > logged) {
+            std::string line = route_line(tr->route_log.back());
+            if (!line.empty() && line.back() == '\n') line.pop_back();
+            copy_report(line, route, route_cap);
+            tr->route_log.resize(logged);
+        }
+    }
+    const hipError_t se = hipStreamSynchronize(st);                       // the descriptor is read by the pack kernel
+    (void)hipFree(desc);
+    if (!err.empty()) return tfail(CCN_EHIP, "ccn_internal_conv_dgrad: " + err);
+    if (se != hipSuccess) return tfail(CCN_EHIP, std::string("ccn_internal_conv_dgrad: ") + hipGetErrorString(se));
     return CCN_OK;
 }
 
