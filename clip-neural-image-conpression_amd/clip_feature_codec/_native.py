@@ -173,8 +173,8 @@ class Workspace:
         base = self.buf.data_ptr()
         self.ptr = (base + 255) // 256 * 256
         self.nbytes = nbytes
-        self.eps: Optional[torch.Tensor] = None     # NativeUNet.sample_guided: the eps of both halves, kept with the workspace
-        # NativeUNet.sample_ms / sample_guided_ms: the x0 history of one state, likewise -- by element count, because the slot is keyed
+        self.eps: Optional[torch.Tensor] = None     # NativeUNet.sample, guided: the eps of both halves, kept with the workspace
+        # NativeUNet.sample, multistep: the x0 history of one state, likewise -- by element count, because the slot is keyed
         # by the PLAN's batch: a guided call of batch B (history of B rows) and an unguided one of batch 2B (2B rows) share it
         self.hist: Dict[int, torch.Tensor] = {}
 
@@ -286,42 +286,16 @@ class NativeUNet:
                                        ws.ptr, ws.nbytes, current_stream(x.device)))
         return out
 
-    def sample(self, z: torch.Tensor, x_T: torch.Tensor, ts, coef, use_graph: bool = True, slot: int = 0,
-               sigma=None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``sigma`` (steps,) + ``noise`` (steps, B, C, H, W) fp32 on the device: the eta > 0 loop (ccn_sample_eta)."""
-        import numpy as np
-        z = require_dev(z, "z_clip"); x_T = require_dev(x_T, "x_T")
-        B, C, H, W = x_T.shape
-        ts = np.ascontiguousarray(ts, dtype=np.int32)
-        coef = np.ascontiguousarray(coef, dtype=np.float32)
-        steps = int(ts.shape[0])
-        if coef.shape != (steps, 4):
-            raise ValueError("coef must be (steps, 4)")
-        if C != self.img_ch or z.shape != (B, self.z_dim):
-            raise ValueError(f"shape mismatch: x_T {tuple(x_T.shape)}, z {tuple(z.shape)}")
-        ws = self.workspace(B, H, W, steps, slot)
-        out = torch.empty_like(x_T)
-        with torch.cuda.device(x_T.device):
-            if sigma is not None:
-                sigma = np.ascontiguousarray(sigma, dtype=np.float32)
-                noise = require_dev(noise, "noise")
-                if sigma.shape != (steps,) or tuple(noise.shape) != (steps, B, C, H, W):
-                    raise ValueError(f"sigma must be ({steps},) and noise ({steps}, {B}, {C}, {H}, {W})")
-                check(self.lib.ccn_sample_eta(self.h, z.data_ptr(), x_T.data_ptr(), out.data_ptr(), B, H, W, steps,
-                                              ts.ctypes.data, coef.ctypes.data, sigma.ctypes.data, noise.data_ptr(), ws.ptr, ws.nbytes,
-                                              current_stream(x_T.device), 1 if use_graph else 0))
-            else:
-                check(self.lib.ccn_sample(self.h, z.data_ptr(), x_T.data_ptr(), out.data_ptr(), B, H, W, steps,
-                                          ts.ctypes.data, coef.ctypes.data, ws.ptr, ws.nbytes,
-                                          current_stream(x_T.device), 1 if use_graph else 0))
-        return out
-
-    def sample_guided(self, z: torch.Tensor, x_T: torch.Tensor, ts, coef, w: float, z_null: Optional[torch.Tensor] = None,
-                      use_graph: bool = True, slot: int = 0, sigma=None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The DDIM loop under classifier-free guidance of scale ``w`` (ccn_sample_guided): the plan and the workspace of batch 2B,
-        ``z`` in the first half, ``z_null`` (``(z_dim,)``; None: zeros) in the second.  ``sigma`` / ``noise`` as for ``sample``,
-        ``noise`` of ``(steps, B, C, H, W)``: one set of draws for both halves.  The eps scratch of the 2B rows is kept with the
-        workspace, so that a later call replays the graph captured with its address."""
+    def sample(self, z: torch.Tensor, x_T: torch.Tensor, ts, coef, use_graph: bool = True, slot: int = 0, sigma=None,
+               noise: Optional[torch.Tensor] = None, w: Optional[float] = None, z_null: Optional[torch.Tensor] = None,
+               hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Every step of a sampler inside the library, through the ``ccn_sample*`` entry that fits.  ``coef`` of ``(steps, 4)``: the
+        DDIM loop; ``sigma`` (steps,) + ``noise`` (steps, B, C, H, W) fp32 on the device make it the eta > 0 one.  ``coef`` of
+        ``(steps, 5)``: the multistep loop (``NoiseScheduler.solver_coefficients``; deterministic), ``hist`` its x0 history, fp32 of
+        ``x_T``'s size.  ``w``: a classifier-free guidance scale (None: unguided) -- the plan and the workspace are then of batch 2B,
+        ``z`` in the first half, ``z_null`` (``(z_dim,)``; None: zeros) in the second, ``noise`` and ``hist`` still of ONE state.  The
+        eps scratch of the 2B rows and, with ``hist=None``, the history are kept with the workspace, so that a later call replays
+        the graph captured with their addresses."""
         import math
         import numpy as np
         z = require_dev(z, "z_clip"); x_T = require_dev(x_T, "x_T")
@@ -329,89 +303,51 @@ class NativeUNet:
         ts = np.ascontiguousarray(ts, dtype=np.int32)
         coef = np.ascontiguousarray(coef, dtype=np.float32)
         steps = int(ts.shape[0])
-        if coef.shape != (steps, 4):
+        ms = coef.shape == (steps, 5)
+        if hist is not None and not ms:
+            raise ValueError("coef must be (steps, 5)")
+        if not ms and coef.shape != (steps, 4):
             raise ValueError("coef must be (steps, 4)")
         if C != self.img_ch or z.shape != (B, self.z_dim):
             raise ValueError(f"shape mismatch: x_T {tuple(x_T.shape)}, z {tuple(z.shape)}")
-        if not math.isfinite(float(w)):
+        if ms and (sigma is not None or noise is not None):
+            raise ValueError("the multistep sampler is deterministic: no sigma / noise")
+        if w is not None and not math.isfinite(float(w)):
             raise ValueError(f"the guidance scale must be finite, got {w}")
-        if z_null is not None:
+        if w is not None and z_null is not None:
             z_null = require_dev(z_null, "null_z")
             if tuple(z_null.shape) != (self.z_dim,):
                 raise ValueError(f"null_z must be ({self.z_dim},), got {tuple(z_null.shape)}")
-        sig_p = None
         if sigma is not None:
             sigma = np.ascontiguousarray(sigma, dtype=np.float32)
             noise = require_dev(noise, "noise")
             if sigma.shape != (steps,) or tuple(noise.shape) != (steps, B, C, H, W):
                 raise ValueError(f"sigma must be ({steps},) and noise ({steps}, {B}, {C}, {H}, {W})")
-            sig_p = sigma.ctypes.data
-        ws = self.workspace(2 * B, H, W, steps, slot)
-        if ws.eps is None:
-            ws.eps = torch.empty((2 * B, C, H, W), dtype=torch.float32, device=self.device)
-        out = torch.empty_like(x_T)
-        with torch.cuda.device(x_T.device):
-            check(self.lib.ccn_sample_guided(self.h, z.data_ptr(), ptr(z_null), x_T.data_ptr(), out.data_ptr(), B, H, W, steps,
-                                             ts.ctypes.data, coef.ctypes.data, sig_p, ptr(noise) if sigma is not None else None, float(w),
-                                             ws.eps.data_ptr(), ws.ptr, ws.nbytes, current_stream(x_T.device), 1 if use_graph else 0))
-        return out
-
-    def _ms_args(self, z, x_T, ts, coef, hist):
-        import numpy as np
-        z = require_dev(z, "z_clip"); x_T = require_dev(x_T, "x_T")
-        B, C, H, W = x_T.shape
-        ts = np.ascontiguousarray(ts, dtype=np.int32)
-        coef = np.ascontiguousarray(coef, dtype=np.float32)
-        steps = int(ts.shape[0])
-        if coef.shape != (steps, 5):
-            raise ValueError("coef must be (steps, 5)")
-        if C != self.img_ch or z.shape != (B, self.z_dim):
-            raise ValueError(f"shape mismatch: x_T {tuple(x_T.shape)}, z {tuple(z.shape)}")
         if hist is not None and not (isinstance(hist, torch.Tensor) and hist.is_cuda and hist.dtype == torch.float32 and hist.is_contiguous()
                                      and hist.numel() == x_T.numel() and hist.data_ptr() % 16 == 0):
             raise ValueError(f"hist must be a contiguous, 16-byte aligned fp32 HIP tensor of {x_T.numel()} elements")
-        return z, x_T, ts, coef, steps
-
-    def sample_ms(self, z: torch.Tensor, x_T: torch.Tensor, ts, coef, use_graph: bool = True, slot: int = 0,
-                  hist: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The multistep loop (ccn_sample_ms): ``coef`` of ``(steps, 5)``, see ``NoiseScheduler.solver_coefficients``.  ``hist``: the
-        x0 history, fp32 of ``x_T``'s size; None: one kept with the workspace, so that a later call replays the graph captured with
-        its address."""
-        z, x_T, ts, coef, steps = self._ms_args(z, x_T, ts, coef, hist)
-        B, C, H, W = x_T.shape
-        ws = self.workspace(B, H, W, steps, slot)
-        if hist is None:
-            hist = ws.history(x_T)
-        out = torch.empty_like(x_T)
-        with torch.cuda.device(x_T.device):
-            check(self.lib.ccn_sample_ms(self.h, z.data_ptr(), x_T.data_ptr(), out.data_ptr(), B, H, W, steps, ts.ctypes.data,
-                                         coef.ctypes.data, hist.data_ptr(), ws.ptr, ws.nbytes, current_stream(x_T.device),
-                                         1 if use_graph else 0))
-        return out
-
-    def sample_guided_ms(self, z: torch.Tensor, x_T: torch.Tensor, ts, coef, w: float, z_null: Optional[torch.Tensor] = None,
-                         use_graph: bool = True, slot: int = 0, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The multistep loop under classifier-free guidance of scale ``w`` (ccn_sample_guided_ms): ``sample_guided``'s plan and
-        workspace of batch 2B, ``coef`` and ``hist`` (of ONE state, ``x_T``'s size) as for ``sample_ms``."""
-        import math
-        z, x_T, ts, coef, steps = self._ms_args(z, x_T, ts, coef, hist)
-        B, C, H, W = x_T.shape
-        if not math.isfinite(float(w)):
-            raise ValueError(f"the guidance scale must be finite, got {w}")
-        if z_null is not None:
-            z_null = require_dev(z_null, "null_z")
-            if tuple(z_null.shape) != (self.z_dim,):
-                raise ValueError(f"null_z must be ({self.z_dim},), got {tuple(z_null.shape)}")
-        ws = self.workspace(2 * B, H, W, steps, slot)
-        if ws.eps is None:
+        ws = self.workspace(B if w is None else 2 * B, H, W, steps, slot)
+        if w is not None and ws.eps is None:
             ws.eps = torch.empty((2 * B, C, H, W), dtype=torch.float32, device=self.device)
-        if hist is None:
+        if ms and hist is None:
             hist = ws.history(x_T)
         out = torch.empty_like(x_T)
+        # every entry's arguments: (h, z[, z_null], x_T, out, B, H, W, steps, ts, coef, <its own>, workspace, bytes, stream, use_graph)
+        zn = () if w is None else (ptr(z_null),)
+        head = (self.h, z.data_ptr(), *zn, x_T.data_ptr(), out.data_ptr(), B, H, W, steps, ts.ctypes.data, coef.ctypes.data)
+        tail = (ws.ptr, ws.nbytes, current_stream(x_T.device), 1 if use_graph else 0)
+        eta = (sigma.ctypes.data, noise.data_ptr()) if sigma is not None else (None, None)
         with torch.cuda.device(x_T.device):
-            check(self.lib.ccn_sample_guided_ms(self.h, z.data_ptr(), ptr(z_null), x_T.data_ptr(), out.data_ptr(), B, H, W, steps,
-                                                ts.ctypes.data, coef.ctypes.data, float(w), ws.eps.data_ptr(), hist.data_ptr(), ws.ptr,
-                                                ws.nbytes, current_stream(x_T.device), 1 if use_graph else 0))
+            if ms and w is None:
+                check(self.lib.ccn_sample_ms(*head, hist.data_ptr(), *tail))
+            elif ms:
+                check(self.lib.ccn_sample_guided_ms(*head, float(w), ws.eps.data_ptr(), hist.data_ptr(), *tail))
+            elif w is not None:
+                check(self.lib.ccn_sample_guided(*head, *eta, float(w), ws.eps.data_ptr(), *tail))
+            elif sigma is not None:
+                check(self.lib.ccn_sample_eta(*head, *eta, *tail))
+            else:
+                check(self.lib.ccn_sample(*head, *tail))
         return out
 
     def resblock(self, prefix: str, x: torch.Tensor, h: torch.Tensor) -> torch.Tensor:

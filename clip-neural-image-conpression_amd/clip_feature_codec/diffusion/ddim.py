@@ -7,7 +7,7 @@ Interface of ``diffusion/ddim.py:14-45`` of the reference.  Two execution routes
   for all steps is hoisted in front of the loop, and the ``steps`` UNet evaluations + DDIM updates
   replay as ONE captured hipGraph (``ccn_sample``; ``eta > 0``: ``ccn_sample_eta``, the N(0,1) draws of all steps made up
   front, one ``normal_()`` per noisy step in loop order, so the torch generator is consumed exactly as by the stepwise loop).
-* stepwise -- any other callable ``model(x, z, t)``: one ``model`` call and one ``ccn_ddim_step`` kernel per step; the
+* stepwise -- any other callable ``model(x, z, t)``: one ``model`` call and one ``ccn_sampler_step`` kernel per step; the
   ``eta > 0`` noise comes from ``torch.randn_like`` on the device.
 
 Reference behaviours kept on purpose: ``ts = linspace(T-1, 0, steps).long()``; ``alpha_bar_prev`` is
@@ -20,8 +20,8 @@ uses ``eps = eps_u + cfg_scale * (eps_c - eps_u)``, ``eps_c`` the prediction wit
 embedding ``null_z`` (``(z_dim,)``; None: zeros, what ``train_step(..., z_drop=p)`` trains).  ``cfg_scale == 1.0`` takes the
 unguided route, same bits.  Otherwise the fused route is ``ccn_sample_guided`` -- the same captured loop at batch 2B, the state
 held twice, one combine-and-update launch per step; ``slot``, ``use_graph`` and the ``eta > 0`` draws (one set, shared by both
-halves) as above -- and the stepwise route calls ``model(x, z, t)`` and ``model(x, z_null, t)`` per step, then
-``ccn_cfg_ddim_step``.  A non-finite ``cfg_scale`` or a ``null_z`` of another shape is a ``ValueError``.
+halves) as above -- and the stepwise route calls ``model(x, z, t)`` and ``model(x, z_null, t)`` per step and hands both to the
+same ``ccn_sampler_step``.  A non-finite ``cfg_scale`` or a ``null_z`` of another shape is a ``ValueError``.
 
 ``DDIMSampler(..., prediction="v")`` (no reference counterpart; default ``"eps"``) is for a network trained to predict
 ``v = sqrt(ab_t) noise - sqrt(1-ab_t) x0`` (``train_step(..., prediction="v")``): everything above that says ``eps`` then holds for the
@@ -31,12 +31,12 @@ how the weights were trained; an unknown string is a ``ValueError``.
 """
 from __future__ import annotations
 
-import math
 from typing import Optional
 
 import torch
 
 from .. import _native
+from . import guidance
 
 
 class DDIMSampler:
@@ -55,27 +55,13 @@ class DDIMSampler:
         self.use_graph = True
         self._noise: dict = {}
 
-    def _guidance(self, z_clip: torch.Tensor, cfg_scale: float):
-        """(scale, null row on z_clip's device) of a guided call, or (None, None): unguided, or the scale is 1.0."""
-        if not self.guided:
-            return None, None
-        w = float(cfg_scale)
-        if not math.isfinite(w):
-            raise ValueError(f"cfg_scale must be finite, got {cfg_scale}")
-        null_z = self.null_z
-        if null_z is not None:
-            if not isinstance(null_z, torch.Tensor) or tuple(null_z.shape) != (z_clip.shape[-1],):
-                raise ValueError(f"null_z must be a tensor of shape ({z_clip.shape[-1]},), got {tuple(getattr(null_z, 'shape', ()))}")
-            null_z = null_z.to(z_clip.device, torch.float32)
-        return (None, None) if w == 1.0 else (w, null_z)
-
     @torch.no_grad()
     def sample(self, model, z_clip: torch.Tensor, shape: tuple, steps: int = 50, cfg_scale: float = 1.0,
                x_T: Optional[torch.Tensor] = None, slot: int = 0) -> torch.Tensor:
         device = z_clip.device
         if device.type != "cuda":
             raise RuntimeError(f"z_clip is on {device}: DDIMSampler (MI355X build) needs a HIP device; no CPU fallback")
-        w, null_z = self._guidance(z_clip, cfg_scale)
+        w, null_z = guidance.resolve(self.guided, self.null_z, z_clip, cfg_scale)
         ts = self.sch.ddim_timesteps(steps)
         coef = self.sch.ddim_coefficients(steps, self.eta)
         x = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
@@ -111,10 +97,5 @@ class DDIMSampler:
             eps_u = model(x, z_u, t_b) if w is not None else None
             sigma = float(coef[i, 4])
             noise = torch.randn_like(x) if (self.eta > 0 and sigma > 0) else None
-            if self.prediction != "eps":
-                _native.sampler_step(x, eps, coef[i, :4], self.prediction, out_u=eps_u, w=w or 0.0, sigma=sigma, noise=noise)
-            elif w is None:
-                _native.ddim_step(x, eps, coef[i, :4], sigma, noise)
-            else:
-                _native.cfg_ddim_step(x, eps, eps_u, w, coef[i, :4], sigma, noise)
+            _native.sampler_step(x, eps, coef[i, :4], self.prediction, out_u=eps_u, w=w or 0.0, sigma=sigma, noise=noise)
         return x

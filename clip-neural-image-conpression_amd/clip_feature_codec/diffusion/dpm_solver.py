@@ -19,8 +19,8 @@ spacing the method is designed for.  Targets that snap to the same table timeste
 ``order=1`` is the same loop without the correction term.  The sampler is deterministic: no ``eta``.
 
 Two routes as in ``DDIMSampler``: fused (``model.sample_ddim`` -> ``ccn_sample_ms`` / ``ccn_sample_guided_ms``, one captured graph)
-and stepwise for any callable ``model(x, z, t)`` (one model call per step, two when guided, then ``ccn_ms_step`` /
-``ccn_cfg_ms_step``).  ``guided=True`` with ``cfg_scale == 1.0`` takes the unguided route.
+and stepwise for any callable ``model(x, z, t)`` (one model call per step, two when guided, then ``ccn_sampler_step``).
+``guided=True`` with ``cfg_scale == 1.0`` takes the unguided route.
 
 ``prediction="v"`` (default ``"eps"``): the network output is ``v = a_t noise - s_t x0``; the first line of the step becomes
 ``x0 = clamp(a_t x - s_t v, -1, 1)``, ``e = s_t x + a_t v`` on the same tables, the rest is unchanged (``ccn_set_prediction`` on the
@@ -28,12 +28,12 @@ fused route, ``ccn_sampler_step`` on the stepwise one).  It must match how the w
 """
 from __future__ import annotations
 
-import math
 from typing import Optional
 
 import torch
 
 from .. import _native
+from . import guidance
 
 _SPACINGS = ("logsnr", "linspace")
 
@@ -63,25 +63,11 @@ class DPMSolverSampler:
         ts = self.sch.solver_timesteps(steps, self.spacing)
         return ts, self.sch.solver_coefficients(ts, self.order)
 
-    def _guidance(self, z_clip: torch.Tensor, cfg_scale: float):
-        """(scale, null row on z_clip's device) of a guided call, or (None, None): unguided, or the scale is 1.0."""
-        if not self.guided:
-            return None, None
-        w = float(cfg_scale)
-        if not math.isfinite(w):
-            raise ValueError(f"cfg_scale must be finite, got {cfg_scale}")
-        null_z = self.null_z
-        if null_z is not None:
-            if not isinstance(null_z, torch.Tensor) or tuple(null_z.shape) != (z_clip.shape[-1],):
-                raise ValueError(f"null_z must be a tensor of shape ({z_clip.shape[-1]},), got {tuple(getattr(null_z, 'shape', ()))}")
-            null_z = null_z.to(z_clip.device, torch.float32)
-        return (None, None) if w == 1.0 else (w, null_z)
-
     @torch.no_grad()
     def sample(self, model, z_clip: torch.Tensor, shape: tuple, steps: int = 20, cfg_scale: float = 1.0,
                x_T: Optional[torch.Tensor] = None, slot: int = 0) -> torch.Tensor:
         ts, coef = self.tables(steps)
-        w, null_z = self._guidance(z_clip, cfg_scale)
+        w, null_z = guidance.resolve(self.guided, self.null_z, z_clip, cfg_scale)
         device = z_clip.device
         if device.type != "cuda":
             raise RuntimeError(f"z_clip is on {device}: DPMSolverSampler (MI355X build) needs a HIP device; no CPU fallback")
@@ -99,10 +85,5 @@ class DPMSolverSampler:
         for i in range(len(ts)):
             t_b = torch.full((shape[0],), int(ts[i]), device=device, dtype=torch.long)
             eps = model(x, z_clip, t_b)
-            if self.prediction != "eps":
-                _native.sampler_step(x, eps, coef[i], self.prediction, out_u=None if w is None else model(x, z_u, t_b), w=w or 0.0, hist=hist)
-            elif w is None:
-                _native.ms_step(x, hist, eps, coef[i])
-            else:
-                _native.cfg_ms_step(x, hist, eps, model(x, z_u, t_b), w, coef[i])
+            _native.sampler_step(x, eps, coef[i], self.prediction, out_u=None if w is None else model(x, z_u, t_b), w=w or 0.0, hist=hist)
         return x

@@ -166,24 +166,17 @@ class CLIPCondUNet(nn.Module):
                     use_graph: bool = True, slot: int = 0, sigma=None, noise: Optional[torch.Tensor] = None,
                     guidance: Optional[float] = None, null_z: Optional[torch.Tensor] = None, c4=None,
                     prediction: str = "eps") -> torch.Tensor:
-        """All DDIM steps (eta = 0) inside the library; see ``ccn_sample`` in include/ccn_hip.h.  ``slot`` selects an independent
-        workspace / captured graph, so that consecutive batches can be in flight on different streams.  ``guidance``: a
-        classifier-free guidance scale; the loop then runs at batch 2B, the second half on ``null_z`` (``(z_dim,)``; None: zeros),
-        see ``ccn_sample_guided``.  ``c4``: a fifth coefficient column ``(steps,)`` -- the loop is then the multistep sampler's
-        (``ccn_sample_ms`` / ``ccn_sample_guided_ms``, eta = 0 only; ``NoiseScheduler.solver_coefficients``).  ``prediction``: what
-        this network's output is, ``"eps"`` or ``"v"`` (``ccn_set_prediction``; the tables are the same)."""
+        """All sampler steps inside the library (``NativeUNet.sample``; the ``ccn_sample*`` entries in include/ccn_hip.h).  ``slot``
+        selects an independent workspace / captured graph, so that consecutive batches can be in flight on different streams.
+        ``sigma`` / ``noise``: the eta > 0 loop.  ``guidance``: a classifier-free guidance scale; the loop then runs at batch 2B, the
+        second half on ``null_z`` (``(z_dim,)``; None: zeros).  ``c4``: a fifth coefficient column ``(steps,)`` -- the loop is then
+        the multistep sampler's (eta = 0 only; ``NoiseScheduler.solver_coefficients``).  ``prediction``: what this network's output
+        is, ``"eps"`` or ``"v"`` (``ccn_set_prediction``; the tables are the same)."""
         nat = self.native(x_T.device)
         nat.set_prediction(prediction)
         if c4 is not None:
-            if sigma is not None or noise is not None:
-                raise ValueError("the multistep sampler is deterministic: no sigma / noise")
-            coef5 = np.concatenate([np.asarray(coef, np.float32).reshape(-1, 4), np.asarray(c4, np.float32).reshape(-1, 1)], axis=1)
-            if guidance is None:
-                return nat.sample_ms(z_clip, x_T, ts, coef5, use_graph=use_graph, slot=slot)
-            return nat.sample_guided_ms(z_clip, x_T, ts, coef5, guidance, z_null=null_z, use_graph=use_graph, slot=slot)
-        if guidance is None:
-            return nat.sample(z_clip, x_T, ts, coef, use_graph=use_graph, slot=slot, sigma=sigma, noise=noise)
-        return nat.sample_guided(z_clip, x_T, ts, coef, guidance, z_null=null_z, use_graph=use_graph, slot=slot, sigma=sigma, noise=noise)
+            coef = np.concatenate([np.asarray(coef, np.float32).reshape(-1, 4), np.asarray(c4, np.float32).reshape(-1, 1)], axis=1)
+        return nat.sample(z_clip, x_T, ts, coef, use_graph=use_graph, slot=slot, sigma=sigma, noise=noise, w=guidance, z_null=null_z)
 
     def read_activation(self, name: str, shape) -> torch.Tensor:
         return self.native().read_activation(name, tuple(shape))

@@ -147,18 +147,40 @@ struct ShapePlan {
     std::vector<RouteRec> routes;        // every conv-family launch of `ops`, in order
 };
 
-struct GraphEntry {
+// One run of a sampler loop (the ccn_sample* entry points): what the step loop is a function of besides the handle, the shape and the
+// tensors.  The host tables are copies, so the record of a captured run outlives the call (GraphEntry).
+struct SamplerRun {
     int steps = 0;
     std::vector<int32_t> ts;
-    std::vector<float> coef;
+    std::vector<float> coef;             // [steps][4]
     std::vector<float> sigma;            // eta > 0 (empty: eta = 0)
-    const float* noise = nullptr;        // ... and the address of the caller's noise tensor the graph was captured with
-    bool guided = false;                 // ccn_sample_guided: the plan's batch is two halves, and each step ends in the combine launch
-    float w = 0.f;                       // ... whose by-value guidance scale
-    const float* eps = nullptr;          // ... and eps scratch address the graph was captured with
-    std::vector<float> c4;               // multistep sampler (empty: none): the fifth coefficient column
-    const float* hist = nullptr;         // ... and the x0 history address the graph was captured with
-    int pred = CCN_PRED_EPS;             // ccn_set_prediction at capture time: the update form is baked into the captured launches
+    const float* noise = nullptr;        // ... and the caller's noise tensor, [steps] x one state
+    // Classifier-free guidance: the plan's batch is 2B rows -- [0, B) carry z, [B, 2B) the null embedding, both the same state -- the
+    // head writes the raw network output of all 2B rows into `eps` (whatever it predicts: the combine launch applies the handle's
+    // parameterisation), and one combine launch per step updates both halves of the state.
+    bool guided = false;
+    const float* z_null = nullptr;       // one row (null: zeros), copied into the workspace on every call
+    float w = 0.f;                       // the by-value guidance scale of the combine launch
+    float* eps = nullptr;
+    // The multistep sampler: per step the coefficient c4 of (x0 - previous x0) (empty: none), and the caller's history tensor of one
+    // state (B rows, also when guided), which the updating launch of every step reads (c4 != 0) and rewrites.
+    std::vector<float> c4;
+    float* hist = nullptr;
+    int pred = CCN_PRED_EPS;             // the handle's ccn_set_prediction at call time: the update form is baked into the launches
+
+    // Does a graph captured for `o` replay this run?  Everything a captured launch holds by value or by address; not z_null.
+    bool same_graph(const SamplerRun& o) const
+    {
+        auto same = [](const auto& a, const auto& b) {              // two tables, bit for bit
+            return a.size() == b.size() && (a.empty() || !std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])));
+        };
+        return steps == o.steps && same(ts, o.ts) && same(coef, o.coef) && noise == o.noise && same(sigma, o.sigma) &&
+               guided == o.guided && (!guided || (w == o.w && eps == o.eps)) && hist == o.hist && same(c4, o.c4) && pred == o.pred;
+    }
+};
+
+struct GraphEntry {
+    SamplerRun run;                      // the run it was captured for
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     void destroy() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); }   // (after draining the device)
@@ -845,53 +867,33 @@ int run_conditioning(ccn_handle_s* h, const Binding* b, hipStream_t s, const int
     return timed(h, F_COND, 2.0 * FR * td * (double)F, 0, s, [&] { return launch_linear(tp, zp, a_div, B, h->film_w, h->film_b, f32(p.film), FR, td, F, 0, s); });
 }
 
-// Classifier-free guidance (ccn_sample_guided): the plan's batch is 2B rows -- [0, B) carry z, [B, 2B) the null embedding, both the
-// same state -- the head writes eps of all 2B rows into `eps`, and one combine launch per step updates both halves of the state.
-// (`eps` holds the raw network output of the 2B rows whatever it predicts: the combine launch applies the handle's parameterisation.)
-struct Guide { const float* z_null; float w; float* eps; };
-// The multistep sampler (ccn_sample_ms, ccn_sample_guided_ms): per step the coefficient c4 of (x0 - previous x0), and the caller's
-// history tensor of one state (B rows, also when guided), which the updating launch of every step reads (c4 != 0) and rewrites.
-struct MultiStep { const float* c4; float* hist; };
-
-int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, int steps, const float* coef, const float* sigma = nullptr, const float* noise = nullptr,
-              const Guide* gd = nullptr, const MultiStep* ms = nullptr)
+int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, const SamplerRun& r)
 {
     const ShapePlan& p = *b->plan;
-    const size_t img = (size_t)(gd ? p.B / 2 : p.B) * h->cfg.img_ch * p.H * p.W;     // one state (and one step's draws)
+    const size_t img = (size_t)(r.guided ? p.B / 2 : p.B) * h->cfg.img_ch * p.H * p.W;     // one state (and one step's draws)
+    const bool ms = !r.c4.empty();
     float* xstate = (float*)(b->ws + p.xstate);
-    for (int i = 0; i < steps; ++i) {
-        const bool noisy = sigma && noise && sigma[i] > 0.f;
+    for (int i = 0; i < r.steps; ++i) {
+        const float* cf = r.coef.data() + i * 4;
+        const float c4 = ms ? r.c4[i] : 0.f;
+        const bool noisy = !r.sigma.empty() && r.noise && r.sigma[i] > 0.f;
+        const float* nz = noisy ? r.noise + (size_t)i * img : nullptr;
+        const float sigma = noisy ? r.sigma[i] : 0.f;
         StepCtx c;
         c.step = i; c.x_in = xstate;
-        if (gd) { c.x_state = nullptr; c.eps_out = gd->eps; c.do_ddim = 0; }
+        if (r.guided) { c.x_state = nullptr; c.eps_out = r.eps; c.do_ddim = 0; }
         else {
             c.x_state = xstate; c.eps_out = nullptr; c.do_ddim = 1;
-            for (int k = 0; k < 4; ++k) c.c[k] = coef[i * 4 + k];
-            if (noisy) { c.noise = noise + (size_t)i * img; c.sigma = sigma[i]; }
-            if (ms) { c.x0_hist = ms->hist; c.c4 = ms->c4[i]; }
+            for (int k = 0; k < 4; ++k) c.c[k] = cf[k];
+            if (noisy) { c.noise = nz; c.sigma = sigma; }
+            if (ms) { c.x0_hist = r.hist; c.c4 = c4; }
         }
         if (int rc = run_ops(h, b, s, c)) return rc;
-        if (gd && h->pred != CCN_PRED_EPS) {
-            // the v form: one kernel for the plain and the multistep combine (the eps forms below keep their own launches)
-            const float* cf = coef + i * 4;
-            const float c4 = ms ? ms->c4[i] : 0.f;
-            const float* nz = noisy ? noise + (size_t)i * img : nullptr;
+        // guided: the combine and the update of both halves (unguided, the update is the head kernel's epilogue)
+        if (r.guided)
             if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * (5 + (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0)), s, [&] {
-                    return launch_sampler_step(xstate, xstate + img, ms ? ms->hist : nullptr, gd->eps, gd->eps + img, nz, h->pred, gd->w, cf[0],
-                                               cf[1], cf[2], cf[3], c4, noisy ? sigma[i] : 0.f, (int64_t)img, s); })) return rc;
-        } else if (gd && ms) {
-            const float* cf = coef + i * 4;
-            const float c4 = ms->c4[i];
-            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * (c4 != 0.f ? 7 : 6), s, [&] {
-                    return launch_cfg_ms_step(xstate, xstate + img, ms->hist, gd->eps, gd->eps + img, gd->w, cf[0], cf[1], cf[2], cf[3], c4,
-                                              (int64_t)img, s); })) return rc;
-        } else if (gd) {
-            const float* cf = coef + i * 4;
-            const float* nz = noisy ? noise + (size_t)i * img : nullptr;
-            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * (nz ? 6 : 5), s, [&] {
-                    return launch_cfg_ddim_step(xstate, xstate + img, gd->eps, gd->eps + img, nz, gd->w, cf[0], cf[1], cf[2], cf[3],
-                                                noisy ? sigma[i] : 0.f, (int64_t)img, s); })) return rc;
-        }
+                    return launch_sampler_step(xstate, xstate + img, ms ? r.hist : nullptr, r.eps, r.eps + img, nz, h->pred, r.w, cf[0], cf[1],
+                                               cf[2], cf[3], c4, sigma, (int64_t)img, s); })) return rc;
     }
     return CCN_OK;
 }
@@ -1166,16 +1168,26 @@ int ccn_forward(ccn_handle_t h, const float* x_dev, const float* z_dev, const in
     return run_ops(h, b, s, c);
 }
 
-static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H, int32_t W,
-                       int32_t steps, const int32_t* ts_host, const float* coef_host, const float* sigma_host, const float* noise_dev,
-                       void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph, const Guide* gd = nullptr,
-                       const MultiStep* ms = nullptr)
+// the checks every ccn_sample* entry starts with, and the run's host tables (`coef`: [steps][4]; `sigma` nullable) copied into `r`
+static int begin_run(ccn_handle_t h, int32_t steps, const int32_t* ts_host, const float* coef_host, const float* sigma_host, SamplerRun& r)
 {
-    int rc = check_ready(h);
-    if (rc) return rc;
-    if (!z_dev || !x_T_dev || !x_out_dev || !ts_host || !coef_host) return fail(CCN_EINVAL, "null pointer");
-    if (gd && (B <= 0 || B > INT32_MAX / 2)) return fail(CCN_EINVAL, "B, H, W, steps must be positive");
-    const int PB = gd ? 2 * B : B;                                  // the plan's batch: guided, the two halves
+    if (int rc = check_ready(h)) return rc;
+    if (!ts_host || !coef_host) return fail(CCN_EINVAL, "null pointer");
+    const size_t n = steps > 0 ? (size_t)steps : 0;                 // (steps <= 0 is get_binding's error)
+    r.steps = steps; r.pred = h->pred;
+    r.ts.assign(ts_host, ts_host + n); r.coef.assign(coef_host, coef_host + n * 4);
+    if (sigma_host) r.sigma.assign(sigma_host, sigma_host + n);
+    return CCN_OK;
+}
+
+static int sample_impl(ccn_handle_t h, const SamplerRun& r, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H,
+                       int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph)
+{
+    int rc;
+    if (!z_dev || !x_T_dev || !x_out_dev) return fail(CCN_EINVAL, "null pointer");
+    if (r.guided && (B <= 0 || B > INT32_MAX / 2)) return fail(CCN_EINVAL, "B, H, W, steps must be positive");
+    const int PB = r.guided ? 2 * B : B;                            // the plan's batch: guided, the two halves
+    const int steps = r.steps;
     Binding* p = nullptr;
     if ((rc = get_binding(h, PB, H, W, steps, workspace_dev, workspace_bytes, &p))) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -1183,44 +1195,34 @@ static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev,
     float* xstate = (float*)(p->ws + p->plan->xstate);
     char* zbuf = p->ws + p->plan->zbuf;
     HIPCHK(hipMemcpyAsync(zbuf, z_dev, (size_t)B * z_row, hipMemcpyDeviceToDevice, s));
-    if (gd && !gd->z_null) HIPCHK(hipMemsetAsync(zbuf + (size_t)B * z_row, 0, (size_t)B * z_row, s));
-    if (gd && gd->z_null) {
+    if (r.guided && !r.z_null) HIPCHK(hipMemsetAsync(zbuf + (size_t)B * z_row, 0, (size_t)B * z_row, s));
+    if (r.guided && r.z_null) {
         // the null row B times: once from the caller, then doubling from the rows already there
         char* zn = zbuf + (size_t)B * z_row;
-        HIPCHK(hipMemcpyAsync(zn, gd->z_null, z_row, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(zn, r.z_null, z_row, hipMemcpyDeviceToDevice, s));
         for (int have = 1; have < B; have *= 2)
             HIPCHK(hipMemcpyAsync(zn + (size_t)have * z_row, zn, (size_t)std::min(have, B - have) * z_row, hipMemcpyDeviceToDevice, s));
     }
     if (x_T_dev != xstate) HIPCHK(hipMemcpyAsync(xstate, x_T_dev, img_bytes, hipMemcpyDeviceToDevice, s));
-    if (gd) HIPCHK(hipMemcpyAsync((char*)xstate + img_bytes, xstate, img_bytes, hipMemcpyDeviceToDevice, s));
+    if (r.guided) HIPCHK(hipMemcpyAsync((char*)xstate + img_bytes, xstate, img_bytes, hipMemcpyDeviceToDevice, s));
 
     // the timestep table of a binding almost never changes: upload it only when it does, and then synchronously after draining
     // the stream (an async copy out of a host vector that the next call rewrites could still be pending)
-    if (p->ts_keep.size() != (size_t)steps || std::memcmp(p->ts_keep.data(), ts_host, (size_t)steps * 4)) {
+    if (p->ts_keep != r.ts) {
         HIPCHK(hipStreamSynchronize(s));
-        p->ts_keep.assign(ts_host, ts_host + steps);
+        p->ts_keep = r.ts;
         HIPCHK(hipMemcpy(p->ws + p->plan->ts_dev, p->ts_keep.data(), (size_t)steps * 4, hipMemcpyHostToDevice));
     }
     if (use_graph && !h->profiling) {
         GraphEntry* ge = nullptr;
         for (auto& g : p->graphs)
-            if (g.steps == steps && !std::memcmp(g.ts.data(), ts_host, (size_t)steps * 4) &&
-                !std::memcmp(g.coef.data(), coef_host, (size_t)steps * 16) && g.noise == noise_dev &&
-                g.sigma.size() == (sigma_host ? (size_t)steps : 0) &&
-                (!sigma_host || !std::memcmp(g.sigma.data(), sigma_host, (size_t)steps * 4)) &&
-                g.guided == (gd != nullptr) && (!gd || (g.w == gd->w && g.eps == gd->eps)) &&
-                g.hist == (ms ? ms->hist : nullptr) && g.c4.size() == (ms ? (size_t)steps : 0) &&
-                (!ms || !std::memcmp(g.c4.data(), ms->c4, (size_t)steps * 4)) && g.pred == h->pred) { ge = &g; break; }
+            if (g.run.same_graph(r)) { ge = &g; break; }
         if (!ge) {
             GraphEntry g;
-            g.steps = steps; g.ts.assign(ts_host, ts_host + steps); g.coef.assign(coef_host, coef_host + steps * 4);
-            if (sigma_host) g.sigma.assign(sigma_host, sigma_host + steps);
-            g.noise = noise_dev; g.pred = h->pred;
-            if (gd) { g.guided = true; g.w = gd->w; g.eps = gd->eps; }
-            if (ms) { g.c4.assign(ms->c4, ms->c4 + steps); g.hist = ms->hist; }
+            g.run = r;
             HIPCHK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeRelaxed));
             rc = run_conditioning(h, p, h->cap_stream, nullptr, steps, steps * PB, PB);
-            if (!rc) rc = run_steps(h, p, h->cap_stream, steps, coef_host, sigma_host, noise_dev, gd, ms);
+            if (!rc) rc = run_steps(h, p, h->cap_stream, r);
             hipGraph_t graph = nullptr;
             const hipError_t ce = hipStreamEndCapture(h->cap_stream, &graph);
             if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -1244,7 +1246,7 @@ static int sample_impl(ccn_handle_t h, const float* z_dev, const float* x_T_dev,
         HIPCHK(hipGraphLaunch(ge->exec, s));
     } else {
         if ((rc = run_conditioning(h, p, s, nullptr, steps, steps * PB, PB))) return rc;
-        if ((rc = run_steps(h, p, s, steps, coef_host, sigma_host, noise_dev, gd, ms))) return rc;
+        if ((rc = run_steps(h, p, s, r))) return rc;
     }
     if (x_out_dev != xstate) HIPCHK(hipMemcpyAsync(x_out_dev, xstate, img_bytes, hipMemcpyDeviceToDevice, s));
     return CCN_OK;
@@ -1254,7 +1256,9 @@ int ccn_sample(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* 
                int32_t steps, const int32_t* ts_host, const float* coef_host, void* workspace_dev, size_t workspace_bytes,
                void* stream, int32_t use_graph)
 {
-    return sample_impl(h, z_dev, x_T_dev, x_out_dev, B, H, W, steps, ts_host, coef_host, nullptr, nullptr, workspace_dev, workspace_bytes, stream, use_graph);
+    SamplerRun r;
+    if (int rc = begin_run(h, steps, ts_host, coef_host, nullptr, r)) return rc;
+    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
 }
 
 int ccn_sample_eta(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H, int32_t W,
@@ -1262,7 +1266,10 @@ int ccn_sample_eta(ccn_handle_t h, const float* z_dev, const float* x_T_dev, flo
                    void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph)
 {
     if (!sigma_host || !noise_dev) return fail(CCN_EINVAL, "null sigma / noise");
-    return sample_impl(h, z_dev, x_T_dev, x_out_dev, B, H, W, steps, ts_host, coef_host, sigma_host, noise_dev, workspace_dev, workspace_bytes, stream, use_graph);
+    SamplerRun r;
+    if (int rc = begin_run(h, steps, ts_host, coef_host, sigma_host, r)) return rc;
+    r.noise = noise_dev;
+    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
 }
 
 int ccn_sample_guided(ccn_handle_t h, const float* z_dev, const float* z_null_dev, const float* x_T_dev, float* x_out_dev, int32_t B,
@@ -1273,12 +1280,14 @@ int ccn_sample_guided(ccn_handle_t h, const float* z_dev, const float* z_null_de
     if (!sigma_host != !noise_dev) return fail(CCN_EINVAL, "sigma and noise must be given together");
     if (!std::isfinite(w)) return fail(CCN_EINVAL, "the guidance scale must be finite");
     if (!eps_scratch_dev || ((uintptr_t)eps_scratch_dev & 15)) return fail(CCN_EINVAL, "the eps scratch must be non-null and 16-byte aligned");
-    const Guide gd{z_null_dev, w, eps_scratch_dev};
-    return sample_impl(h, z_dev, x_T_dev, x_out_dev, B, H, W, steps, ts_host, coef_host, sigma_host, noise_dev, workspace_dev, workspace_bytes, stream,
-                       use_graph, &gd);
+    SamplerRun r;
+    if (int rc = begin_run(h, steps, ts_host, coef_host, sigma_host, r)) return rc;
+    r.noise = noise_dev;
+    r.guided = true; r.z_null = z_null_dev; r.w = w; r.eps = eps_scratch_dev;
+    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
 }
 
-// the [steps][5] table of the multistep entries -> the [steps][4] one of sample_impl and the c4 column, checked
+// the [steps][5] table of the multistep entries -> the [steps][4] one of a SamplerRun and the c4 column, checked
 static int split_ms_table(int32_t steps, const float* coef_host, const float* x0_hist_dev, std::vector<float>& coef4, std::vector<float>& c4)
 {
     if (!coef_host || steps <= 0) return fail(CCN_EINVAL, "null pointer");
@@ -1298,11 +1307,12 @@ int ccn_sample_ms(ccn_handle_t h, const float* z_dev, const float* x_T_dev, floa
                   const int32_t* ts_host, const float* coef_host, float* x0_hist_dev, void* workspace_dev, size_t workspace_bytes,
                   void* stream, int32_t use_graph)
 {
-    std::vector<float> coef4, c4;
-    if (int rc = split_ms_table(steps, coef_host, x0_hist_dev, coef4, c4)) return rc;
-    const MultiStep ms{c4.data(), x0_hist_dev};
-    return sample_impl(h, z_dev, x_T_dev, x_out_dev, B, H, W, steps, ts_host, coef4.data(), nullptr, nullptr, workspace_dev, workspace_bytes, stream,
-                       use_graph, nullptr, &ms);
+    SamplerRun r;
+    std::vector<float> coef4;
+    if (int rc = split_ms_table(steps, coef_host, x0_hist_dev, coef4, r.c4)) return rc;
+    if (int rc = begin_run(h, steps, ts_host, coef4.data(), nullptr, r)) return rc;
+    r.hist = x0_hist_dev;
+    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
 }
 
 int ccn_sample_guided_ms(ccn_handle_t h, const float* z_dev, const float* z_null_dev, const float* x_T_dev, float* x_out_dev, int32_t B,
@@ -1311,19 +1321,21 @@ int ccn_sample_guided_ms(ccn_handle_t h, const float* z_dev, const float* z_null
 {
     if (!std::isfinite(w)) return fail(CCN_EINVAL, "the guidance scale must be finite");
     if (!eps_scratch_dev || ((uintptr_t)eps_scratch_dev & 15)) return fail(CCN_EINVAL, "the eps scratch must be non-null and 16-byte aligned");
-    std::vector<float> coef4, c4;
-    if (int rc = split_ms_table(steps, coef_host, x0_hist_dev, coef4, c4)) return rc;
-    const Guide gd{z_null_dev, w, eps_scratch_dev};
-    const MultiStep ms{c4.data(), x0_hist_dev};
-    return sample_impl(h, z_dev, x_T_dev, x_out_dev, B, H, W, steps, ts_host, coef4.data(), nullptr, nullptr, workspace_dev, workspace_bytes, stream,
-                       use_graph, &gd, &ms);
+    SamplerRun r;
+    std::vector<float> coef4;
+    if (int rc = split_ms_table(steps, coef_host, x0_hist_dev, coef4, r.c4)) return rc;
+    if (int rc = begin_run(h, steps, ts_host, coef4.data(), nullptr, r)) return rc;
+    r.guided = true; r.z_null = z_null_dev; r.w = w; r.eps = eps_scratch_dev;
+    r.hist = x0_hist_dev;
+    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
 }
 
+// The four older stand-alone updates: their own argument checks, then the one kernel in its eps form.
 int ccn_ms_step(float* x_dev, float* x0_hist_dev, const float* eps_dev, float c0, float c1, float c2, float c3, float c4, int64_t n, void* stream)
 {
     if (!x_dev || !x0_hist_dev || !eps_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
     if (n == 0) return CCN_OK;
-    HIPCHK(launch_ms_step(x_dev, x0_hist_dev, eps_dev, c0, c1, c2, c3, c4, n, (hipStream_t)stream));
+    HIPCHK(launch_sampler_step(x_dev, nullptr, x0_hist_dev, eps_dev, nullptr, nullptr, CCN_PRED_EPS, 0.f, c0, c1, c2, c3, c4, 0.f, n, (hipStream_t)stream));
     return CCN_OK;
 }
 
@@ -1332,7 +1344,7 @@ int ccn_cfg_ms_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const fl
 {
     if (!x_dev || !x0_hist_dev || !eps_c_dev || !eps_u_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
     if (n == 0) return CCN_OK;
-    HIPCHK(launch_cfg_ms_step(x_dev, x_dup_dev, x0_hist_dev, eps_c_dev, eps_u_dev, w, c0, c1, c2, c3, c4, n, (hipStream_t)stream));
+    HIPCHK(launch_sampler_step(x_dev, x_dup_dev, x0_hist_dev, eps_c_dev, eps_u_dev, nullptr, CCN_PRED_EPS, w, c0, c1, c2, c3, c4, 0.f, n, (hipStream_t)stream));
     return CCN_OK;
 }
 
@@ -1341,7 +1353,7 @@ int ccn_cfg_ddim_step(float* x_dev, float* x_dup_dev, const float* eps_c_dev, co
 {
     if (!x_dev || !eps_c_dev || !eps_u_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
     if (n == 0) return CCN_OK;
-    HIPCHK(launch_cfg_ddim_step(x_dev, x_dup_dev, eps_c_dev, eps_u_dev, noise_dev, w, c0, c1, c2, c3, sigma, n, (hipStream_t)stream));
+    HIPCHK(launch_sampler_step(x_dev, x_dup_dev, nullptr, eps_c_dev, eps_u_dev, noise_dev, CCN_PRED_EPS, w, c0, c1, c2, c3, 0.f, sigma, n, (hipStream_t)stream));
     return CCN_OK;
 }
 
@@ -1350,7 +1362,7 @@ int ccn_ddim_step(float* x_dev, const float* eps_dev, const float* noise_dev, fl
 {
     if (!x_dev || !eps_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
     if (n == 0) return CCN_OK;
-    HIPCHK(launch_ddim_step(x_dev, eps_dev, noise_dev, c0, c1, c2, c3, sigma, n, (hipStream_t)stream));
+    HIPCHK(launch_sampler_step(x_dev, nullptr, nullptr, eps_dev, nullptr, noise_dev, CCN_PRED_EPS, 0.f, c0, c1, c2, c3, 0.f, sigma, n, (hipStream_t)stream));
     return CCN_OK;
 }
 

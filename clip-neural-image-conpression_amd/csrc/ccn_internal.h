@@ -266,19 +266,8 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
                          float* y, int R, int K, int N, int act_silu, hipStream_t s);
 
 // ---- elementwise ---------------------------------------------------------------------------------
-hipError_t launch_ddim_step(float* x, const float* eps, const float* noise, float c0, float c1, float c2, float c3,
-                            float sigma, int64_t n, hipStream_t s);
-// the guided update: e = eps_u + w*(eps_c - eps_u), launch_ddim_step's update on e; x_dup (nullable) receives a copy of the new x
-hipError_t launch_cfg_ddim_step(float* x, float* x_dup, const float* eps_c, const float* eps_u, const float* noise, float w,
-                                float c0, float c1, float c2, float c3, float sigma, int64_t n, hipStream_t s);
-// the multistep update (sampler_update in ccn_device.h) as its own pass: x in place, hist <- the clamped x0 (read only when c4 != 0);
-// the guided form combines e = eps_u + w*(eps_c - eps_u) first and copies the new x into x_dup (nullable)
-hipError_t launch_ms_step(float* x, float* hist, const float* eps, float c0, float c1, float c2, float c3, float c4, int64_t n, hipStream_t s);
-hipError_t launch_cfg_ms_step(float* x, float* x_dup, float* hist, const float* eps_c, const float* eps_u, float w, float c0, float c1,
-                              float c2, float c3, float c4, int64_t n, hipStream_t s);
-// every stand-alone update in one kernel, either parameterisation (pred = CCN_PRED_*): x_dup, hist, out_u and noise are nullable --
-// no out_u: out_c is the prediction itself; no hist: c4 is not applied and no history is written.  With pred = 0 it computes what
-// the four launchers above compute, bit for bit.
+// the stand-alone sampler update, either parameterisation (pred = CCN_PRED_*): x_dup, hist, out_u and noise are nullable -- no out_u:
+// out_c is the prediction itself; no hist: c4 is not applied and no history is written (hist is read only when c4 != 0)
 hipError_t launch_sampler_step(float* x, float* x_dup, float* hist, const float* out_c, const float* out_u, const float* noise, int pred,
                                float w, float c0, float c1, float c2, float c3, float c4, float sigma, int64_t n, hipStream_t s);
 hipError_t launch_q_sample(float* out, const float* x0, const float* noise, const float* a, const float* sg,

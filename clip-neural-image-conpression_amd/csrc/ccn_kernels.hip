@@ -9,7 +9,7 @@
 //                       and the NEXT GroupNorm's partial sums, so a normalised tensor is never re-read for statistics.
 //   gn_finalize_kernel  partial sums -> per-(sample, channel) scale/shift (fp64 combine).
 //   linear/temb         conditioning vector and FiLM tables for every step, computed once before the loop.
-//   ddim_step/q_sample  stand-alone elementwise forms.
+//   sampler_step/q_sample  stand-alone elementwise forms.
 //
 // Layout: activations NHWC (channel-contiguous), element type T = float (parity mode, v_mfma_f32_32x32x2_f32,
 // bit-identical to an fmaf chain) or bf16 (throughput mode, v_mfma_f32_32x32x16_bf16, fp32 accumulate).
@@ -812,138 +812,11 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
 }
 
 // ---- elementwise ----------------------------------------------------------------------------------------------
-__global__ void ddim_step_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                 float c0, float c1, float c2, float c3, float sigma, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float e = eps[i];
-        float x0 = __fdiv_rn(__fsub_rn(x[i], __fmul_rn(c0, e)), c1);
-        x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        float xn = __fadd_rn(__fmul_rn(c2, x0), __fmul_rn(c3, e));
-        if (noise) xn = __fadd_rn(xn, __fmul_rn(sigma, noise[i]));
-        x[i] = xn;
-    }
-}
-hipError_t launch_ddim_step(float* x, const float* eps, const float* noise, float c0, float c1, float c2, float c3, float sigma,
-                            int64_t n, hipStream_t s)
-{
-    const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(grid > 0 ? grid : 1), dim3(256), 0, s, x, eps, noise, c0, c1, c2, c3, sigma, n);
-    return hipGetLastError();
-}
-
-// Classifier-free guidance and the DDIM update in one pass: e = eps_u + w*(eps_c - eps_u), then ddim_step_kernel's sequence on e, every
-// op rounded to fp32 on its own.  x is updated in place; x_dup (nullable) receives the same values: the unconditional half of the
-// guided loop's state.  VEC: every pointer is 16-byte aligned, four elements per lane and access; the n % 4 tail goes one by one.
-__device__ __forceinline__ float cfg_ddim_one(float x, float ec, float eu, float w, float c0, float c1, float c2, float c3)
-{
-    const float e = __fadd_rn(eu, __fmul_rn(w, __fsub_rn(ec, eu)));
-    float x0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(c0, e)), c1);
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    return __fadd_rn(__fmul_rn(c2, x0), __fmul_rn(c3, e));
-}
-template <bool VEC>
-__global__ void cfg_ddim_step_kernel(float* __restrict__ x, float* __restrict__ x_dup, const float* __restrict__ eps_c,
-                                     const float* __restrict__ eps_u, const float* __restrict__ noise, float w, float c0, float c1,
-                                     float c2, float c3, float sigma, int64_t n)
-{
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    const int64_t n4 = VEC ? n / 4 : 0;
-    for (int64_t q = tid; q < n4; q += nthr) {
-        const float4 xv = ((const float4*)x)[q], cv = ((const float4*)eps_c)[q], uv = ((const float4*)eps_u)[q];
-        float4 o;
-        o.x = cfg_ddim_one(xv.x, cv.x, uv.x, w, c0, c1, c2, c3);
-        o.y = cfg_ddim_one(xv.y, cv.y, uv.y, w, c0, c1, c2, c3);
-        o.z = cfg_ddim_one(xv.z, cv.z, uv.z, w, c0, c1, c2, c3);
-        o.w = cfg_ddim_one(xv.w, cv.w, uv.w, w, c0, c1, c2, c3);
-        if (noise) {
-            const float4 nv = ((const float4*)noise)[q];
-            o.x = __fadd_rn(o.x, __fmul_rn(sigma, nv.x)); o.y = __fadd_rn(o.y, __fmul_rn(sigma, nv.y));
-            o.z = __fadd_rn(o.z, __fmul_rn(sigma, nv.z)); o.w = __fadd_rn(o.w, __fmul_rn(sigma, nv.w));
-        }
-        ((float4*)x)[q] = o;
-        if (x_dup) ((float4*)x_dup)[q] = o;
-    }
-    for (int64_t i = n4 * 4 + tid; i < n; i += nthr) {
-        float xn = cfg_ddim_one(x[i], eps_c[i], eps_u[i], w, c0, c1, c2, c3);
-        if (noise) xn = __fadd_rn(xn, __fmul_rn(sigma, noise[i]));
-        x[i] = xn;
-        if (x_dup) x_dup[i] = xn;
-    }
-}
-hipError_t launch_cfg_ddim_step(float* x, float* x_dup, const float* eps_c, const float* eps_u, const float* noise, float w, float c0,
-                                float c1, float c2, float c3, float sigma, int64_t n, hipStream_t s)
-{
-    const bool vec = !(((uintptr_t)x | (uintptr_t)x_dup | (uintptr_t)eps_c | (uintptr_t)eps_u | (uintptr_t)noise) & 15);
-    const int64_t work = vec ? (n + 3) / 4 : n, blocks = (work + 255) / 256;
-    const int grid = (int)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);      // 256 CUs x 8 blocks, grid-stride beyond
-    if (vec) hipLaunchKernelGGL(cfg_ddim_step_kernel<true>, dim3(grid), dim3(256), 0, s, x, x_dup, eps_c, eps_u, noise, w, c0, c1, c2, c3, sigma, n);
-    else hipLaunchKernelGGL(cfg_ddim_step_kernel<false>, dim3(grid), dim3(256), 0, s, x, x_dup, eps_c, eps_u, noise, w, c0, c1, c2, c3, sigma, n);
-    return hipGetLastError();
-}
-
-// The multistep update as its own pass (DPM-Solver++ 2M, data prediction; sampler_update in ccn_device.h): x in place, hist <- this
-// step's clamped x0; hist is read only when c4 != 0.  GUIDED: e = eps_u + w*(eps_c - eps_u) first (eps = eps_c), and x_dup (nullable)
-// receives a copy of the new x.  VEC as in cfg_ddim_step_kernel.
-template <bool VEC, bool GUIDED>
-__global__ void ms_step_kernel(float* __restrict__ x, float* __restrict__ x_dup, float* __restrict__ hist, const float* __restrict__ eps,
-                               const float* __restrict__ eps_u, float w, float c0, float c1, float c2, float c3, float c4, int64_t n)
-{
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    const int64_t n4 = VEC ? n / 4 : 0;
-    for (int64_t q = tid; q < n4; q += nthr) {
-        const float4 xv = ((const float4*)x)[q];
-        float4 ev = ((const float4*)eps)[q];
-        if (GUIDED) {
-            const float4 uv = ((const float4*)eps_u)[q];
-            ev.x = __fadd_rn(uv.x, __fmul_rn(w, __fsub_rn(ev.x, uv.x))); ev.y = __fadd_rn(uv.y, __fmul_rn(w, __fsub_rn(ev.y, uv.y)));
-            ev.z = __fadd_rn(uv.z, __fmul_rn(w, __fsub_rn(ev.z, uv.z))); ev.w = __fadd_rn(uv.w, __fmul_rn(w, __fsub_rn(ev.w, uv.w)));
-        }
-        float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), o, p;
-        if (c4 != 0.f) hv = ((const float4*)hist)[q];
-        o.x = sampler_update(xv.x, ev.x, c0, c1, c2, c3, c4, hv.x, p.x);
-        o.y = sampler_update(xv.y, ev.y, c0, c1, c2, c3, c4, hv.y, p.y);
-        o.z = sampler_update(xv.z, ev.z, c0, c1, c2, c3, c4, hv.z, p.z);
-        o.w = sampler_update(xv.w, ev.w, c0, c1, c2, c3, c4, hv.w, p.w);
-        ((float4*)hist)[q] = p;
-        ((float4*)x)[q] = o;
-        if (GUIDED && x_dup) ((float4*)x_dup)[q] = o;
-    }
-    for (int64_t i = n4 * 4 + tid; i < n; i += nthr) {
-        float e = eps[i];
-        if (GUIDED) { const float u = eps_u[i]; e = __fadd_rn(u, __fmul_rn(w, __fsub_rn(e, u))); }
-        const float hv = c4 != 0.f ? hist[i] : 0.f;
-        float p;
-        const float xn = sampler_update(x[i], e, c0, c1, c2, c3, c4, hv, p);
-        hist[i] = p;
-        x[i] = xn;
-        if (GUIDED && x_dup) x_dup[i] = xn;
-    }
-}
-template <bool GUIDED>
-static hipError_t launch_ms(float* x, float* x_dup, float* hist, const float* eps, const float* eps_u, float w, float c0, float c1, float c2,
-                            float c3, float c4, int64_t n, hipStream_t s)
-{
-    const bool vec = !(((uintptr_t)x | (uintptr_t)x_dup | (uintptr_t)hist | (uintptr_t)eps | (uintptr_t)eps_u) & 15);
-    const int64_t work = vec ? (n + 3) / 4 : n, blocks = (work + 255) / 256;
-    const int grid = (int)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);      // 256 CUs x 8 blocks, grid-stride beyond
-    if (vec) hipLaunchKernelGGL((ms_step_kernel<true, GUIDED>), dim3(grid), dim3(256), 0, s, x, x_dup, hist, eps, eps_u, w, c0, c1, c2, c3, c4, n);
-    else hipLaunchKernelGGL((ms_step_kernel<false, GUIDED>), dim3(grid), dim3(256), 0, s, x, x_dup, hist, eps, eps_u, w, c0, c1, c2, c3, c4, n);
-    return hipGetLastError();
-}
-hipError_t launch_ms_step(float* x, float* hist, const float* eps, float c0, float c1, float c2, float c3, float c4, int64_t n, hipStream_t s)
-{
-    return launch_ms<false>(x, nullptr, hist, eps, nullptr, 0.f, c0, c1, c2, c3, c4, n, s);
-}
-hipError_t launch_cfg_ms_step(float* x, float* x_dup, float* hist, const float* eps_c, const float* eps_u, float w, float c0, float c1,
-                              float c2, float c3, float c4, int64_t n, hipStream_t s)
-{
-    return launch_ms<true>(x, x_dup, hist, eps_c, eps_u, w, c0, c1, c2, c3, c4, n, s);
-}
-
-// Every stand-alone update above in one kernel, for either parameterisation (`pred`, wave-uniform: sampler_update_p in ccn_device.h).
-// y = out_c, or out_u + w*(out_c - out_u) when out_u is given; hist (nullable) is read when c4 != 0 and receives the clamped x0; the
-// noise term and x_dup as in cfg_ddim_step_kernel.  VEC as there.  With pred == PRED_EPS the op sequence is that of the kernels above.
+// The stand-alone sampler update, for either parameterisation (`pred`, wave-uniform: sampler_update_p in ccn_device.h), every op rounded
+// to fp32 on its own.  y = out_c, or out_u + w*(out_c - out_u) when out_u is given (classifier-free guidance); hist (nullable) is read
+// when c4 != 0 and receives the clamped x0; noise (nullable) adds sigma*noise; x is updated in place and x_dup (nullable) receives the
+// same values: the unconditional half of the guided loop's state.  VEC: every pointer is 16-byte aligned, four elements per lane and
+// access; the n % 4 tail goes one by one.
 template <bool VEC>
 __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x_dup, float* __restrict__ hist, const float* __restrict__ out_c,
                                     const float* __restrict__ out_u, const float* __restrict__ noise, int pred, float w, float c0, float c1,

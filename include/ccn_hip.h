@@ -146,7 +146,7 @@ int ccn_ddim_step(float* x_dev, const float* eps_dev, const float* noise_dev,
  * with the null embedding, then the update of ccn_sample / ccn_sample_eta on that eps.  (No reference counterpart: the reference's
  * sampler accepts cfg_scale and never reads it, diffusion/ddim.py:22.)
  * The loop is the plan of batch 2B: rows [0, B) carry z_dev (B,z_dim), rows [B, 2B) carry z_null_dev (z_dim,) (NULL: zeros), both
- * halves the same state.  Each step evaluates the UNet on the 2B rows, the head writing eps, and one ccn_cfg_ddim_step launch
+ * halves the same state.  Each step evaluates the UNet on the 2B rows, the head writing eps, and one ccn_sampler_step launch
  * writes the new state into both halves.  Conditioning of all steps is hoisted in front of the loop as in ccn_sample.
  * workspace_dev: the one of ccn_workspace_bytes(h, 2*B, H, W, steps).  eps_scratch_dev: 2*B*img_ch*H*W floats, 16-byte aligned,
  * owned by the caller like the workspace, and to be kept at the same address while a captured graph for it is cached.
@@ -186,7 +186,7 @@ int ccn_sample_ms(ccn_handle_t h, const float* z_dev, const float* x_T_dev, floa
                   void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph);
 
 /* The same sampler under classifier-free guidance: ccn_sample_guided's loop at batch 2B (eta = 0 only: no sigma, no noise), each step
- * ending in one ccn_cfg_ms_step launch that writes the new state into both halves.  coef_host[steps][5] and the CCN_EINVAL cases as for
+ * ending in one ccn_sampler_step launch that writes the new state into both halves.  coef_host[steps][5] and the CCN_EINVAL cases as for
  * ccn_sample_ms; x0_hist_dev holds ONE state, B*img_ch*H*W floats; workspace_dev and eps_scratch_dev as for ccn_sample_guided.
  * The captured graph is cached per (table, c4 column, w, eps scratch address, history address). */
 int ccn_sample_guided_ms(ccn_handle_t h, const float* z_dev, const float* z_null_dev, const float* x_T_dev, float* x_out_dev,
@@ -227,7 +227,7 @@ int ccn_set_prediction(ccn_handle_t h, int32_t pred);
  *   out_u_dev   NULL, or the unconditional output: y = out_u + w*(out_c - out_u) is used (w is ignored when NULL);
  *   x0_hist_dev NULL (c4 is not applied, nothing is stored), or the x0 history: read only when c4 != 0, then receives this step's x0;
  *   noise_dev   NULL, or N(0,1) draws added as sigma*noise;   x_dup_dev  NULL, or receives a copy of the new x.
- * With pred = CCN_PRED_EPS the result equals that of the four older entry points bit for bit.  The output tensors are not written.
+ * The four older entry points are this one with pred = CCN_PRED_EPS, bit for bit.  The output tensors are not written.
  * n elements each.  Four elements per lane when every non-NULL pointer is 16-byte aligned, one otherwise.
  * CCN_EINVAL: x_dev, out_c_dev or coef_host NULL, n < 0, an unknown pred. */
 int ccn_sampler_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,

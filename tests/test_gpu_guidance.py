@@ -276,9 +276,9 @@ def test_guided_error_paths(tiny_net, inputs, gpu_guided_cosine):
     nat = tiny_net.native()
     ts, coef = sch.ddim_timesteps(T), sch.ddim_coefficients(T, 0.0)
     with pytest.raises(ValueError, match="null_z"):
-        nat.sample_guided(z, xT, ts, coef[:, :4], W_G, z_null=torch.zeros(3, device=DEV))
+        nat.sample(z, xT, ts, coef[:, :4], w=W_G, z_null=torch.zeros(3, device=DEV))
     with pytest.raises(ValueError, match="finite"):
-        nat.sample_guided(z, xT, ts, coef[:, :4], float("nan"))
+        nat.sample(z, xT, ts, coef[:, :4], w=float("nan"))
     again = guided.sample(tiny_net, z, shape, steps=T, cfg_scale=W_G, x_T=xT)
     torch.cuda.synchronize()
     tiny_net.native().poll_errors()

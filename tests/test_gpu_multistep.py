@@ -354,17 +354,17 @@ def test_error_paths(tiny_net, inputs, gpu_2m_cosine):
     nat = tiny_net.native()
     ts, coef = sampler.tables(T)
     with pytest.raises(ValueError, match="coef"):
-        nat.sample_ms(z, xT, ts, coef[:, :4])
+        nat.sample(z, xT, ts, coef[:, :4], hist=torch.empty_like(xT))
     for bad in (torch.empty(xT.numel() - 1, device=DEV), torch.empty(xT.numel(), device=DEV, dtype=torch.float64),
                 torch.empty(xT.numel()), torch.empty(xT.numel() + 1, device=DEV)[1:]):
         with pytest.raises(ValueError, match="hist"):
-            nat.sample_ms(z, xT, ts, coef, hist=bad)
+            nat.sample(z, xT, ts, coef, hist=bad)
         with pytest.raises(ValueError, match="hist"):
-            nat.sample_guided_ms(z, xT, ts, coef, W_G, hist=bad)
+            nat.sample(z, xT, ts, coef, w=W_G, hist=bad)
     with pytest.raises(ValueError, match="finite"):
-        nat.sample_guided_ms(z, xT, ts, coef, float("inf"))
+        nat.sample(z, xT, ts, coef, w=float("inf"))
     with pytest.raises(ValueError, match="null_z"):
-        nat.sample_guided_ms(z, xT, ts, coef, W_G, z_null=torch.zeros(3, device=DEV))
+        nat.sample(z, xT, ts, coef, w=W_G, z_null=torch.zeros(3, device=DEV))
     with pytest.raises(ValueError, match="same number"):
         _native.ms_step(xT.clone(), torch.empty(5, device=DEV), xT, coef[1])
     with pytest.raises(ValueError, match="same number"):
@@ -374,9 +374,9 @@ def test_error_paths(tiny_net, inputs, gpu_2m_cosine):
         bad = coef.copy()
         bad[i, j] = v
         with pytest.raises(ValueError, match="c4 must be 0 on step 0" if k == 0 else "non-finite"):
-            nat.sample_ms(z, xT, ts, bad)
+            nat.sample(z, xT, ts, bad)
         with pytest.raises(ValueError, match="c4 must be 0 on step 0" if k == 0 else "non-finite"):
-            nat.sample_guided_ms(z, xT, ts, bad, W_G)
+            nat.sample(z, xT, ts, bad, w=W_G)
     ws = nat.workspace(B, S, S, T)
     out = torch.empty_like(xT)
     tsc, cc = np.ascontiguousarray(ts, np.int32), np.ascontiguousarray(coef, np.float32)

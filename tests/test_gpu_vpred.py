@@ -347,6 +347,68 @@ def test_eps_and_v_graphs_on_one_slot(tiny_sd, tiny_net, inputs):
     net.native().poll_errors()
 
 
+def test_every_variant_finds_its_own_graph_on_one_slot(tiny_sd, inputs):
+    """The whole graph key at once: every sampler variant in turn on ONE net and ONE slot with graphs on, each result against the
+    same call on a second net of the same weights that launches step by step (``use_graph = False``; that the two loops agree bit
+    for bit is test_routes_are_bit_equal_in_v_mode and test_guided_routes_and_graphs).  Neighbouring calls differ in one clause of
+    the key only: the sigma table (one sampler object, so one noise buffer), the c4 column (same timesteps), the history address,
+    the prediction, the guidance scale; the first call comes back after the four-entry LRU has dropped it.  4 steps.
+    eta = 0.5 and 0.3 give NaN in every element on both nets (the imaginary direction coefficient at t = 999, see
+    test_eta_v_matches_oracle), so equality counts NaN as equal to NaN, and to nothing else; eta = 0.03 and 0.02 are the same pair
+    of calls in numbers."""
+    z, xT = to_dev(inputs[0]), to_dev(inputs[1])
+    sch = NoiseScheduler(1000, "linear", DEV)
+    net, ref = make_net(tiny_sd), make_net(tiny_sd)
+    steps = 4
+
+    def same(a, b):
+        return torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(torch.nan_to_num(a), torch.nan_to_num(b))
+
+    def pair(make):
+        graphed, plain = make(), make()
+        plain.use_graph = False
+        return graphed, plain
+
+    def run(what, samplers, seed=None, **kw):
+        outs = []
+        for s, n in zip(samplers, (net, ref)):
+            if seed is not None:
+                torch.manual_seed(seed)                               # eta > 0: the same draws on both nets
+            outs.append(s.sample(n, z, SHAPE, steps=steps, x_T=xT, **kw))
+        assert same(*outs), what
+        return outs[0]
+
+    ddim = pair(lambda: DDIMSampler(sch))
+    first = run("ddim", ddim)
+    noisy = {}
+    for eta in (0.5, 0.3, 0.03, 0.02):
+        for s in ddim:
+            s.eta = eta
+        noisy[eta] = run(f"ddim, eta {eta}", ddim, seed=77)
+    assert len(ddim[0]._noise) == 1 and bool(torch.isfinite(noisy[0.03]).all()) and not torch.equal(noisy[0.03], noisy[0.02])
+    for s in ddim:
+        s.eta = 0.0
+    m2 = run("2m", pair(lambda: DPMSolverSampler(sch, order=2, spacing="linspace")))
+    m1 = run("2m, order 1", pair(lambda: DPMSolverSampler(sch, order=1, spacing="linspace")))
+    assert not torch.equal(m1, m2)
+    ts, coef = DPMSolverSampler(sch, order=2, spacing="linspace").tables(steps)
+    h1, h2, h_ref = (torch.empty_like(xT) for _ in range(3))
+    for h in (h1, h2):
+        got = net.native().sample(z, xT, ts, coef, hist=h)
+        assert same(got, ref.native().sample(z, xT, ts, coef, use_graph=False, hist=h_ref)) and torch.equal(got, m2)
+        assert torch.equal(h, h_ref)
+    v = run("ddim, v", pair(lambda: DDIMSampler(sch, prediction="v")))
+    assert not torch.equal(v, first)
+    assert torch.equal(run("ddim again", ddim), first)
+    guided = pair(lambda: DDIMSampler(sch, guided=True))
+    g = [run(f"guided ddim, w = {w}", guided, cfg_scale=w) for w in (3.0, 2.0, 3.0)]
+    assert torch.equal(g[0], g[2]) and not torch.equal(g[0], g[1])
+    run("guided 2m", pair(lambda: DPMSolverSampler(sch, spacing="linspace", guided=True)), cfg_scale=3.0)
+    torch.cuda.synchronize()
+    net.native().poll_errors()
+    ref.native().poll_errors()
+
+
 # ----------------------------------------------------------------------------------------------------------------- 6. the fast modes
 @pytest.mark.parametrize("dtype", ["bf16", "f16x3"])
 def test_fast_modes_run_v_mode(tiny_sd, inputs, gpu_v_ddim, dtype):
