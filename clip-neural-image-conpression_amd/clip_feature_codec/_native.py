@@ -24,6 +24,7 @@ PRED_EPS, PRED_V = 0, 1
 _PREDICTIONS = {"eps": PRED_EPS, "v": PRED_V}
 
 c_i32, c_i64, c_f32, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
+c_u32 = ctypes.c_uint32
 
 
 class CcnConfig(ctypes.Structure):
@@ -42,6 +43,11 @@ SIGNATURES = {
     "ccn_set_weight_rounding": (c_i32, [c_vp, c_i32]),
     "ccn_set_prediction": (c_i32, [c_vp, c_i32]),
     "ccn_sampler_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, ctypes.POINTER(c_f32), c_f32, c_i64, c_vp]),
+    "ccn_normal_fill": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_u32, c_vp]),
+    "ccn_sampler_step_seeded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_i64, c_i32, c_f32, ctypes.POINTER(c_f32), c_f32, c_i64, c_vp]),
+    "ccn_sample_seeded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_i32]),
+    "ccn_sample_guided_seeded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_sz,
+                                         c_vp, c_i32]),
     "ccn_workspace_bytes": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
     "ccn_release_workspace": (c_i32, [c_vp, c_vp]),
     "ccn_forward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
@@ -161,6 +167,22 @@ def require_dev(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor
     return t.contiguous()
 
 
+def seeds_tensor(seeds, B: int, device) -> torch.Tensor:
+    """One 64-bit seed per record as the C ABI wants them: a contiguous int64 ``(B,)`` tensor (on ``device`` if it is not a tensor
+    yet; a tensor keeps its device).  ``seeds``: a sequence of ints -- any int is taken modulo 2^64, so a negative one is its two's-complement bits -- or an
+    int64 tensor.  Anything but ``B`` entries is a ``ValueError``."""
+    if isinstance(seeds, torch.Tensor):
+        if seeds.dtype != torch.int64:
+            raise ValueError(f"a seeds tensor must be int64, got {seeds.dtype}")
+        t = seeds.reshape(-1).contiguous()
+    else:
+        vals = [((int(v) & 0xFFFFFFFFFFFFFFFF) ^ (1 << 63)) - (1 << 63) for v in seeds]       # the same bits as a signed int64
+        t = torch.tensor(vals, dtype=torch.int64, device=device)
+    if t.numel() != B:
+        raise ValueError(f"seeds must hold one entry per record: expected {B}, got {t.numel()}")
+    return t
+
+
 def current_stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -174,6 +196,8 @@ class Workspace:
         self.ptr = (base + 255) // 256 * 256
         self.nbytes = nbytes
         self.eps: Optional[torch.Tensor] = None     # NativeUNet.sample, guided: the eps of both halves, kept with the workspace
+        # (and, unguided with seeds, the raw output of the plan's rows: the same number of rows either way)
+        self.seeds: Optional[torch.Tensor] = None   # NativeUNet.sample with seeds: int64, one per row of the plan's batch, likewise
         # NativeUNet.sample, multistep: the x0 history of one state, likewise -- by element count, because the slot is keyed
         # by the PLAN's batch: a guided call of batch B (history of B rows) and an unguided one of batch 2B (2B rows) share it
         self.hist: Dict[int, torch.Tensor] = {}
@@ -288,14 +312,18 @@ class NativeUNet:
 
     def sample(self, z: torch.Tensor, x_T: torch.Tensor, ts, coef, use_graph: bool = True, slot: int = 0, sigma=None,
                noise: Optional[torch.Tensor] = None, w: Optional[float] = None, z_null: Optional[torch.Tensor] = None,
-               hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+               hist: Optional[torch.Tensor] = None, seeds=None) -> torch.Tensor:
         """Every step of a sampler inside the library, through the ``ccn_sample*`` entry that fits.  ``coef`` of ``(steps, 4)``: the
         DDIM loop; ``sigma`` (steps,) + ``noise`` (steps, B, C, H, W) fp32 on the device make it the eta > 0 one.  ``coef`` of
         ``(steps, 5)``: the multistep loop (``NoiseScheduler.solver_coefficients``; deterministic), ``hist`` its x0 history, fp32 of
         ``x_T``'s size.  ``w``: a classifier-free guidance scale (None: unguided) -- the plan and the workspace are then of batch 2B,
         ``z`` in the first half, ``z_null`` (``(z_dim,)``; None: zeros) in the second, ``noise`` and ``hist`` still of ONE state.  The
         eps scratch of the 2B rows and, with ``hist=None``, the history are kept with the workspace, so that a later call replays
-        the graph captured with their addresses."""
+        the graph captured with their addresses.  ``seeds`` (``seeds_tensor``'s input, ``B`` entries) instead of ``noise``: the
+        seeded entries -- step ``i`` adds ``sigma[i]`` times draw ``1 + i`` of each record, generated in the loop; the seeds are
+        copied, in stream order, into an int64 buffer kept with the workspace, so a later call with other seeds replays the same
+        graph (a seeds tensor on another device is moved first: from the host that is a synchronous upload of ``8 B`` bytes).
+        ``sigma=None`` with seeds is eta = 0: nothing is drawn, the seeds are only checked and the unseeded entry runs."""
         import math
         import numpy as np
         z = require_dev(z, "z_clip"); x_T = require_dev(x_T, "x_T")
@@ -318,7 +346,17 @@ class NativeUNet:
             z_null = require_dev(z_null, "null_z")
             if tuple(z_null.shape) != (self.z_dim,):
                 raise ValueError(f"null_z must be ({self.z_dim},), got {tuple(z_null.shape)}")
-        if sigma is not None:
+        if seeds is not None:
+            if ms or noise is not None:
+                raise ValueError("seeds replace the noise tensor of the eta > 0 loop: no noise with them, and not the multistep sampler")
+            seeds = seeds_tensor(seeds, B, self.device).to(self.device)
+            if sigma is None:
+                seeds = None                          # eta = 0: no draw, no scratch, no seeded entry
+        if seeds is not None:
+            sigma = np.ascontiguousarray(sigma, dtype=np.float32)
+            if sigma.shape != (steps,):
+                raise ValueError(f"sigma must be ({steps},)")
+        elif sigma is not None:
             sigma = np.ascontiguousarray(sigma, dtype=np.float32)
             noise = require_dev(noise, "noise")
             if sigma.shape != (steps,) or tuple(noise.shape) != (steps, B, C, H, W):
@@ -327,8 +365,12 @@ class NativeUNet:
                                      and hist.numel() == x_T.numel() and hist.data_ptr() % 16 == 0):
             raise ValueError(f"hist must be a contiguous, 16-byte aligned fp32 HIP tensor of {x_T.numel()} elements")
         ws = self.workspace(B if w is None else 2 * B, H, W, steps, slot)
-        if w is not None and ws.eps is None:
-            ws.eps = torch.empty((2 * B, C, H, W), dtype=torch.float32, device=self.device)
+        if (w is not None or seeds is not None) and ws.eps is None:
+            ws.eps = torch.empty((B if w is None else 2 * B, C, H, W), dtype=torch.float32, device=self.device)
+        if seeds is not None:
+            if ws.seeds is None:
+                ws.seeds = torch.zeros(B if w is None else 2 * B, dtype=torch.int64, device=self.device)
+            ws.seeds[:B].copy_(seeds)                 # on the current stream, in front of the launch
         if ms and hist is None:
             hist = ws.history(x_T)
         out = torch.empty_like(x_T)
@@ -336,9 +378,14 @@ class NativeUNet:
         zn = () if w is None else (ptr(z_null),)
         head = (self.h, z.data_ptr(), *zn, x_T.data_ptr(), out.data_ptr(), B, H, W, steps, ts.ctypes.data, coef.ctypes.data)
         tail = (ws.ptr, ws.nbytes, current_stream(x_T.device), 1 if use_graph else 0)
-        eta = (sigma.ctypes.data, noise.data_ptr()) if sigma is not None else (None, None)
+        eta = (sigma.ctypes.data, noise.data_ptr()) if sigma is not None and seeds is None else (None, None)
+        seeded = () if seeds is None else (sigma.ctypes.data, ws.seeds.data_ptr())
         with torch.cuda.device(x_T.device):
-            if ms and w is None:
+            if seeds is not None and w is None:
+                check(self.lib.ccn_sample_seeded(*head, *seeded, ws.eps.data_ptr(), *tail))
+            elif seeds is not None:
+                check(self.lib.ccn_sample_guided_seeded(*head, *seeded, float(w), ws.eps.data_ptr(), *tail))
+            elif ms and w is None:
                 check(self.lib.ccn_sample_ms(*head, hist.data_ptr(), *tail))
             elif ms:
                 check(self.lib.ccn_sample_guided_ms(*head, float(w), ws.eps.data_ptr(), hist.data_ptr(), *tail))
@@ -787,13 +834,37 @@ def cfg_ms_step(x: torch.Tensor, hist: torch.Tensor, eps_c: torch.Tensor, eps_u:
     return x
 
 
+def normal_fill(seeds, shape, draw: int = 0, out: Optional[torch.Tensor] = None, device="cuda") -> torch.Tensor:
+    """N(0,1) draws that belong to the records (ccn_normal_fill; DESIGN.md section 1, Noise): an fp32 tensor of ``shape`` whose row
+    ``b`` is draw ``draw`` of the record with seed ``seeds[b]`` -- 0 is the start noise, ``1 + i`` the noise of sampler step ``i``.
+    ``seeds``: ``shape[0]`` ints or an int64 tensor (``seeds_tensor``).  ``out``: a contiguous fp32 HIP tensor of ``shape`` to fill
+    (it may start at any 4-byte boundary), else a new one on the seeds tensor's device, or ``device``."""
+    lib = load_library()
+    shape = tuple(int(v) for v in shape)
+    if len(shape) < 1 or any(v <= 0 for v in shape):
+        raise ValueError(f"shape must be (B, ...) with positive sizes, got {shape}")
+    if not 0 <= int(draw) < 1 << 32:
+        raise ValueError(f"draw must be in [0, 2^32), got {draw}")
+    dev = out.device if out is not None else seeds.device if isinstance(seeds, torch.Tensor) and seeds.is_cuda else torch.device(device)
+    sd = require_dev(seeds_tensor(seeds, shape[0], dev).to(dev), "seeds", torch.int64)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+        raise ValueError(f"out must be a contiguous fp32 HIP tensor of shape {shape}")
+    with torch.cuda.device(out.device):
+        check(lib.ccn_normal_fill(out.data_ptr(), sd.data_ptr(), shape[0], out.numel() // shape[0], int(draw), current_stream(out.device)))
+    return out
+
+
 def sampler_step(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], prediction: str = "eps", out_u: Optional[torch.Tensor] = None,
                  w: float = 0.0, hist: Optional[torch.Tensor] = None, sigma: float = 0.0, noise: Optional[torch.Tensor] = None,
-                 x_dup: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 x_dup: Optional[torch.Tensor] = None, seeds=None, draw: int = 0) -> torch.Tensor:
     """One in-place sampler update of ``x`` for either parameterisation (ccn_sampler_step): ``out_c`` is the network output
     (``prediction`` says whether it is eps or v), ``out_u`` the unconditional one of a guided step (the update then acts on
     ``out_u + w * (out_c - out_u)``), ``coef`` = (c0, c1, c2, c3[, c4]), ``hist`` the multistep sampler's x0 history (read when
-    ``c4 != 0``, then rewritten), ``noise`` the eta > 0 draw added as ``sigma * noise``, ``x_dup`` a copy of the new ``x``."""
+    ``c4 != 0``, then rewritten), ``noise`` the eta > 0 draw added as ``sigma * noise``, ``x_dup`` a copy of the new ``x``.  ``seeds`` (``x.shape[0]`` of them)
+    instead of ``noise``: the draw ``draw`` of each record of ``x`` is generated in the kernel (ccn_sampler_step_seeded), the same
+    bits as ``noise=normal_fill(seeds, x.shape, draw)``."""
     lib = load_library()
     pred = prediction_code(prediction)
     x = require_dev(x, "x"); out_c = require_dev(out_c, "out_c")
@@ -808,6 +879,16 @@ def sampler_step(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], pr
     if len(c) not in (4, 5) or (hist is not None and len(c) != 5):
         raise ValueError("coef must be (c0, c1, c2, c3) or, with hist, (c0, c1, c2, c3, c4)")
     c5 = (c_f32 * 5)(*(c + [0.0] * (5 - len(c))))
+    if seeds is not None:
+        if noise is not None:
+            raise ValueError("seeds and noise exclude each other")
+        if x.dim() < 1 or not 0 <= int(draw) < 1 << 32:
+            raise ValueError("x must be (B, ...) and draw in [0, 2^32)")
+        sd = require_dev(seeds_tensor(seeds, x.shape[0], x.device).to(x.device), "seeds", torch.int64)
+        with torch.cuda.device(x.device):
+            check(lib.ccn_sampler_step_seeded(x.data_ptr(), ptr(x_dup), ptr(hist), out_c.data_ptr(), ptr(out_u), sd.data_ptr(), int(draw),
+                                              x.numel() // x.shape[0], pred, float(w), c5, float(sigma), x.numel(), current_stream(x.device)))
+        return x
     with torch.cuda.device(x.device):
         check(lib.ccn_sampler_step(x.data_ptr(), ptr(x_dup), ptr(hist), out_c.data_ptr(), ptr(out_u), ptr(nz), pred, float(w), c5,
                                    float(sigma), x.numel(), current_stream(x.device)))

@@ -54,6 +54,17 @@ def check_sampler_flags(sampler: str, eta: float) -> None:
         raise SystemExit("--sampler dpmpp2m is deterministic: --eta must be 0")
 
 
+def check_noise_flags(device_noise: bool, seed: int | None) -> None:
+    """``--device_noise`` keys every draw to the record's seed, so it needs ``--seed`` (both CLIs call this right after parsing)."""
+    if device_noise and seed is None:
+        raise SystemExit("--device_noise needs --seed: record i draws from seed + i")
+
+
+def record_seeds(indices: Sequence[int], seed: int) -> list:
+    """The 64-bit seeds of ``--device_noise``: record ``i`` of the manifest gets ``seed + i``, the rule of ``start_noise``."""
+    return [int(seed) + int(i) for i in indices]
+
+
 def build_sampler(eta: float, device: str, guided: bool = False, sampler: str = "ddim", spacing: str = "logsnr", prediction: str = "eps"):
     """``guided``: the sampler gives ``cfg_scale`` its meaning (classifier-free guidance against the zero embedding).
     ``sampler="dpmpp2m"``: the second-order multistep solver on the ``spacing`` timestep table (deterministic: no ``eta``).

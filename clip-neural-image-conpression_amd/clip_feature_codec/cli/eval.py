@@ -17,6 +17,10 @@ at a time on one device:
   table; the default ``ddim`` is the reference's sampler, bit for bit.  ``--eta > 0`` with ``dpmpp2m`` is an error.
 * ``--device_metrics`` (off by default) scores PSNR and SSIM on the GPU (``ccn_psnr_ssim_f32``): the originals go up as uint8, 16 bytes
   per record come back, and no host thread scores anything.  Without the flag nothing differs from a build that lacks it.
+* ``--device_noise`` (off by default; needs ``--seed``) takes every draw of record i from the device generator keyed by ``seed + i``
+  (``DDIMSampler.sample(seeds=)``): no host thread draws, no start noise is uploaded, ``--eta > 0`` is reproducible per record
+  whatever the batch size or sharding, and then runs pipelined like ``--eta 0``.  It is another generator than ``--seed`` alone
+  uses, so the numbers differ from that route; ``--seed`` alone is unchanged.
 """
 from __future__ import annotations
 
@@ -144,7 +148,7 @@ class DeviceScorer:
 def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstruct: Callable, size: int, batch: int,
              seed: Optional[int], rank: int, world: int, device: str, start_noise_fn: Callable, submit: Optional[Callable] = None,
              fetch: Optional[Callable] = None, workers: Optional[int] = None, u8: bool = False, marks: Optional[list] = None,
-             device_metrics: bool = False, learned: bool = False) -> np.ndarray:
+             device_metrics: bool = False, learned: bool = False, device_noise: bool = False) -> np.ndarray:
     """Shard, reconstruct in batches, score on the host, gather.  ``reconstruct(z, x_T) -> (b,3,S,S)`` numpy in [-1,1].
 
     With ``submit(z, x_T, slot) -> handle`` / ``fetch(handle) -> numpy`` (the GPU path) two batches are kept in flight: batch k+1 is
@@ -158,7 +162,11 @@ def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstru
     ``device_metrics``: PSNR / SSIM come from the GPU (``DeviceScorer``).  ``submit`` / ``reconstruct`` then take the batch's uint8
     originals, (b,3,S,S), as one more argument, and ``fetch`` / ``reconstruct`` return ``(scores, recon)``: the (b,2) float64
     ``[psnr, ssim]`` block and, with ``learned`` (LPIPS / CLIP similarity can produce numbers here), the float reconstruction for
-    those two columns -- else ``None``, and no worker thread scores anything."""
+    those two columns -- else ``None``, and no worker thread scores anything.
+
+    ``device_noise`` (with a ``seed``): no start noise is drawn here -- ``x_T`` is None and ``submit`` / ``reconstruct`` get the batch's
+    record seeds, ``seeds=[seed + i, ...]``, as a keyword."""
+    from ._common import record_seeds
     mine = shard_indices(len(manifest), rank, world)
     nw = workers or default_workers(world)
     batches = [mine[lo:lo + batch] for lo in range(0, len(mine), batch)]
@@ -172,7 +180,7 @@ def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstru
                         origf=[pool.submit(load_original, manifest[i]["image"], size) for i in idx] if device_metrics and learned else None,
                         orig=[pool.submit(load, manifest[i]["image"], size) for i in idx],
                         z=[pool.submit(z_of, manifest[i]) for i in idx],
-                        noise=None if seed is None else [pool.submit(start_noise_fn, [i], size, seed) for i in idx])
+                        noise=None if seed is None or device_noise else [pool.submit(start_noise_fn, [i], size, seed) for i in idx])
 
         def inputs(p):
             z = np.concatenate([f.result() for f in p["z"]], 0)
@@ -208,13 +216,14 @@ def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstru
                 marks.append((time.perf_counter(), sum(len(b) for b in batches[:bi])))   # (when batch bi is handed over, records before it)
             # (device_metrics: the originals were decoded while the previous batch was sampled)
             extra = (np.stack([f.result() for f in cur["orig"]], 0),) if device_metrics else ()
+            kw = dict(seeds=record_seeds(cur["idx"], seed)) if device_noise else {}
             if submit is not None and fetch is not None:
-                handle = submit(z, x_T, bi & 1, *extra)
+                handle = submit(z, x_T, bi & 1, *extra, **kw)
                 if pending is not None:
                     score(pending[1], fetch(pending[0]))
                 pending = (handle, cur)
             else:
-                score(cur, reconstruct(z, x_T, *extra))
+                score(cur, reconstruct(z, x_T, *extra, **kw))
         if pending is not None:
             score(pending[1], fetch(pending[0]))
         rows = [f.result() if hasattr(f, "result") else f for f in rows_f]
@@ -249,6 +258,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--device_metrics", action="store_true",
                     help="score PSNR and SSIM on the GPU (one kernel on the sampler's output; the originals go up as uint8, 16 bytes per "
                          "record come back) instead of on host threads; off by default")
+    ap.add_argument("--device_noise", action="store_true",
+                    help="with --seed: start noise and the --eta > 0 noise of record i come from the device generator keyed by seed + i "
+                         "(no host draws, no upload; --eta > 0 then runs pipelined); another generator than --seed alone, so other numbers")
     ap.add_argument("--timing", action="store_true", help="print set-up and loop wall time (records/s of the loop) to stderr")
     ap.add_argument("--workers", type=int, default=None, help="host threads for decode / metrics (default: this rank's share of the CPUs, 2..16)")
     ap.add_argument("--force-process-group", action="store_true",
@@ -262,8 +274,9 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
-    from ._common import check_sampler_flags
+    from ._common import check_sampler_flags, check_noise_flags
     check_sampler_flags(args.sampler, args.eta)                    # (before any rank is started)
+    check_noise_flags(args.device_noise, args.seed)
 
     from ..utils.launch import ensure_ranks, init_process_group, rank_env, single_rank_env
     if args.gpus is not None:
@@ -296,11 +309,12 @@ def main(argv=None) -> None:
     sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0, sampler=args.sampler, spacing=args.spacing,
                             prediction=args.prediction)
 
-    def reconstruct(z: np.ndarray, x_T: Optional[torch.Tensor], orig_u8: Optional[np.ndarray] = None):
+    def reconstruct(z: np.ndarray, x_T: Optional[torch.Tensor], orig_u8: Optional[np.ndarray] = None, seeds=None):
         zt = torch.from_numpy(z).to(device)
+        noise_kw = {} if seeds is None else dict(seeds=seeds)      # --device_noise
         with torch.no_grad():
             x = sampler.sample(net, zt, shape=(zt.shape[0], 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale,
-                               x_T=None if x_T is None else x_T.to(device))
+                               x_T=None if x_T is None else x_T.to(device), **noise_kw)
             if orig_u8 is not None:                                # --device_metrics on the sequential route
                 ticket = scorer.enqueue(x, orig_u8, 0)
                 recon = None if u8 else x.clamp(-1, 1).cpu().numpy()
@@ -318,13 +332,15 @@ def main(argv=None) -> None:
     u8 = not learned_metrics_available()
     scorer = DeviceScorer(device, args.batch, 3, args.size) if args.device_metrics else None
 
-    def submit(z: np.ndarray, x_T: Optional[torch.Tensor], slot: int, orig_u8: Optional[np.ndarray] = None):
+    def submit(z: np.ndarray, x_T: Optional[torch.Tensor], slot: int, orig_u8: Optional[np.ndarray] = None, seeds=None):
         zt = torch.from_numpy(z).to(device)
         xt = None if x_T is None else x_T.to(device)
+        noise_kw = {} if seeds is None else dict(seeds=seeds)      # --device_noise
         st = streams[slot]
         st.wait_stream(torch.cuda.current_stream(device))
         with torch.no_grad(), torch.cuda.stream(st):
-            x = sampler.sample(net, zt, shape=(zt.shape[0], 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale, x_T=xt, slot=slot)
+            x = sampler.sample(net, zt, shape=(zt.shape[0], 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale, x_T=xt, slot=slot,
+                               **noise_kw)
             if orig_u8 is not None:                                # --device_metrics: only the (b,2) block returns, unless LPIPS / CLIP need floats
                 ticket = scorer.enqueue(x, orig_u8, slot)
                 host = None
@@ -355,13 +371,14 @@ def main(argv=None) -> None:
             return scorer.collect(handle[5]), None if handle[0] is None else handle[0].numpy().copy()
         return handle[0].numpy().copy()                            # the pinned buffer of this slot is reused two batches later
 
-    pipelined = args.eta == 0                                      # the fused sampler; eta > 0 draws noise step by step
+    # the fused sampler; eta > 0 draws noise step by step from the device's one generator -- unless the draws are the records' own
+    pipelined = args.eta == 0 or args.device_noise
     t_loop = time.perf_counter()
     marks: list = []
     rows = evaluate(manifest, lambda rec: load_embedding(Path(rec["bitstream"]), scale, zero), reconstruct,
                     args.size, args.batch, args.seed, rank, world, device, start_noise,
                     submit if pipelined else None, fetch if pipelined else None, workers=args.workers, u8=u8 and pipelined,
-                    marks=marks, device_metrics=args.device_metrics, learned=args.device_metrics and not u8)
+                    marks=marks, device_metrics=args.device_metrics, learned=args.device_metrics and not u8, device_noise=args.device_noise)
     if args.timing and rank == 0:
         t_end = time.perf_counter()
         print(f"[eval] set-up {t_loop - t_start:.2f} s (checkpoint load + weight repack), loop {t_end - t_loop:.2f} s for {len(manifest)} records = "

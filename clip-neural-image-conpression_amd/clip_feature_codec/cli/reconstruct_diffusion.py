@@ -5,8 +5,9 @@ Same flags, defaults and output as the reference CLI (cli/reconstruct_diffusion.
 the PNG is written from ``((clamp(x,-1,1)+1)*127.5).astype(uint8)`` (truncation).  Additions that
 default to the reference behaviour: ``--seed`` (reproducible CPU-generated start noise; the reference
 never seeds), ``--dtype {fp32,bf16,f16x3}``, ``--cfg_scale`` (classifier-free guidance; 1.0 = off), ``--sampler {ddim,dpmpp2m}`` with ``--spacing {linspace,logsnr}``
-(the second-order multistep solver of ``diffusion/dpm_solver.py``; default ``ddim``) and the architecture is read
-from the checkpoint's shapes.
+(the second-order multistep solver of ``diffusion/dpm_solver.py``; default ``ddim``), ``--device_noise`` (with ``--seed``: the start
+noise and the ``--eta > 0`` noise come from the device generator keyed by the seed, nothing is drawn on the host or uploaded; another
+generator than ``--seed`` alone, so another image) and the architecture is read from the checkpoint's shapes.
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ._common import check_sampler_flags, pick_device, load_codec_meta, load_embedding, build_model, build_sampler, start_noise
+from ._common import check_noise_flags, check_sampler_flags, pick_device, record_seeds, load_codec_meta, load_embedding, build_model, build_sampler, start_noise
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -31,6 +32,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--device", type=str, default=None)
     ap.add_argument("--seed", type=int, default=None, help="seed of the CPU-generated start noise (default: unseeded, like the reference)")
+    ap.add_argument("--device_noise", action="store_true",
+                    help="with --seed: every draw comes from the device generator keyed by the seed (reproducible also with --eta > 0); "
+                         "another generator than --seed alone")
     ap.add_argument("--dtype", choices=["fp32", "bf16", "f16x3"], default="fp32")
     ap.add_argument("--cfg_scale", type=float, default=1.0,
                     help="classifier-free guidance scale w: eps = eps_u + w * (eps_c - eps_u), eps_u predicted from the zero embedding "
@@ -50,6 +54,7 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
     check_sampler_flags(args.sampler, args.eta)
+    check_noise_flags(args.device_noise, args.seed)
 
     device = pick_device(args.device)
     scale, zero = load_codec_meta(Path(args.store_dir))
@@ -57,10 +62,11 @@ def main(argv=None) -> None:
     net = build_model(args.weights, device, z.shape[1], args.dtype)
     sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0, sampler=args.sampler, spacing=args.spacing,
                             prediction=args.prediction)
-    x_T = start_noise([0], args.size, args.seed)
+    x_T = None if args.device_noise else start_noise([0], args.size, args.seed)
+    noise_kw = dict(seeds=record_seeds([0], args.seed)) if args.device_noise else {}
     with torch.no_grad():
         x = sampler.sample(net, z, shape=(1, 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale,
-                           x_T=None if x_T is None else x_T.to(device))
+                           x_T=None if x_T is None else x_T.to(device), **noise_kw)
     img = x[0].clamp(-1, 1).cpu().numpy().transpose(1, 2, 0)
     Image.fromarray(((img + 1.0) * 127.5).astype(np.uint8)).save(args.out)
     print(f"Saved to {args.out}")

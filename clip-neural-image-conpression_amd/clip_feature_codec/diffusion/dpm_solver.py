@@ -25,6 +25,10 @@ and stepwise for any callable ``model(x, z, t)`` (one model call per step, two w
 ``prediction="v"`` (default ``"eps"``): the network output is ``v = a_t noise - s_t x0``; the first line of the step becomes
 ``x0 = clamp(a_t x - s_t v, -1, 1)``, ``e = s_t x + a_t v`` on the same tables, the rest is unchanged (``ccn_set_prediction`` on the
 fused route, ``ccn_sampler_step`` on the stepwise one).  It must match how the weights were trained.
+
+``sample(..., seeds=...)``: one 64-bit seed per record (ints or an int64 tensor of ``B`` entries, as for ``DDIMSampler``); ``x_T=None``
+is then the records' own start noise, ``normal_fill(seeds, shape, 0)``.  The steps draw nothing, so a given ``x_T`` makes the
+seeds irrelevant; a wrong length is still a ``ValueError``.
 """
 from __future__ import annotations
 
@@ -65,13 +69,17 @@ class DPMSolverSampler:
 
     @torch.no_grad()
     def sample(self, model, z_clip: torch.Tensor, shape: tuple, steps: int = 20, cfg_scale: float = 1.0,
-               x_T: Optional[torch.Tensor] = None, slot: int = 0) -> torch.Tensor:
+               x_T: Optional[torch.Tensor] = None, slot: int = 0, seeds=None) -> torch.Tensor:
         ts, coef = self.tables(steps)
         w, null_z = guidance.resolve(self.guided, self.null_z, z_clip, cfg_scale)
         device = z_clip.device
         if device.type != "cuda":
             raise RuntimeError(f"z_clip is on {device}: DPMSolverSampler (MI355X build) needs a HIP device; no CPU fallback")
-        x = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
+        if seeds is not None:
+            seeds = _native.seeds_tensor(seeds, int(shape[0]), device).to(device)
+            x = _native.normal_fill(seeds, shape, 0) if x_T is None else x_T.to(device)
+        else:
+            x = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
         if hasattr(model, "sample_ddim"):
             guide = {} if w is None else dict(guidance=w, null_z=null_z)
             if self.prediction != "eps":

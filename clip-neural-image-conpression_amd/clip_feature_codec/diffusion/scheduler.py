@@ -62,11 +62,17 @@ class NoiseScheduler:
         """``linspace(T-1, 0, steps).long()`` -- fp32 linspace truncated, like the reference."""
         return torch.linspace(self.timesteps - 1, 0, steps).long().numpy().astype(np.int32)
 
-    def ddim_coefficients(self, steps: int, eta: float = 0.0) -> np.ndarray:
+    def ddim_coefficients(self, steps: int, eta: float = 0.0, cap_sigma: bool = False) -> np.ndarray:
         """(steps, 5) fp32: sqrt(1-ab_t), sqrt(ab_t), sqrt(ab_s), sqrt(ab_s - sigma^2), sigma.
 
         ab_s is ``alphas_cumprod_prev[t]`` (the reference's choice, ddim.py:35) and 1.0 on the
-        last step; the direction coefficient has no "1 -" (ddim.py:42).  Both are reproduced.
+        last step; the direction coefficient has no "1 -" (ddim.py:42).  Both are reproduced --
+        and with them the reference's NaN: where ``sigma^2 > ab_s`` (step 0 of the cosine table for
+        any ``eta > 1.5e-3``) the direction coefficient is the root of a negative number and every
+        later state is NaN.  ``cap_sigma`` (the seeded samplers; default off, the table above bit
+        for bit): on such a step sigma is capped at ``sqrt(ab_s)`` and the direction coefficient is
+        0, the end point of the same formula (``c3^2 + sigma^2 = ab_s`` still holds); every other
+        row is unchanged.
         """
         ts = torch.linspace(self.timesteps - 1, 0, steps).long()
         acp, prev = self.host["alphas_cumprod"], self.host["alphas_cumprod_prev"]
@@ -81,6 +87,8 @@ class NoiseScheduler:
                 sigma = torch.tensor(0.0)
             rows[i] = (float(torch.sqrt(1 - ab_t)), float(torch.sqrt(ab_t)), float(torch.sqrt(ab_s)),
                        float(torch.sqrt(ab_s - sigma ** 2)), float(sigma))
+            if cap_sigma and float(ab_s - sigma ** 2) < 0:
+                rows[i, 3], rows[i, 4] = 0.0, rows[i, 2]
         return rows
 
     # -- multistep solver host-side tables (diffusion/dpm_solver.py; no reference counterpart) ----

@@ -11,6 +11,7 @@
 #include "../../include/ccn_hip.h"
 #include "ccn_internal.h"
 #include "ccn_arch.h"
+#include "ccn_philox.h"
 
 #include <algorithm>
 #include <cmath>
@@ -155,6 +156,10 @@ struct SamplerRun {
     std::vector<float> coef;             // [steps][4]
     std::vector<float> sigma;            // eta > 0 (empty: eta = 0)
     const float* noise = nullptr;        // ... and the caller's noise tensor, [steps] x one state
+    // ... or, instead of `noise`, one seed per record of the state: step i's noise is draw 1 + i of each record, generated by the
+    // updating launch.  The address is captured, the contents are read at run time.  Unguided, the head then writes the raw output
+    // of the B rows into `eps` on the steps with sigma > 0 and one sampler-step launch follows it, as in the guided loop.
+    const uint64_t* seeds = nullptr;
     // Classifier-free guidance: the plan's batch is 2B rows -- [0, B) carry z, [B, 2B) the null embedding, both the same state -- the
     // head writes the raw network output of all 2B rows into `eps` (whatever it predicts: the combine launch applies the handle's
     // parameterisation), and one combine launch per step updates both halves of the state.
@@ -174,8 +179,9 @@ struct SamplerRun {
         auto same = [](const auto& a, const auto& b) {              // two tables, bit for bit
             return a.size() == b.size() && (a.empty() || !std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])));
         };
-        return steps == o.steps && same(ts, o.ts) && same(coef, o.coef) && noise == o.noise && same(sigma, o.sigma) &&
-               guided == o.guided && (!guided || (w == o.w && eps == o.eps)) && hist == o.hist && same(c4, o.c4) && pred == o.pred;
+        return steps == o.steps && same(ts, o.ts) && same(coef, o.coef) && noise == o.noise && seeds == o.seeds && same(sigma, o.sigma) &&
+               guided == o.guided && (!guided || w == o.w) && ((!guided && !seeds) || eps == o.eps) && hist == o.hist && same(c4, o.c4) &&
+               pred == o.pred;
     }
 };
 
@@ -876,12 +882,14 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, const SamplerRun
     for (int i = 0; i < r.steps; ++i) {
         const float* cf = r.coef.data() + i * 4;
         const float c4 = ms ? r.c4[i] : 0.f;
-        const bool noisy = !r.sigma.empty() && r.noise && r.sigma[i] > 0.f;
-        const float* nz = noisy ? r.noise + (size_t)i * img : nullptr;
+        const bool noisy = !r.sigma.empty() && (r.noise || r.seeds) && r.sigma[i] > 0.f;
+        const float* nz = noisy && r.noise ? r.noise + (size_t)i * img : nullptr;
         const float sigma = noisy ? r.sigma[i] : 0.f;
+        const uint64_t* seeds = noisy ? r.seeds : nullptr;          // this step's update generates draw 1 + i
+        const bool split = r.guided || seeds;                       // the head writes the raw output, a sampler-step launch updates
         StepCtx c;
         c.step = i; c.x_in = xstate;
-        if (r.guided) { c.x_state = nullptr; c.eps_out = r.eps; c.do_ddim = 0; }
+        if (split) { c.x_state = nullptr; c.eps_out = r.eps; c.do_ddim = 0; }
         else {
             c.x_state = xstate; c.eps_out = nullptr; c.do_ddim = 1;
             for (int k = 0; k < 4; ++k) c.c[k] = cf[k];
@@ -890,10 +898,13 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, const SamplerRun
         }
         if (int rc = run_ops(h, b, s, c)) return rc;
         // guided: the combine and the update of both halves (unguided, the update is the head kernel's epilogue)
-        if (r.guided)
-            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * (5 + (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0)), s, [&] {
-                    return launch_sampler_step(xstate, xstate + img, ms ? r.hist : nullptr, r.eps, r.eps + img, nz, h->pred, r.w, cf[0], cf[1],
-                                               cf[2], cf[3], c4, sigma, (int64_t)img, s); })) return rc;
+        // (unguided with seeds, a noisy step: the same launch without the second half -- 3 passes over one state)
+        const double passes = r.guided ? 5 + (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0) : 3;
+        if (split)
+            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * passes, s, [&] {
+                    return launch_sampler_step(xstate, r.guided ? xstate + img : nullptr, ms ? r.hist : nullptr, r.eps, r.guided ? r.eps + img : nullptr,
+                                               nz, h->pred, r.w, cf[0], cf[1], cf[2], cf[3], c4, sigma, (int64_t)img, s, seeds, 1u + (uint32_t)i,
+                                               (int64_t)h->cfg.img_ch * p.H * p.W); })) return rc;
     }
     return CCN_OK;
 }
@@ -1285,6 +1296,56 @@ int ccn_sample_guided(ccn_handle_t h, const float* z_dev, const float* z_null_de
     r.noise = noise_dev;
     r.guided = true; r.z_null = z_null_dev; r.w = w; r.eps = eps_scratch_dev;
     return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
+}
+
+// the seeded entries' own checks; sigma_host NULL (eta = 0) leaves the run unseeded: nothing would be drawn
+static int seed_run(SamplerRun& r, const uint64_t* seeds_dev, int32_t H, int32_t W, int img_ch)
+{
+    if (!seeds_dev || ((uintptr_t)seeds_dev & 7)) return fail(CCN_EINVAL, "the seeds must be non-null and 8-byte aligned");
+    if (H > 0 && W > 0 && (int64_t)img_ch * H * W >= kDrawMaxPerRecord) return fail(CCN_EINVAL, "a record of 2^34 elements or more cannot be drawn");
+    if (!r.sigma.empty()) r.seeds = seeds_dev;
+    return CCN_OK;
+}
+
+int ccn_sample_seeded(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H, int32_t W,
+                      int32_t steps, const int32_t* ts_host, const float* coef_host, const float* sigma_host, const uint64_t* seeds_dev,
+                      float* out_scratch_dev, void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph)
+{
+    if (!out_scratch_dev || ((uintptr_t)out_scratch_dev & 15)) return fail(CCN_EINVAL, "the output scratch must be non-null and 16-byte aligned");
+    SamplerRun r;
+    if (int rc = begin_run(h, steps, ts_host, coef_host, sigma_host, r)) return rc;
+    if (int rc = seed_run(r, seeds_dev, H, W, h->cfg.img_ch)) return rc;
+    if (r.seeds) r.eps = out_scratch_dev;
+    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
+}
+
+int ccn_sample_guided_seeded(ccn_handle_t h, const float* z_dev, const float* z_null_dev, const float* x_T_dev, float* x_out_dev, int32_t B,
+                             int32_t H, int32_t W, int32_t steps, const int32_t* ts_host, const float* coef_host, const float* sigma_host,
+                             const uint64_t* seeds_dev, float w, float* eps_scratch_dev, void* workspace_dev, size_t workspace_bytes,
+                             void* stream, int32_t use_graph)
+{
+    if (!std::isfinite(w)) return fail(CCN_EINVAL, "the guidance scale must be finite");
+    if (!eps_scratch_dev || ((uintptr_t)eps_scratch_dev & 15)) return fail(CCN_EINVAL, "the eps scratch must be non-null and 16-byte aligned");
+    SamplerRun r;
+    if (int rc = begin_run(h, steps, ts_host, coef_host, sigma_host, r)) return rc;
+    if (int rc = seed_run(r, seeds_dev, H, W, h->cfg.img_ch)) return rc;
+    r.guided = true; r.z_null = z_null_dev; r.w = w; r.eps = eps_scratch_dev;
+    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
+}
+
+int ccn_sampler_step_seeded(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,
+                            const uint64_t* seeds_dev, uint32_t draw, int64_t per_record, int32_t pred, float w, const float* coef_host,
+                            float sigma, int64_t n, void* stream)
+{
+    if (!x_dev || !out_c_dev || !coef_host || n < 0) return fail(CCN_EINVAL, "bad argument");
+    if (pred != CCN_PRED_EPS && pred != CCN_PRED_V) return fail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
+    if (!seeds_dev || ((uintptr_t)seeds_dev & 7)) return fail(CCN_EINVAL, "the seeds must be non-null and 8-byte aligned");
+    if (per_record <= 0 || per_record >= kDrawMaxPerRecord || n % per_record) return fail(CCN_EINVAL, "per_record must be in [1, 2^34) and divide n");
+    if (n / per_record > 65535) return fail(CCN_EINVAL, "at most 65535 records per launch");
+    if (n == 0) return CCN_OK;
+    HIPCHK(launch_sampler_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, nullptr, pred, w, coef_host[0], coef_host[1], coef_host[2],
+                               coef_host[3], x0_hist_dev ? coef_host[4] : 0.f, sigma, n, (hipStream_t)stream, seeds_dev, draw, per_record));
+    return CCN_OK;
 }
 
 // the [steps][5] table of the multistep entries -> the [steps][4] one of a SamplerRun and the c4 column, checked

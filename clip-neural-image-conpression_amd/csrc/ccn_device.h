@@ -2,6 +2,7 @@
 // the GroupNorm+SiLU prologue transform).
 #pragma once
 #include "ccn_internal.h"
+#include "ccn_philox.h"
 
 namespace ccn {
 
@@ -58,6 +59,28 @@ __device__ __forceinline__ float sampler_update_p(int pred, float x, float y, fl
                                                   float& x0_out)
 {
     return pred == PRED_V ? sampler_update_v(x, y, c0, c1, c2, c3, c4, hist, x0_out) : sampler_update(x, y, c0, c1, c2, c3, c4, hist, x0_out);
+}
+
+// ---- record-keyed normals (Noise) ----------------------------------------------------------------------------
+// Element j of draw d of the record with seed s: the Philox words of quad q = j >> 2 (ccn_philox.h), pair p = (j & 3) >> 1 of them
+// through Box-Muller with the precise library functions.  u = ((r >> 9) + 0.5) * 2^-23 is exact in fp32 and inside (0, 1), so
+// |n| <= sqrt(-2 ln 2^-24) = 5.768.  draw_quad (a lane owns elements 4q .. 4q+3) and draw_element (one element) run the same
+// operations on the same words: the value of an element does not depend on which computed it.
+__device__ __forceinline__ float draw_unit(uint32_t r) { return __fmul_rn(__fadd_rn((float)(r >> 9), 0.5f), 1.1920928955078125e-07f); }
+__device__ __forceinline__ float draw_radius(uint32_t r) { return sqrtf(__fmul_rn(-2.0f, logf(draw_unit(r)))); }
+__device__ __forceinline__ float draw_turn(uint32_t r) { return __fmul_rn(2.0f, draw_unit(r)); }      // cospif / sinpif argument
+__device__ __forceinline__ float4 draw_quad(uint64_t seed, uint32_t draw, uint32_t q)
+{
+    const Philox4 r = draw_words(seed, draw, q);
+    const float rad0 = draw_radius(r.v[0]), th0 = draw_turn(r.v[1]), rad1 = draw_radius(r.v[2]), th1 = draw_turn(r.v[3]);
+    return make_float4(__fmul_rn(rad0, cospif(th0)), __fmul_rn(rad0, sinpif(th0)), __fmul_rn(rad1, cospif(th1)), __fmul_rn(rad1, sinpif(th1)));
+}
+__device__ __forceinline__ float draw_element(uint64_t seed, uint32_t draw, int64_t j)
+{
+    const Philox4 r = draw_words(seed, draw, (uint32_t)(j >> 2));
+    const int p = (int)(j & 2);                                     // 2 * pair
+    const float rad = draw_radius(r.v[p]), th = draw_turn(r.v[p + 1]);
+    return __fmul_rn(rad, (j & 1) ? sinpif(th) : cospif(th));
 }
 
 template <typename T> __device__ __forceinline__ float silu_f(float v);

@@ -817,12 +817,26 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
 // when c4 != 0 and receives the clamped x0; noise (nullable) adds sigma*noise; x is updated in place and x_dup (nullable) receives the
 // same values: the unconditional half of the guided loop's state.  VEC: every pointer is 16-byte aligned, four elements per lane and
 // access; the n % 4 tail goes one by one.
-template <bool VEC>
+// SEEDED: the value `noise` would have held is generated instead (Noise): x is gridDim.y records of `per`
+// elements, the blocks of row blockIdx.y work on record b = blockIdx.y alone (one seed load per lane, no division), and element j
+// of it is draw_quad / draw_element(seeds[b], draw, j).  VEC then also means per % 4 == 0, so that every record starts 16-byte
+// aligned and a lane's four elements are one quad of it.  The unseeded instantiations (gridDim.y == 1) are the kernel as it was.
+template <bool VEC, bool SEEDED>
 __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x_dup, float* __restrict__ hist, const float* __restrict__ out_c,
                                     const float* __restrict__ out_u, const float* __restrict__ noise, int pred, float w, float c0, float c1,
-                                    float c2, float c3, float c4, float sigma, int64_t n)
+                                    float c2, float c3, float c4, float sigma, int64_t n, const uint64_t* __restrict__ seeds, uint32_t draw,
+                                    int64_t per)
 {
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+    uint64_t seed = 0;
+    if constexpr (SEEDED) {                                         // this record's slice of every tensor
+        const int64_t off = (int64_t)blockIdx.y * per;
+        seed = seeds[blockIdx.y];
+        x += off; out_c += off; n = per;
+        if (x_dup) x_dup += off;
+        if (hist) hist += off;
+        if (out_u) out_u += off;
+    }
     const int64_t n4 = VEC ? n / 4 : 0;
     if (!hist) c4 = 0.f;
     for (int64_t q = tid; q < n4; q += nthr) {
@@ -839,8 +853,10 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         o.y = sampler_update_p(pred, xv.y, yv.y, c0, c1, c2, c3, c4, hv.y, p.y);
         o.z = sampler_update_p(pred, xv.z, yv.z, c0, c1, c2, c3, c4, hv.z, p.z);
         o.w = sampler_update_p(pred, xv.w, yv.w, c0, c1, c2, c3, c4, hv.w, p.w);
-        if (noise) {
-            const float4 nv = ((const float4*)noise)[q];
+        if (SEEDED || noise) {
+            float4 nv;
+            if constexpr (SEEDED) nv = draw_quad(seed, draw, (uint32_t)q);
+            else nv = ((const float4*)noise)[q];
             o.x = __fadd_rn(o.x, __fmul_rn(sigma, nv.x)); o.y = __fadd_rn(o.y, __fmul_rn(sigma, nv.y));
             o.z = __fadd_rn(o.z, __fmul_rn(sigma, nv.z)); o.w = __fadd_rn(o.w, __fmul_rn(sigma, nv.w));
         }
@@ -854,20 +870,36 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         const float hv = c4 != 0.f ? hist[i] : 0.f;
         float p;
         float xn = sampler_update_p(pred, x[i], y, c0, c1, c2, c3, c4, hv, p);
-        if (noise) xn = __fadd_rn(xn, __fmul_rn(sigma, noise[i]));
+        if constexpr (SEEDED) xn = __fadd_rn(xn, __fmul_rn(sigma, draw_element(seed, draw, i)));
+        else if (noise) xn = __fadd_rn(xn, __fmul_rn(sigma, noise[i]));
         if (hist) hist[i] = p;
         x[i] = xn;
         if (x_dup) x_dup[i] = xn;
     }
 }
+// seeds given and sigma > 0: the seeded form (the caller has checked per > 0 and n % per == 0; `noise` is then not read)
 hipError_t launch_sampler_step(float* x, float* x_dup, float* hist, const float* out_c, const float* out_u, const float* noise, int pred,
-                               float w, float c0, float c1, float c2, float c3, float c4, float sigma, int64_t n, hipStream_t s)
+                               float w, float c0, float c1, float c2, float c3, float c4, float sigma, int64_t n, hipStream_t s,
+                               const uint64_t* seeds, uint32_t draw, int64_t per)
 {
-    const bool vec = !(((uintptr_t)x | (uintptr_t)x_dup | (uintptr_t)hist | (uintptr_t)out_c | (uintptr_t)out_u | (uintptr_t)noise) & 15);
-    const int64_t work = vec ? (n + 3) / 4 : n, blocks = (work + 255) / 256;
-    const int grid = (int)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);      // 256 CUs x 8 blocks, grid-stride beyond
-    if (vec) hipLaunchKernelGGL(sampler_step_kernel<true>, dim3(grid), dim3(256), 0, s, x, x_dup, hist, out_c, out_u, noise, pred, w, c0, c1, c2, c3, c4, sigma, n);
-    else hipLaunchKernelGGL(sampler_step_kernel<false>, dim3(grid), dim3(256), 0, s, x, x_dup, hist, out_c, out_u, noise, pred, w, c0, c1, c2, c3, c4, sigma, n);
+    const bool seeded = seeds && sigma > 0.f;
+    if (seeded) noise = nullptr;
+    if (seeded && (per <= 0 || n % per || n / per > 65535)) return hipErrorInvalidValue;     // one grid row per record
+    const bool vec = !(((uintptr_t)x | (uintptr_t)x_dup | (uintptr_t)hist | (uintptr_t)out_c | (uintptr_t)out_u | (uintptr_t)noise) & 15) &&
+                     !(seeded && (per & 3));
+    const int64_t rows = seeded ? n / per : 1, row = seeded ? per : n;
+    const int64_t work = vec ? (row + 3) / 4 : row, blocks = (work + 255) / 256;
+    const int gx = (int)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);        // 256 CUs x 8 blocks, grid-stride beyond
+    const dim3 grid(gx, (unsigned)rows);
+#define CCN_STEP_ARGS x, x_dup, hist, out_c, out_u, noise, pred, w, c0, c1, c2, c3, c4, sigma, n, seeds, draw, per
+    if (seeded) {
+        if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, true>), grid, dim3(256), 0, s, CCN_STEP_ARGS);
+        else hipLaunchKernelGGL((sampler_step_kernel<false, true>), grid, dim3(256), 0, s, CCN_STEP_ARGS);
+    } else {
+        if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, false>), grid, dim3(256), 0, s, CCN_STEP_ARGS);
+        else hipLaunchKernelGGL((sampler_step_kernel<false, false>), grid, dim3(256), 0, s, CCN_STEP_ARGS);
+    }
+#undef CCN_STEP_ARGS
     return hipGetLastError();
 }
 

@@ -234,6 +234,56 @@ int ccn_sampler_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const f
                      const float* noise_dev, int32_t pred, float w, const float* coef_host /* [5] */, float sigma, int64_t n,
                      void* stream);
 
+/* ---- seeded device noise: a record's draws are a function of its seed ------------------------------------------------------------ *
+ * (No reference counterpart: the reference draws torch.randn / randn_like from whatever generator is current.)  A counter-based
+ * generator, Philox4x32-10 with the Random123 constants, through Box-Muller.  Element j (NCHW index inside the record, j < C*H*W) of
+ * draw d of the record with 64-bit seed s:
+ *   key      (s & 0xffffffff, s >> 32);
+ *   counter  (q, d, 0, 0) with q = j >> 2; d = 0 is the start noise, d = 1 + i the noise of loop step i; words 2 and 3 are reserved;
+ *   normals  the output words r0..r3 give elements 4q..4q+3: pair p = (j & 3) >> 1 has u1 = ((r[2p] >> 9) + 0.5) * 2^-23 and
+ *            u2 = ((r[2p+1] >> 9) + 0.5) * 2^-23 (exact in fp32, inside (0, 1)), rad = sqrtf(-2 logf(u1)); an even j is
+ *            rad * cospif(2 u2), an odd j rad * sinpif(2 u2), the precise library functions; |n| <= 5.77.
+ * Batch position, batch size, rank and call history do not enter, and neither does how a kernel walks the record (a quad per lane
+ * or an element per lane).  per_record >= 2^34 is CCN_EINVAL (q is one counter word).
+ *
+ * ccn_normal_fill: out_dev (B, per_record) fp32, row b the draw `draw` of the record with seed seeds_dev[b] (B x uint64 on the
+ * device, read when the kernel runs).  16-byte stores in the rows that start 16-byte aligned, 4-byte stores in the others
+ * (per_record % 4 != 0 puts later rows off alignment).  CCN_EINVAL: a NULL pointer, out_dev not 4-byte or seeds_dev not 8-byte
+ * aligned, B outside [1, 65535], per_record <= 0 or >= 2^34. */
+int ccn_normal_fill(float* out_dev, const uint64_t* seeds_dev, int32_t B, int64_t per_record, uint32_t draw, void* stream);
+
+/* ccn_sampler_step whose noise is generated where it is consumed: x_dev holds n / per_record records of per_record elements (one
+ * state; x_dup_dev receives the same values), record b drawing from seeds_dev[b].  With sigma > 0 the update adds sigma * n with
+ * n the element's value of draw `draw`, by the same two separately rounded ops as sigma * noise_dev[i]: the result equals
+ * ccn_sampler_step on a noise tensor filled by ccn_normal_fill, bit for bit.  sigma <= 0: no noise, seeds_dev is not read.
+ * CCN_EINVAL: as for ccn_sampler_step, and seeds_dev NULL or not 8-byte aligned, per_record <= 0 or >= 2^34, n % per_record != 0, more than
+ * 65535 records. */
+int ccn_sampler_step_seeded(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,
+                            const uint64_t* seeds_dev, uint32_t draw, int64_t per_record, int32_t pred, float w,
+                            const float* coef_host /* [5] */, float sigma, int64_t n, void* stream);
+
+/* ccn_sample_eta with the noise of step i generated as draw 1 + i of each record: no noise tensor exists.  seeds_dev: B x uint64 on
+ * the device, owned by the caller and kept at the same address while a captured graph for it is cached; its CONTENTS are read when
+ * the loop runs, so a replay after the caller rewrote them gives the new records' draws.  sigma_host NULL: eta = 0, the loop is
+ * ccn_sample's and the seeds only matter to the caller's start noise (ccn_normal_fill, draw 0).  out_scratch_dev: B*img_ch*H*W
+ * floats, 16-byte aligned, owned by the caller like the workspace: on a step with sigma > 0 the head writes the raw network output
+ * there and one ccn_sampler_step_seeded launch applies the update; the other steps update in the head as in ccn_sample.  The result
+ * equals ccn_sample_eta on the materialised draws, bit for bit.  The captured graph is cached per (table, sigma, seeds address,
+ * scratch address); the draw index of a step is a by-value kernel argument. */
+int ccn_sample_seeded(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev,
+                      int32_t B, int32_t H, int32_t W, int32_t steps,
+                      const int32_t* ts_host, const float* coef_host, const float* sigma_host, const uint64_t* seeds_dev,
+                      float* out_scratch_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph);
+
+/* ccn_sample_guided likewise: the combine launch of a step with sigma > 0 generates the draws, one set for both halves.
+ * eps_scratch_dev as for ccn_sample_guided (2*B*img_ch*H*W floats). */
+int ccn_sample_guided_seeded(ccn_handle_t h, const float* z_dev, const float* z_null_dev, const float* x_T_dev, float* x_out_dev,
+                             int32_t B, int32_t H, int32_t W, int32_t steps,
+                             const int32_t* ts_host, const float* coef_host, const float* sigma_host, const uint64_t* seeds_dev,
+                             float w, float* eps_scratch_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph);
+
 /* NoiseScheduler.q_sample (diffusion/scheduler.py:46-49): out[b] = a[b]*x0[b] + s[b]*noise[b];
  * a_dev/s_dev are the gathered per-sample coefficients, (B,) fp32; per_sample = C*H*W. */
 int ccn_q_sample(float* out_dev, const float* x0_dev, const float* noise_dev,

@@ -3,8 +3,12 @@
 decode, reconstruction (two batches in flight), PSNR / SSIM on the host -- against the GPU-only rate of bench.py.
 
     python tools/eval_e2e.py [--n 64] [--size 256] [--dtype bf16] [--sampler ddim|dpmpp2m] [--steps 50] [--workers N] [--device-metrics]
+                             [--device-noise] [--eta E]
 
-``--device-metrics`` passes ``--device_metrics`` on (PSNR / SSIM scored on the GPU); ``--workers`` the number of host threads.
+``--device-metrics`` passes ``--device_metrics`` on (PSNR / SSIM scored on the GPU); ``--workers`` the number of host threads;
+``--device-noise`` passes ``--device_noise`` on (the records' draws come from the device generator: no host randn, no upload);
+``--eta`` the sampler's eta (under the CLI's cosine table anything above 1.5e-3 makes step 0's direction coefficient NaN unless
+``--device-noise`` is given, whose table caps sigma there).
 """
 import argparse, io, sys, tempfile, time
 from contextlib import redirect_stdout
@@ -24,6 +28,7 @@ def main():
     ap.add_argument("--n", type=int, default=256); ap.add_argument("--size", type=int, default=256); ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--sampler", choices=["ddim", "dpmpp2m"], default="ddim"); ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--workers", type=int, default=None); ap.add_argument("--device-metrics", action="store_true")
+    ap.add_argument("--device-noise", action="store_true"); ap.add_argument("--eta", type=float, default=0.0)
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as d:
         d = Path(d)
@@ -36,6 +41,10 @@ def main():
             argv += ["--workers", str(a.workers)]
         if a.device_metrics:
             argv += ["--device_metrics"]
+        if a.device_noise:
+            argv += ["--device_noise"]
+        if a.eta:
+            argv += ["--eta", str(a.eta)]
         for it in range(2):                                   # first pass pays checkpoint repack + graph capture
             buf = io.StringIO()
             torch.cuda.synchronize(); t0 = time.perf_counter()
