@@ -48,6 +48,12 @@ SIGNATURES = {
     "ccn_sample_seeded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_i32]),
     "ccn_sample_guided_seeded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_sz,
                                          c_vp, c_i32]),
+    "ccn_x0_threshold_scratch_bytes": (c_i32, [c_i32, c_i64, ctypes.POINTER(c_sz)]),
+    "ccn_x0_threshold": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_f32, c_i32, c_i64, ctypes.c_double, c_f32, c_vp, c_vp, c_sz, c_vp]),
+    "ccn_sampler_step_thr": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_i64, c_i32, c_f32, ctypes.POINTER(c_f32), c_f32, c_i64,
+                                     c_vp, c_vp]),
+    "ccn_set_dynamic_threshold": (c_i32, [c_vp, ctypes.c_double, c_f32, c_vp, c_sz]),
+    "ccn_dynamic_threshold_scratch_bytes": (c_i32, [c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
     "ccn_workspace_bytes": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
     "ccn_release_workspace": (c_i32, [c_vp, c_vp]),
     "ccn_forward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
@@ -201,6 +207,9 @@ class Workspace:
         # NativeUNet.sample, multistep: the x0 history of one state, likewise -- by element count, because the slot is keyed
         # by the PLAN's batch: a guided call of batch B (history of B rows) and an unguided one of batch 2B (2B rows) share it
         self.hist: Dict[int, torch.Tensor] = {}
+        # NativeUNet.sample with a dynamic threshold: the handle's threshold scratch (ccn_set_dynamic_threshold), by image count --
+        # likewise kept, because the captured graph holds its address
+        self.thr: Dict[int, torch.Tensor] = {}
 
     def history(self, like: torch.Tensor) -> torch.Tensor:
         """The kept x0 history of ``like``'s size (allocated on first use; never freed before the workspace, so that a captured
@@ -312,7 +321,8 @@ class NativeUNet:
 
     def sample(self, z: torch.Tensor, x_T: torch.Tensor, ts, coef, use_graph: bool = True, slot: int = 0, sigma=None,
                noise: Optional[torch.Tensor] = None, w: Optional[float] = None, z_null: Optional[torch.Tensor] = None,
-               hist: Optional[torch.Tensor] = None, seeds=None) -> torch.Tensor:
+               hist: Optional[torch.Tensor] = None, seeds=None, dynamic_threshold: Optional[float] = None,
+               threshold_max: Optional[float] = None) -> torch.Tensor:
         """Every step of a sampler inside the library, through the ``ccn_sample*`` entry that fits.  ``coef`` of ``(steps, 4)``: the
         DDIM loop; ``sigma`` (steps,) + ``noise`` (steps, B, C, H, W) fp32 on the device make it the eta > 0 one.  ``coef`` of
         ``(steps, 5)``: the multistep loop (``NoiseScheduler.solver_coefficients``; deterministic), ``hist`` its x0 history, fp32 of
@@ -323,7 +333,10 @@ class NativeUNet:
         seeded entries -- step ``i`` adds ``sigma[i]`` times draw ``1 + i`` of each record, generated in the loop; the seeds are
         copied, in stream order, into an int64 buffer kept with the workspace, so a later call with other seeds replays the same
         graph (a seeds tensor on another device is moved first: from the host that is a synchronous upload of ``8 B`` bytes).
-        ``sigma=None`` with seeds is eta = 0: nothing is drawn, the seeds are only checked and the unseeded entry runs."""
+        ``sigma=None`` with seeds is eta = 0: nothing is drawn, the seeds are only checked and the unseeded entry runs.
+        ``dynamic_threshold`` (a quantile in (0, 1]; None: off, the handle state is cleared) with ``threshold_max`` (None: no upper
+        bound): every step of whichever loop runs clamps x0 to the record's own threshold (ccn_set_dynamic_threshold); the scratch is
+        kept with the workspace."""
         import math
         import numpy as np
         z = require_dev(z, "z_clip"); x_T = require_dev(x_T, "x_T")
@@ -373,6 +386,15 @@ class NativeUNet:
             ws.seeds[:B].copy_(seeds)                 # on the current stream, in front of the launch
         if ms and hist is None:
             hist = ws.history(x_T)
+        if dynamic_threshold is None:
+            check(self.lib.ccn_set_dynamic_threshold(self.h, 0.0, 0.0, None, 0))
+        else:
+            tp, tm = threshold_args(dynamic_threshold, threshold_max)
+            if B not in ws.thr:
+                n = c_sz()
+                check(self.lib.ccn_dynamic_threshold_scratch_bytes(self.h, B, H, W, ctypes.byref(n)))
+                ws.thr[B] = torch.empty(n.value, dtype=torch.uint8, device=self.device)
+            check(self.lib.ccn_set_dynamic_threshold(self.h, tp, tm, ws.thr[B].data_ptr(), ws.thr[B].numel()))
         out = torch.empty_like(x_T)
         # every entry's arguments: (h, z[, z_null], x_T, out, B, H, W, steps, ts, coef, <its own>, workspace, bytes, stream, use_graph)
         zn = () if w is None else (ptr(z_null),)
@@ -858,13 +880,14 @@ def normal_fill(seeds, shape, draw: int = 0, out: Optional[torch.Tensor] = None,
 
 def sampler_step(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], prediction: str = "eps", out_u: Optional[torch.Tensor] = None,
                  w: float = 0.0, hist: Optional[torch.Tensor] = None, sigma: float = 0.0, noise: Optional[torch.Tensor] = None,
-                 x_dup: Optional[torch.Tensor] = None, seeds=None, draw: int = 0) -> torch.Tensor:
+                 x_dup: Optional[torch.Tensor] = None, seeds=None, draw: int = 0, thr: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One in-place sampler update of ``x`` for either parameterisation (ccn_sampler_step): ``out_c`` is the network output
     (``prediction`` says whether it is eps or v), ``out_u`` the unconditional one of a guided step (the update then acts on
     ``out_u + w * (out_c - out_u)``), ``coef`` = (c0, c1, c2, c3[, c4]), ``hist`` the multistep sampler's x0 history (read when
     ``c4 != 0``, then rewritten), ``noise`` the eta > 0 draw added as ``sigma * noise``, ``x_dup`` a copy of the new ``x``.  ``seeds`` (``x.shape[0]`` of them)
     instead of ``noise``: the draw ``draw`` of each record of ``x`` is generated in the kernel (ccn_sampler_step_seeded), the same
-    bits as ``noise=normal_fill(seeds, x.shape, draw)``."""
+    bits as ``noise=normal_fill(seeds, x.shape, draw)``.  ``thr`` (``(B,)`` fp32, ``x0_threshold``'s result): record ``b`` clamps its
+    x0 to ``[-thr[b], thr[b]]`` and divides by it instead of clamping to +-1 (ccn_sampler_step_thr; with noise or with seeds)."""
     lib = load_library()
     pred = prediction_code(prediction)
     x = require_dev(x, "x"); out_c = require_dev(out_c, "out_c")
@@ -879,12 +902,23 @@ def sampler_step(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], pr
     if len(c) not in (4, 5) or (hist is not None and len(c) != 5):
         raise ValueError("coef must be (c0, c1, c2, c3) or, with hist, (c0, c1, c2, c3, c4)")
     c5 = (c_f32 * 5)(*(c + [0.0] * (5 - len(c))))
+    sd = None
     if seeds is not None:
         if noise is not None:
             raise ValueError("seeds and noise exclude each other")
         if x.dim() < 1 or not 0 <= int(draw) < 1 << 32:
             raise ValueError("x must be (B, ...) and draw in [0, 2^32)")
         sd = require_dev(seeds_tensor(seeds, x.shape[0], x.device).to(x.device), "seeds", torch.int64)
+    if thr is not None:
+        thr = require_dev(thr, "thr")
+        if x.dim() < 1 or thr.numel() != x.shape[0]:
+            raise ValueError("thr must hold one threshold per record of x, (B,)")
+        with torch.cuda.device(x.device):
+            check(lib.ccn_sampler_step_thr(x.data_ptr(), ptr(x_dup), ptr(hist), out_c.data_ptr(), ptr(out_u), ptr(nz), ptr(sd), int(draw),
+                                           x.numel() // x.shape[0], pred, float(w), c5, float(sigma), x.numel(), thr.data_ptr(),
+                                           current_stream(x.device)))
+        return x
+    if seeds is not None:
         with torch.cuda.device(x.device):
             check(lib.ccn_sampler_step_seeded(x.data_ptr(), ptr(x_dup), ptr(hist), out_c.data_ptr(), ptr(out_u), sd.data_ptr(), int(draw),
                                               x.numel() // x.shape[0], pred, float(w), c5, float(sigma), x.numel(), current_stream(x.device)))
@@ -893,6 +927,55 @@ def sampler_step(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], pr
         check(lib.ccn_sampler_step(x.data_ptr(), ptr(x_dup), ptr(hist), out_c.data_ptr(), ptr(out_u), ptr(nz), pred, float(w), c5,
                                    float(sigma), x.numel(), current_stream(x.device)))
     return x
+
+
+def threshold_args(p, max_value=None) -> Tuple[float, float]:
+    """``(p, max_value)`` of a dynamic threshold as the C ABI takes them, checked: ``p`` in (0, 1], ``max_value`` (None: +inf, no
+    upper bound) at least 1; anything else is a ``ValueError``."""
+    import math
+    p = float(p)
+    m = math.inf if max_value is None else float(max_value)
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"dynamic_threshold must be a quantile in (0, 1], got {p}")
+    if not m >= 1.0:
+        raise ValueError(f"threshold_max must be at least 1, got {m}")
+    return p, m
+
+
+def x0_threshold(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], prediction: str = "eps", p: float = 0.995,
+                 max_value: Optional[float] = None, out_u: Optional[torch.Tensor] = None, w: float = 0.0,
+                 scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The dynamic threshold of every record of ``x`` (ccn_x0_threshold; DESIGN.md section 1, Thresholding): a ``(B,)`` fp32 tensor,
+    ``min(max(Q_p(|x0_b|), 1), max_value)`` with x0 formed from ``x``, ``out_c`` (``out_u``, ``w``: the guidance combine first),
+    ``prediction`` and ``coef[:2]`` exactly as ``sampler_step`` forms it -- pass the result as its ``thr=``.  ``scratch``: a uint8 HIP
+    tensor of ``x0_threshold_scratch_bytes(B)`` bytes to reuse across calls (any contents), else a new one."""
+    lib = load_library()
+    pred = prediction_code(prediction)
+    p, m = threshold_args(p, max_value)
+    x = require_dev(x, "x"); out_c = require_dev(out_c, "out_c")
+    out_u = require_dev(out_u, "out_u") if out_u is not None else None
+    if x.dim() < 1 or x.shape[0] < 1 or any(t is not None and t.numel() != x.numel() for t in (out_c, out_u)):
+        raise ValueError("x must be (B, ...) and the outputs must hold as many elements")
+    B = int(x.shape[0])
+    c = [float(v) for v in coef]
+    if len(c) < 2:
+        raise ValueError("coef must hold at least (c0, c1)")
+    need = x0_threshold_scratch_bytes(B, x.numel() // B)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=x.device)
+    elif not (isinstance(scratch, torch.Tensor) and scratch.is_cuda and scratch.is_contiguous() and scratch.dtype == torch.uint8):
+        raise ValueError("scratch must be a contiguous uint8 HIP tensor")
+    thr = torch.empty(B, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib.ccn_x0_threshold(x.data_ptr(), out_c.data_ptr(), ptr(out_u), pred, float(w), c[0], c[1], B, x.numel() // B, p, m,
+                                   thr.data_ptr(), scratch.data_ptr(), scratch.numel(), current_stream(x.device)))
+    return thr
+
+
+def x0_threshold_scratch_bytes(B: int, per_record: int) -> int:
+    n = c_sz()
+    check(load_library().ccn_x0_threshold_scratch_bytes(int(B), int(per_record), ctypes.byref(n)))
+    return int(n.value)
 
 
 def _per_sample(fn_name: str, a0: torch.Tensor, a1: torch.Tensor, ca: torch.Tensor, cs: torch.Tensor, out=None) -> torch.Tensor:

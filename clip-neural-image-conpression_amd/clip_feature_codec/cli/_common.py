@@ -60,22 +60,45 @@ def check_noise_flags(device_noise: bool, seed: int | None) -> None:
         raise SystemExit("--device_noise needs --seed: record i draws from seed + i")
 
 
+def add_threshold_flags(ap) -> None:
+    """``--dynamic_threshold P [--threshold_max S]`` (both CLIs): dynamic thresholding of x0 instead of the static clamp, off by default."""
+    ap.add_argument("--dynamic_threshold", type=float, default=None, metavar="P",
+                    help="dynamic thresholding of x0 (Imagen): per image and step s = max(quantile(|x0|, P), 1), x0 = clamp(x0, -s, s) / s "
+                         "instead of clamp(x0, -1, 1); P in (0, 1], e.g. 0.995; meant for --cfg_scale > 1; off by default")
+    ap.add_argument("--threshold_max", type=float, default=None, metavar="S", help="with --dynamic_threshold: an upper bound S >= 1 on s (default: none)")
+
+
+def check_threshold_flags(dynamic_threshold: float | None, threshold_max: float | None) -> None:
+    """Both CLIs call this right after parsing: a quantile in (0, 1], a maximum of at least 1 and only with the quantile."""
+    if dynamic_threshold is None:
+        if threshold_max is not None:
+            raise SystemExit("--threshold_max needs --dynamic_threshold")
+        return
+    if not 0.0 < dynamic_threshold <= 1.0:
+        raise SystemExit("--dynamic_threshold must be a quantile in (0, 1]")
+    if threshold_max is not None and not threshold_max >= 1.0:
+        raise SystemExit("--threshold_max must be at least 1")
+
+
 def record_seeds(indices: Sequence[int], seed: int) -> list:
     """The 64-bit seeds of ``--device_noise``: record ``i`` of the manifest gets ``seed + i``, the rule of ``start_noise``."""
     return [int(seed) + int(i) for i in indices]
 
 
-def build_sampler(eta: float, device: str, guided: bool = False, sampler: str = "ddim", spacing: str = "logsnr", prediction: str = "eps"):
+def build_sampler(eta: float, device: str, guided: bool = False, sampler: str = "ddim", spacing: str = "logsnr", prediction: str = "eps",
+                  dynamic_threshold: float | None = None, threshold_max: float | None = None):
     """``guided``: the sampler gives ``cfg_scale`` its meaning (classifier-free guidance against the zero embedding).
     ``sampler="dpmpp2m"``: the second-order multistep solver on the ``spacing`` timestep table (deterministic: no ``eta``).
-    ``prediction``: ``"eps"`` or ``"v"``, how the checkpoint was trained."""
+    ``prediction``: ``"eps"`` or ``"v"``, how the checkpoint was trained.  ``dynamic_threshold`` / ``threshold_max``: dynamic
+    thresholding of x0 (None: the static clamp)."""
     check_sampler_flags(sampler, eta)
+    thr = dict(dynamic_threshold=dynamic_threshold, threshold_max=threshold_max)
     if sampler == "dpmpp2m":
         return DPMSolverSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), order=2, spacing=spacing, guided=guided,
-                                prediction=prediction)
+                                prediction=prediction, **thr)
     if sampler != "ddim":
         raise SystemExit(f"unknown sampler {sampler}")
-    return DDIMSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), eta=eta, guided=guided, prediction=prediction)
+    return DDIMSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), eta=eta, guided=guided, prediction=prediction, **thr)
 
 
 def start_noise(indices: Sequence[int], size: int, seed: int | None, img_ch: int = 3) -> torch.Tensor | None:

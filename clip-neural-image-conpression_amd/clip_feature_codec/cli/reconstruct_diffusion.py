@@ -7,7 +7,8 @@ default to the reference behaviour: ``--seed`` (reproducible CPU-generated start
 never seeds), ``--dtype {fp32,bf16,f16x3}``, ``--cfg_scale`` (classifier-free guidance; 1.0 = off), ``--sampler {ddim,dpmpp2m}`` with ``--spacing {linspace,logsnr}``
 (the second-order multistep solver of ``diffusion/dpm_solver.py``; default ``ddim``), ``--device_noise`` (with ``--seed``: the start
 noise and the ``--eta > 0`` noise come from the device generator keyed by the seed, nothing is drawn on the host or uploaded; another
-generator than ``--seed`` alone, so another image) and the architecture is read from the checkpoint's shapes.
+generator than ``--seed`` alone, so another image), ``--dynamic_threshold P [--threshold_max S]`` (dynamic thresholding of x0 instead
+of the static clamp, for guided sampling; off by default) and the architecture is read from the checkpoint's shapes.
 """
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ._common import check_noise_flags, check_sampler_flags, pick_device, record_seeds, load_codec_meta, load_embedding, build_model, build_sampler, start_noise
+from ._common import add_threshold_flags, check_noise_flags, check_sampler_flags, check_threshold_flags, pick_device, record_seeds, load_codec_meta, load_embedding, build_model, build_sampler, start_noise
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -48,6 +49,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--spacing", choices=["linspace", "logsnr"], default="logsnr",
                     help="timestep table of --sampler dpmpp2m (read only then): uniform in log-SNR (may merge into fewer than "
                          "--steps entries) or the reference's linspace")
+    add_threshold_flags(ap)
     return ap
 
 
@@ -55,13 +57,14 @@ def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
     check_sampler_flags(args.sampler, args.eta)
     check_noise_flags(args.device_noise, args.seed)
+    check_threshold_flags(args.dynamic_threshold, args.threshold_max)
 
     device = pick_device(args.device)
     scale, zero = load_codec_meta(Path(args.store_dir))
     z = torch.from_numpy(load_embedding(Path(args.bitstream), scale, zero)).to(device)
     net = build_model(args.weights, device, z.shape[1], args.dtype)
     sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0, sampler=args.sampler, spacing=args.spacing,
-                            prediction=args.prediction)
+                            prediction=args.prediction, dynamic_threshold=args.dynamic_threshold, threshold_max=args.threshold_max)
     x_T = None if args.device_noise else start_noise([0], args.size, args.seed)
     noise_kw = dict(seeds=record_seeds([0], args.seed)) if args.device_noise else {}
     with torch.no_grad():

@@ -29,6 +29,10 @@ fused route, ``ccn_sampler_step`` on the stepwise one).  It must match how the w
 ``sample(..., seeds=...)``: one 64-bit seed per record (ints or an int64 tensor of ``B`` entries, as for ``DDIMSampler``); ``x_T=None``
 is then the records' own start noise, ``normal_fill(seeds, shape, 0)``.  The steps draw nothing, so a given ``x_T`` makes the
 seeds irrelevant; a wrong length is still a ``ValueError``.
+
+``DPMSolverSampler(..., dynamic_threshold=p, threshold_max=s_max)`` (default None: unchanged): dynamic thresholding of x0 as in
+``DDIMSampler`` -- ``s = min(max(quantile(|x0|, p), 1), s_max)`` per image and step, ``x0 = clamp(x0, -s, s) / s`` -- and the x0
+history holds the thresholded x0, so the second-order term differences what the solver actually used.
 """
 from __future__ import annotations
 
@@ -46,9 +50,15 @@ class DPMSolverSampler:
     """Deterministic DPM-Solver++ 2M (``order=2``) / its first-order form (``order=1``); ``guided=True``: classifier-free guidance."""
 
     def __init__(self, scheduler, order: int = 2, spacing: str = "logsnr", guided: bool = False,
-                 null_z: Optional[torch.Tensor] = None, prediction: str = "eps") -> None:
+                 null_z: Optional[torch.Tensor] = None, prediction: str = "eps", dynamic_threshold: Optional[float] = None,
+                 threshold_max: Optional[float] = None) -> None:
         _native.prediction_code(prediction)  # ValueError for an unknown parameterisation
         self.prediction = prediction
+        if dynamic_threshold is not None:
+            _native.threshold_args(dynamic_threshold, threshold_max)     # ValueError for p outside (0, 1] or a maximum below 1
+        elif threshold_max is not None:
+            raise ValueError("threshold_max needs dynamic_threshold")
+        self.dynamic_threshold, self.threshold_max = dynamic_threshold, threshold_max
         if order not in (1, 2):
             raise ValueError(f"order must be 1 or 2, got {order}")
         if spacing not in _SPACINGS:
@@ -84,6 +94,8 @@ class DPMSolverSampler:
             guide = {} if w is None else dict(guidance=w, null_z=null_z)
             if self.prediction != "eps":
                 guide["prediction"] = self.prediction
+            if self.dynamic_threshold is not None:
+                guide.update(dynamic_threshold=self.dynamic_threshold, threshold_max=self.threshold_max)
             return model.sample_ddim(z_clip, x, ts, coef[:, :4], use_graph=self.use_graph, slot=slot, c4=coef[:, 4], **guide)
         x = _native.require_dev(x, "x_T").clone()
         hist = torch.empty_like(x)
@@ -93,5 +105,9 @@ class DPMSolverSampler:
         for i in range(len(ts)):
             t_b = torch.full((shape[0],), int(ts[i]), device=device, dtype=torch.long)
             eps = model(x, z_clip, t_b)
-            _native.sampler_step(x, eps, coef[i], self.prediction, out_u=None if w is None else model(x, z_u, t_b), w=w or 0.0, hist=hist)
+            eps_u = None if w is None else model(x, z_u, t_b)
+            thr = None
+            if self.dynamic_threshold is not None:
+                thr = _native.x0_threshold(x, eps, coef[i, :2], self.prediction, self.dynamic_threshold, self.threshold_max, out_u=eps_u, w=w or 0.0)
+            _native.sampler_step(x, eps, coef[i], self.prediction, out_u=eps_u, w=w or 0.0, hist=hist, thr=thr)
         return x

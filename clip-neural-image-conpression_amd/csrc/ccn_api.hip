@@ -172,6 +172,14 @@ struct SamplerRun {
     std::vector<float> c4;
     float* hist = nullptr;
     int pred = CCN_PRED_EPS;             // the handle's ccn_set_prediction at call time: the update form is baked into the launches
+    // Dynamic thresholding (the handle's ccn_set_dynamic_threshold at call time; thr_p == 0: off).  EVERY step then takes the split
+    // route: the head writes the raw output into `eps` (the guided / seeded scratch where the run has one, else the raw-output part
+    // of the handle's threshold scratch), the threshold launches leave one float per record in `thr`, and the sampler-step launch
+    // clamps to it.  `thr` and `thr_sel` are parts of the handle's scratch: captured by address.
+    double thr_p = 0.0;
+    float thr_max = 0.f;
+    float* thr = nullptr;
+    void* thr_sel = nullptr;
 
     // Does a graph captured for `o` replay this run?  Everything a captured launch holds by value or by address; not z_null.
     bool same_graph(const SamplerRun& o) const
@@ -180,8 +188,9 @@ struct SamplerRun {
             return a.size() == b.size() && (a.empty() || !std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])));
         };
         return steps == o.steps && same(ts, o.ts) && same(coef, o.coef) && noise == o.noise && seeds == o.seeds && same(sigma, o.sigma) &&
-               guided == o.guided && (!guided || w == o.w) && ((!guided && !seeds) || eps == o.eps) && hist == o.hist && same(c4, o.c4) &&
-               pred == o.pred;
+               guided == o.guided && (!guided || w == o.w) && ((!guided && !seeds && thr_p == 0.0) || eps == o.eps) && hist == o.hist &&
+               same(c4, o.c4) && pred == o.pred && thr_p == o.thr_p &&
+               (thr_p == 0.0 || (thr_max == o.thr_max && thr == o.thr && thr_sel == o.thr_sel));
     }
 };
 
@@ -224,6 +233,10 @@ struct ccn_handle_s {
     int weight_rounding = CCN_ROUND_DIFFUSED_PHASES;   // how bf16 mode rounds the conv weights in ccn_commit_params (ccn_set_weight_rounding)
     int nphase = 1;                                     // versions per conv weight of the committed model (round_version)
     int pred = CCN_PRED_EPS;                            // what the network output is to the ccn_sample* loops (ccn_set_prediction)
+    double thr_p = 0.0;                                 // dynamic thresholding of x0 in the ccn_sample* loops (ccn_set_dynamic_threshold);
+    float thr_max = 0.f;                                // 0: off
+    char* thr_scratch = nullptr;                        // caller-owned: [raw output of one state | B thresholds | select state]
+    size_t thr_scratch_bytes = 0;
     std::vector<std::unique_ptr<ShapePlan>> shape_plans;   // of the committed model, one per (B, H, W, steps)
     std::vector<std::unique_ptr<Binding>> bindings;         // plan x workspace address, least recently used first
     hipStream_t cap_stream = nullptr;
@@ -886,7 +899,8 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, const SamplerRun
         const float* nz = noisy && r.noise ? r.noise + (size_t)i * img : nullptr;
         const float sigma = noisy ? r.sigma[i] : 0.f;
         const uint64_t* seeds = noisy ? r.seeds : nullptr;          // this step's update generates draw 1 + i
-        const bool split = r.guided || seeds;                       // the head writes the raw output, a sampler-step launch updates
+        const bool thresholded = r.thr_p > 0.0;
+        const bool split = r.guided || seeds || thresholded;        // the head writes the raw output, a sampler-step launch updates
         StepCtx c;
         c.step = i; c.x_in = xstate;
         if (split) { c.x_state = nullptr; c.eps_out = r.eps; c.do_ddim = 0; }
@@ -899,12 +913,20 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, const SamplerRun
         if (int rc = run_ops(h, b, s, c)) return rc;
         // guided: the combine and the update of both halves (unguided, the update is the head kernel's epilogue)
         // (unguided with seeds, a noisy step: the same launch without the second half -- 3 passes over one state)
-        const double passes = r.guided ? 5 + (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0) : 3;
+        // (thresholded: the same launch with the record's threshold; the noise tensor and the history enter as in the head's epilogue)
+        const double passes = r.guided ? 5 + (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0)
+                                       : 3 + (thresholded ? (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0) : 0);
+        const int64_t per = (int64_t)h->cfg.img_ch * p.H * p.W;
+        // the quantile of |x0| per record, on the combined output when guided: three select passes over the state and the output(s)
+        if (thresholded)
+            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * 3 * (r.guided ? 3 : 2), s, [&] {
+                    return launch_x0_threshold(xstate, r.eps, r.guided ? r.eps + img : nullptr, h->pred, r.w, cf[0], cf[1], (int)(img / (size_t)per),
+                                               per, r.thr_p, r.thr_max, r.thr, r.thr_sel, s); })) return rc;
         if (split)
             if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * passes, s, [&] {
                     return launch_sampler_step(xstate, r.guided ? xstate + img : nullptr, ms ? r.hist : nullptr, r.eps, r.guided ? r.eps + img : nullptr,
                                                nz, h->pred, r.w, cf[0], cf[1], cf[2], cf[3], c4, sigma, (int64_t)img, s, seeds, 1u + (uint32_t)i,
-                                               (int64_t)h->cfg.img_ch * p.H * p.W); })) return rc;
+                                               per, thresholded ? r.thr : nullptr); })) return rc;
     }
     return CCN_OK;
 }
@@ -1081,6 +1103,59 @@ int ccn_set_prediction(ccn_handle_t h, int32_t pred)
     return CCN_OK;
 }
 
+// Dynamic thresholding is handle state: every ccn_sample* entry picks it up here.  The scratch of ccn_set_dynamic_threshold is cut
+// into [raw output of one state | B thresholds | select state], each part 16-byte aligned (threshold_scratch_layout).
+struct ThrLayout { size_t thr, sel, total; };
+static int threshold_scratch_layout(const ccn_handle_s* h, int32_t B, int32_t H, int32_t W, ThrLayout& l)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return fail(CCN_EINVAL, "B, H, W must be positive");
+    if (B > 65535) return fail(CCN_EINVAL, "dynamic thresholding takes at most 65535 records: one grid row each");
+    const int64_t per = (int64_t)h->cfg.img_ch * H * W;
+    if (per >= kThrMaxPerRecord) return fail(CCN_EINVAL, "a record of 2^34 elements or more cannot be thresholded");
+    l.thr = ((size_t)B * (size_t)per * 4 + 15) / 16 * 16;
+    l.sel = l.thr + ((size_t)B * 4 + 15) / 16 * 16;
+    l.total = l.sel + x0_threshold_scratch_bytes(B);
+    return CCN_OK;
+}
+static int threshold_run(const ccn_handle_s* h, SamplerRun& r, int32_t B, int32_t H, int32_t W)
+{
+    ThrLayout l;
+    if (int rc = threshold_scratch_layout(h, B, H, W, l)) return rc;
+    if (h->thr_scratch_bytes < l.total)
+        return fail(CCN_EINVAL, "the dynamic-threshold scratch is too small for this shape: need " + std::to_string(l.total) + " bytes");
+    r.thr_p = h->thr_p; r.thr_max = h->thr_max;
+    r.thr = (float*)(h->thr_scratch + l.thr); r.thr_sel = h->thr_scratch + l.sel;
+    if (!r.eps) r.eps = (float*)h->thr_scratch;                     // a run without a scratch of its own: the raw output goes here
+    return CCN_OK;
+}
+
+int ccn_set_dynamic_threshold(ccn_handle_t h, double p, float max_value, void* scratch_dev, size_t scratch_bytes)
+{
+    // the arguments first (they can be judged without a handle), then the handle
+    if (!(p >= 0.0 && p <= 1.0)) return fail(CCN_EINVAL, "the quantile p must be in [0, 1] (0: off)");
+    if (p > 0.0) {
+        if (!(max_value >= 1.0f)) return fail(CCN_EINVAL, "max_value must be at least 1 (+inf: no upper bound)");
+        if (!scratch_dev || ((uintptr_t)scratch_dev & 15)) return fail(CCN_EINVAL, "the dynamic-threshold scratch must be non-null and 16-byte aligned");
+        // the smallest shape there is (one record of one element): a scratch below that fits no call
+        if (scratch_bytes < 32 + x0_threshold_scratch_bytes(1))
+            return fail(CCN_EINVAL, "the dynamic-threshold scratch is too small (ccn_dynamic_threshold_scratch_bytes)");
+    }
+    if (!h) return fail(CCN_EINVAL, "null handle");
+    if (p == 0.0) { h->thr_p = 0.0; h->thr_max = 0.f; h->thr_scratch = nullptr; h->thr_scratch_bytes = 0; return CCN_OK; }
+    h->thr_p = p; h->thr_max = max_value; h->thr_scratch = (char*)scratch_dev; h->thr_scratch_bytes = scratch_bytes;
+    return CCN_OK;
+}
+
+int ccn_dynamic_threshold_scratch_bytes(ccn_handle_t h, int32_t B, int32_t H, int32_t W, size_t* bytes)
+{
+    if (!h) return fail(CCN_EINVAL, "null handle");
+    if (!bytes) return fail(CCN_EINVAL, "null argument");
+    ThrLayout l;
+    if (int rc = threshold_scratch_layout(h, B, H, W, l)) return rc;
+    *bytes = l.total;
+    return CCN_OK;
+}
+
 int ccn_commit_params(ccn_handle_t h)
 {
     if (!h) return fail(CCN_EINVAL, "null handle");
@@ -1191,12 +1266,18 @@ static int begin_run(ccn_handle_t h, int32_t steps, const int32_t* ts_host, cons
     return CCN_OK;
 }
 
-static int sample_impl(ccn_handle_t h, const SamplerRun& r, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H,
+static int sample_impl(ccn_handle_t h, const SamplerRun& run, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H,
                        int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph)
 {
     int rc;
     if (!z_dev || !x_T_dev || !x_out_dev) return fail(CCN_EINVAL, "null pointer");
-    if (r.guided && (B <= 0 || B > INT32_MAX / 2)) return fail(CCN_EINVAL, "B, H, W, steps must be positive");
+    if (run.guided && (B <= 0 || B > INT32_MAX / 2)) return fail(CCN_EINVAL, "B, H, W, steps must be positive");
+    SamplerRun thresholded;                                         // the run with the handle's dynamic threshold, if one is set
+    if (h->thr_p > 0.0) {
+        thresholded = run;
+        if ((rc = threshold_run(h, thresholded, B, H, W))) return rc;
+    }
+    const SamplerRun& r = h->thr_p > 0.0 ? thresholded : run;
     const int PB = r.guided ? 2 * B : B;                            // the plan's batch: guided, the two halves
     const int steps = r.steps;
     Binding* p = nullptr;
@@ -1435,6 +1516,22 @@ int ccn_sampler_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const f
     if (n == 0) return CCN_OK;
     HIPCHK(launch_sampler_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, noise_dev, pred, w, coef_host[0], coef_host[1], coef_host[2],
                                coef_host[3], x0_hist_dev ? coef_host[4] : 0.f, sigma, n, (hipStream_t)stream));
+    return CCN_OK;
+}
+
+int ccn_sampler_step_thr(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,
+                         const float* noise_dev, const uint64_t* seeds_dev, uint32_t draw, int64_t per_record, int32_t pred, float w,
+                         const float* coef_host, float sigma, int64_t n, const float* thr_dev, void* stream)
+{
+    if (!x_dev || !out_c_dev || !coef_host || n < 0) return fail(CCN_EINVAL, "bad argument");
+    if (pred != CCN_PRED_EPS && pred != CCN_PRED_V) return fail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
+    if (noise_dev && seeds_dev) return fail(CCN_EINVAL, "noise_dev and seeds_dev exclude each other");
+    if (seeds_dev && ((uintptr_t)seeds_dev & 7)) return fail(CCN_EINVAL, "the seeds must be 8-byte aligned");
+    if (per_record <= 0 || per_record >= kThrMaxPerRecord || n % per_record) return fail(CCN_EINVAL, "per_record must be in [1, 2^34) and divide n");
+    if (n / per_record > 65535) return fail(CCN_EINVAL, "at most 65535 records per launch");
+    if (n == 0) return CCN_OK;
+    HIPCHK(launch_sampler_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, noise_dev, pred, w, coef_host[0], coef_host[1], coef_host[2],
+                               coef_host[3], x0_hist_dev ? coef_host[4] : 0.f, sigma, n, (hipStream_t)stream, seeds_dev, draw, per_record, thr_dev));
     return CCN_OK;
 }
 

@@ -36,9 +36,13 @@ __device__ __forceinline__ float sampler_tail(float x0, float e, float c2, float
     x0_out = x0;
     return xn;
 }
+// The x0 prediction before any clamp, either parameterisation: the ONE formation, shared by the updates below and by the dynamic
+// threshold's quantile (ccn_threshold.hip), so that the order statistic is taken on the very bits the update clamps.
+__device__ __forceinline__ float raw_x0_eps(float x, float e, float c0, float c1) { return __fdiv_rn(__fsub_rn(x, __fmul_rn(c0, e)), c1); }
+__device__ __forceinline__ float raw_x0_v(float x, float y, float c0, float c1) { return __fsub_rn(__fmul_rn(c1, x), __fmul_rn(c0, y)); }
 __device__ __forceinline__ float sampler_update(float x, float e, float c0, float c1, float c2, float c3, float c4, float hist, float& x0_out)
 {
-    float x0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(c0, e)), c1);
+    float x0 = raw_x0_eps(x, e, c0, c1);
     x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
     return sampler_tail(x0, e, c2, c3, c4, hist, x0_out);
 }
@@ -48,7 +52,7 @@ __device__ __forceinline__ float sampler_update(float x, float e, float c0, floa
 // so (x - c0*e)/c1 cancels to nothing, while c1*x - c0*y has no division and no cancellation (Parameterisation).
 __device__ __forceinline__ float sampler_update_v(float x, float y, float c0, float c1, float c2, float c3, float c4, float hist, float& x0_out)
 {
-    float x0 = __fsub_rn(__fmul_rn(c1, x), __fmul_rn(c0, y));
+    float x0 = raw_x0_v(x, y, c0, c1);
     x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
     const float e = __fadd_rn(__fmul_rn(c0, x), __fmul_rn(c1, y));
     return sampler_tail(x0, e, c2, c3, c4, hist, x0_out);
@@ -59,6 +63,21 @@ __device__ __forceinline__ float sampler_update_p(int pred, float x, float y, fl
                                                   float& x0_out)
 {
     return pred == PRED_V ? sampler_update_v(x, y, c0, c1, c2, c3, c4, hist, x0_out) : sampler_update(x, y, c0, c1, c2, c3, c4, hist, x0_out);
+}
+// Dynamic thresholding (Thresholding): the record's threshold s >= 1 replaces the static clamp,
+//     x0 = clamp(raw, -s, s) / s
+// and everything after it is the update above.  s == 1 is the static clamp bit for bit (a division by 1.0f is exact).  A NaN
+// threshold (a record whose quantile fell on a NaN) passes fmaxf / fminf through and makes every x0 of that record NaN.
+__device__ __forceinline__ float raw_x0_p(int pred, float x, float y, float c0, float c1)
+{
+    return pred == PRED_V ? raw_x0_v(x, y, c0, c1) : raw_x0_eps(x, y, c0, c1);
+}
+__device__ __forceinline__ float sampler_update_thr(int pred, float s, float x, float y, float c0, float c1, float c2, float c3, float c4,
+                                                    float hist, float& x0_out)
+{
+    const float x0 = __fdiv_rn(fminf(fmaxf(raw_x0_p(pred, x, y, c0, c1), -s), s), s);
+    const float e = pred == PRED_V ? __fadd_rn(__fmul_rn(c0, x), __fmul_rn(c1, y)) : y;
+    return sampler_tail(x0, e, c2, c3, c4, hist, x0_out);
 }
 
 // ---- record-keyed normals (Noise) ----------------------------------------------------------------------------

@@ -269,10 +269,18 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
 // the stand-alone sampler update, either parameterisation (pred = CCN_PRED_*): x_dup, hist, out_u and noise are nullable -- no out_u:
 // out_c is the prediction itself; no hist: c4 is not applied and no history is written (hist is read only when c4 != 0).  `seeds`
 // (nullable; one uint64 per record of per_record elements, n a multiple of it) with sigma > 0: the noise is draw `draw` of each record,
-// generated in the kernel, and `noise` is not read
+// generated in the kernel, and `noise` is not read.  `thr` (nullable; one float per record, per_record as above): the record's dynamic
+// threshold replaces the +-1 clamp of x0
 hipError_t launch_sampler_step(float* x, float* x_dup, float* hist, const float* out_c, const float* out_u, const float* noise, int pred,
                                float w, float c0, float c1, float c2, float c3, float c4, float sigma, int64_t n, hipStream_t s,
-                               const uint64_t* seeds = nullptr, uint32_t draw = 0, int64_t per_record = 0);
+                               const uint64_t* seeds = nullptr, uint32_t draw = 0, int64_t per_record = 0, const float* thr = nullptr);
+// the dynamic threshold of every record (ccn_threshold.hip; ccn_x0_threshold in ccn_hip.h): thr[b] = min(max(Q_p(|x0_b|), 1), max_value)
+// of the raw x0 the launch above would form.  `scratch`: x0_threshold_scratch_bytes(B) bytes, 16-byte aligned, any contents.  The
+// caller has checked the arguments (0 <= p <= 1, 1 <= B <= 65535, 0 < per < 2^34).  Five launches, nothing else.
+constexpr int64_t kThrMaxPerRecord = (int64_t)1 << 34;
+size_t x0_threshold_scratch_bytes(int B);
+hipError_t launch_x0_threshold(const float* x, const float* out_c, const float* out_u, int pred, float w, float c0, float c1, int B, int64_t per,
+                               double p, float max_value, float* thr, void* scratch, hipStream_t s);
 hipError_t launch_q_sample(float* out, const float* x0, const float* noise, const float* a, const float* sg,
                            int B, int64_t per, hipStream_t s);
 hipError_t launch_predict_x0(float* out, const float* xt, const float* eps, const float* a, const float* sg,

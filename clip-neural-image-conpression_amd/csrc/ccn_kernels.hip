@@ -821,24 +821,34 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
 // elements, the blocks of row blockIdx.y work on record b = blockIdx.y alone (one seed load per lane, no division), and element j
 // of it is draw_quad / draw_element(seeds[b], draw, j).  VEC then also means per % 4 == 0, so that every record starts 16-byte
 // aligned and a lane's four elements are one quad of it.  The unseeded instantiations (gridDim.y == 1) are the kernel as it was.
-template <bool VEC, bool SEEDED>
+// THR: the same grid rows, and record b's dynamic threshold thr[b] replaces the +-1 clamp of x0 (sampler_update_thr; DESIGN.md
+// section 1, Thresholding); a noise tensor is then walked by record too.  Without THR nothing of it is compiled in.
+template <bool VEC, bool SEEDED, bool THR>
 __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x_dup, float* __restrict__ hist, const float* __restrict__ out_c,
                                     const float* __restrict__ out_u, const float* __restrict__ noise, int pred, float w, float c0, float c1,
                                     float c2, float c3, float c4, float sigma, int64_t n, const uint64_t* __restrict__ seeds, uint32_t draw,
-                                    int64_t per)
+                                    int64_t per, const float* __restrict__ thr)
 {
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     uint64_t seed = 0;
-    if constexpr (SEEDED) {                                         // this record's slice of every tensor
+    float s = 1.0f;
+    if constexpr (SEEDED || THR) {                                  // this record's slice of every tensor
         const int64_t off = (int64_t)blockIdx.y * per;
-        seed = seeds[blockIdx.y];
+        if constexpr (SEEDED) seed = seeds[blockIdx.y];
+        if constexpr (THR) s = thr[blockIdx.y];
         x += off; out_c += off; n = per;
         if (x_dup) x_dup += off;
         if (hist) hist += off;
         if (out_u) out_u += off;
+        if constexpr (THR) { if (noise) noise += off; }
     }
     const int64_t n4 = VEC ? n / 4 : 0;
     if (!hist) c4 = 0.f;
+    // one element's update: the threshold form only where it was asked for
+    auto update = [&](float xv, float yv, float hv, float& p) {
+        if constexpr (THR) return sampler_update_thr(pred, s, xv, yv, c0, c1, c2, c3, c4, hv, p);
+        else return sampler_update_p(pred, xv, yv, c0, c1, c2, c3, c4, hv, p);
+    };
     for (int64_t q = tid; q < n4; q += nthr) {
         const float4 xv = ((const float4*)x)[q];
         float4 yv = ((const float4*)out_c)[q];
@@ -849,10 +859,10 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         }
         float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), o, p;
         if (c4 != 0.f) hv = ((const float4*)hist)[q];
-        o.x = sampler_update_p(pred, xv.x, yv.x, c0, c1, c2, c3, c4, hv.x, p.x);
-        o.y = sampler_update_p(pred, xv.y, yv.y, c0, c1, c2, c3, c4, hv.y, p.y);
-        o.z = sampler_update_p(pred, xv.z, yv.z, c0, c1, c2, c3, c4, hv.z, p.z);
-        o.w = sampler_update_p(pred, xv.w, yv.w, c0, c1, c2, c3, c4, hv.w, p.w);
+        o.x = update(xv.x, yv.x, hv.x, p.x);
+        o.y = update(xv.y, yv.y, hv.y, p.y);
+        o.z = update(xv.z, yv.z, hv.z, p.z);
+        o.w = update(xv.w, yv.w, hv.w, p.w);
         if (SEEDED || noise) {
             float4 nv;
             if constexpr (SEEDED) nv = draw_quad(seed, draw, (uint32_t)q);
@@ -869,7 +879,7 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         if (out_u) { const float u = out_u[i]; y = __fadd_rn(u, __fmul_rn(w, __fsub_rn(y, u))); }
         const float hv = c4 != 0.f ? hist[i] : 0.f;
         float p;
-        float xn = sampler_update_p(pred, x[i], y, c0, c1, c2, c3, c4, hv, p);
+        float xn = update(x[i], y, hv, p);
         if constexpr (SEEDED) xn = __fadd_rn(xn, __fmul_rn(sigma, draw_element(seed, draw, i)));
         else if (noise) xn = __fadd_rn(xn, __fmul_rn(sigma, noise[i]));
         if (hist) hist[i] = p;
@@ -877,28 +887,33 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         if (x_dup) x_dup[i] = xn;
     }
 }
-// seeds given and sigma > 0: the seeded form (the caller has checked per > 0 and n % per == 0; `noise` is then not read)
+// seeds given and sigma > 0: the seeded form; thr given: the threshold form; either walks the state record by record, one grid row
+// each (the caller has checked per > 0 and n % per == 0).  With seeds `noise` is not read.
 hipError_t launch_sampler_step(float* x, float* x_dup, float* hist, const float* out_c, const float* out_u, const float* noise, int pred,
                                float w, float c0, float c1, float c2, float c3, float c4, float sigma, int64_t n, hipStream_t s,
-                               const uint64_t* seeds, uint32_t draw, int64_t per)
+                               const uint64_t* seeds, uint32_t draw, int64_t per, const float* thr)
 {
     const bool seeded = seeds && sigma > 0.f;
     if (seeded) noise = nullptr;
-    if (seeded && (per <= 0 || n % per || n / per > 65535)) return hipErrorInvalidValue;     // one grid row per record
+    const bool rowed = seeded || thr;
+    if (rowed && (per <= 0 || n % per || n / per > 65535)) return hipErrorInvalidValue;      // one grid row per record
     const bool vec = !(((uintptr_t)x | (uintptr_t)x_dup | (uintptr_t)hist | (uintptr_t)out_c | (uintptr_t)out_u | (uintptr_t)noise) & 15) &&
-                     !(seeded && (per & 3));
-    const int64_t rows = seeded ? n / per : 1, row = seeded ? per : n;
+                     !(rowed && (per & 3));
+    const int64_t rows = rowed ? n / per : 1, row = rowed ? per : n;
     const int64_t work = vec ? (row + 3) / 4 : row, blocks = (work + 255) / 256;
     const int gx = (int)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);        // 256 CUs x 8 blocks, grid-stride beyond
     const dim3 grid(gx, (unsigned)rows);
-#define CCN_STEP_ARGS x, x_dup, hist, out_c, out_u, noise, pred, w, c0, c1, c2, c3, c4, sigma, n, seeds, draw, per
-    if (seeded) {
-        if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, true>), grid, dim3(256), 0, s, CCN_STEP_ARGS);
-        else hipLaunchKernelGGL((sampler_step_kernel<false, true>), grid, dim3(256), 0, s, CCN_STEP_ARGS);
-    } else {
-        if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, false>), grid, dim3(256), 0, s, CCN_STEP_ARGS);
-        else hipLaunchKernelGGL((sampler_step_kernel<false, false>), grid, dim3(256), 0, s, CCN_STEP_ARGS);
-    }
+#define CCN_STEP_ARGS x, x_dup, hist, out_c, out_u, noise, pred, w, c0, c1, c2, c3, c4, sigma, n, seeds, draw, per, thr
+#define CCN_STEP_GO(SEEDED, THR)                                                                                             \
+    do {                                                                                                                     \
+        if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, SEEDED, THR>), grid, dim3(256), 0, s, CCN_STEP_ARGS);         \
+        else hipLaunchKernelGGL((sampler_step_kernel<false, SEEDED, THR>), grid, dim3(256), 0, s, CCN_STEP_ARGS);            \
+    } while (0)
+    if (seeded && thr) CCN_STEP_GO(true, true);
+    else if (seeded) CCN_STEP_GO(true, false);
+    else if (thr) CCN_STEP_GO(false, true);
+    else CCN_STEP_GO(false, false);
+#undef CCN_STEP_GO
 #undef CCN_STEP_ARGS
     return hipGetLastError();
 }

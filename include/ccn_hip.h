@@ -284,6 +284,59 @@ int ccn_sample_guided_seeded(ccn_handle_t h, const float* z_dev, const float* z_
                              float w, float* eps_scratch_dev,
                              void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph);
 
+/* ---- dynamic thresholding of x0 -------------------------------------------------------------------------------------------------- *
+ * (No reference counterpart: the reference clamps x0 to [-1, 1].  Saharia et al. 2022, Imagen section 2.3.)  Per record b and step,
+ *     s = min(max(Q_p(|x0_b|), 1), max_value);   x0 = clamp(x0, -s, s) / s
+ * replaces the static clamp of every update above; the rest of the update is unchanged, and s == 1 is the static clamp bit for bit.
+ * Q_p is the linearly interpolated quantile over the per_record elements of the record: with v the ascending |x0| (the raw x0 as the
+ * update forms it, after the guidance combine, each op rounded to fp32), pos = p*(per_record - 1) and k = floor(pos) in double,
+ * frac = (float)(pos - k):  q = v[k] + frac * (v[min(k+1, per_record-1)] - v[k]),  three separately rounded fp32 ops.  v[k] and
+ * v[k+1] are exact order statistics (a radix select on the bit patterns; integer counting only), so the threshold is reproducible
+ * bit for bit and does not depend on B, on the record's position in the batch, on the launch shape or on pointer alignment (16-byte
+ * loads when every pointer is 16-byte aligned and per_record % 4 == 0, 4-byte loads otherwise).
+ * Non-finite input is not looked for: in the order of the bit patterns NaNs sort last, so a record whose rank-k or rank-(k+1) element
+ * is a NaN gets s = NaN and with it a NaN update, other records are unaffected; +inf is an ordinary largest value (an interpolation
+ * that meets inf - inf or 0 * inf is NaN like any other).
+ *
+ * ccn_x0_threshold: thr_dev[b] = s of record b, b < B, for x0 formed from x_dev / out_c_dev / out_u_dev (NULL: w ignored) / pred /
+ * c0, c1 exactly as ccn_sampler_step forms it.  scratch_dev: ccn_x0_threshold_scratch_bytes bytes, 16-byte aligned, caller-owned, any
+ * contents (every call zeroes what it uses, on the stream; two calls in flight need two scratches).  Five small launches on `stream`;
+ * never synchronises, allocates nothing, capturable.  p = 0 is the minimum, p = 1 the maximum.
+ * CCN_EINVAL: a NULL tensor, an unknown pred, p outside [0, 1] or NaN, max_value below 1 or NaN (+inf: no upper bound), B outside
+ * [1, 65535], per_record <= 0 or >= 2^34, a NULL, misaligned or short scratch. */
+int ccn_x0_threshold_scratch_bytes(int32_t B, int64_t per_record, size_t* bytes);
+int ccn_x0_threshold(const float* x_dev, const float* out_c_dev, const float* out_u_dev,
+                     int32_t pred, float w, float c0, float c1,
+                     int32_t B, int64_t per_record, double p, float max_value,
+                     float* thr_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
+
+/* The superset of ccn_sampler_step and ccn_sampler_step_seeded plus thr_dev: n / per_record records, record b clamping its x0 to
+ * thr_dev[b] (one float per record, read when the kernel runs) as above.  noise_dev / seeds_dev exclude each other (both NULL: no
+ * noise).  thr_dev NULL: those two entries, bit for bit.
+ * CCN_EINVAL: as for those entries, and both noise_dev and seeds_dev given, per_record <= 0 or >= 2^34, n % per_record != 0, more than
+ * 65535 records. */
+int ccn_sampler_step_thr(float* x_dev, float* x_dup_dev, float* x0_hist_dev,
+                         const float* out_c_dev, const float* out_u_dev,
+                         const float* noise_dev, const uint64_t* seeds_dev, uint32_t draw,
+                         int64_t per_record, int32_t pred, float w,
+                         const float* coef_host /* [5] */, float sigma, int64_t n,
+                         const float* thr_dev, void* stream);
+
+/* Handle state, like ccn_set_prediction: read by every ccn_sample* entry when it enqueues or captures, and part of every captured
+ * graph's cache key (p, max_value, the scratch address), so toggling finds each mode's own graph on a shared workspace and a run with
+ * p == 0 replays the graph it had.  p == 0: off (the default; scratch_dev may be NULL).  With p in (0, 1] EVERY step of every loop --
+ * plain, eta, seeded, guided, multistep, guided multistep, either parameterisation -- runs as: the head writes the raw network
+ * output, ccn_x0_threshold's launches take the quantile (on the combined output when guided: one threshold per image, both halves of
+ * the state get the same update), one ccn_sampler_step_thr launch updates; the multistep history receives the thresholded x0.
+ * scratch_dev: ccn_dynamic_threshold_scratch_bytes(h, B, H, W) bytes for the largest shape sampled with it (B images, also when
+ * guided), 16-byte aligned, owned by the caller and kept at its address while a graph captured with it is cached, like the workspace.
+ * It holds the raw output of one state (runs with an eps / output scratch of their own keep using theirs), the B thresholds and the
+ * select state.  ccn_workspace_bytes is unchanged.
+ * CCN_EINVAL: p outside [0, 1] or NaN; with p > 0: max_value below 1 or NaN, a NULL, misaligned or short scratch (a scratch too
+ * small for the shape of a later ccn_sample* call is that call's CCN_EINVAL), more than 65535 images, C*H*W >= 2^34. */
+int ccn_set_dynamic_threshold(ccn_handle_t h, double p, float max_value, void* scratch_dev, size_t scratch_bytes);
+int ccn_dynamic_threshold_scratch_bytes(ccn_handle_t h, int32_t B, int32_t H, int32_t W, size_t* bytes);
+
 /* NoiseScheduler.q_sample (diffusion/scheduler.py:46-49): out[b] = a[b]*x0[b] + s[b]*noise[b];
  * a_dev/s_dev are the gathered per-sample coefficients, (B,) fp32; per_sample = C*H*W. */
 int ccn_q_sample(float* out_dev, const float* x0_dev, const float* noise_dev,
