@@ -32,6 +32,13 @@ class CcnConfig(ctypes.Structure):
                 ("time_dim", c_i32), ("img_ch", c_i32), ("groups", c_i32), ("dtype", c_i32)]
 
 
+class CcnSamplerRun(ctypes.Structure):
+    """ccn_sampler_run_t: one run of the sampler loop (include/ccn_hip.h).  Unset fields are 0 / NULL: the feature is absent."""
+    _fields_ = [("size", c_u32), ("steps", c_i32), ("ts_host", c_vp), ("coef_host", c_vp), ("coef_cols", c_i32),
+                ("sigma_host", c_vp), ("noise_dev", c_vp), ("seeds_dev", c_vp), ("guided", c_i32), ("w", c_f32),
+                ("z_null_dev", c_vp), ("out_scratch_dev", c_vp), ("x0_hist_dev", c_vp)]
+
+
 # name -> (restype, argtypes); must list every symbol include/ccn_hip.h declares
 SIGNATURES = {
     "ccn_create": (c_i32, [ctypes.POINTER(CcnConfig), ctypes.POINTER(c_vp)]),
@@ -54,6 +61,7 @@ SIGNATURES = {
                                      c_vp, c_vp]),
     "ccn_set_dynamic_threshold": (c_i32, [c_vp, ctypes.c_double, c_f32, c_vp, c_sz]),
     "ccn_dynamic_threshold_scratch_bytes": (c_i32, [c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
+    "ccn_sample_run": (c_i32, [c_vp, ctypes.POINTER(CcnSamplerRun), c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp, c_i32]),
     "ccn_workspace_bytes": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
     "ccn_release_workspace": (c_i32, [c_vp, c_vp]),
     "ccn_forward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
@@ -323,7 +331,7 @@ class NativeUNet:
                noise: Optional[torch.Tensor] = None, w: Optional[float] = None, z_null: Optional[torch.Tensor] = None,
                hist: Optional[torch.Tensor] = None, seeds=None, dynamic_threshold: Optional[float] = None,
                threshold_max: Optional[float] = None) -> torch.Tensor:
-        """Every step of a sampler inside the library, through the ``ccn_sample*`` entry that fits.  ``coef`` of ``(steps, 4)``: the
+        """Every step of a sampler inside the library, through ``ccn_sample_run``.  ``coef`` of ``(steps, 4)``: the
         DDIM loop; ``sigma`` (steps,) + ``noise`` (steps, B, C, H, W) fp32 on the device make it the eta > 0 one.  ``coef`` of
         ``(steps, 5)``: the multistep loop (``NoiseScheduler.solver_coefficients``; deterministic), ``hist`` its x0 history, fp32 of
         ``x_T``'s size.  ``w``: a classifier-free guidance scale (None: unguided) -- the plan and the workspace are then of batch 2B,
@@ -395,28 +403,23 @@ class NativeUNet:
                 check(self.lib.ccn_dynamic_threshold_scratch_bytes(self.h, B, H, W, ctypes.byref(n)))
                 ws.thr[B] = torch.empty(n.value, dtype=torch.uint8, device=self.device)
             check(self.lib.ccn_set_dynamic_threshold(self.h, tp, tm, ws.thr[B].data_ptr(), ws.thr[B].numel()))
-        out = torch.empty_like(x_T)
-        # every entry's arguments: (h, z[, z_null], x_T, out, B, H, W, steps, ts, coef, <its own>, workspace, bytes, stream, use_graph)
-        zn = () if w is None else (ptr(z_null),)
-        head = (self.h, z.data_ptr(), *zn, x_T.data_ptr(), out.data_ptr(), B, H, W, steps, ts.ctypes.data, coef.ctypes.data)
-        tail = (ws.ptr, ws.nbytes, current_stream(x_T.device), 1 if use_graph else 0)
-        eta = (sigma.ctypes.data, noise.data_ptr()) if sigma is not None and seeds is None else (None, None)
-        seeded = () if seeds is None else (sigma.ctypes.data, ws.seeds.data_ptr())
-        with torch.cuda.device(x_T.device):
-            if seeds is not None and w is None:
-                check(self.lib.ccn_sample_seeded(*head, *seeded, ws.eps.data_ptr(), *tail))
-            elif seeds is not None:
-                check(self.lib.ccn_sample_guided_seeded(*head, *seeded, float(w), ws.eps.data_ptr(), *tail))
-            elif ms and w is None:
-                check(self.lib.ccn_sample_ms(*head, hist.data_ptr(), *tail))
-            elif ms:
-                check(self.lib.ccn_sample_guided_ms(*head, float(w), ws.eps.data_ptr(), hist.data_ptr(), *tail))
-            elif w is not None:
-                check(self.lib.ccn_sample_guided(*head, *eta, float(w), ws.eps.data_ptr(), *tail))
-            elif sigma is not None:
-                check(self.lib.ccn_sample_eta(*head, *eta, *tail))
+        # the run as the library takes it (ccn_sampler_run_t): an absent feature stays NULL / 0
+        run = CcnSamplerRun(size=ctypes.sizeof(CcnSamplerRun), steps=steps, ts_host=ts.ctypes.data, coef_host=coef.ctypes.data,
+                            coef_cols=coef.shape[1], x0_hist_dev=ptr(hist))
+        if sigma is not None:
+            run.sigma_host = sigma.ctypes.data
+            if seeds is not None:
+                run.seeds_dev = ws.seeds.data_ptr()
             else:
-                check(self.lib.ccn_sample(*head, *tail))
+                run.noise_dev = noise.data_ptr()
+        if w is not None:
+            run.guided, run.w, run.z_null_dev = 1, float(w), ptr(z_null)
+        if w is not None or seeds is not None:
+            run.out_scratch_dev = ws.eps.data_ptr()
+        out = torch.empty_like(x_T)
+        with torch.cuda.device(x_T.device):
+            check(self.lib.ccn_sample_run(self.h, ctypes.byref(run), z.data_ptr(), x_T.data_ptr(), out.data_ptr(), B, H, W,
+                                          ws.ptr, ws.nbytes, current_stream(x_T.device), 1 if use_graph else 0))
         return out
 
     def resblock(self, prefix: str, x: torch.Tensor, h: torch.Tensor) -> torch.Tensor:

@@ -18,7 +18,7 @@ spacing the method is designed for.  Targets that snap to the same table timeste
 ``steps`` entries (``NoiseScheduler.solver_timesteps``).  The first step and the last one (``h`` is infinite there) are first order.
 ``order=1`` is the same loop without the correction term.  The sampler is deterministic: no ``eta``.
 
-Two routes as in ``DDIMSampler``: fused (``model.sample_ddim`` -> ``ccn_sample_ms`` / ``ccn_sample_guided_ms``, one captured graph)
+Two routes as in ``DDIMSampler``: fused (``model.sample_ddim`` -> the loop of ``ccn_sample_ms`` / ``ccn_sample_guided_ms``, one captured graph)
 and stepwise for any callable ``model(x, z, t)`` (one model call per step, two when guided, then ``ccn_sampler_step``).
 ``guided=True`` with ``cfg_scale == 1.0`` takes the unguided route.
 
@@ -40,8 +40,7 @@ from typing import Optional
 
 import torch
 
-from .. import _native
-from . import guidance
+from . import guidance, sampling
 
 _SPACINGS = ("logsnr", "linspace")
 
@@ -52,13 +51,7 @@ class DPMSolverSampler:
     def __init__(self, scheduler, order: int = 2, spacing: str = "logsnr", guided: bool = False,
                  null_z: Optional[torch.Tensor] = None, prediction: str = "eps", dynamic_threshold: Optional[float] = None,
                  threshold_max: Optional[float] = None) -> None:
-        _native.prediction_code(prediction)  # ValueError for an unknown parameterisation
-        self.prediction = prediction
-        if dynamic_threshold is not None:
-            _native.threshold_args(dynamic_threshold, threshold_max)     # ValueError for p outside (0, 1] or a maximum below 1
-        elif threshold_max is not None:
-            raise ValueError("threshold_max needs dynamic_threshold")
-        self.dynamic_threshold, self.threshold_max = dynamic_threshold, threshold_max
+        sampling.set_options(self, prediction, dynamic_threshold, threshold_max)
         if order not in (1, 2):
             raise ValueError(f"order must be 1 or 2, got {order}")
         if spacing not in _SPACINGS:
@@ -85,29 +78,7 @@ class DPMSolverSampler:
         device = z_clip.device
         if device.type != "cuda":
             raise RuntimeError(f"z_clip is on {device}: DPMSolverSampler (MI355X build) needs a HIP device; no CPU fallback")
-        if seeds is not None:
-            seeds = _native.seeds_tensor(seeds, int(shape[0]), device).to(device)
-            x = _native.normal_fill(seeds, shape, 0) if x_T is None else x_T.to(device)
-        else:
-            x = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
+        seeds, x = sampling.start_state(shape, device, x_T, seeds)
         if hasattr(model, "sample_ddim"):
-            guide = {} if w is None else dict(guidance=w, null_z=null_z)
-            if self.prediction != "eps":
-                guide["prediction"] = self.prediction
-            if self.dynamic_threshold is not None:
-                guide.update(dynamic_threshold=self.dynamic_threshold, threshold_max=self.threshold_max)
-            return model.sample_ddim(z_clip, x, ts, coef[:, :4], use_graph=self.use_graph, slot=slot, c4=coef[:, 4], **guide)
-        x = _native.require_dev(x, "x_T").clone()
-        hist = torch.empty_like(x)
-        z_u = None
-        if w is not None:
-            z_u = (torch.zeros_like(z_clip[0]) if null_z is None else null_z).expand(shape[0], -1).contiguous()
-        for i in range(len(ts)):
-            t_b = torch.full((shape[0],), int(ts[i]), device=device, dtype=torch.long)
-            eps = model(x, z_clip, t_b)
-            eps_u = None if w is None else model(x, z_u, t_b)
-            thr = None
-            if self.dynamic_threshold is not None:
-                thr = _native.x0_threshold(x, eps, coef[i, :2], self.prediction, self.dynamic_threshold, self.threshold_max, out_u=eps_u, w=w or 0.0)
-            _native.sampler_step(x, eps, coef[i], self.prediction, out_u=eps_u, w=w or 0.0, hist=hist, thr=thr)
-        return x
+            return model.sample_ddim(z_clip, x, ts, coef[:, :4], c4=coef[:, 4], **sampling.fused_kwargs(self, w, null_z, slot))
+        return sampling.stepwise(self, model, x, z_clip, ts, coef, w, null_z, multistep=True)

@@ -1,0 +1,69 @@
+"""What ``DDIMSampler`` and ``DPMSolverSampler`` share: the constructor's checks of the parameterisation and the dynamic threshold, the
+start state, the keyword arguments of the fused route and the stepwise loop.  What differs stays in the two classes: the tables."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from .. import _native
+
+
+def set_options(sampler, prediction: str, dynamic_threshold: Optional[float], threshold_max: Optional[float]) -> None:
+    """Check and keep ``prediction``, ``dynamic_threshold`` and ``threshold_max`` on ``sampler``; a bad one is a ``ValueError``."""
+    _native.prediction_code(prediction)  # ValueError for an unknown parameterisation
+    if dynamic_threshold is not None:
+        _native.threshold_args(dynamic_threshold, threshold_max)     # ValueError for p outside (0, 1] or a maximum below 1
+    elif threshold_max is not None:
+        raise ValueError("threshold_max needs dynamic_threshold")
+    sampler.prediction = prediction
+    sampler.dynamic_threshold, sampler.threshold_max = dynamic_threshold, threshold_max
+
+
+def start_state(shape: tuple, device, x_T: Optional[torch.Tensor], seeds):
+    """``(seeds, x)``: the seeds as the library takes them (None: unseeded) and the start state on ``device`` -- a given ``x_T`` as it
+    is, else draw 0 of every record with seeds, else ``torch.randn`` from the current generator."""
+    if seeds is not None:
+        seeds = _native.seeds_tensor(seeds, int(shape[0]), device).to(device)
+        return seeds, (_native.normal_fill(seeds, shape, 0) if x_T is None else x_T.to(device))
+    return None, (torch.randn(shape, device=device) if x_T is None else x_T.to(device))
+
+
+def fused_kwargs(sampler, w: Optional[float], null_z: Optional[torch.Tensor], slot: int) -> dict:
+    """The keyword arguments of ``model.sample_ddim`` that do not depend on the tables."""
+    kw = dict(use_graph=sampler.use_graph, slot=slot)
+    if w is not None:
+        kw.update(guidance=w, null_z=null_z)
+    if sampler.prediction != "eps":
+        kw["prediction"] = sampler.prediction
+    if sampler.dynamic_threshold is not None:
+        kw.update(dynamic_threshold=sampler.dynamic_threshold, threshold_max=sampler.threshold_max)
+    return kw
+
+
+def stepwise(sampler, model, x: torch.Tensor, z_clip: torch.Tensor, ts, coef, w: Optional[float], null_z: Optional[torch.Tensor],
+             sigma=None, seeds: Optional[torch.Tensor] = None, multistep: bool = False) -> torch.Tensor:
+    """The loop for any callable ``model(x, z, t)``.  Per step: the model call (two when guided), the dynamic threshold if the
+    sampler has one, then one ``sampler_step`` on ``coef[i]`` -- with ``sigma[i] > 0`` it adds draw ``1 + i`` of the seeds or, unseeded,
+    one ``torch.randn_like`` (drawn on those steps only); ``multistep``: with the x0 history."""
+    x = _native.require_dev(x, "x_T").clone()
+    B, device = x.shape[0], z_clip.device
+    hist = torch.empty_like(x) if multistep else None
+    z_u = None
+    if w is not None:
+        z_u = (torch.zeros_like(z_clip[0]) if null_z is None else null_z).expand(B, -1).contiguous()
+    for i in range(len(ts)):
+        t_b = torch.full((B,), int(ts[i]), device=device, dtype=torch.long)
+        out = model(x, z_clip, t_b)
+        out_u = model(x, z_u, t_b) if w is not None else None
+        s = float(sigma[i]) if sigma is not None else 0.0
+        thr = None
+        if sampler.dynamic_threshold is not None:
+            thr = _native.x0_threshold(x, out, coef[i, :2], sampler.prediction, sampler.dynamic_threshold, sampler.threshold_max, out_u=out_u,
+                                       w=w or 0.0)
+        if s > 0 and seeds is not None:
+            noise = dict(seeds=seeds, draw=1 + i)
+        else:
+            noise = dict(noise=torch.randn_like(x) if s > 0 else None)
+        _native.sampler_step(x, out, coef[i], sampler.prediction, out_u=out_u, w=w or 0.0, hist=hist, sigma=s, thr=thr, **noise)
+    return x

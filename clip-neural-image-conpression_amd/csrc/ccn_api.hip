@@ -96,6 +96,7 @@ struct StepCtx {
     float sigma = 0.f;
     float* x0_hist = nullptr;      // multistep sampler: the previous step's x0 (caller-owned, outside the workspace), else null
     float c4 = 0.f;                // ... and its coefficient in this step's update
+    int pred = CCN_PRED_EPS;       // the run's parameterisation (SamplerRun::pred), read by the head's update
 };
 
 const char* kFamilies[] = {"conv3x3_s1_igemm", "conv3x3_s2_igemm", "convT4x4_s2_igemm", "stem_conv_igemm",
@@ -148,8 +149,9 @@ struct ShapePlan {
     std::vector<RouteRec> routes;        // every conv-family launch of `ops`, in order
 };
 
-// One run of a sampler loop (the ccn_sample* entry points): what the step loop is a function of besides the handle, the shape and the
-// tensors.  The host tables are copies, so the record of a captured run outlives the call (GraphEntry).
+// One run of a sampler loop: what the step loop is a function of besides the handle, the shape and the tensors.  build_run makes it
+// from a ccn_sampler_run_t and the handle's state, checked and NORMALISED: a field the run does not use holds the fixed value named
+// below, whatever the caller passed.  The host tables are copies, so the record of a captured run outlives the call (GraphEntry).
 struct SamplerRun {
     int steps = 0;
     std::vector<int32_t> ts;
@@ -158,39 +160,41 @@ struct SamplerRun {
     const float* noise = nullptr;        // ... and the caller's noise tensor, [steps] x one state
     // ... or, instead of `noise`, one seed per record of the state: step i's noise is draw 1 + i of each record, generated by the
     // updating launch.  The address is captured, the contents are read at run time.  Unguided, the head then writes the raw output
-    // of the B rows into `eps` on the steps with sigma > 0 and one sampler-step launch follows it, as in the guided loop.
-    const uint64_t* seeds = nullptr;
+    // of the B rows into `out_scratch` on the steps with sigma > 0 and one sampler-step launch follows it, as in the guided loop.
+    const uint64_t* seeds = nullptr;     // (null without sigma: nothing would be drawn)
     // Classifier-free guidance: the plan's batch is 2B rows -- [0, B) carry z, [B, 2B) the null embedding, both the same state -- the
-    // head writes the raw network output of all 2B rows into `eps` (whatever it predicts: the combine launch applies the handle's
-    // parameterisation), and one combine launch per step updates both halves of the state.
+    // head writes the raw network output of all 2B rows into `out_scratch` (whatever it predicts: the combine launch applies `pred`),
+    // and one combine launch per step updates both halves of the state.
     bool guided = false;
-    const float* z_null = nullptr;       // one row (null: zeros), copied into the workspace on every call
-    float w = 0.f;                       // the by-value guidance scale of the combine launch
-    float* eps = nullptr;
+    const float* z_null = nullptr;       // one row (null: zeros), copied into the workspace on every call: not part of a capture
+    float w = 0.f;                       // the by-value guidance scale of the combine launch (0 unless guided)
+    // The raw network output of the steps that update in a launch of their own (the split route: guided, seeded on a step with
+    // sigma > 0, every step when thresholded): the caller's scratch in a guided or seeded run (2B / B states), else the head of the
+    // handle's threshold scratch in a thresholded one, else null.
+    float* out_scratch = nullptr;
     // The multistep sampler: per step the coefficient c4 of (x0 - previous x0) (empty: none), and the caller's history tensor of one
-    // state (B rows, also when guided), which the updating launch of every step reads (c4 != 0) and rewrites.
+    // state (B rows, also when guided; null without c4), which the updating launch of every step reads (c4 != 0) and rewrites.
     std::vector<float> c4;
     float* hist = nullptr;
-    int pred = CCN_PRED_EPS;             // the handle's ccn_set_prediction at call time: the update form is baked into the launches
-    // Dynamic thresholding (the handle's ccn_set_dynamic_threshold at call time; thr_p == 0: off).  EVERY step then takes the split
-    // route: the head writes the raw output into `eps` (the guided / seeded scratch where the run has one, else the raw-output part
-    // of the handle's threshold scratch), the threshold launches leave one float per record in `thr`, and the sampler-step launch
-    // clamps to it.  `thr` and `thr_sel` are parts of the handle's scratch: captured by address.
+    int pred = CCN_PRED_EPS;             // the handle's ccn_set_prediction when the run was built: the update form of every launch
+    // Dynamic thresholding (the handle's ccn_set_dynamic_threshold when the run was built; thr_p == 0: off, and the three fields
+    // below are zero).  EVERY step then takes the split route: the threshold launches leave one float per record in `thr`, and the
+    // sampler-step launch clamps to it.  `thr` and `thr_sel` are parts of the handle's scratch: captured by address.
     double thr_p = 0.0;
     float thr_max = 0.f;
     float* thr = nullptr;
     void* thr_sel = nullptr;
 
-    // Does a graph captured for `o` replay this run?  Everything a captured launch holds by value or by address; not z_null.
+    // Does a graph captured for `o` replay this run?  Every member a captured launch holds by value or by address, that is all but
+    // z_null, the tables bit for bit.  No feature decides which members count: the ones a run does not use are normalised above.
     bool same_graph(const SamplerRun& o) const
     {
-        auto same = [](const auto& a, const auto& b) {              // two tables, bit for bit
-            return a.size() == b.size() && (a.empty() || !std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])));
+        auto same = [](const std::vector<float>& a, const std::vector<float>& b) {
+            return a.size() == b.size() && (a.empty() || !std::memcmp(a.data(), b.data(), a.size() * sizeof(float)));
         };
-        return steps == o.steps && same(ts, o.ts) && same(coef, o.coef) && noise == o.noise && seeds == o.seeds && same(sigma, o.sigma) &&
-               guided == o.guided && (!guided || w == o.w) && ((!guided && !seeds && thr_p == 0.0) || eps == o.eps) && hist == o.hist &&
-               same(c4, o.c4) && pred == o.pred && thr_p == o.thr_p &&
-               (thr_p == 0.0 || (thr_max == o.thr_max && thr == o.thr && thr_sel == o.thr_sel));
+        return steps == o.steps && ts == o.ts && same(coef, o.coef) && same(sigma, o.sigma) && noise == o.noise && seeds == o.seeds &&
+               guided == o.guided && w == o.w && out_scratch == o.out_scratch && same(c4, o.c4) && hist == o.hist && pred == o.pred &&
+               thr_p == o.thr_p && thr_max == o.thr_max && thr == o.thr && thr_sel == o.thr_sel;
     }
 };
 
@@ -240,6 +244,7 @@ struct ccn_handle_s {
     std::vector<std::unique_ptr<ShapePlan>> shape_plans;   // of the committed model, one per (B, H, W, steps)
     std::vector<std::unique_ptr<Binding>> bindings;         // plan x workspace address, least recently used first
     hipStream_t cap_stream = nullptr;
+    int captures = 0;                   // sampler graphs captured so far (ccn_internal_graph_captures)
     unsigned* err_host = nullptr;       // pinned, device-mapped error word the kernels OR into (ConvArgs::err)
     unsigned* err_dev = nullptr;
     // profiling
@@ -763,7 +768,7 @@ hipError_t launch(const ccn_handle_s* h, const ShapePlan& pl, const Launch& L, c
     if (cw.kind == KIND_HEAD) {
         k.x_state = c.x_state; k.eps_out = c.eps_out; k.do_ddim = c.do_ddim;
         k.c0 = c.c[0]; k.c1 = c.c[1]; k.c2 = c.c[2]; k.c3 = c.c[3]; k.noise = c.noise; k.sigma = c.sigma;
-        k.x0_hist = c.x0_hist; k.c4 = c.c4; k.pred = h->pred;
+        k.x0_hist = c.x0_hist; k.c4 = c.c4; k.pred = c.pred;
     }
     if (L.op == OP_HEAD2) return launch_head2(k, (const float2*)at(L.gn_ab), h->head_w_f32, at(L.scratch), c.step, s);
     const int v = c.step % cw.nphase;
@@ -902,8 +907,8 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, const SamplerRun
         const bool thresholded = r.thr_p > 0.0;
         const bool split = r.guided || seeds || thresholded;        // the head writes the raw output, a sampler-step launch updates
         StepCtx c;
-        c.step = i; c.x_in = xstate;
-        if (split) { c.x_state = nullptr; c.eps_out = r.eps; c.do_ddim = 0; }
+        c.step = i; c.x_in = xstate; c.pred = r.pred;
+        if (split) { c.x_state = nullptr; c.eps_out = r.out_scratch; c.do_ddim = 0; }
         else {
             c.x_state = xstate; c.eps_out = nullptr; c.do_ddim = 1;
             for (int k = 0; k < 4; ++k) c.c[k] = cf[k];
@@ -911,22 +916,24 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, const SamplerRun
             if (ms) { c.x0_hist = r.hist; c.c4 = c4; }
         }
         if (int rc = run_ops(h, b, s, c)) return rc;
+        if (!split) continue;
         // guided: the combine and the update of both halves (unguided, the update is the head kernel's epilogue)
         // (unguided with seeds, a noisy step: the same launch without the second half -- 3 passes over one state)
         // (thresholded: the same launch with the record's threshold; the noise tensor and the history enter as in the head's epilogue)
         const double passes = r.guided ? 5 + (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0)
                                        : 3 + (thresholded ? (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0) : 0);
-        const int64_t per = (int64_t)h->cfg.img_ch * p.H * p.W;
+        SamplerStep u;
+        u.x = xstate; u.hist = r.hist; u.out_c = r.out_scratch; u.noise = nz; u.pred = r.pred; u.w = r.w;
+        if (r.guided) { u.x_dup = xstate + img; u.out_u = r.out_scratch + img; }
+        for (int k = 0; k < 4; ++k) u.c[k] = cf[k];
+        u.c[4] = c4; u.sigma = sigma; u.n = (int64_t)img;
+        u.seeds = seeds; u.draw = 1u + (uint32_t)i; u.per_record = (int64_t)h->cfg.img_ch * p.H * p.W; u.thr = r.thr;
         // the quantile of |x0| per record, on the combined output when guided: three select passes over the state and the output(s)
         if (thresholded)
             if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * 3 * (r.guided ? 3 : 2), s, [&] {
-                    return launch_x0_threshold(xstate, r.eps, r.guided ? r.eps + img : nullptr, h->pred, r.w, cf[0], cf[1], (int)(img / (size_t)per),
-                                               per, r.thr_p, r.thr_max, r.thr, r.thr_sel, s); })) return rc;
-        if (split)
-            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * passes, s, [&] {
-                    return launch_sampler_step(xstate, r.guided ? xstate + img : nullptr, ms ? r.hist : nullptr, r.eps, r.guided ? r.eps + img : nullptr,
-                                               nz, h->pred, r.w, cf[0], cf[1], cf[2], cf[3], c4, sigma, (int64_t)img, s, seeds, 1u + (uint32_t)i,
-                                               per, thresholded ? r.thr : nullptr); })) return rc;
+                    return launch_x0_threshold(u.x, u.out_c, u.out_u, u.pred, u.w, cf[0], cf[1], (int)(u.n / u.per_record), u.per_record, r.thr_p,
+                                               r.thr_max, r.thr, r.thr_sel, s); })) return rc;
+        if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * passes, s, [&] { return launch_sampler_step(u, s); })) return rc;
     }
     return CCN_OK;
 }
@@ -1117,17 +1124,6 @@ static int threshold_scratch_layout(const ccn_handle_s* h, int32_t B, int32_t H,
     l.total = l.sel + x0_threshold_scratch_bytes(B);
     return CCN_OK;
 }
-static int threshold_run(const ccn_handle_s* h, SamplerRun& r, int32_t B, int32_t H, int32_t W)
-{
-    ThrLayout l;
-    if (int rc = threshold_scratch_layout(h, B, H, W, l)) return rc;
-    if (h->thr_scratch_bytes < l.total)
-        return fail(CCN_EINVAL, "the dynamic-threshold scratch is too small for this shape: need " + std::to_string(l.total) + " bytes");
-    r.thr_p = h->thr_p; r.thr_max = h->thr_max;
-    r.thr = (float*)(h->thr_scratch + l.thr); r.thr_sel = h->thr_scratch + l.sel;
-    if (!r.eps) r.eps = (float*)h->thr_scratch;                     // a run without a scratch of its own: the raw output goes here
-    return CCN_OK;
-}
 
 int ccn_set_dynamic_threshold(ccn_handle_t h, double p, float max_value, void* scratch_dev, size_t scratch_bytes)
 {
@@ -1254,30 +1250,64 @@ int ccn_forward(ccn_handle_t h, const float* x_dev, const float* z_dev, const in
     return run_ops(h, b, s, c);
 }
 
-// the checks every ccn_sample* entry starts with, and the run's host tables (`coef`: [steps][4]; `sigma` nullable) copied into `r`
-static int begin_run(ccn_handle_t h, int32_t steps, const int32_t* ts_host, const float* coef_host, const float* sigma_host, SamplerRun& r)
+// (handle, descriptor, shape) -> the run: every check of the descriptor, the host tables copied, the handle's prediction and dynamic
+// threshold read -- here and nowhere else -- and every unused field at its fixed value (SamplerRun)
+static int build_run(ccn_handle_t h, const ccn_sampler_run_t* d, int32_t B, int32_t H, int32_t W, SamplerRun& r)
 {
+    if (!d) return fail(CCN_EINVAL, "null sampler run descriptor");
+    if (d->size != sizeof(ccn_sampler_run_t))
+        return fail(CCN_EINVAL, "ccn_sampler_run_t: size " + std::to_string(d->size) + ", this library's is " + std::to_string(sizeof(ccn_sampler_run_t)));
+    const bool ms = d->coef_cols == 5, guided = d->guided != 0;
+    if (d->coef_cols != 4 && !ms) return fail(CCN_EINVAL, "coef_cols must be 4 or 5");
+    if (d->steps <= 0) return fail(CCN_EINVAL, "B, H, W, steps must be positive");
+    if (!d->ts_host || !d->coef_host) return fail(CCN_EINVAL, "null pointer");
+    if (ms && (d->sigma_host || d->noise_dev || d->seeds_dev))
+        return fail(CCN_EINVAL, "a fifth coefficient column with sigma, noise or seeds: no ccn_sample* entry expresses this run");
+    if (d->noise_dev && d->seeds_dev) return fail(CCN_EINVAL, "noise_dev with seeds_dev: no ccn_sample* entry expresses this run");
+    if (d->sigma_host ? !d->noise_dev && !d->seeds_dev : d->noise_dev != nullptr) return fail(CCN_EINVAL, "sigma and noise must be given together");
+    if ((uintptr_t)d->seeds_dev & 7) return fail(CCN_EINVAL, "the seeds must be 8-byte aligned");
+    const uint64_t* seeds = d->sigma_host ? d->seeds_dev : nullptr;
+    if (guided && !std::isfinite(d->w)) return fail(CCN_EINVAL, "the guidance scale must be finite");
+    if (guided && (B <= 0 || B > INT32_MAX / 2)) return fail(CCN_EINVAL, "B, H, W, steps must be positive");
+    if ((guided || seeds) && (!d->out_scratch_dev || ((uintptr_t)d->out_scratch_dev & 15)))
+        return fail(CCN_EINVAL, "the output scratch (guided: eps scratch) must be non-null and 16-byte aligned");
+    if (ms && (!d->x0_hist_dev || ((uintptr_t)d->x0_hist_dev & 15))) return fail(CCN_EINVAL, "the x0 history must be non-null and 16-byte aligned");
+    const size_t n = (size_t)d->steps, cols = (size_t)d->coef_cols;
+    for (size_t i = 0; ms && i < n * 5; ++i)
+        if (!std::isfinite(d->coef_host[i])) return fail(CCN_EINVAL, "non-finite sampler coefficient");
+    if (ms && d->coef_host[4] != 0.f) return fail(CCN_EINVAL, "c4 must be 0 on step 0: there is no x0 history yet");
     if (int rc = check_ready(h)) return rc;
-    if (!ts_host || !coef_host) return fail(CCN_EINVAL, "null pointer");
-    const size_t n = steps > 0 ? (size_t)steps : 0;                 // (steps <= 0 is get_binding's error)
-    r.steps = steps; r.pred = h->pred;
-    r.ts.assign(ts_host, ts_host + n); r.coef.assign(coef_host, coef_host + n * 4);
-    if (sigma_host) r.sigma.assign(sigma_host, sigma_host + n);
+    if (d->seeds_dev && H > 0 && W > 0 && (int64_t)h->cfg.img_ch * H * W >= kDrawMaxPerRecord)
+        return fail(CCN_EINVAL, "a record of 2^34 elements or more cannot be drawn");
+
+    r.steps = d->steps; r.pred = h->pred;
+    r.ts.assign(d->ts_host, d->ts_host + n);
+    r.coef.resize(n * 4);
+    for (size_t i = 0; i < n; ++i) std::copy_n(d->coef_host + i * cols, 4, r.coef.begin() + i * 4);
+    for (size_t i = 0; ms && i < n; ++i) r.c4.push_back(d->coef_host[i * 5 + 4]);
+    if (d->sigma_host) { r.sigma.assign(d->sigma_host, d->sigma_host + n); r.noise = d->noise_dev; r.seeds = seeds; }
+    if (guided) { r.guided = true; r.w = d->w; r.z_null = d->z_null_dev; }
+    if (ms) r.hist = d->x0_hist_dev;
+    if (guided || seeds) r.out_scratch = d->out_scratch_dev;
+    if (h->thr_p > 0.0) {
+        ThrLayout l;
+        if (int rc = threshold_scratch_layout(h, B, H, W, l)) return rc;
+        if (h->thr_scratch_bytes < l.total)
+            return fail(CCN_EINVAL, "the dynamic-threshold scratch is too small for this shape: need " + std::to_string(l.total) + " bytes");
+        r.thr_p = h->thr_p; r.thr_max = h->thr_max;
+        r.thr = (float*)(h->thr_scratch + l.thr); r.thr_sel = h->thr_scratch + l.sel;
+        if (!r.out_scratch) r.out_scratch = (float*)h->thr_scratch;   // a run without a scratch of its own: the head of the handle's
+    }
     return CCN_OK;
 }
 
-static int sample_impl(ccn_handle_t h, const SamplerRun& run, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H,
-                       int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph)
+int ccn_sample_run(ccn_handle_t h, const ccn_sampler_run_t* run, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H,
+                   int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph)
 {
     int rc;
+    SamplerRun r;
+    if ((rc = build_run(h, run, B, H, W, r))) return rc;
     if (!z_dev || !x_T_dev || !x_out_dev) return fail(CCN_EINVAL, "null pointer");
-    if (run.guided && (B <= 0 || B > INT32_MAX / 2)) return fail(CCN_EINVAL, "B, H, W, steps must be positive");
-    SamplerRun thresholded;                                         // the run with the handle's dynamic threshold, if one is set
-    if (h->thr_p > 0.0) {
-        thresholded = run;
-        if ((rc = threshold_run(h, thresholded, B, H, W))) return rc;
-    }
-    const SamplerRun& r = h->thr_p > 0.0 ? thresholded : run;
     const int PB = r.guided ? 2 * B : B;                            // the plan's batch: guided, the two halves
     const int steps = r.steps;
     Binding* p = nullptr;
@@ -1321,6 +1351,7 @@ static int sample_impl(ccn_handle_t h, const SamplerRun& run, const float* z_dev
             if (ce != hipSuccess) return fail(CCN_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
             g.graph = graph;
             HIPCHK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
+            ++h->captures;
             // at most kMaxGraphsPerBinding captured graphs per binding, least recently used first (a caller that passes a fresh noise
             // tensor / coefficient table every call would otherwise grow the list without bound); an exec may still be replaying
             // on a caller stream, so the device is drained before one is destroyed
@@ -1344,13 +1375,21 @@ static int sample_impl(ccn_handle_t h, const SamplerRun& run, const float* z_dev
     return CCN_OK;
 }
 
+// The seven fixed-shape entries: each fills a descriptor from its arguments, keeps the checks the descriptor cannot express (an entry
+// that insists on a pointer its run may not use), and calls ccn_sample_run.
+static ccn_sampler_run_t run_of(int32_t steps, const int32_t* ts_host, const float* coef_host, int32_t coef_cols)
+{
+    ccn_sampler_run_t d{};
+    d.size = sizeof(d); d.steps = steps; d.ts_host = ts_host; d.coef_host = coef_host; d.coef_cols = coef_cols;
+    return d;
+}
+
 int ccn_sample(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H, int32_t W,
                int32_t steps, const int32_t* ts_host, const float* coef_host, void* workspace_dev, size_t workspace_bytes,
                void* stream, int32_t use_graph)
 {
-    SamplerRun r;
-    if (int rc = begin_run(h, steps, ts_host, coef_host, nullptr, r)) return rc;
-    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
+    const ccn_sampler_run_t d = run_of(steps, ts_host, coef_host, 4);
+    return ccn_sample_run(h, &d, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
 }
 
 int ccn_sample_eta(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H, int32_t W,
@@ -1358,10 +1397,9 @@ int ccn_sample_eta(ccn_handle_t h, const float* z_dev, const float* x_T_dev, flo
                    void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph)
 {
     if (!sigma_host || !noise_dev) return fail(CCN_EINVAL, "null sigma / noise");
-    SamplerRun r;
-    if (int rc = begin_run(h, steps, ts_host, coef_host, sigma_host, r)) return rc;
-    r.noise = noise_dev;
-    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
+    ccn_sampler_run_t d = run_of(steps, ts_host, coef_host, 4);
+    d.sigma_host = sigma_host; d.noise_dev = noise_dev;
+    return ccn_sample_run(h, &d, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
 }
 
 int ccn_sample_guided(ccn_handle_t h, const float* z_dev, const float* z_null_dev, const float* x_T_dev, float* x_out_dev, int32_t B,
@@ -1369,35 +1407,22 @@ int ccn_sample_guided(ccn_handle_t h, const float* z_dev, const float* z_null_de
                       const float* noise_dev, float w, float* eps_scratch_dev, void* workspace_dev, size_t workspace_bytes, void* stream,
                       int32_t use_graph)
 {
-    if (!sigma_host != !noise_dev) return fail(CCN_EINVAL, "sigma and noise must be given together");
-    if (!std::isfinite(w)) return fail(CCN_EINVAL, "the guidance scale must be finite");
-    if (!eps_scratch_dev || ((uintptr_t)eps_scratch_dev & 15)) return fail(CCN_EINVAL, "the eps scratch must be non-null and 16-byte aligned");
-    SamplerRun r;
-    if (int rc = begin_run(h, steps, ts_host, coef_host, sigma_host, r)) return rc;
-    r.noise = noise_dev;
-    r.guided = true; r.z_null = z_null_dev; r.w = w; r.eps = eps_scratch_dev;
-    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
-}
-
-// the seeded entries' own checks; sigma_host NULL (eta = 0) leaves the run unseeded: nothing would be drawn
-static int seed_run(SamplerRun& r, const uint64_t* seeds_dev, int32_t H, int32_t W, int img_ch)
-{
-    if (!seeds_dev || ((uintptr_t)seeds_dev & 7)) return fail(CCN_EINVAL, "the seeds must be non-null and 8-byte aligned");
-    if (H > 0 && W > 0 && (int64_t)img_ch * H * W >= kDrawMaxPerRecord) return fail(CCN_EINVAL, "a record of 2^34 elements or more cannot be drawn");
-    if (!r.sigma.empty()) r.seeds = seeds_dev;
-    return CCN_OK;
+    ccn_sampler_run_t d = run_of(steps, ts_host, coef_host, 4);
+    d.sigma_host = sigma_host; d.noise_dev = noise_dev;
+    d.guided = 1; d.w = w; d.z_null_dev = z_null_dev; d.out_scratch_dev = eps_scratch_dev;
+    return ccn_sample_run(h, &d, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
 }
 
 int ccn_sample_seeded(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H, int32_t W,
                       int32_t steps, const int32_t* ts_host, const float* coef_host, const float* sigma_host, const uint64_t* seeds_dev,
                       float* out_scratch_dev, void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph)
 {
+    // (also with sigma_host NULL, where the run uses neither)
     if (!out_scratch_dev || ((uintptr_t)out_scratch_dev & 15)) return fail(CCN_EINVAL, "the output scratch must be non-null and 16-byte aligned");
-    SamplerRun r;
-    if (int rc = begin_run(h, steps, ts_host, coef_host, sigma_host, r)) return rc;
-    if (int rc = seed_run(r, seeds_dev, H, W, h->cfg.img_ch)) return rc;
-    if (r.seeds) r.eps = out_scratch_dev;
-    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
+    if (!seeds_dev) return fail(CCN_EINVAL, "the seeds must be non-null and 8-byte aligned");
+    ccn_sampler_run_t d = run_of(steps, ts_host, coef_host, 4);
+    d.sigma_host = sigma_host; d.seeds_dev = seeds_dev; d.out_scratch_dev = out_scratch_dev;
+    return ccn_sample_run(h, &d, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
 }
 
 int ccn_sample_guided_seeded(ccn_handle_t h, const float* z_dev, const float* z_null_dev, const float* x_T_dev, float* x_out_dev, int32_t B,
@@ -1405,134 +1430,133 @@ int ccn_sample_guided_seeded(ccn_handle_t h, const float* z_dev, const float* z_
                              const uint64_t* seeds_dev, float w, float* eps_scratch_dev, void* workspace_dev, size_t workspace_bytes,
                              void* stream, int32_t use_graph)
 {
-    if (!std::isfinite(w)) return fail(CCN_EINVAL, "the guidance scale must be finite");
-    if (!eps_scratch_dev || ((uintptr_t)eps_scratch_dev & 15)) return fail(CCN_EINVAL, "the eps scratch must be non-null and 16-byte aligned");
-    SamplerRun r;
-    if (int rc = begin_run(h, steps, ts_host, coef_host, sigma_host, r)) return rc;
-    if (int rc = seed_run(r, seeds_dev, H, W, h->cfg.img_ch)) return rc;
-    r.guided = true; r.z_null = z_null_dev; r.w = w; r.eps = eps_scratch_dev;
-    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
-}
-
-int ccn_sampler_step_seeded(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,
-                            const uint64_t* seeds_dev, uint32_t draw, int64_t per_record, int32_t pred, float w, const float* coef_host,
-                            float sigma, int64_t n, void* stream)
-{
-    if (!x_dev || !out_c_dev || !coef_host || n < 0) return fail(CCN_EINVAL, "bad argument");
-    if (pred != CCN_PRED_EPS && pred != CCN_PRED_V) return fail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
-    if (!seeds_dev || ((uintptr_t)seeds_dev & 7)) return fail(CCN_EINVAL, "the seeds must be non-null and 8-byte aligned");
-    if (per_record <= 0 || per_record >= kDrawMaxPerRecord || n % per_record) return fail(CCN_EINVAL, "per_record must be in [1, 2^34) and divide n");
-    if (n / per_record > 65535) return fail(CCN_EINVAL, "at most 65535 records per launch");
-    if (n == 0) return CCN_OK;
-    HIPCHK(launch_sampler_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, nullptr, pred, w, coef_host[0], coef_host[1], coef_host[2],
-                               coef_host[3], x0_hist_dev ? coef_host[4] : 0.f, sigma, n, (hipStream_t)stream, seeds_dev, draw, per_record));
-    return CCN_OK;
-}
-
-// the [steps][5] table of the multistep entries -> the [steps][4] one of a SamplerRun and the c4 column, checked
-static int split_ms_table(int32_t steps, const float* coef_host, const float* x0_hist_dev, std::vector<float>& coef4, std::vector<float>& c4)
-{
-    if (!coef_host || steps <= 0) return fail(CCN_EINVAL, "null pointer");
-    if (!x0_hist_dev || ((uintptr_t)x0_hist_dev & 15)) return fail(CCN_EINVAL, "the x0 history must be non-null and 16-byte aligned");
-    coef4.resize((size_t)steps * 4); c4.resize((size_t)steps);
-    for (int i = 0; i < steps; ++i) {
-        for (int k = 0; k < 5; ++k)
-            if (!std::isfinite(coef_host[i * 5 + k])) return fail(CCN_EINVAL, "non-finite sampler coefficient");
-        for (int k = 0; k < 4; ++k) coef4[(size_t)i * 4 + k] = coef_host[i * 5 + k];
-        c4[i] = coef_host[i * 5 + 4];
-    }
-    if (c4[0] != 0.f) return fail(CCN_EINVAL, "c4 must be 0 on step 0: there is no x0 history yet");
-    return CCN_OK;
+    if (!seeds_dev) return fail(CCN_EINVAL, "the seeds must be non-null and 8-byte aligned");
+    ccn_sampler_run_t d = run_of(steps, ts_host, coef_host, 4);
+    d.sigma_host = sigma_host; d.seeds_dev = seeds_dev;
+    d.guided = 1; d.w = w; d.z_null_dev = z_null_dev; d.out_scratch_dev = eps_scratch_dev;
+    return ccn_sample_run(h, &d, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
 }
 
 int ccn_sample_ms(ccn_handle_t h, const float* z_dev, const float* x_T_dev, float* x_out_dev, int32_t B, int32_t H, int32_t W, int32_t steps,
                   const int32_t* ts_host, const float* coef_host, float* x0_hist_dev, void* workspace_dev, size_t workspace_bytes,
                   void* stream, int32_t use_graph)
 {
-    SamplerRun r;
-    std::vector<float> coef4;
-    if (int rc = split_ms_table(steps, coef_host, x0_hist_dev, coef4, r.c4)) return rc;
-    if (int rc = begin_run(h, steps, ts_host, coef4.data(), nullptr, r)) return rc;
-    r.hist = x0_hist_dev;
-    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
+    ccn_sampler_run_t d = run_of(steps, ts_host, coef_host, 5);
+    d.x0_hist_dev = x0_hist_dev;
+    return ccn_sample_run(h, &d, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
 }
 
 int ccn_sample_guided_ms(ccn_handle_t h, const float* z_dev, const float* z_null_dev, const float* x_T_dev, float* x_out_dev, int32_t B,
                          int32_t H, int32_t W, int32_t steps, const int32_t* ts_host, const float* coef_host, float w, float* eps_scratch_dev,
                          float* x0_hist_dev, void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph)
 {
-    if (!std::isfinite(w)) return fail(CCN_EINVAL, "the guidance scale must be finite");
-    if (!eps_scratch_dev || ((uintptr_t)eps_scratch_dev & 15)) return fail(CCN_EINVAL, "the eps scratch must be non-null and 16-byte aligned");
-    SamplerRun r;
-    std::vector<float> coef4;
-    if (int rc = split_ms_table(steps, coef_host, x0_hist_dev, coef4, r.c4)) return rc;
-    if (int rc = begin_run(h, steps, ts_host, coef4.data(), nullptr, r)) return rc;
-    r.guided = true; r.z_null = z_null_dev; r.w = w; r.eps = eps_scratch_dev;
-    r.hist = x0_hist_dev;
-    return sample_impl(h, r, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
+    ccn_sampler_run_t d = run_of(steps, ts_host, coef_host, 5);
+    d.guided = 1; d.w = w; d.z_null_dev = z_null_dev; d.out_scratch_dev = eps_scratch_dev; d.x0_hist_dev = x0_hist_dev;
+    return ccn_sample_run(h, &d, z_dev, x_T_dev, x_out_dev, B, H, W, workspace_dev, workspace_bytes, stream, use_graph);
 }
 
-// The four older stand-alone updates: their own argument checks, then the one kernel in its eps form.
+// ---- the stand-alone updates: their own argument checks, then the one kernel ----------------------------------------------------
+static int enqueue_step(const SamplerStep& a, void* stream)
+{
+    if (a.n == 0) return CCN_OK;
+    HIPCHK(launch_sampler_step(a, (hipStream_t)stream));
+    return CCN_OK;
+}
+// the four older entries: the eps form on by-value coefficients
+static SamplerStep eps_step(float* x, const float* eps_c, float c0, float c1, float c2, float c3, int64_t n)
+{
+    SamplerStep a;
+    a.x = x; a.out_c = eps_c; a.c[0] = c0; a.c[1] = c1; a.c[2] = c2; a.c[3] = c3; a.n = n;
+    return a;
+}
+
 int ccn_ms_step(float* x_dev, float* x0_hist_dev, const float* eps_dev, float c0, float c1, float c2, float c3, float c4, int64_t n, void* stream)
 {
     if (!x_dev || !x0_hist_dev || !eps_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
-    if (n == 0) return CCN_OK;
-    HIPCHK(launch_sampler_step(x_dev, nullptr, x0_hist_dev, eps_dev, nullptr, nullptr, CCN_PRED_EPS, 0.f, c0, c1, c2, c3, c4, 0.f, n, (hipStream_t)stream));
-    return CCN_OK;
+    SamplerStep a = eps_step(x_dev, eps_dev, c0, c1, c2, c3, n);
+    a.hist = x0_hist_dev; a.c[4] = c4;
+    return enqueue_step(a, stream);
 }
 
 int ccn_cfg_ms_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* eps_c_dev, const float* eps_u_dev, float w,
                     float c0, float c1, float c2, float c3, float c4, int64_t n, void* stream)
 {
     if (!x_dev || !x0_hist_dev || !eps_c_dev || !eps_u_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
-    if (n == 0) return CCN_OK;
-    HIPCHK(launch_sampler_step(x_dev, x_dup_dev, x0_hist_dev, eps_c_dev, eps_u_dev, nullptr, CCN_PRED_EPS, w, c0, c1, c2, c3, c4, 0.f, n, (hipStream_t)stream));
-    return CCN_OK;
+    SamplerStep a = eps_step(x_dev, eps_c_dev, c0, c1, c2, c3, n);
+    a.x_dup = x_dup_dev; a.out_u = eps_u_dev; a.w = w; a.hist = x0_hist_dev; a.c[4] = c4;
+    return enqueue_step(a, stream);
 }
 
 int ccn_cfg_ddim_step(float* x_dev, float* x_dup_dev, const float* eps_c_dev, const float* eps_u_dev, const float* noise_dev, float w,
                       float c0, float c1, float c2, float c3, float sigma, int64_t n, void* stream)
 {
     if (!x_dev || !eps_c_dev || !eps_u_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
-    if (n == 0) return CCN_OK;
-    HIPCHK(launch_sampler_step(x_dev, x_dup_dev, nullptr, eps_c_dev, eps_u_dev, noise_dev, CCN_PRED_EPS, w, c0, c1, c2, c3, 0.f, sigma, n, (hipStream_t)stream));
-    return CCN_OK;
+    SamplerStep a = eps_step(x_dev, eps_c_dev, c0, c1, c2, c3, n);
+    a.x_dup = x_dup_dev; a.out_u = eps_u_dev; a.w = w; a.noise = noise_dev; a.sigma = sigma;
+    return enqueue_step(a, stream);
 }
 
 int ccn_ddim_step(float* x_dev, const float* eps_dev, const float* noise_dev, float c0, float c1, float c2, float c3,
                   float sigma, int64_t n, void* stream)
 {
     if (!x_dev || !eps_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
-    if (n == 0) return CCN_OK;
-    HIPCHK(launch_sampler_step(x_dev, nullptr, nullptr, eps_dev, nullptr, noise_dev, CCN_PRED_EPS, 0.f, c0, c1, c2, c3, 0.f, sigma, n, (hipStream_t)stream));
+    SamplerStep a = eps_step(x_dev, eps_dev, c0, c1, c2, c3, n);
+    a.noise = noise_dev; a.sigma = sigma;
+    return enqueue_step(a, stream);
+}
+
+// the three general entries: the checks of ccn_sampler_step and what all three take, into `a`
+static int general_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev, int32_t pred, float w,
+                        const float* coef_host, float sigma, int64_t n, SamplerStep& a)
+{
+    if (!x_dev || !out_c_dev || !coef_host || n < 0) return fail(CCN_EINVAL, "bad argument");
+    if (pred != CCN_PRED_EPS && pred != CCN_PRED_V) return fail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
+    a = eps_step(x_dev, out_c_dev, coef_host[0], coef_host[1], coef_host[2], coef_host[3], n);
+    a.x_dup = x_dup_dev; a.hist = x0_hist_dev; a.out_u = out_u_dev; a.pred = pred; a.w = w; a.sigma = sigma;
+    if (x0_hist_dev) a.c[4] = coef_host[4];
+    return CCN_OK;
+}
+// ... and of the two that walk the state record by record
+static_assert(kDrawMaxPerRecord == kThrMaxPerRecord, "one per_record limit for the draws and the select");
+static int check_records(int64_t per_record, int64_t n)
+{
+    if (per_record <= 0 || per_record >= kDrawMaxPerRecord || n % per_record) return fail(CCN_EINVAL, "per_record must be in [1, 2^34) and divide n");
+    if (n / per_record > 65535) return fail(CCN_EINVAL, "at most 65535 records per launch");
     return CCN_OK;
 }
 
 int ccn_sampler_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,
                      const float* noise_dev, int32_t pred, float w, const float* coef_host, float sigma, int64_t n, void* stream)
 {
-    if (!x_dev || !out_c_dev || !coef_host || n < 0) return fail(CCN_EINVAL, "bad argument");
-    if (pred != CCN_PRED_EPS && pred != CCN_PRED_V) return fail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
-    if (n == 0) return CCN_OK;
-    HIPCHK(launch_sampler_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, noise_dev, pred, w, coef_host[0], coef_host[1], coef_host[2],
-                               coef_host[3], x0_hist_dev ? coef_host[4] : 0.f, sigma, n, (hipStream_t)stream));
-    return CCN_OK;
+    SamplerStep a;
+    if (int rc = general_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, pred, w, coef_host, sigma, n, a)) return rc;
+    a.noise = noise_dev;
+    return enqueue_step(a, stream);
+}
+
+int ccn_sampler_step_seeded(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,
+                            const uint64_t* seeds_dev, uint32_t draw, int64_t per_record, int32_t pred, float w, const float* coef_host,
+                            float sigma, int64_t n, void* stream)
+{
+    SamplerStep a;
+    if (int rc = general_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, pred, w, coef_host, sigma, n, a)) return rc;
+    if (!seeds_dev || ((uintptr_t)seeds_dev & 7)) return fail(CCN_EINVAL, "the seeds must be non-null and 8-byte aligned");
+    if (int rc = check_records(per_record, n)) return rc;
+    a.seeds = seeds_dev; a.draw = draw; a.per_record = per_record;
+    return enqueue_step(a, stream);
 }
 
 int ccn_sampler_step_thr(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,
                          const float* noise_dev, const uint64_t* seeds_dev, uint32_t draw, int64_t per_record, int32_t pred, float w,
                          const float* coef_host, float sigma, int64_t n, const float* thr_dev, void* stream)
 {
-    if (!x_dev || !out_c_dev || !coef_host || n < 0) return fail(CCN_EINVAL, "bad argument");
-    if (pred != CCN_PRED_EPS && pred != CCN_PRED_V) return fail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
+    SamplerStep a;
+    if (int rc = general_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, pred, w, coef_host, sigma, n, a)) return rc;
     if (noise_dev && seeds_dev) return fail(CCN_EINVAL, "noise_dev and seeds_dev exclude each other");
     if (seeds_dev && ((uintptr_t)seeds_dev & 7)) return fail(CCN_EINVAL, "the seeds must be 8-byte aligned");
-    if (per_record <= 0 || per_record >= kThrMaxPerRecord || n % per_record) return fail(CCN_EINVAL, "per_record must be in [1, 2^34) and divide n");
-    if (n / per_record > 65535) return fail(CCN_EINVAL, "at most 65535 records per launch");
-    if (n == 0) return CCN_OK;
-    HIPCHK(launch_sampler_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, noise_dev, pred, w, coef_host[0], coef_host[1], coef_host[2],
-                               coef_host[3], x0_hist_dev ? coef_host[4] : 0.f, sigma, n, (hipStream_t)stream, seeds_dev, draw, per_record, thr_dev));
-    return CCN_OK;
+    if (int rc = check_records(per_record, n)) return rc;
+    a.noise = noise_dev; a.seeds = seeds_dev; a.draw = draw; a.per_record = per_record; a.thr = thr_dev;
+    return enqueue_step(a, stream);
 }
 
 int ccn_q_sample(float* out_dev, const float* x0_dev, const float* noise_dev, const float* a_dev, const float* s_dev,
@@ -1656,6 +1680,8 @@ extern "C" int ccn_internal_plan_kernels_of(ccn_handle_t h, int32_t B, int32_t H
     if (!h || !h->committed || shape_plan(h, B, H, W, steps, &pl)) return -1;
     return copy_report(routes_text(*pl, true), buf, cap);
 }
+// How many sampler-loop graphs the handle has captured so far: a call that replays a cached graph leaves it unchanged.
+extern "C" int ccn_internal_graph_captures(ccn_handle_t h) { return h ? h->captures : -1; }
 extern "C" int ccn_internal_plan_layout(ccn_handle_t h, int32_t B, int32_t H, int32_t W, int32_t steps, char* buf, size_t cap)
 {
     const ShapePlan* pl;

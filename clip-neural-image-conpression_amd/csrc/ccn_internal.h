@@ -270,10 +270,25 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
 // out_c is the prediction itself; no hist: c4 is not applied and no history is written (hist is read only when c4 != 0).  `seeds`
 // (nullable; one uint64 per record of per_record elements, n a multiple of it) with sigma > 0: the noise is draw `draw` of each record,
 // generated in the kernel, and `noise` is not read.  `thr` (nullable; one float per record, per_record as above): the record's dynamic
-// threshold replaces the +-1 clamp of x0
-hipError_t launch_sampler_step(float* x, float* x_dup, float* hist, const float* out_c, const float* out_u, const float* noise, int pred,
-                               float w, float c0, float c1, float c2, float c3, float c4, float sigma, int64_t n, hipStream_t s,
-                               const uint64_t* seeds = nullptr, uint32_t draw = 0, int64_t per_record = 0, const float* thr = nullptr);
+// threshold replaces the +-1 clamp of x0.  A caller fills the fields it uses; the rest stay absent.
+struct SamplerStep {
+    float* x = nullptr;
+    float* x_dup = nullptr;
+    float* hist = nullptr;
+    const float* out_c = nullptr;
+    const float* out_u = nullptr;
+    const float* noise = nullptr;
+    int pred = 0;                          // CCN_PRED_EPS
+    float w = 0.f;
+    float c[5] = {0.f, 0.f, 0.f, 0.f, 0.f};   // c0..c4
+    float sigma = 0.f;
+    int64_t n = 0;
+    const uint64_t* seeds = nullptr;
+    uint32_t draw = 0;
+    int64_t per_record = 0;
+    const float* thr = nullptr;
+};
+hipError_t launch_sampler_step(const SamplerStep& a, hipStream_t s);
 // the dynamic threshold of every record (ccn_threshold.hip; ccn_x0_threshold in ccn_hip.h): thr[b] = min(max(Q_p(|x0_b|), 1), max_value)
 // of the raw x0 the launch above would form.  `scratch`: x0_threshold_scratch_bytes(B) bytes, 16-byte aligned, any contents.  The
 // caller has checked the arguments (0 <= p <= 1, 1 <= B <= 65535, 0 < per < 2^34).  Five launches, nothing else.

@@ -889,21 +889,21 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
 }
 // seeds given and sigma > 0: the seeded form; thr given: the threshold form; either walks the state record by record, one grid row
 // each (the caller has checked per > 0 and n % per == 0).  With seeds `noise` is not read.
-hipError_t launch_sampler_step(float* x, float* x_dup, float* hist, const float* out_c, const float* out_u, const float* noise, int pred,
-                               float w, float c0, float c1, float c2, float c3, float c4, float sigma, int64_t n, hipStream_t s,
-                               const uint64_t* seeds, uint32_t draw, int64_t per, const float* thr)
+hipError_t launch_sampler_step(const SamplerStep& a, hipStream_t s)
 {
-    const bool seeded = seeds && sigma > 0.f;
-    if (seeded) noise = nullptr;
+    const int64_t n = a.n, per = a.per_record;
+    const float* thr = a.thr;
+    const bool seeded = a.seeds && a.sigma > 0.f;
+    const float* noise = seeded ? nullptr : a.noise;
     const bool rowed = seeded || thr;
     if (rowed && (per <= 0 || n % per || n / per > 65535)) return hipErrorInvalidValue;      // one grid row per record
-    const bool vec = !(((uintptr_t)x | (uintptr_t)x_dup | (uintptr_t)hist | (uintptr_t)out_c | (uintptr_t)out_u | (uintptr_t)noise) & 15) &&
+    const bool vec = !(((uintptr_t)a.x | (uintptr_t)a.x_dup | (uintptr_t)a.hist | (uintptr_t)a.out_c | (uintptr_t)a.out_u | (uintptr_t)noise) & 15) &&
                      !(rowed && (per & 3));
     const int64_t rows = rowed ? n / per : 1, row = rowed ? per : n;
     const int64_t work = vec ? (row + 3) / 4 : row, blocks = (work + 255) / 256;
     const int gx = (int)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);        // 256 CUs x 8 blocks, grid-stride beyond
     const dim3 grid(gx, (unsigned)rows);
-#define CCN_STEP_ARGS x, x_dup, hist, out_c, out_u, noise, pred, w, c0, c1, c2, c3, c4, sigma, n, seeds, draw, per, thr
+#define CCN_STEP_ARGS a.x, a.x_dup, a.hist, a.out_c, a.out_u, noise, a.pred, a.w, a.c[0], a.c[1], a.c[2], a.c[3], a.c[4], a.sigma, n, a.seeds, a.draw, per, thr
 #define CCN_STEP_GO(SEEDED, THR)                                                                                             \
     do {                                                                                                                     \
         if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, SEEDED, THR>), grid, dim3(256), 0, s, CCN_STEP_ARGS);         \

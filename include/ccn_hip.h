@@ -337,6 +337,57 @@ int ccn_sampler_step_thr(float* x_dev, float* x_dup_dev, float* x0_hist_dev,
 int ccn_set_dynamic_threshold(ccn_handle_t h, double p, float max_value, void* scratch_dev, size_t scratch_bytes);
 int ccn_dynamic_threshold_scratch_bytes(ccn_handle_t h, int32_t B, int32_t H, int32_t W, size_t* bytes);
 
+/* ---- the sampler loop, described by one record ------------------------------------------------------------------------------------ *
+ * Everything a run of the loop is a function of besides the handle (its prediction and dynamic threshold are read like by every
+ * other ccn_sample* entry), the tensors and the shape.  ccn_sample, ccn_sample_eta, ccn_sample_guided, ccn_sample_seeded,
+ * ccn_sample_guided_seeded, ccn_sample_ms and ccn_sample_guided_ms above are fixed-shape conveniences: each fills this record from
+ * its arguments and calls ccn_sample_run; their comments hold the formulas, the ownership rules and the graph keys, which are not
+ * restated here.  A new caller binds this entry alone.  Plain C, natural alignment, no bit-fields: a ctypes.Structure with the same
+ * fields in the same order mirrors it.  An absent feature is a NULL pointer or a 0; a field the run does not use is ignored.
+ *   size             sizeof(ccn_sampler_run_t) as the caller compiled it; any other value is CCN_EINVAL;
+ *   steps, ts_host   the timestep table, ts_host[steps] (ccn_sample);
+ *   coef_host        [steps][coef_cols] fp32;  coef_cols  4: c0..c3 (ccn_sample), 5: the multistep table c0..c4 (ccn_sample_ms),
+ *                    which needs x0_hist_dev and excludes sigma_host, noise_dev and seeds_dev;
+ *   sigma_host       NULL: eta = 0.  Else [steps], together with ONE of
+ *   noise_dev        the (steps,B,img_ch,H,W) draws made by the caller (ccn_sample_eta), or
+ *   seeds_dev        B x uint64 on the device, 8-byte aligned: step i adds draw 1 + i of each record (ccn_sample_seeded); with
+ *                    sigma_host NULL the seeds are not read and the run is the unseeded one;
+ *   guided, w,       guided != 0: classifier-free guidance of finite scale w at plan batch 2B (ccn_sample_guided); z_null_dev
+ *   z_null_dev       (z_dim,), NULL: zeros.  workspace_dev is then the one of ccn_workspace_bytes(h, 2*B, H, W, steps);
+ *   out_scratch_dev  the raw network output of the steps that update in a launch of their own: 2*B*img_ch*H*W floats when guided
+ *                    (the eps scratch of ccn_sample_guided), B*img_ch*H*W when seeds_dev draws (the output scratch of
+ *                    ccn_sample_seeded), 16-byte aligned; not read by any other run -- under a dynamic threshold those keep the raw
+ *                    output in the head of the handle's threshold scratch;
+ *   x0_hist_dev      the multistep sampler's x0 history, B*img_ch*H*W floats, 16-byte aligned (ccn_sample_ms).
+ * Every pointer with _dev is owned by the caller like the workspace and stays at its address while a captured graph is cached.
+ * The captured graph is cached per workspace and per everything above that a launch holds by value or by address (the tables bit
+ * for bit; not z_null_dev, which is copied on every call) plus the handle's prediction and dynamic threshold: the keys the seven
+ * entries document, and a run reached through an entry and the same run described here share one graph.
+ * CCN_EINVAL: what the entries refuse (a NULL table, sigma without noise or seeds or noise without sigma, a non-finite w, a missing
+ * or misaligned scratch, history or seeds, a non-finite multistep coefficient, c4 != 0 on step 0, C*H*W >= 2^34 with seeds), a NULL
+ * run or a wrong size, coef_cols other than 4 or 5, and the runs no entry expresses: a fifth coefficient column together with
+ * sigma, noise or seeds, and noise_dev together with seeds_dev. */
+typedef struct ccn_sampler_run {
+    uint32_t size;
+    int32_t steps;
+    const int32_t* ts_host;
+    const float* coef_host;
+    int32_t coef_cols;
+    const float* sigma_host;
+    const float* noise_dev;
+    const uint64_t* seeds_dev;
+    int32_t guided;
+    float w;
+    const float* z_null_dev;
+    float* out_scratch_dev;
+    float* x0_hist_dev;
+} ccn_sampler_run_t;
+
+int ccn_sample_run(ccn_handle_t h, const ccn_sampler_run_t* run,
+                   const float* z_dev, const float* x_T_dev, float* x_out_dev,
+                   int32_t B, int32_t H, int32_t W,
+                   void* workspace_dev, size_t workspace_bytes, void* stream, int32_t use_graph);
+
 /* NoiseScheduler.q_sample (diffusion/scheduler.py:46-49): out[b] = a[b]*x0[b] + s[b]*noise[b];
  * a_dev/s_dev are the gathered per-sample coefficients, (B,) fp32; per_sample = C*H*W. */
 int ccn_q_sample(float* out_dev, const float* x0_dev, const float* noise_dev,
