@@ -61,6 +61,13 @@ SIGNATURES = {
                                      c_vp, c_vp]),
     "ccn_set_dynamic_threshold": (c_i32, [c_vp, ctypes.c_double, c_f32, c_vp, c_sz]),
     "ccn_dynamic_threshold_scratch_bytes": (c_i32, [c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
+    "ccn_guidance_rescale_scratch_bytes": (c_i32, [c_i32, c_i64, ctypes.POINTER(c_sz)]),
+    "ccn_guidance_rescale": (c_i32, [c_vp, c_vp, c_f32, ctypes.c_double, c_i32, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "ccn_x0_threshold_rs": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_f32, c_i32, c_i64, ctypes.c_double, c_f32, c_vp, c_vp, c_sz, c_vp,
+                                    c_vp]),
+    "ccn_sampler_step_rs": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_i64, c_i32, c_f32, ctypes.POINTER(c_f32), c_f32, c_i64,
+                                    c_vp, c_vp, c_vp]),
+    "ccn_set_guidance_rescale": (c_i32, [c_vp, ctypes.c_double, c_vp, c_sz]),
     "ccn_sample_run": (c_i32, [c_vp, ctypes.POINTER(CcnSamplerRun), c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp, c_i32]),
     "ccn_workspace_bytes": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
     "ccn_release_workspace": (c_i32, [c_vp, c_vp]),
@@ -218,6 +225,8 @@ class Workspace:
         # NativeUNet.sample with a dynamic threshold: the handle's threshold scratch (ccn_set_dynamic_threshold), by image count --
         # likewise kept, because the captured graph holds its address
         self.thr: Dict[int, torch.Tensor] = {}
+        # NativeUNet.sample with guidance rescale: the handle's rescale scratch (ccn_set_guidance_rescale), likewise
+        self.rs: Dict[int, torch.Tensor] = {}
 
     def history(self, like: torch.Tensor) -> torch.Tensor:
         """The kept x0 history of ``like``'s size (allocated on first use; never freed before the workspace, so that a captured
@@ -330,7 +339,7 @@ class NativeUNet:
     def sample(self, z: torch.Tensor, x_T: torch.Tensor, ts, coef, use_graph: bool = True, slot: int = 0, sigma=None,
                noise: Optional[torch.Tensor] = None, w: Optional[float] = None, z_null: Optional[torch.Tensor] = None,
                hist: Optional[torch.Tensor] = None, seeds=None, dynamic_threshold: Optional[float] = None,
-               threshold_max: Optional[float] = None) -> torch.Tensor:
+               threshold_max: Optional[float] = None, guidance_rescale: Optional[float] = None) -> torch.Tensor:
         """Every step of a sampler inside the library, through ``ccn_sample_run``.  ``coef`` of ``(steps, 4)``: the
         DDIM loop; ``sigma`` (steps,) + ``noise`` (steps, B, C, H, W) fp32 on the device make it the eta > 0 one.  ``coef`` of
         ``(steps, 5)``: the multistep loop (``NoiseScheduler.solver_coefficients``; deterministic), ``hist`` its x0 history, fp32 of
@@ -344,7 +353,9 @@ class NativeUNet:
         ``sigma=None`` with seeds is eta = 0: nothing is drawn, the seeds are only checked and the unseeded entry runs.
         ``dynamic_threshold`` (a quantile in (0, 1]; None: off, the handle state is cleared) with ``threshold_max`` (None: no upper
         bound): every step of whichever loop runs clamps x0 to the record's own threshold (ccn_set_dynamic_threshold); the scratch is
-        kept with the workspace."""
+        kept with the workspace.  ``guidance_rescale`` (phi in (0, 1]; None: off, the handle state is cleared): every step of a
+        guided loop multiplies the combined output by the record's ``phi std(y_c) / std(y) + 1 - phi`` (ccn_set_guidance_rescale);
+        the scratch is kept with the workspace likewise, and an unguided run ignores it."""
         import math
         import numpy as np
         z = require_dev(z, "z_clip"); x_T = require_dev(x_T, "x_T")
@@ -403,6 +414,13 @@ class NativeUNet:
                 check(self.lib.ccn_dynamic_threshold_scratch_bytes(self.h, B, H, W, ctypes.byref(n)))
                 ws.thr[B] = torch.empty(n.value, dtype=torch.uint8, device=self.device)
             check(self.lib.ccn_set_dynamic_threshold(self.h, tp, tm, ws.thr[B].data_ptr(), ws.thr[B].numel()))
+        if guidance_rescale is None or w is None:
+            check(self.lib.ccn_set_guidance_rescale(self.h, 0.0, None, 0))
+        else:
+            phi = rescale_arg(guidance_rescale)
+            if B not in ws.rs:
+                ws.rs[B] = torch.empty(guidance_rescale_scratch_bytes(B, C * H * W), dtype=torch.uint8, device=self.device)
+            check(self.lib.ccn_set_guidance_rescale(self.h, phi, ws.rs[B].data_ptr(), ws.rs[B].numel()))
         # the run as the library takes it (ccn_sampler_run_t): an absent feature stays NULL / 0
         run = CcnSamplerRun(size=ctypes.sizeof(CcnSamplerRun), steps=steps, ts_host=ts.ctypes.data, coef_host=coef.ctypes.data,
                             coef_cols=coef.shape[1], x0_hist_dev=ptr(hist))
@@ -883,14 +901,17 @@ def normal_fill(seeds, shape, draw: int = 0, out: Optional[torch.Tensor] = None,
 
 def sampler_step(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], prediction: str = "eps", out_u: Optional[torch.Tensor] = None,
                  w: float = 0.0, hist: Optional[torch.Tensor] = None, sigma: float = 0.0, noise: Optional[torch.Tensor] = None,
-                 x_dup: Optional[torch.Tensor] = None, seeds=None, draw: int = 0, thr: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 x_dup: Optional[torch.Tensor] = None, seeds=None, draw: int = 0, thr: Optional[torch.Tensor] = None,
+                 gscale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One in-place sampler update of ``x`` for either parameterisation (ccn_sampler_step): ``out_c`` is the network output
     (``prediction`` says whether it is eps or v), ``out_u`` the unconditional one of a guided step (the update then acts on
     ``out_u + w * (out_c - out_u)``), ``coef`` = (c0, c1, c2, c3[, c4]), ``hist`` the multistep sampler's x0 history (read when
     ``c4 != 0``, then rewritten), ``noise`` the eta > 0 draw added as ``sigma * noise``, ``x_dup`` a copy of the new ``x``.  ``seeds`` (``x.shape[0]`` of them)
     instead of ``noise``: the draw ``draw`` of each record of ``x`` is generated in the kernel (ccn_sampler_step_seeded), the same
     bits as ``noise=normal_fill(seeds, x.shape, draw)``.  ``thr`` (``(B,)`` fp32, ``x0_threshold``'s result): record ``b`` clamps its
-    x0 to ``[-thr[b], thr[b]]`` and divides by it instead of clamping to +-1 (ccn_sampler_step_thr; with noise or with seeds)."""
+    x0 to ``[-thr[b], thr[b]]`` and divides by it instead of clamping to +-1 (ccn_sampler_step_thr; with noise or with seeds).
+    ``gscale`` (``(B,)`` fp32, ``guidance_rescale``'s result): record ``b`` multiplies its (combined) output by ``gscale[b]`` before
+    anything else reads it (ccn_sampler_step_rs)."""
     lib = load_library()
     pred = prediction_code(prediction)
     x = require_dev(x, "x"); out_c = require_dev(out_c, "out_c")
@@ -916,6 +937,16 @@ def sampler_step(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], pr
         thr = require_dev(thr, "thr")
         if x.dim() < 1 or thr.numel() != x.shape[0]:
             raise ValueError("thr must hold one threshold per record of x, (B,)")
+    if gscale is not None:
+        gscale = require_dev(gscale, "gscale")
+        if x.dim() < 1 or gscale.numel() != x.shape[0]:
+            raise ValueError("gscale must hold one factor per record of x, (B,)")
+        with torch.cuda.device(x.device):
+            check(lib.ccn_sampler_step_rs(x.data_ptr(), ptr(x_dup), ptr(hist), out_c.data_ptr(), ptr(out_u), ptr(nz), ptr(sd), int(draw),
+                                          x.numel() // x.shape[0], pred, float(w), c5, float(sigma), x.numel(), ptr(thr), gscale.data_ptr(),
+                                          current_stream(x.device)))
+        return x
+    if thr is not None:
         with torch.cuda.device(x.device):
             check(lib.ccn_sampler_step_thr(x.data_ptr(), ptr(x_dup), ptr(hist), out_c.data_ptr(), ptr(out_u), ptr(nz), ptr(sd), int(draw),
                                            x.numel() // x.shape[0], pred, float(w), c5, float(sigma), x.numel(), thr.data_ptr(),
@@ -947,11 +978,12 @@ def threshold_args(p, max_value=None) -> Tuple[float, float]:
 
 def x0_threshold(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], prediction: str = "eps", p: float = 0.995,
                  max_value: Optional[float] = None, out_u: Optional[torch.Tensor] = None, w: float = 0.0,
-                 scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 scratch: Optional[torch.Tensor] = None, gscale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The dynamic threshold of every record of ``x`` (ccn_x0_threshold; DESIGN.md section 1, Thresholding): a ``(B,)`` fp32 tensor,
     ``min(max(Q_p(|x0_b|), 1), max_value)`` with x0 formed from ``x``, ``out_c`` (``out_u``, ``w``: the guidance combine first),
     ``prediction`` and ``coef[:2]`` exactly as ``sampler_step`` forms it -- pass the result as its ``thr=``.  ``scratch``: a uint8 HIP
-    tensor of ``x0_threshold_scratch_bytes(B)`` bytes to reuse across calls (any contents), else a new one."""
+    tensor of ``x0_threshold_scratch_bytes(B)`` bytes to reuse across calls (any contents), else a new one.  ``gscale`` (``(B,)`` fp32,
+    ``guidance_rescale``'s result): the quantile of the x0 that ``sampler_step(gscale=)`` forms (ccn_x0_threshold_rs)."""
     lib = load_library()
     pred = prediction_code(prediction)
     p, m = threshold_args(p, max_value)
@@ -969,6 +1001,14 @@ def x0_threshold(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], pr
     elif not (isinstance(scratch, torch.Tensor) and scratch.is_cuda and scratch.is_contiguous() and scratch.dtype == torch.uint8):
         raise ValueError("scratch must be a contiguous uint8 HIP tensor")
     thr = torch.empty(B, dtype=torch.float32, device=x.device)
+    if gscale is not None:
+        gscale = require_dev(gscale, "gscale")
+        if gscale.numel() != B:
+            raise ValueError("gscale must hold one factor per record of x, (B,)")
+        with torch.cuda.device(x.device):
+            check(lib.ccn_x0_threshold_rs(x.data_ptr(), out_c.data_ptr(), ptr(out_u), pred, float(w), c[0], c[1], B, x.numel() // B, p, m,
+                                          thr.data_ptr(), scratch.data_ptr(), scratch.numel(), gscale.data_ptr(), current_stream(x.device)))
+        return thr
     with torch.cuda.device(x.device):
         check(lib.ccn_x0_threshold(x.data_ptr(), out_c.data_ptr(), ptr(out_u), pred, float(w), c[0], c[1], B, x.numel() // B, p, m,
                                    thr.data_ptr(), scratch.data_ptr(), scratch.numel(), current_stream(x.device)))
@@ -978,6 +1018,46 @@ def x0_threshold(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], pr
 def x0_threshold_scratch_bytes(B: int, per_record: int) -> int:
     n = c_sz()
     check(load_library().ccn_x0_threshold_scratch_bytes(int(B), int(per_record), ctypes.byref(n)))
+    return int(n.value)
+
+
+def rescale_arg(phi) -> float:
+    """The ``phi`` of a guidance rescale as the C ABI takes it, checked: in (0, 1]; anything else is a ``ValueError``."""
+    phi = float(phi)
+    if not 0.0 < phi <= 1.0:
+        raise ValueError(f"guidance_rescale must be a factor phi in (0, 1], got {phi}")
+    return phi
+
+
+def guidance_rescale(out_c: torch.Tensor, out_u: torch.Tensor, w: float, phi: float, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The guidance-rescale factor of every record (ccn_guidance_rescale; DESIGN.md section 1, Guidance rescale): a ``(B,)`` fp32
+    tensor, ``phi std(out_c[b]) / std(y[b]) + 1 - phi`` with ``y = out_u + w (out_c - out_u)`` as ``sampler_step`` combines it -- pass
+    the result as its ``gscale=`` (and ``x0_threshold``'s).  ``scratch``: a uint8 HIP tensor of ``guidance_rescale_scratch_bytes(B,
+    per_record)`` bytes to reuse across calls (any contents), else a new one."""
+    import math
+    lib = load_library()
+    phi = rescale_arg(phi)
+    if not math.isfinite(float(w)):
+        raise ValueError(f"the guidance scale must be finite, got {w}")
+    out_c = require_dev(out_c, "out_c"); out_u = require_dev(out_u, "out_u")
+    if out_c.dim() < 1 or out_c.shape[0] < 1 or out_u.numel() != out_c.numel():
+        raise ValueError("out_c must be (B, ...) and out_u must hold as many elements")
+    B = int(out_c.shape[0])
+    need = guidance_rescale_scratch_bytes(B, out_c.numel() // B)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=out_c.device)
+    elif not (isinstance(scratch, torch.Tensor) and scratch.is_cuda and scratch.is_contiguous() and scratch.dtype == torch.uint8):
+        raise ValueError("scratch must be a contiguous uint8 HIP tensor")
+    k = torch.empty(B, dtype=torch.float32, device=out_c.device)
+    with torch.cuda.device(out_c.device):
+        check(lib.ccn_guidance_rescale(out_c.data_ptr(), out_u.data_ptr(), float(w), phi, B, out_c.numel() // B, k.data_ptr(),
+                                       scratch.data_ptr(), scratch.numel(), current_stream(out_c.device)))
+    return k
+
+
+def guidance_rescale_scratch_bytes(B: int, per_record: int) -> int:
+    n = c_sz()
+    check(load_library().ccn_guidance_rescale_scratch_bytes(int(B), int(per_record), ctypes.byref(n)))
     return int(n.value)
 
 

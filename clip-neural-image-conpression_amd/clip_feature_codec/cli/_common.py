@@ -80,25 +80,52 @@ def check_threshold_flags(dynamic_threshold: float | None, threshold_max: float 
         raise SystemExit("--threshold_max must be at least 1")
 
 
+def add_rescale_flags(ap) -> None:
+    """``--guidance_rescale PHI`` and ``--zero_snr`` (both CLIs), the two fixes of Lin et al. 2023; both off by default."""
+    ap.add_argument("--guidance_rescale", type=float, default=None, metavar="PHI",
+                    help="guidance rescale (Lin et al. 2023; diffusers' guidance_rescale): per image and step the guided output is multiplied "
+                         "by PHI std(cond) / std(guided) + 1 - PHI; PHI in (0, 1], the paper suggests 0.7; needs --cfg_scale other than 1; "
+                         "off by default")
+    ap.add_argument("--zero_snr", action="store_true",
+                    help="sample on the schedule rescaled to zero terminal SNR (same paper); needs --prediction v and must match how the "
+                         "checkpoint was trained (train_diffusion(zero_snr=)): the checkpoint itself does not say")
+
+
+def check_rescale_flags(guidance_rescale: float | None, cfg_scale: float, zero_snr: bool, prediction: str) -> None:
+    """Both CLIs call this right after parsing: PHI in (0, 1] and only under guidance; ``--zero_snr`` only with ``--prediction v``."""
+    if guidance_rescale is not None:
+        if not 0.0 < guidance_rescale <= 1.0:
+            raise SystemExit("--guidance_rescale must be a factor in (0, 1]")
+        if cfg_scale == 1.0:
+            raise SystemExit("--guidance_rescale needs guidance: --cfg_scale other than 1")
+    if zero_snr and prediction != "v":
+        raise SystemExit("--zero_snr needs --prediction v: the eps form divides by sqrt(alpha_bar_t), which is 0 at t = T-1")
+
+
 def record_seeds(indices: Sequence[int], seed: int) -> list:
     """The 64-bit seeds of ``--device_noise``: record ``i`` of the manifest gets ``seed + i``, the rule of ``start_noise``."""
     return [int(seed) + int(i) for i in indices]
 
 
 def build_sampler(eta: float, device: str, guided: bool = False, sampler: str = "ddim", spacing: str = "logsnr", prediction: str = "eps",
-                  dynamic_threshold: float | None = None, threshold_max: float | None = None):
+                  dynamic_threshold: float | None = None, threshold_max: float | None = None, guidance_rescale: float | None = None,
+                  zero_snr: bool = False):
     """``guided``: the sampler gives ``cfg_scale`` its meaning (classifier-free guidance against the zero embedding).
     ``sampler="dpmpp2m"``: the second-order multistep solver on the ``spacing`` timestep table (deterministic: no ``eta``).
     ``prediction``: ``"eps"`` or ``"v"``, how the checkpoint was trained.  ``dynamic_threshold`` / ``threshold_max``: dynamic
-    thresholding of x0 (None: the static clamp)."""
+    thresholding of x0 (None: the static clamp).  ``guidance_rescale``: the guidance rescale's phi (None: off; needs ``guided``).
+    ``zero_snr``: the scheduler is built with ``rescale_zero_snr=True``, refused without ``prediction="v"``."""
     check_sampler_flags(sampler, eta)
-    thr = dict(dynamic_threshold=dynamic_threshold, threshold_max=threshold_max)
+    if zero_snr and prediction != "v":
+        raise SystemExit("--zero_snr needs --prediction v: the eps form divides by sqrt(alpha_bar_t), which is 0 at t = T-1")
+    thr = dict(dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale)
+    sch = NoiseScheduler(timesteps=1000, schedule="cosine", device=device, rescale_zero_snr=zero_snr)
     if sampler == "dpmpp2m":
-        return DPMSolverSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), order=2, spacing=spacing, guided=guided,
+        return DPMSolverSampler(sch, order=2, spacing=spacing, guided=guided,
                                 prediction=prediction, **thr)
     if sampler != "ddim":
         raise SystemExit(f"unknown sampler {sampler}")
-    return DDIMSampler(NoiseScheduler(timesteps=1000, schedule="cosine", device=device), eta=eta, guided=guided, prediction=prediction, **thr)
+    return DDIMSampler(sch, eta=eta, guided=guided, prediction=prediction, **thr)
 
 
 def start_noise(indices: Sequence[int], size: int, seed: int | None, img_ch: int = 3) -> torch.Tensor | None:

@@ -24,6 +24,9 @@ at a time on one device:
 * ``--dynamic_threshold P [--threshold_max S]`` (off by default) replaces the static clamp of x0 by dynamic thresholding, per image and
   step ``s = min(max(quantile(|x0|, P), 1), S)``, ``x0 = clamp(x0, -s, s) / s`` (``DDIMSampler`` / ``DPMSolverSampler``
   ``dynamic_threshold=``); it composes with every flag above.
+* ``--guidance_rescale PHI`` (off by default; needs ``--cfg_scale`` other than 1) rescales the guided output towards the conditional
+  output's per-image standard deviation (Lin et al. 2023; the paper suggests 0.7), and ``--zero_snr`` (needs ``--prediction v``)
+  samples on the schedule rescaled to zero terminal SNR -- like ``--prediction``, it must match how the checkpoint was trained.
 """
 from __future__ import annotations
 
@@ -264,8 +267,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--device_noise", action="store_true",
                     help="with --seed: start noise and the --eta > 0 noise of record i come from the device generator keyed by seed + i "
                          "(no host draws, no upload; --eta > 0 then runs pipelined); another generator than --seed alone, so other numbers")
-    from ._common import add_threshold_flags
+    from ._common import add_threshold_flags, add_rescale_flags
     add_threshold_flags(ap)
+    add_rescale_flags(ap)
     ap.add_argument("--timing", action="store_true", help="print set-up and loop wall time (records/s of the loop) to stderr")
     ap.add_argument("--workers", type=int, default=None, help="host threads for decode / metrics (default: this rank's share of the CPUs, 2..16)")
     ap.add_argument("--force-process-group", action="store_true",
@@ -279,10 +283,11 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
-    from ._common import check_sampler_flags, check_noise_flags, check_threshold_flags
+    from ._common import check_sampler_flags, check_noise_flags, check_threshold_flags, check_rescale_flags
     check_sampler_flags(args.sampler, args.eta)                    # (before any rank is started)
     check_noise_flags(args.device_noise, args.seed)
     check_threshold_flags(args.dynamic_threshold, args.threshold_max)
+    check_rescale_flags(args.guidance_rescale, args.cfg_scale, args.zero_snr, args.prediction)
 
     from ..utils.launch import ensure_ranks, init_process_group, rank_env, single_rank_env
     if args.gpus is not None:
@@ -313,7 +318,8 @@ def main(argv=None) -> None:
     scale, zero = load_codec_meta(store_dir)
     net = build_model(args.weights, device, scale.shape[0], args.dtype)
     sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0, sampler=args.sampler, spacing=args.spacing,
-                            prediction=args.prediction, dynamic_threshold=args.dynamic_threshold, threshold_max=args.threshold_max)
+                            prediction=args.prediction, dynamic_threshold=args.dynamic_threshold, threshold_max=args.threshold_max,
+                            guidance_rescale=args.guidance_rescale, zero_snr=args.zero_snr)
 
     def reconstruct(z: np.ndarray, x_T: Optional[torch.Tensor], orig_u8: Optional[np.ndarray] = None, seeds=None):
         zt = torch.from_numpy(z).to(device)

@@ -8,7 +8,10 @@ never seeds), ``--dtype {fp32,bf16,f16x3}``, ``--cfg_scale`` (classifier-free gu
 (the second-order multistep solver of ``diffusion/dpm_solver.py``; default ``ddim``), ``--device_noise`` (with ``--seed``: the start
 noise and the ``--eta > 0`` noise come from the device generator keyed by the seed, nothing is drawn on the host or uploaded; another
 generator than ``--seed`` alone, so another image), ``--dynamic_threshold P [--threshold_max S]`` (dynamic thresholding of x0 instead
-of the static clamp, for guided sampling; off by default) and the architecture is read from the checkpoint's shapes.
+of the static clamp, for guided sampling; off by default), ``--guidance_rescale PHI`` (with ``--cfg_scale`` other than 1: the guided
+output rescaled towards the conditional output's per-image standard deviation, Lin et al. 2023; off by default), ``--zero_snr`` (with
+``--prediction v``: the schedule rescaled to zero terminal SNR, for a checkpoint trained on it) and the architecture is read from the
+checkpoint's shapes.
 """
 from __future__ import annotations
 
@@ -19,7 +22,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ._common import add_threshold_flags, check_noise_flags, check_sampler_flags, check_threshold_flags, pick_device, record_seeds, load_codec_meta, load_embedding, build_model, build_sampler, start_noise
+from ._common import add_rescale_flags, add_threshold_flags, check_rescale_flags, check_noise_flags, check_sampler_flags, check_threshold_flags, pick_device, record_seeds, load_codec_meta, load_embedding, build_model, build_sampler, start_noise
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -50,6 +53,7 @@ def build_parser() -> argparse.ArgumentParser:
                     help="timestep table of --sampler dpmpp2m (read only then): uniform in log-SNR (may merge into fewer than "
                          "--steps entries) or the reference's linspace")
     add_threshold_flags(ap)
+    add_rescale_flags(ap)
     return ap
 
 
@@ -58,13 +62,15 @@ def main(argv=None) -> None:
     check_sampler_flags(args.sampler, args.eta)
     check_noise_flags(args.device_noise, args.seed)
     check_threshold_flags(args.dynamic_threshold, args.threshold_max)
+    check_rescale_flags(args.guidance_rescale, args.cfg_scale, args.zero_snr, args.prediction)
 
     device = pick_device(args.device)
     scale, zero = load_codec_meta(Path(args.store_dir))
     z = torch.from_numpy(load_embedding(Path(args.bitstream), scale, zero)).to(device)
     net = build_model(args.weights, device, z.shape[1], args.dtype)
     sampler = build_sampler(args.eta, device, guided=args.cfg_scale != 1.0, sampler=args.sampler, spacing=args.spacing,
-                            prediction=args.prediction, dynamic_threshold=args.dynamic_threshold, threshold_max=args.threshold_max)
+                            prediction=args.prediction, dynamic_threshold=args.dynamic_threshold, threshold_max=args.threshold_max,
+                            guidance_rescale=args.guidance_rescale, zero_snr=args.zero_snr)
     x_T = None if args.device_noise else start_noise([0], args.size, args.seed)
     noise_kw = dict(seeds=record_seeds([0], args.seed)) if args.device_noise else {}
     with torch.no_grad():

@@ -33,6 +33,13 @@ seeds irrelevant; a wrong length is still a ``ValueError``.
 ``DPMSolverSampler(..., dynamic_threshold=p, threshold_max=s_max)`` (default None: unchanged): dynamic thresholding of x0 as in
 ``DDIMSampler`` -- ``s = min(max(quantile(|x0|, p), 1), s_max)`` per image and step, ``x0 = clamp(x0, -s, s) / s`` -- and the x0
 history holds the thresholded x0, so the second-order term differences what the solver actually used.
+
+``DPMSolverSampler(..., guided=True, guidance_rescale=phi)`` (default None: unchanged): the guidance rescale as in ``DDIMSampler`` --
+the combined output times ``phi std(y_c) / std(y) + 1 - phi`` per image and step, before x0 is formed.
+
+A scheduler made with ``rescale_zero_snr=True`` needs ``prediction="v"`` (``"eps"`` is a ``ValueError``).  ``lambda(T-1)`` is then
+``-inf``: the ``logsnr`` table places ``steps - 1`` targets between ``lambda(T-2)`` and ``lambda(0)`` and starts at ``T-1``; the step
+out of ``T-1`` has an infinite ``h``, so it and the step after it are first order.
 """
 from __future__ import annotations
 
@@ -50,8 +57,8 @@ class DPMSolverSampler:
 
     def __init__(self, scheduler, order: int = 2, spacing: str = "logsnr", guided: bool = False,
                  null_z: Optional[torch.Tensor] = None, prediction: str = "eps", dynamic_threshold: Optional[float] = None,
-                 threshold_max: Optional[float] = None) -> None:
-        sampling.set_options(self, prediction, dynamic_threshold, threshold_max)
+                 threshold_max: Optional[float] = None, guidance_rescale: Optional[float] = None) -> None:
+        sampling.set_options(self, prediction, dynamic_threshold, threshold_max, guidance_rescale, guided, scheduler)
         if order not in (1, 2):
             raise ValueError(f"order must be 1 or 2, got {order}")
         if spacing not in _SPACINGS:

@@ -1,5 +1,6 @@
-"""What ``DDIMSampler`` and ``DPMSolverSampler`` share: the constructor's checks of the parameterisation and the dynamic threshold, the
-start state, the keyword arguments of the fused route and the stepwise loop.  What differs stays in the two classes: the tables."""
+"""What ``DDIMSampler`` and ``DPMSolverSampler`` share: the constructor's checks of the parameterisation, the dynamic threshold, the
+guidance rescale and the schedule's terminal SNR, the start state, the keyword arguments of the fused route and the stepwise loop.
+What differs stays in the two classes: the tables."""
 from __future__ import annotations
 
 from typing import Optional
@@ -9,9 +10,19 @@ import torch
 from .. import _native
 
 
-def set_options(sampler, prediction: str, dynamic_threshold: Optional[float], threshold_max: Optional[float]) -> None:
-    """Check and keep ``prediction``, ``dynamic_threshold`` and ``threshold_max`` on ``sampler``; a bad one is a ``ValueError``."""
+def set_options(sampler, prediction: str, dynamic_threshold: Optional[float], threshold_max: Optional[float],
+                guidance_rescale: Optional[float] = None, guided: bool = False, scheduler=None) -> None:
+    """Check and keep ``prediction``, ``dynamic_threshold``, ``threshold_max`` and ``guidance_rescale`` on ``sampler``; a bad one is a
+    ``ValueError``, and so are a rescale on an unguided sampler and ``prediction="eps"`` on a zero-terminal-SNR ``scheduler``."""
     _native.prediction_code(prediction)  # ValueError for an unknown parameterisation
+    if prediction == "eps" and getattr(scheduler, "rescale_zero_snr", False):
+        raise ValueError('prediction="eps" with a rescale_zero_snr=True scheduler: the eps form divides by sqrt(alpha_bar_t), which is 0 '
+                         'at t = T-1; use prediction="v"')
+    if guidance_rescale is not None:
+        _native.rescale_arg(guidance_rescale)                        # ValueError for phi outside (0, 1]
+        if not guided:
+            raise ValueError("guidance_rescale needs guided=True: it rescales the guided combination")
+    sampler.guidance_rescale = guidance_rescale
     if dynamic_threshold is not None:
         _native.threshold_args(dynamic_threshold, threshold_max)     # ValueError for p outside (0, 1] or a maximum below 1
     elif threshold_max is not None:
@@ -34,6 +45,8 @@ def fused_kwargs(sampler, w: Optional[float], null_z: Optional[torch.Tensor], sl
     kw = dict(use_graph=sampler.use_graph, slot=slot)
     if w is not None:
         kw.update(guidance=w, null_z=null_z)
+        if sampler.guidance_rescale is not None:
+            kw["guidance_rescale"] = sampler.guidance_rescale
     if sampler.prediction != "eps":
         kw["prediction"] = sampler.prediction
     if sampler.dynamic_threshold is not None:
@@ -43,8 +56,9 @@ def fused_kwargs(sampler, w: Optional[float], null_z: Optional[torch.Tensor], sl
 
 def stepwise(sampler, model, x: torch.Tensor, z_clip: torch.Tensor, ts, coef, w: Optional[float], null_z: Optional[torch.Tensor],
              sigma=None, seeds: Optional[torch.Tensor] = None, multistep: bool = False) -> torch.Tensor:
-    """The loop for any callable ``model(x, z, t)``.  Per step: the model call (two when guided), the dynamic threshold if the
-    sampler has one, then one ``sampler_step`` on ``coef[i]`` -- with ``sigma[i] > 0`` it adds draw ``1 + i`` of the seeds or, unseeded,
+    """The loop for any callable ``model(x, z, t)``.  Per step: the model call (two when guided), the guidance-rescale factors if the
+    sampler has a rescale and the step is guided, the dynamic threshold if the sampler has one, then one ``sampler_step`` on
+    ``coef[i]`` -- with ``sigma[i] > 0`` it adds draw ``1 + i`` of the seeds or, unseeded,
     one ``torch.randn_like`` (drawn on those steps only); ``multistep``: with the x0 history."""
     x = _native.require_dev(x, "x_T").clone()
     B, device = x.shape[0], z_clip.device
@@ -57,13 +71,15 @@ def stepwise(sampler, model, x: torch.Tensor, z_clip: torch.Tensor, ts, coef, w:
         out = model(x, z_clip, t_b)
         out_u = model(x, z_u, t_b) if w is not None else None
         s = float(sigma[i]) if sigma is not None else 0.0
-        thr = None
+        thr = gscale = None
+        if sampler.guidance_rescale is not None and w is not None:
+            gscale = _native.guidance_rescale(out, out_u, w, sampler.guidance_rescale)
         if sampler.dynamic_threshold is not None:
             thr = _native.x0_threshold(x, out, coef[i, :2], sampler.prediction, sampler.dynamic_threshold, sampler.threshold_max, out_u=out_u,
-                                       w=w or 0.0)
+                                       w=w or 0.0, gscale=gscale)
         if s > 0 and seeds is not None:
             noise = dict(seeds=seeds, draw=1 + i)
         else:
             noise = dict(noise=torch.randn_like(x) if s > 0 else None)
-        _native.sampler_step(x, out, coef[i], sampler.prediction, out_u=out_u, w=w or 0.0, hist=hist, sigma=s, thr=thr, **noise)
+        _native.sampler_step(x, out, coef[i], sampler.prediction, out_u=out_u, w=w or 0.0, hist=hist, sigma=s, thr=thr, gscale=gscale, **noise)
     return x

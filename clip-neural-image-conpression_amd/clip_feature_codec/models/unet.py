@@ -166,7 +166,7 @@ class CLIPCondUNet(nn.Module):
                     use_graph: bool = True, slot: int = 0, sigma=None, noise: Optional[torch.Tensor] = None,
                     guidance: Optional[float] = None, null_z: Optional[torch.Tensor] = None, c4=None,
                     prediction: str = "eps", seeds: Optional[torch.Tensor] = None, dynamic_threshold: Optional[float] = None,
-                    threshold_max: Optional[float] = None) -> torch.Tensor:
+                    threshold_max: Optional[float] = None, guidance_rescale: Optional[float] = None) -> torch.Tensor:
         """All sampler steps inside the library (``NativeUNet.sample``; the ``ccn_sample*`` entries in include/ccn_hip.h).  ``slot``
         selects an independent workspace / captured graph, so that consecutive batches can be in flight on different streams.
         ``sigma`` / ``noise``: the eta > 0 loop.  ``guidance``: a classifier-free guidance scale; the loop then runs at batch 2B, the
@@ -176,13 +176,15 @@ class CLIPCondUNet(nn.Module):
         ``(B,)`` tensor instead of ``noise`` -- step ``i`` adds draw ``1 + i`` of each record, generated in the loop
         (``ccn_sample_seeded`` / ``ccn_sample_guided_seeded``).  ``dynamic_threshold`` (a quantile in (0, 1]; None: off) and
         ``threshold_max`` (None: unbounded): x0 is clamped to the record's own threshold on every step of whichever loop runs
-        (``ccn_set_dynamic_threshold``; DESIGN.md section 1, Thresholding)."""
+        (``ccn_set_dynamic_threshold``; DESIGN.md section 1, Thresholding).  ``guidance_rescale`` (phi in (0, 1]; None: off): with
+        ``guidance``, every step matches the per-image std of the combined output to the conditional one's
+        (``ccn_set_guidance_rescale``; DESIGN.md section 1, Guidance rescale)."""
         nat = self.native(x_T.device)
         nat.set_prediction(prediction)
         if c4 is not None:
             coef = np.concatenate([np.asarray(coef, np.float32).reshape(-1, 4), np.asarray(c4, np.float32).reshape(-1, 1)], axis=1)
         return nat.sample(z_clip, x_T, ts, coef, use_graph=use_graph, slot=slot, sigma=sigma, noise=noise, w=guidance, z_null=null_z,
-                          seeds=seeds, dynamic_threshold=dynamic_threshold, threshold_max=threshold_max)
+                          seeds=seeds, dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale)
 
     def read_activation(self, name: str, shape) -> torch.Tensor:
         return self.native().read_activation(name, tuple(shape))

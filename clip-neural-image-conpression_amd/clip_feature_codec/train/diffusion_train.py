@@ -538,6 +538,8 @@ def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[tor
     auxiliary gradient carries the factor ``s <= 1`` where the eps form has ``s/a`` (up to 6.4e4 on the cosine schedule); with both
     weights 0 it is the v-MSE step.  ``q_sample``, forward, backward, buckets, guard, EMA and ``z_drop`` are the same, and
     ``last_loss_terms`` is always filled (l1 and tv read 0 when their weights are 0).Sample such weights with ``DDIMSampler(..., prediction="v")``.
+    A zero-terminal-SNR scheduler (``NoiseScheduler(rescale_zero_snr=True)``) needs ``prediction="v"`` -- at ``t = T-1`` the target is
+    then ``-x0`` and ``x0_pred = -v_hat``, no division -- and is refused with ``"eps"``, whose ``x0_pred`` divides by ``a_t = 0``.
 
     ``z_drop`` (usually 0.1): ``z_dropout`` zeroes whole rows of ``z`` with that probability before the copy into the static buffer,
     which trains the unconditional branch that guided sampling needs.  Under data parallelism each rank draws its own mask.  With 0
@@ -564,6 +566,7 @@ def train_step(net, sch, opt, x0: torch.Tensor, z: torch.Tensor, t: Optional[tor
     for this step (7.98 vs 7.33 ms; 7.53 without the side-stream branch), hence off by default.  The returned loss is a view of a
     static buffer: read it before the next step."""
     v_pred = _native.prediction_code(prediction) == _native.PRED_V
+    check_zero_snr_prediction(getattr(sch, "rescale_zero_snr", False), prediction)
     state: TrainState = net.train_state()
     fp = state.fp
     fp.rebind_grads()
@@ -727,12 +730,28 @@ def check_resume_prediction(ck, prediction: str, resume="the resumed state") -> 
         raise ValueError(f"{resume} was trained with prediction={had!r}, this run asks for prediction={prediction!r}")
 
 
+def check_zero_snr_prediction(zero_snr: bool, prediction: str) -> None:
+    """A zero-terminal-SNR schedule has ``sqrt(alphas_cumprod[T-1]) == 0`` and the eps form divides by it: only ``prediction="v"``
+    trains on it; anything else is a ``ValueError`` naming both settings."""
+    if zero_snr and prediction != "v":
+        raise ValueError(f'zero_snr=True (a rescale_zero_snr scheduler) needs prediction="v", not prediction={prediction!r}: the eps form '
+                         'divides by sqrt(alpha_bar_t), which is 0 at t = T-1')
+
+
+def check_resume_zero_snr(ck, zero_snr: bool, resume="the resumed state") -> None:
+    """``train_state.pt`` records whether its weights were trained on the zero-terminal-SNR schedule (a file from before the option:
+    ``False``); continuing it on the other schedule is a ``ValueError`` naming both."""
+    had = bool(ck.get("zero_snr", False))
+    if had != bool(zero_snr):
+        raise ValueError(f"{resume} was trained with zero_snr={had}, this run asks for zero_snr={bool(zero_snr)}")
+
+
 def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size: int = 8, lr: float = 2e-4, timesteps: int = 1000,
                     schedule: str = "cosine", recon_w: float = 0.05, clip_w: float = 0.1, tv_w: float = 1e-4, device: str = "cuda",
                     save_dir=None, base: int = 128, ch_mult=(1, 2, 2), dtype: str = "bf16", num_workers: int = 2, log=print,
                     fused_objective: bool = True, grad_scaler: bool = False, max_grad_norm: Optional[float] = None,
                     ema_decay: Optional[float] = None, ema_warmup: bool = False, resume=None, z_drop: float = 0.0,
-                    prediction: str = "eps"):
+                    prediction: str = "eps", zero_snr: bool = False):
     """The reference's ``train_diffusion`` (same arguments, defaults, checkpoint names and log line) on the MI355X kernels.
 
     Per batch (train/diffusion_train.py:115-140): t ~ U{0..T-1}, noise ~ N, then ``train_step`` with the ``t`` / ``noise`` drawn here:
@@ -761,6 +780,11 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
     ``prediction="v"`` trains the v-parameterisation (``train_step``).  The checkpoints keep the reference's key set, so they do NOT
     say how they were trained: pass the same ``prediction`` to the samplers and the CLIs.  ``train_state.pt`` does record it, and
     ``resume=`` with another one is a ``ValueError`` naming both.
+
+    ``zero_snr=True`` trains on the schedule rescaled to zero terminal SNR (``NoiseScheduler(rescale_zero_snr=True)``), so that
+    ``t = T-1``, where every sampler starts, is pure noise in training too.  It needs ``prediction="v"`` (a ``ValueError`` otherwise).
+    Like ``prediction`` it is not in the checkpoints -- pass ``--zero_snr`` to the CLIs -- but ``train_state.pt`` records it and
+    ``resume=`` with the other value is a ``ValueError`` naming both (a file from before the option reads as ``False``).
     """
     import os
     from pathlib import Path
@@ -770,6 +794,7 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
     if not 0.0 <= z_drop <= 1.0:
         raise ValueError(f"z_drop must be in [0, 1], not {z_drop}")
     _native.prediction_code(prediction)
+    check_zero_snr_prediction(zero_snr, prediction)
     save_dir = Path(save_dir or store_dir)
     save_dir.mkdir(parents=True, exist_ok=True)
     ds = StoreDataset(store_dir, out_size=out_size)
@@ -784,13 +809,14 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
         from ..models.unet import infer_arch
         ck = torch.load(resume, map_location="cpu", weights_only=True)
         check_resume_prediction(ck, prediction, resume)
+        check_resume_zero_snr(ck, zero_snr, resume)
         if infer_arch(ck["net"]) != net.arch:
             raise ValueError(f"{resume} holds a model of architecture {infer_arch(ck['net'])}, this run builds {net.arch}")
         net.load_state_dict(ck["net"], strict=True)        # the optimiser's load_state_dict below refuses another parameter count
     if ddp:                                                    # same initial weights on every rank
         for p in net.parameters():
             dist.broadcast(p.data, src=0)
-    sch = NoiseScheduler(timesteps=timesteps, schedule=schedule, device=device)
+    sch = NoiseScheduler(timesteps=timesteps, schedule=schedule, device=device, rescale_zero_snr=zero_snr)
     net.train()
     state = net.train_state(device)
     # data parallel: finished ranges of the flat gradient buffer are all-reduced (RCCL) while the backward still runs
@@ -852,7 +878,8 @@ def train_diffusion(store_dir, out_size: int = 256, epochs: int = 40, batch_size
                 torch.save(opt.ema_state_dict(), save_dir / f"diffusion_unet_ep{ep + 1}_ema.pt")
             tmp_path = save_dir / "train_state.pt.tmp"
             torch.save(dict(epoch=ep + 1, net=net.state_dict(), opt=opt.state_dict(), scaler=None if scaler is None else scaler.state_dict(),
-                            rng_cpu=torch.get_rng_state(), rng_device=torch.cuda.get_rng_state(device), prediction=prediction), tmp_path)
+                            rng_cpu=torch.get_rng_state(), rng_device=torch.cuda.get_rng_state(device), prediction=prediction,
+                            zero_snr=bool(zero_snr)), tmp_path)
             os.replace(tmp_path, save_dir / "train_state.pt")
             log(f"[train] epoch {ep + 1}/{epochs} loss={running / max(seen, 1):.4f}")
             if skipped:

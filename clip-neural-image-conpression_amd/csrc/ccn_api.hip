@@ -184,6 +184,13 @@ struct SamplerRun {
     float thr_max = 0.f;
     float* thr = nullptr;
     void* thr_sel = nullptr;
+    // Guidance rescale (the handle's ccn_set_guidance_rescale when the run was built; rs_phi == 0: off or unguided, and the two
+    // fields below are null).  Every step then runs the two rescale launches after the network: they leave one factor per record in
+    // `gscale`, which the threshold launches (if any) and the sampler-step launch multiply the combined output by.  `gscale` and
+    // `rs_part` are parts of the handle's rescale scratch: captured by address.
+    double rs_phi = 0.0;
+    float* gscale = nullptr;
+    void* rs_part = nullptr;
 
     // Does a graph captured for `o` replay this run?  Every member a captured launch holds by value or by address, that is all but
     // z_null, the tables bit for bit.  No feature decides which members count: the ones a run does not use are normalised above.
@@ -194,7 +201,8 @@ struct SamplerRun {
         };
         return steps == o.steps && ts == o.ts && same(coef, o.coef) && same(sigma, o.sigma) && noise == o.noise && seeds == o.seeds &&
                guided == o.guided && w == o.w && out_scratch == o.out_scratch && same(c4, o.c4) && hist == o.hist && pred == o.pred &&
-               thr_p == o.thr_p && thr_max == o.thr_max && thr == o.thr && thr_sel == o.thr_sel;
+               thr_p == o.thr_p && thr_max == o.thr_max && thr == o.thr && thr_sel == o.thr_sel && rs_phi == o.rs_phi &&
+               gscale == o.gscale && rs_part == o.rs_part;
     }
 };
 
@@ -241,6 +249,9 @@ struct ccn_handle_s {
     float thr_max = 0.f;                                // 0: off
     char* thr_scratch = nullptr;                        // caller-owned: [raw output of one state | B thresholds | select state]
     size_t thr_scratch_bytes = 0;
+    double rs_phi = 0.0;                                // guidance rescale in the guided ccn_sample* loops (ccn_set_guidance_rescale); 0: off
+    char* rs_scratch = nullptr;                         // caller-owned: [B factors | the partial sums]
+    size_t rs_scratch_bytes = 0;
     std::vector<std::unique_ptr<ShapePlan>> shape_plans;   // of the committed model, one per (B, H, W, steps)
     std::vector<std::unique_ptr<Binding>> bindings;         // plan x workspace address, least recently used first
     hipStream_t cap_stream = nullptr;
@@ -927,12 +938,17 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, const SamplerRun
         if (r.guided) { u.x_dup = xstate + img; u.out_u = r.out_scratch + img; }
         for (int k = 0; k < 4; ++k) u.c[k] = cf[k];
         u.c[4] = c4; u.sigma = sigma; u.n = (int64_t)img;
-        u.seeds = seeds; u.draw = 1u + (uint32_t)i; u.per_record = (int64_t)h->cfg.img_ch * p.H * p.W; u.thr = r.thr;
+        u.seeds = seeds; u.draw = 1u + (uint32_t)i; u.per_record = (int64_t)h->cfg.img_ch * p.H * p.W; u.thr = r.thr; u.gscale = r.gscale;
+        // guidance rescale: the factor of every record, one read of both halves of the output scratch
+        if (r.rs_phi > 0.0)
+            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * 2, s, [&] {
+                    return launch_guidance_rescale(u.out_c, u.out_u, u.w, r.rs_phi, (int)(u.n / u.per_record), u.per_record, r.gscale, r.rs_part, s); }))
+                return rc;
         // the quantile of |x0| per record, on the combined output when guided: three select passes over the state and the output(s)
         if (thresholded)
             if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * 3 * (r.guided ? 3 : 2), s, [&] {
                     return launch_x0_threshold(u.x, u.out_c, u.out_u, u.pred, u.w, cf[0], cf[1], (int)(u.n / u.per_record), u.per_record, r.thr_p,
-                                               r.thr_max, r.thr, r.thr_sel, s); })) return rc;
+                                               r.thr_max, r.thr, r.thr_sel, s, r.gscale); })) return rc;
         if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * passes, s, [&] { return launch_sampler_step(u, s); })) return rc;
     }
     return CCN_OK;
@@ -1152,6 +1168,24 @@ int ccn_dynamic_threshold_scratch_bytes(ccn_handle_t h, int32_t B, int32_t H, in
     return CCN_OK;
 }
 
+// Guidance rescale is handle state likewise.  The scratch of ccn_set_guidance_rescale is the one of ccn_guidance_rescale: the B
+// factors first, then the partial sums.
+int ccn_set_guidance_rescale(ccn_handle_t h, double phi, void* scratch_dev, size_t scratch_bytes)
+{
+    // the arguments first (they can be judged without a handle), then the handle
+    if (!(phi >= 0.0 && phi <= 1.0)) return fail(CCN_EINVAL, "the rescale factor phi must be in [0, 1] (0: off)");
+    if (phi > 0.0) {
+        if (!scratch_dev || ((uintptr_t)scratch_dev & 15)) return fail(CCN_EINVAL, "the guidance-rescale scratch must be non-null and 16-byte aligned");
+        // the smallest shape there is (one record of two elements): a scratch below that fits no call
+        if (scratch_bytes < guidance_rescale_scratch_bytes(1, 2))
+            return fail(CCN_EINVAL, "the guidance-rescale scratch is too small (ccn_guidance_rescale_scratch_bytes)");
+    }
+    if (!h) return fail(CCN_EINVAL, "null handle");
+    if (phi == 0.0) { h->rs_phi = 0.0; h->rs_scratch = nullptr; h->rs_scratch_bytes = 0; return CCN_OK; }
+    h->rs_phi = phi; h->rs_scratch = (char*)scratch_dev; h->rs_scratch_bytes = scratch_bytes;
+    return CCN_OK;
+}
+
 int ccn_commit_params(ccn_handle_t h)
 {
     if (!h) return fail(CCN_EINVAL, "null handle");
@@ -1250,8 +1284,8 @@ int ccn_forward(ccn_handle_t h, const float* x_dev, const float* z_dev, const in
     return run_ops(h, b, s, c);
 }
 
-// (handle, descriptor, shape) -> the run: every check of the descriptor, the host tables copied, the handle's prediction and dynamic
-// threshold read -- here and nowhere else -- and every unused field at its fixed value (SamplerRun)
+// (handle, descriptor, shape) -> the run: every check of the descriptor, the host tables copied, the handle's prediction, dynamic
+// threshold and guidance rescale read -- here and nowhere else -- and every unused field at its fixed value (SamplerRun)
 static int build_run(ccn_handle_t h, const ccn_sampler_run_t* d, int32_t B, int32_t H, int32_t W, SamplerRun& r)
 {
     if (!d) return fail(CCN_EINVAL, "null sampler run descriptor");
@@ -1297,6 +1331,16 @@ static int build_run(ccn_handle_t h, const ccn_sampler_run_t* d, int32_t B, int3
         r.thr_p = h->thr_p; r.thr_max = h->thr_max;
         r.thr = (float*)(h->thr_scratch + l.thr); r.thr_sel = h->thr_scratch + l.sel;
         if (!r.out_scratch) r.out_scratch = (float*)h->thr_scratch;   // a run without a scratch of its own: the head of the handle's
+    }
+    if (h->rs_phi > 0.0 && guided) {                                // (an unguided run ignores it: there is nothing to match)
+        if (H <= 0 || W <= 0) return fail(CCN_EINVAL, "B, H, W must be positive");
+        if (B > 65535) return fail(CCN_EINVAL, "guidance rescale takes at most 65535 records: one grid row each");
+        const int64_t per = (int64_t)h->cfg.img_ch * H * W;
+        if (per < 2 || per >= kThrMaxPerRecord) return fail(CCN_EINVAL, "guidance rescale needs records of 2 to 2^34 - 1 elements");
+        const size_t need = guidance_rescale_scratch_bytes(B, per);
+        if (h->rs_scratch_bytes < need)
+            return fail(CCN_EINVAL, "the guidance-rescale scratch is too small for this shape: need " + std::to_string(need) + " bytes");
+        r.rs_phi = h->rs_phi; r.gscale = (float*)h->rs_scratch; r.rs_part = guidance_rescale_partials(h->rs_scratch, B);
     }
     return CCN_OK;
 }
@@ -1550,12 +1594,20 @@ int ccn_sampler_step_thr(float* x_dev, float* x_dup_dev, float* x0_hist_dev, con
                          const float* noise_dev, const uint64_t* seeds_dev, uint32_t draw, int64_t per_record, int32_t pred, float w,
                          const float* coef_host, float sigma, int64_t n, const float* thr_dev, void* stream)
 {
+    return ccn_sampler_step_rs(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, noise_dev, seeds_dev, draw, per_record, pred, w, coef_host,
+                               sigma, n, thr_dev, nullptr, stream);
+}
+
+int ccn_sampler_step_rs(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,
+                        const float* noise_dev, const uint64_t* seeds_dev, uint32_t draw, int64_t per_record, int32_t pred, float w,
+                        const float* coef_host, float sigma, int64_t n, const float* thr_dev, const float* gscale_dev, void* stream)
+{
     SamplerStep a;
     if (int rc = general_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, pred, w, coef_host, sigma, n, a)) return rc;
     if (noise_dev && seeds_dev) return fail(CCN_EINVAL, "noise_dev and seeds_dev exclude each other");
     if (seeds_dev && ((uintptr_t)seeds_dev & 7)) return fail(CCN_EINVAL, "the seeds must be 8-byte aligned");
     if (int rc = check_records(per_record, n)) return rc;
-    a.noise = noise_dev; a.seeds = seeds_dev; a.draw = draw; a.per_record = per_record; a.thr = thr_dev;
+    a.noise = noise_dev; a.seeds = seeds_dev; a.draw = draw; a.per_record = per_record; a.thr = thr_dev; a.gscale = gscale_dev;
     return enqueue_step(a, stream);
 }
 

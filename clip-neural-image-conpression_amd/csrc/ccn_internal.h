@@ -270,7 +270,8 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
 // out_c is the prediction itself; no hist: c4 is not applied and no history is written (hist is read only when c4 != 0).  `seeds`
 // (nullable; one uint64 per record of per_record elements, n a multiple of it) with sigma > 0: the noise is draw `draw` of each record,
 // generated in the kernel, and `noise` is not read.  `thr` (nullable; one float per record, per_record as above): the record's dynamic
-// threshold replaces the +-1 clamp of x0.  A caller fills the fields it uses; the rest stay absent.
+// threshold replaces the +-1 clamp of x0.  `gscale` (nullable; one float per record likewise): the record's guidance-rescale factor
+// multiplies the (combined) output before anything else reads it.  A caller fills the fields it uses; the rest stay absent.
 struct SamplerStep {
     float* x = nullptr;
     float* x_dup = nullptr;
@@ -287,6 +288,7 @@ struct SamplerStep {
     uint32_t draw = 0;
     int64_t per_record = 0;
     const float* thr = nullptr;
+    const float* gscale = nullptr;
 };
 hipError_t launch_sampler_step(const SamplerStep& a, hipStream_t s);
 // the dynamic threshold of every record (ccn_threshold.hip; ccn_x0_threshold in ccn_hip.h): thr[b] = min(max(Q_p(|x0_b|), 1), max_value)
@@ -295,7 +297,15 @@ hipError_t launch_sampler_step(const SamplerStep& a, hipStream_t s);
 constexpr int64_t kThrMaxPerRecord = (int64_t)1 << 34;
 size_t x0_threshold_scratch_bytes(int B);
 hipError_t launch_x0_threshold(const float* x, const float* out_c, const float* out_u, int pred, float w, float c0, float c1, int B, int64_t per,
-                               double p, float max_value, float* thr, void* scratch, hipStream_t s);
+                               double p, float max_value, float* thr, void* scratch, hipStream_t s, const float* gscale = nullptr);
+// the guidance-rescale factor of every record (ccn_rescale.hip; ccn_guidance_rescale in ccn_hip.h): k[b] = phi std(out_c[b]) / std(y[b])
+// + 1 - phi, y the combined output.  `partials`: guidance_rescale_partials(scratch, B) of a scratch of guidance_rescale_scratch_bytes
+// bytes (its head holds B floats: the factors of a caller that keeps them there), 16-byte aligned, any contents.  The caller has
+// checked the arguments (1 <= B <= 65535, 2 <= per < 2^34).  Two launches, nothing else.
+size_t guidance_rescale_scratch_bytes(int B, int64_t per);
+void* guidance_rescale_partials(void* scratch, int B);
+hipError_t launch_guidance_rescale(const float* out_c, const float* out_u, float w, double phi, int B, int64_t per, float* k, void* partials,
+                                   hipStream_t s);
 hipError_t launch_q_sample(float* out, const float* x0, const float* noise, const float* a, const float* sg,
                            int B, int64_t per, hipStream_t s);
 hipError_t launch_predict_x0(float* out, const float* xt, const float* eps, const float* a, const float* sg,

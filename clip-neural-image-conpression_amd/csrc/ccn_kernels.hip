@@ -823,24 +823,27 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
 // aligned and a lane's four elements are one quad of it.  The unseeded instantiations (gridDim.y == 1) are the kernel as it was.
 // THR: the same grid rows, and record b's dynamic threshold thr[b] replaces the +-1 clamp of x0 (sampler_update_thr; DESIGN.md
 // section 1, Thresholding); a noise tensor is then walked by record too.  Without THR nothing of it is compiled in.
-template <bool VEC, bool SEEDED, bool THR>
+// RS: the same grid rows, and record b's guidance-rescale factor gscale[b] multiplies y right after the combine (DESIGN.md section 1,
+// Guidance rescale): everything downstream -- the raw x0, e, the history -- is formed from k y.  Without RS nothing of it is compiled in.
+template <bool VEC, bool SEEDED, bool THR, bool RS>
 __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x_dup, float* __restrict__ hist, const float* __restrict__ out_c,
                                     const float* __restrict__ out_u, const float* __restrict__ noise, int pred, float w, float c0, float c1,
                                     float c2, float c3, float c4, float sigma, int64_t n, const uint64_t* __restrict__ seeds, uint32_t draw,
-                                    int64_t per, const float* __restrict__ thr)
+                                    int64_t per, const float* __restrict__ thr, const float* __restrict__ gscale)
 {
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     uint64_t seed = 0;
-    float s = 1.0f;
-    if constexpr (SEEDED || THR) {                                  // this record's slice of every tensor
+    float s = 1.0f, k = 1.0f;
+    if constexpr (SEEDED || THR || RS) {                            // this record's slice of every tensor
         const int64_t off = (int64_t)blockIdx.y * per;
         if constexpr (SEEDED) seed = seeds[blockIdx.y];
         if constexpr (THR) s = thr[blockIdx.y];
+        if constexpr (RS) k = gscale[blockIdx.y];
         x += off; out_c += off; n = per;
         if (x_dup) x_dup += off;
         if (hist) hist += off;
         if (out_u) out_u += off;
-        if constexpr (THR) { if (noise) noise += off; }
+        if constexpr (THR || RS) { if (noise) noise += off; }
     }
     const int64_t n4 = VEC ? n / 4 : 0;
     if (!hist) c4 = 0.f;
@@ -857,6 +860,7 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
             yv.x = __fadd_rn(uv.x, __fmul_rn(w, __fsub_rn(yv.x, uv.x))); yv.y = __fadd_rn(uv.y, __fmul_rn(w, __fsub_rn(yv.y, uv.y)));
             yv.z = __fadd_rn(uv.z, __fmul_rn(w, __fsub_rn(yv.z, uv.z))); yv.w = __fadd_rn(uv.w, __fmul_rn(w, __fsub_rn(yv.w, uv.w)));
         }
+        if constexpr (RS) { yv.x = __fmul_rn(k, yv.x); yv.y = __fmul_rn(k, yv.y); yv.z = __fmul_rn(k, yv.z); yv.w = __fmul_rn(k, yv.w); }
         float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), o, p;
         if (c4 != 0.f) hv = ((const float4*)hist)[q];
         o.x = update(xv.x, yv.x, hv.x, p.x);
@@ -877,6 +881,7 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
     for (int64_t i = n4 * 4 + tid; i < n; i += nthr) {
         float y = out_c[i];
         if (out_u) { const float u = out_u[i]; y = __fadd_rn(u, __fmul_rn(w, __fsub_rn(y, u))); }
+        if constexpr (RS) y = __fmul_rn(k, y);
         const float hv = c4 != 0.f ? hist[i] : 0.f;
         float p;
         float xn = update(x[i], y, hv, p);
@@ -887,15 +892,15 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         if (x_dup) x_dup[i] = xn;
     }
 }
-// seeds given and sigma > 0: the seeded form; thr given: the threshold form; either walks the state record by record, one grid row
-// each (the caller has checked per > 0 and n % per == 0).  With seeds `noise` is not read.
+// seeds given and sigma > 0: the seeded form; thr given: the threshold form; gscale given: the rescaled form; each walks the state
+// record by record, one grid row each (the caller has checked per > 0 and n % per == 0).  With seeds `noise` is not read.
 hipError_t launch_sampler_step(const SamplerStep& a, hipStream_t s)
 {
     const int64_t n = a.n, per = a.per_record;
-    const float* thr = a.thr;
+    const float *thr = a.thr, *gscale = a.gscale;
     const bool seeded = a.seeds && a.sigma > 0.f;
     const float* noise = seeded ? nullptr : a.noise;
-    const bool rowed = seeded || thr;
+    const bool rowed = seeded || thr || gscale;
     if (rowed && (per <= 0 || n % per || n / per > 65535)) return hipErrorInvalidValue;      // one grid row per record
     const bool vec = !(((uintptr_t)a.x | (uintptr_t)a.x_dup | (uintptr_t)a.hist | (uintptr_t)a.out_c | (uintptr_t)a.out_u | (uintptr_t)noise) & 15) &&
                      !(rowed && (per & 3));
@@ -903,11 +908,16 @@ hipError_t launch_sampler_step(const SamplerStep& a, hipStream_t s)
     const int64_t work = vec ? (row + 3) / 4 : row, blocks = (work + 255) / 256;
     const int gx = (int)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);        // 256 CUs x 8 blocks, grid-stride beyond
     const dim3 grid(gx, (unsigned)rows);
-#define CCN_STEP_ARGS a.x, a.x_dup, a.hist, a.out_c, a.out_u, noise, a.pred, a.w, a.c[0], a.c[1], a.c[2], a.c[3], a.c[4], a.sigma, n, a.seeds, a.draw, per, thr
+#define CCN_STEP_ARGS a.x, a.x_dup, a.hist, a.out_c, a.out_u, noise, a.pred, a.w, a.c[0], a.c[1], a.c[2], a.c[3], a.c[4], a.sigma, n, a.seeds, a.draw, per, thr, gscale
 #define CCN_STEP_GO(SEEDED, THR)                                                                                             \
     do {                                                                                                                     \
-        if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, SEEDED, THR>), grid, dim3(256), 0, s, CCN_STEP_ARGS);         \
-        else hipLaunchKernelGGL((sampler_step_kernel<false, SEEDED, THR>), grid, dim3(256), 0, s, CCN_STEP_ARGS);            \
+        if (gscale) {                                                                                                        \
+            if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, SEEDED, THR, true>), grid, dim3(256), 0, s, CCN_STEP_ARGS);   \
+            else hipLaunchKernelGGL((sampler_step_kernel<false, SEEDED, THR, true>), grid, dim3(256), 0, s, CCN_STEP_ARGS);      \
+        } else {                                                                                                             \
+            if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, SEEDED, THR, false>), grid, dim3(256), 0, s, CCN_STEP_ARGS);  \
+            else hipLaunchKernelGGL((sampler_step_kernel<false, SEEDED, THR, false>), grid, dim3(256), 0, s, CCN_STEP_ARGS);     \
+        }                                                                                                                    \
     } while (0)
     if (seeded && thr) CCN_STEP_GO(true, true);
     else if (seeded) CCN_STEP_GO(true, false);

@@ -9,7 +9,8 @@
 // looks for them), +inf is an ordinary largest value, -0 and +0 are one key, denormals keep their order.
 //
 // The raw x0 of an element is formed by raw_x0_p (ccn_device.h), the function the sampler update itself calls, after the same
-// guidance combine: the quantile is taken on the bits the update clamps.
+// guidance combine -- and, with `gscale`, after the multiplication by the record's guidance-rescale factor (ccn_rescale.hip): the
+// quantile is taken on the bits the update clamps.
 //
 // Launches (all on the caller's stream, nothing synchronises, nothing is allocated):
 //   thr_zero_kernel            zeroes the select state of the B records: any scratch contents are fine, every call starts from zero
@@ -51,6 +52,7 @@ struct ThrArgs {
     float frac, max_value;
     float* thr;
     char* scratch;
+    const float* gscale;               // nullable: the record's guidance-rescale factor multiplies the (combined) output first
 };
 
 __global__ __launch_bounds__(256) void thr_zero_kernel(uint4* __restrict__ p, long long n16)
@@ -145,8 +147,11 @@ __global__ __launch_bounds__(256) void thr_pass_kernel(ThrArgs a)
     const float* yc = a.yc + off;
     const float* yu = a.yu ? a.yu + off : nullptr;
     const uint32_t pre0 = pre[0], pre1 = pre[1];
+    const bool rs = a.gscale != nullptr;
+    const float gk = rs ? a.gscale[b] : 1.0f;
     auto count = [&](float xv, float yv, float uv) {
         if (yu) yv = __fadd_rn(uv, __fmul_rn(a.w, __fsub_rn(yv, uv)));
+        if (rs) yv = __fmul_rn(gk, yv);
         const uint32_t key = __float_as_uint(raw_x0_p(a.pred, xv, yv, a.c0, a.c1)) & 0x7fffffffu;
         if (PASS == 0) atomicAdd(&lh[key >> SH], 1u);
         else {
@@ -195,7 +200,7 @@ __global__ __launch_bounds__(256) void thr_final_kernel(ThrArgs a)
 size_t x0_threshold_scratch_bytes(int B) { return (size_t)(B > 0 ? B : 0) * kRecBytes; }
 
 hipError_t launch_x0_threshold(const float* x, const float* out_c, const float* out_u, int pred, float w, float c0, float c1, int B, int64_t per,
-                               double p, float max_value, float* thr, void* scratch, hipStream_t s)
+                               double p, float max_value, float* thr, void* scratch, hipStream_t s, const float* gscale)
 {
     if (B <= 0 || B > 65535 || per <= 0 || per >= kThrMaxPerRecord || !(p >= 0.0 && p <= 1.0)) return hipErrorInvalidValue;
     ThrArgs a;
@@ -206,7 +211,7 @@ hipError_t launch_x0_threshold(const float* x, const float* out_c, const float* 
     a.k0 = (unsigned long long)kf;
     a.k1 = a.k0 + 1 < (unsigned long long)per ? a.k0 + 1 : (unsigned long long)per - 1;
     a.frac = (float)(pos - kf);
-    a.max_value = max_value; a.thr = thr; a.scratch = (char*)scratch;
+    a.max_value = max_value; a.thr = thr; a.scratch = (char*)scratch; a.gscale = gscale;
 
     const bool vec = !(((uintptr_t)x | (uintptr_t)out_c | (uintptr_t)out_u) & 15) && !(per & 3);
     // about four workgroups per CU over the batch, never more than the record has work for; a workgroup's LDS counts are 32-bit,
@@ -248,6 +253,14 @@ int ccn_x0_threshold(const float* x_dev, const float* out_c_dev, const float* ou
                      int32_t B, int64_t per_record, double p, float max_value, float* thr_dev, void* scratch_dev, size_t scratch_bytes,
                      void* stream)
 {
+    return ccn_x0_threshold_rs(x_dev, out_c_dev, out_u_dev, pred, w, c0, c1, B, per_record, p, max_value, thr_dev, scratch_dev, scratch_bytes,
+                               nullptr, stream);
+}
+
+int ccn_x0_threshold_rs(const float* x_dev, const float* out_c_dev, const float* out_u_dev, int32_t pred, float w, float c0, float c1,
+                        int32_t B, int64_t per_record, double p, float max_value, float* thr_dev, void* scratch_dev, size_t scratch_bytes,
+                        const float* gscale_dev, void* stream)
+{
     if (!x_dev || !out_c_dev || !thr_dev) return tfail(CCN_EINVAL, "a tensor pointer is NULL");
     if (pred != CCN_PRED_EPS && pred != CCN_PRED_V) return tfail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
     if (B <= 0 || B > 65535) return tfail(CCN_EINVAL, "B must be in [1, 65535]: one grid row per record");
@@ -258,7 +271,7 @@ int ccn_x0_threshold(const float* x_dev, const float* out_c_dev, const float* ou
     if (scratch_bytes < x0_threshold_scratch_bytes(B))
         return tfail(CCN_EINVAL, "the scratch is too small: need " + std::to_string(x0_threshold_scratch_bytes(B)) + " bytes");
     if (launch_x0_threshold(x_dev, out_c_dev, out_u_dev, pred, w, c0, c1, B, per_record, p, max_value, thr_dev, scratch_dev,
-                            (hipStream_t)stream) != hipSuccess)
+                            (hipStream_t)stream, gscale_dev) != hipSuccess)
         return tfail(CCN_EHIP, "x0_threshold launch failed");
     return CCN_OK;
 }

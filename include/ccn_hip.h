@@ -337,6 +337,67 @@ int ccn_sampler_step_thr(float* x_dev, float* x_dup_dev, float* x0_hist_dev,
 int ccn_set_dynamic_threshold(ccn_handle_t h, double p, float max_value, void* scratch_dev, size_t scratch_bytes);
 int ccn_dynamic_threshold_scratch_bytes(ccn_handle_t h, int32_t B, int32_t H, int32_t W, size_t* bytes);
 
+/* ---- guidance rescale -------------------------------------------------------------------------------------------------------------- *
+ * (No reference counterpart.  Lin et al. 2023, Common Diffusion Noise Schedules and Sample Steps are Flawed, section 3.4; diffusers'
+ * guidance_rescale.)  Under guidance the combined output has a much larger per-image standard deviation than anything the network
+ * emits; the rescale matches it to the conditional output's.  Per record b of per_record elements and per step, with y_c the
+ * conditional output, y = y_u + w (y_c - y_u) the combined one (the three separately rounded fp32 ops of ccn_sampler_step) and phi
+ * in (0, 1]:
+ *     std_c = std(y_c[b]),  std_cfg = std(y[b])          unbiased (n - 1), over the whole record
+ *     k_b   = phi * std_c / std_cfg + (1 - phi)           double arithmetic, rounded ONCE to fp32
+ *     y'    = k_b * y                                      one fp32 multiplication per element
+ * and y' replaces y everywhere downstream: in the raw x0 of either parameterisation, in e (eps form: e = y'), in the dynamic
+ * threshold's quantile and, through x0, in the multistep history.  (diffusers' phi (y r) + (1 - phi) y up to rounding; the single
+ * factor is the format here.)  The sums S(y_c), S(y_c^2), S(y), S(y^2) are accumulated in double -- the square of an fp32 value is exact
+ * there -- and the variance is (S(v^2) - S(v)^2 / n) / (n - 1), clamped at 0.  std_cfg == 0 gives k_b = 1 (nothing to rescale: a
+ * zero-initialised head).  A NaN or an inf anywhere in a record makes that record's k_b NaN and with it its update; other records
+ * are unaffected.
+ * The order of summation is a function of (j, per_record) only -- not of B, of the record's position, of pointer alignment or of the
+ * load width: with gx = clamp(ceil(per_record / 4096), 1, 64), quad q = j >> 2 of the record belongs to thread q mod (256 gx) of the
+ * record's gx workgroups of 256, which adds its quads in increasing q and a quad's elements in increasing j; the 64 lanes of a wave
+ * combine by an xor-shuffle tree (32, 16, .., 1), the 4 waves of a workgroup in index order, the gx workgroups in index order.  So k_b
+ * is reproducible bit for bit (16-byte loads when both pointers are 16-byte aligned and per_record % 4 == 0, 4-byte loads otherwise).
+ *
+ * ccn_guidance_rescale: k_dev[b] = k_b, b < B.  scratch_dev: ccn_guidance_rescale_scratch_bytes bytes -- room for B factors first
+ * (16-byte aligned; the handle state below keeps its factors there), then the workgroups' partial sums -- 16-byte aligned,
+ * caller-owned, any contents (every slot read is written by the same call; two calls in flight need two scratches).  Two small launches
+ * on `stream`: no floating-point atomics, no memset, never synchronises, allocates nothing, capturable.
+ * CCN_EINVAL: a NULL tensor (out_u_dev included), a non-finite w, phi outside [0, 1] or NaN, B outside [1, 65535], per_record outside
+ * [2, 2^34), a NULL, misaligned or short scratch. */
+int ccn_guidance_rescale_scratch_bytes(int32_t B, int64_t per_record, size_t* bytes);
+int ccn_guidance_rescale(const float* out_c_dev, const float* out_u_dev, float w, double phi,
+                         int32_t B, int64_t per_record, float* k_dev,
+                         void* scratch_dev, size_t scratch_bytes, void* stream);
+
+/* ccn_x0_threshold plus gscale_dev (B floats, read when the kernels run): the quantile is taken on the x0 formed from k_b * y, the
+ * bits the rescaled update clamps.  gscale_dev NULL: ccn_x0_threshold, bit for bit. */
+int ccn_x0_threshold_rs(const float* x_dev, const float* out_c_dev, const float* out_u_dev,
+                        int32_t pred, float w, float c0, float c1,
+                        int32_t B, int64_t per_record, double p, float max_value,
+                        float* thr_dev, void* scratch_dev, size_t scratch_bytes,
+                        const float* gscale_dev, void* stream);
+
+/* ccn_sampler_step_thr plus gscale_dev (one float per record): record b multiplies its (combined) output by gscale_dev[b] right
+ * after the combine, and the state is walked record by record like the seeded and threshold forms.  gscale_dev NULL:
+ * ccn_sampler_step_thr, bit for bit.  CCN_EINVAL: as for that entry. */
+int ccn_sampler_step_rs(float* x_dev, float* x_dup_dev, float* x0_hist_dev,
+                        const float* out_c_dev, const float* out_u_dev,
+                        const float* noise_dev, const uint64_t* seeds_dev, uint32_t draw,
+                        int64_t per_record, int32_t pred, float w,
+                        const float* coef_host /* [5] */, float sigma, int64_t n,
+                        const float* thr_dev, const float* gscale_dev, void* stream);
+
+/* Handle state, exactly like ccn_set_dynamic_threshold: read by every ccn_sample* entry when it enqueues or captures, and part of
+ * every captured graph's cache key (phi and the two scratch addresses), so toggling finds each mode's own graph on a shared workspace
+ * and a run with phi == 0 replays the graph it had.  phi == 0: off (the default; scratch_dev may be NULL).  With phi in (0, 1] every
+ * step of every GUIDED loop runs, after the network: ccn_guidance_rescale's two launches, the threshold launches (if a dynamic
+ * threshold is set) with the factors, one ccn_sampler_step_rs launch.  An unguided run ignores it.  scratch_dev:
+ * ccn_guidance_rescale_scratch_bytes(B, img_ch*H*W) bytes for the largest shape sampled with it (B images), 16-byte aligned, owned by
+ * the caller and kept at its address while a graph captured with it is cached.  ccn_workspace_bytes is unchanged.
+ * CCN_EINVAL: phi outside [0, 1] or NaN; with phi > 0 a NULL, misaligned or short scratch (a scratch too small for the shape of a
+ * later guided ccn_sample* call is that call's CCN_EINVAL, as are more than 65535 images or C*H*W outside [2, 2^34)). */
+int ccn_set_guidance_rescale(ccn_handle_t h, double phi, void* scratch_dev, size_t scratch_bytes);
+
 /* ---- the sampler loop, described by one record ------------------------------------------------------------------------------------ *
  * Everything a run of the loop is a function of besides the handle (its prediction and dynamic threshold are read like by every
  * other ccn_sample* entry), the tensors and the shape.  ccn_sample, ccn_sample_eta, ccn_sample_guided, ccn_sample_seeded,
