@@ -68,6 +68,13 @@ SIGNATURES = {
     "ccn_sampler_step_rs": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_i64, c_i32, c_f32, ctypes.POINTER(c_f32), c_f32, c_i64,
                                     c_vp, c_vp, c_vp]),
     "ccn_set_guidance_rescale": (c_i32, [c_vp, ctypes.c_double, c_vp, c_sz]),
+    "ccn_block_mean": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "ccn_lowres_delta": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp, c_vp,
+                                 c_vp]),
+    "ccn_sampler_step_lr": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_i64, c_i32, c_f32, ctypes.POINTER(c_f32), c_f32, c_i64,
+                                    c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "ccn_set_lowres_guide": (c_i32, [c_vp, c_vp, c_i32, c_f32, c_i32, c_vp, c_sz]),
+    "ccn_lowres_guide_scratch_bytes": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
     "ccn_sample_run": (c_i32, [c_vp, ctypes.POINTER(CcnSamplerRun), c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp, c_i32]),
     "ccn_workspace_bytes": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
     "ccn_release_workspace": (c_i32, [c_vp, c_vp]),
@@ -227,6 +234,9 @@ class Workspace:
         self.thr: Dict[int, torch.Tensor] = {}
         # NativeUNet.sample with guidance rescale: the handle's rescale scratch (ccn_set_guidance_rescale), likewise
         self.rs: Dict[int, torch.Tensor] = {}
+        # NativeUNet.sample with a low-resolution guide: per (image count, N) the persistent guide buffer the caller's thumbnails are
+        # copied into and the handle's guide scratch (ccn_set_lowres_guide), likewise kept: the captured graph holds both addresses
+        self.lr: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
 
     def history(self, like: torch.Tensor) -> torch.Tensor:
         """The kept x0 history of ``like``'s size (allocated on first use; never freed before the workspace, so that a captured
@@ -339,7 +349,8 @@ class NativeUNet:
     def sample(self, z: torch.Tensor, x_T: torch.Tensor, ts, coef, use_graph: bool = True, slot: int = 0, sigma=None,
                noise: Optional[torch.Tensor] = None, w: Optional[float] = None, z_null: Optional[torch.Tensor] = None,
                hist: Optional[torch.Tensor] = None, seeds=None, dynamic_threshold: Optional[float] = None,
-               threshold_max: Optional[float] = None, guidance_rescale: Optional[float] = None) -> torch.Tensor:
+               threshold_max: Optional[float] = None, guidance_rescale: Optional[float] = None, guide: Optional[torch.Tensor] = None,
+               guide_strength: float = 1.0, guide_t_min: int = 0) -> torch.Tensor:
         """Every step of a sampler inside the library, through ``ccn_sample_run``.  ``coef`` of ``(steps, 4)``: the
         DDIM loop; ``sigma`` (steps,) + ``noise`` (steps, B, C, H, W) fp32 on the device make it the eta > 0 one.  ``coef`` of
         ``(steps, 5)``: the multistep loop (``NoiseScheduler.solver_coefficients``; deterministic), ``hist`` its x0 history, fp32 of
@@ -355,7 +366,11 @@ class NativeUNet:
         bound): every step of whichever loop runs clamps x0 to the record's own threshold (ccn_set_dynamic_threshold); the scratch is
         kept with the workspace.  ``guidance_rescale`` (phi in (0, 1]; None: off, the handle state is cleared): every step of a
         guided loop multiplies the combined output by the record's ``phi std(y_c) / std(y) + 1 - phi`` (ccn_set_guidance_rescale);
-        the scratch is kept with the workspace likewise, and an unguided run ignores it."""
+        the scratch is kept with the workspace likewise, and an unguided run ignores it.  ``guide`` (``(B, C, H/N, W/N)`` fp32, a
+        thumbnail per image with values in [-1, 1]; None: off, the handle state is cleared) with ``guide_strength`` (lambda in (0, 1])
+        and ``guide_t_min``: every step with ``ts[i] >= guide_t_min`` moves each N x N block mean of x0 towards the guide
+        (ccn_set_lowres_guide; DESIGN.md section 1, Low-resolution guide); the guide is copied, in stream order, into a buffer kept
+        with the workspace -- like the seeds, so other thumbnails replay the same graph -- and so is the scratch."""
         import math
         import numpy as np
         z = require_dev(z, "z_clip"); x_T = require_dev(x_T, "x_T")
@@ -421,6 +436,18 @@ class NativeUNet:
             if B not in ws.rs:
                 ws.rs[B] = torch.empty(guidance_rescale_scratch_bytes(B, C * H * W), dtype=torch.uint8, device=self.device)
             check(self.lib.ccn_set_guidance_rescale(self.h, phi, ws.rs[B].data_ptr(), ws.rs[B].numel()))
+        if guide is None:
+            check(self.lib.ccn_set_lowres_guide(self.h, None, 0, 0.0, 0, None, 0))
+        else:
+            N, lam, t_min = guide_args(guide, (B, C, H, W), guide_strength, guide_t_min)
+            if (B, N) not in ws.lr:
+                n = c_sz()
+                check(self.lib.ccn_lowres_guide_scratch_bytes(self.h, B, H, W, N, ctypes.byref(n)))
+                ws.lr[(B, N)] = (torch.empty((B, C, H // N, W // N), dtype=torch.float32, device=self.device),
+                                 torch.empty(n.value, dtype=torch.uint8, device=self.device))
+            gbuf, gscr = ws.lr[(B, N)]
+            gbuf.copy_(guide)                         # on the current stream, in front of the launch
+            check(self.lib.ccn_set_lowres_guide(self.h, gbuf.data_ptr(), N, lam, t_min, gscr.data_ptr(), gscr.numel()))
         # the run as the library takes it (ccn_sampler_run_t): an absent feature stays NULL / 0
         run = CcnSamplerRun(size=ctypes.sizeof(CcnSamplerRun), steps=steps, ts_host=ts.ctypes.data, coef_host=coef.ctypes.data,
                             coef_cols=coef.shape[1], x0_hist_dev=ptr(hist))
@@ -902,7 +929,7 @@ def normal_fill(seeds, shape, draw: int = 0, out: Optional[torch.Tensor] = None,
 def sampler_step(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], prediction: str = "eps", out_u: Optional[torch.Tensor] = None,
                  w: float = 0.0, hist: Optional[torch.Tensor] = None, sigma: float = 0.0, noise: Optional[torch.Tensor] = None,
                  x_dup: Optional[torch.Tensor] = None, seeds=None, draw: int = 0, thr: Optional[torch.Tensor] = None,
-                 gscale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 gscale: Optional[torch.Tensor] = None, delta: Optional[torch.Tensor] = None, factor: Optional[int] = None) -> torch.Tensor:
     """One in-place sampler update of ``x`` for either parameterisation (ccn_sampler_step): ``out_c`` is the network output
     (``prediction`` says whether it is eps or v), ``out_u`` the unconditional one of a guided step (the update then acts on
     ``out_u + w * (out_c - out_u)``), ``coef`` = (c0, c1, c2, c3[, c4]), ``hist`` the multistep sampler's x0 history (read when
@@ -911,7 +938,9 @@ def sampler_step(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], pr
     bits as ``noise=normal_fill(seeds, x.shape, draw)``.  ``thr`` (``(B,)`` fp32, ``x0_threshold``'s result): record ``b`` clamps its
     x0 to ``[-thr[b], thr[b]]`` and divides by it instead of clamping to +-1 (ccn_sampler_step_thr; with noise or with seeds).
     ``gscale`` (``(B,)`` fp32, ``guidance_rescale``'s result): record ``b`` multiplies its (combined) output by ``gscale[b]`` before
-    anything else reads it (ccn_sampler_step_rs)."""
+    anything else reads it (ccn_sampler_step_rs).  ``delta`` (``lowres_delta``'s result for the same state, ``(B, C, H/N, W/N)``) with
+    ``factor`` = N (None: inferred from the shapes): ``x`` must be ``(B, C, H, W)``, and every element adds its block's ``delta`` to the
+    clamped x0 (ccn_sampler_step_lr)."""
     lib = load_library()
     pred = prediction_code(prediction)
     x = require_dev(x, "x"); out_c = require_dev(out_c, "out_c")
@@ -941,6 +970,18 @@ def sampler_step(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], pr
         gscale = require_dev(gscale, "gscale")
         if x.dim() < 1 or gscale.numel() != x.shape[0]:
             raise ValueError("gscale must hold one factor per record of x, (B,)")
+    if delta is not None:
+        delta = require_dev(delta, "delta")
+        if x.dim() != 4:
+            raise ValueError("delta needs x of shape (B, C, H, W)")
+        N = guide_factor(delta, tuple(x.shape), factor, "delta")
+        B, C, H, W = x.shape
+        with torch.cuda.device(x.device):
+            check(lib.ccn_sampler_step_lr(x.data_ptr(), ptr(x_dup), ptr(hist), out_c.data_ptr(), ptr(out_u), ptr(nz), ptr(sd), int(draw),
+                                          x.numel() // x.shape[0], pred, float(w), c5, float(sigma), x.numel(), ptr(thr), ptr(gscale),
+                                          C, H, W, N, delta.data_ptr(), current_stream(x.device)))
+        return x
+    if gscale is not None:
         with torch.cuda.device(x.device):
             check(lib.ccn_sampler_step_rs(x.data_ptr(), ptr(x_dup), ptr(hist), out_c.data_ptr(), ptr(out_u), ptr(nz), ptr(sd), int(draw),
                                           x.numel() // x.shape[0], pred, float(w), c5, float(sigma), x.numel(), ptr(thr), gscale.data_ptr(),
@@ -1059,6 +1100,91 @@ def guidance_rescale_scratch_bytes(B: int, per_record: int) -> int:
     n = c_sz()
     check(load_library().ccn_guidance_rescale_scratch_bytes(int(B), int(per_record), ctypes.byref(n)))
     return int(n.value)
+
+
+def guide_factor(guide, shape, factor: Optional[int] = None, name: str = "guide") -> int:
+    """The block size N of a ``(B, C, H/N, W/N)`` table against a ``(B, C, H, W)`` state, checked: a power of two in 2..64 that divides
+    H and W, the same along both axes (and ``factor`` if given); anything else is a ``ValueError``."""
+    B, C, H, W = (int(v) for v in shape)
+    g = tuple(int(v) for v in guide.shape)
+    if len(g) != 4 or g[:2] != (B, C) or g[2] < 1 or g[3] < 1 or H % g[2] or W % g[3] or H // g[2] != W // g[3]:
+        raise ValueError(f"{name} must be ({B}, {C}, {H}/N, {W}/N) for one block size N, got {g}")
+    N = H // g[2]
+    if factor is not None and int(factor) != N:
+        raise ValueError(f"{name} of shape {g} means N = {N}, not factor = {factor}")
+    if N < 2 or N > 64 or N & (N - 1):
+        raise ValueError(f"the block size must be a power of two in 2..64, got {N}")
+    return N
+
+
+def guide_args(guide, shape, strength, t_min) -> Tuple[int, float, int]:
+    """(N, lambda, t_min) of a low-resolution guide as the C ABI takes them, checked: ``guide_factor``'s shape rules, ``strength`` in (0, 1], ``t_min >= 0``; anything else is a ``ValueError``."""
+    if not isinstance(guide, torch.Tensor):
+        raise ValueError("guide must be a tensor")
+    N = guide_factor(guide, shape)
+    lam = float(strength)
+    if not 0.0 < lam <= 1.0:
+        raise ValueError(f"guide_strength must be in (0, 1], got {strength}")
+    if int(t_min) != t_min or int(t_min) < 0:
+        raise ValueError(f"guide_t_min must be a non-negative integer, got {t_min}")
+    return N, lam, int(t_min)
+
+
+def block_mean(x: torch.Tensor, factor: int) -> torch.Tensor:
+    """The N x N block means of ``clamp(x, -1, 1)`` (ccn_block_mean; N = ``factor``): ``(..., H/N, W/N)`` fp32 from ``(..., H, W)``, the
+    fixed-point mean the low-resolution guide is held against -- the guide of an original, or the thumbnail of a result."""
+    lib = load_library()
+    x = require_dev(x, "x")
+    if x.dim() < 2:
+        raise ValueError("x must be (..., H, W)")
+    H, W, N = int(x.shape[-2]), int(x.shape[-1]), int(factor)
+    if N < 2 or N > 64 or N & (N - 1) or H % N or W % N:
+        raise ValueError(f"factor must be a power of two in 2..64 that divides H = {H} and W = {W}, got {factor}")
+    planes = x.numel() // (H * W)
+    if planes < 1:
+        raise ValueError("x holds no plane")
+    out = torch.empty(tuple(x.shape[:-2]) + (H // N, W // N), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib.ccn_block_mean(x.data_ptr(), planes, H, W, N, out.data_ptr(), current_stream(x.device)))
+    return out
+
+
+def lowres_delta(x: torch.Tensor, out_c: torch.Tensor, coef: Sequence[float], guide: torch.Tensor, strength: float = 1.0,
+                 prediction: str = "eps", out_u: Optional[torch.Tensor] = None, w: float = 0.0, thr: Optional[torch.Tensor] = None,
+                 gscale: Optional[torch.Tensor] = None, factor: Optional[int] = None) -> torch.Tensor:
+    """The low-resolution guide's correction of every block (ccn_lowres_delta; DESIGN.md section 1, Low-resolution guide): a
+    ``(B, C, H/N, W/N)`` fp32 tensor ``strength * (guide - block mean of x0)`` with x0 formed from ``x`` ``(B, C, H, W)``, ``out_c``
+    (``out_u``, ``w``, ``gscale``, ``thr``) and ``coef[:2]`` exactly as ``sampler_step`` forms and clamps it -- pass the result as its
+    ``delta=``."""
+    lib = load_library()
+    pred = prediction_code(prediction)
+    x = require_dev(x, "x"); out_c = require_dev(out_c, "out_c")
+    if x.dim() != 4 or out_c.numel() != x.numel():
+        raise ValueError("x must be (B, C, H, W) and out_c must hold as many elements")
+    N, lam, _ = guide_args(guide, tuple(x.shape), strength, 0)
+    guide = require_dev(guide, "guide")
+    if factor is not None:
+        guide_factor(guide, tuple(x.shape), factor)
+    B, C, H, W = x.shape
+    if out_u is not None:
+        out_u = require_dev(out_u, "out_u")
+        if out_u.numel() != x.numel():
+            raise ValueError("out_u must hold as many elements as x")
+    if thr is not None:
+        thr = require_dev(thr, "thr")
+    if gscale is not None:
+        gscale = require_dev(gscale, "gscale")
+    for t, name in ((thr, "thr"), (gscale, "gscale")):
+        if t is not None and t.numel() != B:
+            raise ValueError(f"{name} must hold one value per record of x, (B,)")
+    c = [float(v) for v in coef]
+    if len(c) < 2:
+        raise ValueError("coef must hold at least c0, c1")
+    d = torch.empty(tuple(guide.shape), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib.ccn_lowres_delta(x.data_ptr(), out_c.data_ptr(), ptr(out_u), pred, float(w), c[0], c[1], B, C, H, W, N, guide.data_ptr(), lam,
+                                   ptr(thr), ptr(gscale), d.data_ptr(), current_stream(x.device)))
+    return d
 
 
 def _per_sample(fn_name: str, a0: torch.Tensor, a1: torch.Tensor, ca: torch.Tensor, cs: torch.Tensor, out=None) -> torch.Tensor:

@@ -102,6 +102,85 @@ def check_rescale_flags(guidance_rescale: float | None, cfg_scale: float, zero_s
         raise SystemExit("--zero_snr needs --prediction v: the eps form divides by sqrt(alpha_bar_t), which is 0 at t = T-1")
 
 
+def add_guide_flags(ap, source: str) -> None:
+    """``--lowres_guide`` with ``--guide_strength`` and ``--guide_t_min`` (both CLIs), the low-resolution guide; off by default.
+    ``source="original"`` (eval): the value is the block size N and the thumbnail is derived from the record's original, with
+    ``--guide_bits``; ``source="file"`` (reconstruct_diffusion): the value is the thumbnail's file."""
+    if source == "original":
+        ap.add_argument("--lowres_guide", type=int, default=None, metavar="N",
+                        help="hold every step's x0 to a thumbnail of the original (ILVR / DDNM in x0 space): the N x N block means of the "
+                             "original, quantised to --guide_bits, are what a codec would send next to the embedding "
+                             "(side_bytes_per_record in --out_json); N a power of two in 2..64 that divides --size; off by default")
+        ap.add_argument("--guide_bits", type=int, default=8, metavar="BITS",
+                        help="with --lowres_guide: levels per thumbnail value, 2^BITS over [-1, 1]; 1..8 (default 8: uint8)")
+    else:
+        ap.add_argument("--lowres_guide", type=str, default=None, metavar="FILE",
+                        help="hold every step's x0 to this thumbnail (ILVR / DDNM in x0 space): an image that PIL opens, or a uint8 .npy of "
+                             "shape (h, w, 3); it must be square and --size / h a power of two in 2..64; off by default")
+    ap.add_argument("--guide_strength", type=float, default=None, metavar="L",
+                    help="with --lowres_guide: the fraction of the block-mean error removed per step, in (0, 1] (default 1)")
+    ap.add_argument("--guide_t_min", type=int, default=None, metavar="T",
+                    help="with --lowres_guide: only the steps at timestep T or above are guided (default 0: all)")
+
+
+def check_guide_flags(lowres_guide, guide_strength: float | None, guide_t_min: int | None, size: int, guide_bits: int | None = None) -> None:
+    """Both CLIs call this right after parsing: the strength in (0, 1], ``T >= 0``, ``BITS`` in 1..8, none of them without
+    ``--lowres_guide``; an integer N (eval) must be a power of two in 2..64 that divides ``--size``."""
+    if lowres_guide is None:
+        if guide_strength is not None or guide_t_min is not None or guide_bits not in (None, 8):
+            raise SystemExit("--guide_strength, --guide_t_min and --guide_bits need --lowres_guide")
+        return
+    if guide_strength is not None and not 0.0 < guide_strength <= 1.0:
+        raise SystemExit("--guide_strength (with --lowres_guide) must be in (0, 1]")
+    if guide_t_min is not None and guide_t_min < 0:
+        raise SystemExit("--guide_t_min (with --lowres_guide) must not be negative")
+    if guide_bits is not None and not 1 <= guide_bits <= 8:
+        raise SystemExit("--guide_bits (with --lowres_guide) must be in 1..8")
+    if isinstance(lowres_guide, int):
+        check_guide_factor(size, lowres_guide)
+
+
+def check_guide_factor(size: int, n: int) -> None:
+    if n < 2 or n > 64 or n & (n - 1) or size % n:
+        raise SystemExit(f"--lowres_guide: the block size must be a power of two in 2..64 that divides --size {size}, got {n}")
+
+
+def derive_guide(orig: np.ndarray, n: int, bits: int = 8) -> np.ndarray:
+    """The thumbnail a codec would send for ``orig`` -- ``(C, H, W)``, float in [-1, 1] or the uint8 form of it (``v / 127.5 - 1``) --
+    as the decoder uses it: the float64 ``n x n`` block means, quantised to ``2^bits`` levels over [-1, 1] (8: the uint8 levels) and
+    mapped back, ``(C, H/n, W/n)`` float32."""
+    v = np.asarray(orig)
+    v = v.astype(np.float64) / 127.5 - 1.0 if v.dtype == np.uint8 else v.astype(np.float64)
+    c, h, w = v.shape
+    m = v.reshape(c, h // n, n, w // n, n).mean(axis=(2, 4))
+    top = float(2 ** bits - 1)
+    q = np.clip(np.rint((m + 1.0) * 0.5 * top), 0.0, top)
+    return (q / top * 2.0 - 1.0).astype(np.float32)
+
+
+def guide_side_bytes(size: int, n: int, bits: int = 8, channels: int = 3) -> int:
+    """Bytes of one record's thumbnail: ``channels (size / n)^2`` values of ``bits`` bits, rounded up."""
+    return (channels * (size // n) ** 2 * bits + 7) // 8
+
+
+def load_guide_file(path: str, size: int) -> np.ndarray:
+    """``--lowres_guide FILE`` of reconstruct_diffusion: an image that PIL opens (read as RGB) or a uint8 ``.npy`` of shape
+    ``(h, w, 3)``, as ``(1, 3, h, w)`` float32 in [-1, 1] (``v / 127.5 - 1``).  ``N = size / h``: a size that does not divide, a
+    thumbnail that is not square or an N that is no power of two in 2..64 is refused."""
+    if str(path).endswith(".npy"):
+        a = np.load(path)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise SystemExit(f"--lowres_guide: {path} must hold a uint8 array of shape (h, w, 3), got {a.dtype} {a.shape}")
+    else:
+        from PIL import Image
+        a = np.array(Image.open(path).convert("RGB"))
+    h, w = a.shape[:2]
+    if h != w or h < 1 or size % h:
+        raise SystemExit(f"--lowres_guide: a {h} x {w} thumbnail does not divide --size {size} into square blocks")
+    check_guide_factor(size, size // h)
+    return (a.astype(np.float32) / np.float32(127.5) - np.float32(1.0)).transpose(2, 0, 1)[None].copy()
+
+
 def record_seeds(indices: Sequence[int], seed: int) -> list:
     """The 64-bit seeds of ``--device_noise``: record ``i`` of the manifest gets ``seed + i``, the rule of ``start_noise``."""
     return [int(seed) + int(i) for i in indices]

@@ -27,6 +27,9 @@ at a time on one device:
 * ``--guidance_rescale PHI`` (off by default; needs ``--cfg_scale`` other than 1) rescales the guided output towards the conditional
   output's per-image standard deviation (Lin et al. 2023; the paper suggests 0.7), and ``--zero_snr`` (needs ``--prediction v``)
   samples on the schedule rescaled to zero terminal SNR -- like ``--prediction``, it must match how the checkpoint was trained.
+* ``--lowres_guide N [--guide_strength L] [--guide_t_min T] [--guide_bits 8]`` (off by default) holds every step's x0 to a thumbnail of
+  the record's original -- its N x N block means in float64, quantised to ``2^BITS`` levels: what a codec would send next to the
+  embedding -- and every record of ``--out_json`` then carries ``side_bytes_per_record``, the thumbnail's size.
 """
 from __future__ import annotations
 
@@ -154,7 +157,8 @@ class DeviceScorer:
 def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstruct: Callable, size: int, batch: int,
              seed: Optional[int], rank: int, world: int, device: str, start_noise_fn: Callable, submit: Optional[Callable] = None,
              fetch: Optional[Callable] = None, workers: Optional[int] = None, u8: bool = False, marks: Optional[list] = None,
-             device_metrics: bool = False, learned: bool = False, device_noise: bool = False) -> np.ndarray:
+             device_metrics: bool = False, learned: bool = False, device_noise: bool = False,
+             guide_fn: Optional[Callable] = None) -> np.ndarray:
     """Shard, reconstruct in batches, score on the host, gather.  ``reconstruct(z, x_T) -> (b,3,S,S)`` numpy in [-1,1].
 
     With ``submit(z, x_T, slot) -> handle`` / ``fetch(handle) -> numpy`` (the GPU path) two batches are kept in flight: batch k+1 is
@@ -171,7 +175,11 @@ def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstru
     those two columns -- else ``None``, and no worker thread scores anything.
 
     ``device_noise`` (with a ``seed``): no start noise is drawn here -- ``x_T`` is None and ``submit`` / ``reconstruct`` get the batch's
-    record seeds, ``seeds=[seed + i, ...]``, as a keyword."""
+    record seeds, ``seeds=[seed + i, ...]``, as a keyword.
+
+    ``guide_fn(orig) -> (3, s, s)`` (``--lowres_guide``): every record's thumbnail is derived on the pool from the original the batch
+    loads anyway (float or uint8, whichever this run scores on), and ``submit`` / ``reconstruct`` get the batch's, ``guide=`` of
+    ``(b, 3, s, s)``, as a keyword."""
     from ._common import record_seeds
     mine = shard_indices(len(manifest), rank, world)
     nw = workers or default_workers(world)
@@ -182,6 +190,12 @@ def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstru
         def prepare(idx):
             """Futures of one batch's inputs: originals (float or uint8), z rows, start-noise rows (None when unseeded)."""
             load = original_u8 if u8 or device_metrics else load_original
+            p = prepare_inputs(idx, load)
+            # (a guide future waits for an original's future that was queued before it: the pool is first in, first out)
+            p["guide"] = None if guide_fn is None else [pool.submit(lambda of: guide_fn(of.result()), o) for o in p["orig"]]
+            return p
+
+        def prepare_inputs(idx, load):
             return dict(idx=idx,
                         origf=[pool.submit(load_original, manifest[i]["image"], size) for i in idx] if device_metrics and learned else None,
                         orig=[pool.submit(load, manifest[i]["image"], size) for i in idx],
@@ -223,6 +237,8 @@ def evaluate(manifest: List[dict], z_of: Callable[[dict], np.ndarray], reconstru
             # (device_metrics: the originals were decoded while the previous batch was sampled)
             extra = (np.stack([f.result() for f in cur["orig"]], 0),) if device_metrics else ()
             kw = dict(seeds=record_seeds(cur["idx"], seed)) if device_noise else {}
+            if cur["guide"] is not None:
+                kw["guide"] = np.stack([f.result() for f in cur["guide"]], 0)
             if submit is not None and fetch is not None:
                 handle = submit(z, x_T, bi & 1, *extra, **kw)
                 if pending is not None:
@@ -267,9 +283,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--device_noise", action="store_true",
                     help="with --seed: start noise and the --eta > 0 noise of record i come from the device generator keyed by seed + i "
                          "(no host draws, no upload; --eta > 0 then runs pipelined); another generator than --seed alone, so other numbers")
-    from ._common import add_threshold_flags, add_rescale_flags
+    from ._common import add_threshold_flags, add_rescale_flags, add_guide_flags
     add_threshold_flags(ap)
     add_rescale_flags(ap)
+    add_guide_flags(ap, "original")
     ap.add_argument("--timing", action="store_true", help="print set-up and loop wall time (records/s of the loop) to stderr")
     ap.add_argument("--workers", type=int, default=None, help="host threads for decode / metrics (default: this rank's share of the CPUs, 2..16)")
     ap.add_argument("--force-process-group", action="store_true",
@@ -283,11 +300,12 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
-    from ._common import check_sampler_flags, check_noise_flags, check_threshold_flags, check_rescale_flags
+    from ._common import check_sampler_flags, check_noise_flags, check_threshold_flags, check_rescale_flags, check_guide_flags
     check_sampler_flags(args.sampler, args.eta)                    # (before any rank is started)
     check_noise_flags(args.device_noise, args.seed)
     check_threshold_flags(args.dynamic_threshold, args.threshold_max)
     check_rescale_flags(args.guidance_rescale, args.cfg_scale, args.zero_snr, args.prediction)
+    check_guide_flags(args.lowres_guide, args.guide_strength, args.guide_t_min, args.size, args.guide_bits)
 
     from ..utils.launch import ensure_ranks, init_process_group, rank_env, single_rank_env
     if args.gpus is not None:
@@ -321,9 +339,17 @@ def main(argv=None) -> None:
                             prediction=args.prediction, dynamic_threshold=args.dynamic_threshold, threshold_max=args.threshold_max,
                             guidance_rescale=args.guidance_rescale, zero_snr=args.zero_snr)
 
-    def reconstruct(z: np.ndarray, x_T: Optional[torch.Tensor], orig_u8: Optional[np.ndarray] = None, seeds=None):
+    def guide_kwargs(guide: Optional[np.ndarray]) -> dict:
+        """``--lowres_guide``: the batch's thumbnails with the strength and the first guided timestep, as ``sampler.sample`` takes them."""
+        if guide is None:
+            return {}
+        return dict(guide=torch.from_numpy(guide), guide_strength=1.0 if args.guide_strength is None else args.guide_strength,
+                    guide_t_min=args.guide_t_min or 0)
+
+    def reconstruct(z: np.ndarray, x_T: Optional[torch.Tensor], orig_u8: Optional[np.ndarray] = None, seeds=None, guide=None):
         zt = torch.from_numpy(z).to(device)
         noise_kw = {} if seeds is None else dict(seeds=seeds)      # --device_noise
+        noise_kw.update(guide_kwargs(guide))
         with torch.no_grad():
             x = sampler.sample(net, zt, shape=(zt.shape[0], 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale,
                                x_T=None if x_T is None else x_T.to(device), **noise_kw)
@@ -344,10 +370,11 @@ def main(argv=None) -> None:
     u8 = not learned_metrics_available()
     scorer = DeviceScorer(device, args.batch, 3, args.size) if args.device_metrics else None
 
-    def submit(z: np.ndarray, x_T: Optional[torch.Tensor], slot: int, orig_u8: Optional[np.ndarray] = None, seeds=None):
+    def submit(z: np.ndarray, x_T: Optional[torch.Tensor], slot: int, orig_u8: Optional[np.ndarray] = None, seeds=None, guide=None):
         zt = torch.from_numpy(z).to(device)
         xt = None if x_T is None else x_T.to(device)
         noise_kw = {} if seeds is None else dict(seeds=seeds)      # --device_noise
+        noise_kw.update(guide_kwargs(guide))
         st = streams[slot]
         st.wait_stream(torch.cuda.current_stream(device))
         with torch.no_grad(), torch.cuda.stream(st):
@@ -387,10 +414,15 @@ def main(argv=None) -> None:
     pipelined = args.eta == 0 or args.device_noise
     t_loop = time.perf_counter()
     marks: list = []
+    guide_fn = None
+    if args.lowres_guide is not None:
+        from ._common import derive_guide
+        guide_fn = lambda orig: derive_guide(orig, args.lowres_guide, args.guide_bits)   # noqa: E731
     rows = evaluate(manifest, lambda rec: load_embedding(Path(rec["bitstream"]), scale, zero), reconstruct,
                     args.size, args.batch, args.seed, rank, world, device, start_noise,
                     submit if pipelined else None, fetch if pipelined else None, workers=args.workers, u8=u8 and pipelined,
-                    marks=marks, device_metrics=args.device_metrics, learned=args.device_metrics and not u8, device_noise=args.device_noise)
+                    marks=marks, device_metrics=args.device_metrics, learned=args.device_metrics and not u8, device_noise=args.device_noise,
+                    guide_fn=guide_fn)
     if args.timing and rank == 0:
         t_end = time.perf_counter()
         print(f"[eval] set-up {t_loop - t_start:.2f} s (checkpoint load + weight repack), loop {t_end - t_loop:.2f} s for {len(manifest)} records = "
@@ -407,6 +439,10 @@ def main(argv=None) -> None:
         if args.out_json:
             recs = [dict(image=manifest[i]["image"], **{k: float(rows[i, j]) for j, k in enumerate(METRIC_KEYS)})
                     for i in range(len(manifest))]
+            if args.lowres_guide is not None:                      # what the thumbnail adds to the record's bitstream
+                from ._common import guide_side_bytes
+                for rec in recs:
+                    rec["side_bytes_per_record"] = guide_side_bytes(args.size, args.lowres_guide, args.guide_bits)
             with open(args.out_json, "w", encoding="utf-8") as f:
                 json.dump(recs, f, ensure_ascii=False, indent=2)
     if use_pg:

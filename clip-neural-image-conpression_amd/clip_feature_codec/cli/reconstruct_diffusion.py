@@ -10,8 +10,10 @@ noise and the ``--eta > 0`` noise come from the device generator keyed by the se
 generator than ``--seed`` alone, so another image), ``--dynamic_threshold P [--threshold_max S]`` (dynamic thresholding of x0 instead
 of the static clamp, for guided sampling; off by default), ``--guidance_rescale PHI`` (with ``--cfg_scale`` other than 1: the guided
 output rescaled towards the conditional output's per-image standard deviation, Lin et al. 2023; off by default), ``--zero_snr`` (with
-``--prediction v``: the schedule rescaled to zero terminal SNR, for a checkpoint trained on it) and the architecture is read from the
-checkpoint's shapes.
+``--prediction v``: the schedule rescaled to zero terminal SNR, for a checkpoint trained on it), ``--lowres_guide FILE
+[--guide_strength L] [--guide_t_min T]`` (a thumbnail that travels next to the bitstream -- an image or a uint8 ``.npy`` of shape
+``(h, w, 3)``, ``N = size / h`` -- to which every step's x0 is held block mean by block mean; off by default) and the architecture is
+read from the checkpoint's shapes.
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ._common import add_rescale_flags, add_threshold_flags, check_rescale_flags, check_noise_flags, check_sampler_flags, check_threshold_flags, pick_device, record_seeds, load_codec_meta, load_embedding, build_model, build_sampler, start_noise
+from ._common import add_guide_flags, check_guide_flags, load_guide_file, add_rescale_flags, add_threshold_flags, check_rescale_flags, check_noise_flags, check_sampler_flags, check_threshold_flags, pick_device, record_seeds, load_codec_meta, load_embedding, build_model, build_sampler, start_noise
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -54,6 +56,7 @@ def build_parser() -> argparse.ArgumentParser:
                          "--steps entries) or the reference's linspace")
     add_threshold_flags(ap)
     add_rescale_flags(ap)
+    add_guide_flags(ap, "file")
     return ap
 
 
@@ -63,6 +66,11 @@ def main(argv=None) -> None:
     check_noise_flags(args.device_noise, args.seed)
     check_threshold_flags(args.dynamic_threshold, args.threshold_max)
     check_rescale_flags(args.guidance_rescale, args.cfg_scale, args.zero_snr, args.prediction)
+    check_guide_flags(args.lowres_guide, args.guide_strength, args.guide_t_min, args.size)
+    guide_kw = {}
+    if args.lowres_guide is not None:                              # (read before the device is touched: a bad file exits here)
+        guide_kw = dict(guide=torch.from_numpy(load_guide_file(args.lowres_guide, args.size)),
+                        guide_strength=1.0 if args.guide_strength is None else args.guide_strength, guide_t_min=args.guide_t_min or 0)
 
     device = pick_device(args.device)
     scale, zero = load_codec_meta(Path(args.store_dir))
@@ -75,7 +83,7 @@ def main(argv=None) -> None:
     noise_kw = dict(seeds=record_seeds([0], args.seed)) if args.device_noise else {}
     with torch.no_grad():
         x = sampler.sample(net, z, shape=(1, 3, args.size, args.size), steps=args.steps, cfg_scale=args.cfg_scale,
-                           x_T=None if x_T is None else x_T.to(device), **noise_kw)
+                           x_T=None if x_T is None else x_T.to(device), **noise_kw, **guide_kw)
     img = x[0].clamp(-1, 1).cpu().numpy().transpose(1, 2, 0)
     Image.fromarray(((img + 1.0) * 127.5).astype(np.uint8)).save(args.out)
     print(f"Saved to {args.out}")

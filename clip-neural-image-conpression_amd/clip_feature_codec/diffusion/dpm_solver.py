@@ -40,6 +40,10 @@ the combined output times ``phi std(y_c) / std(y) + 1 - phi`` per image and step
 A scheduler made with ``rescale_zero_snr=True`` needs ``prediction="v"`` (``"eps"`` is a ``ValueError``).  ``lambda(T-1)`` is then
 ``-inf``: the ``logsnr`` table places ``steps - 1`` targets between ``lambda(T-2)`` and ``lambda(0)`` and starts at ``T-1``; the step
 out of ``T-1`` has an infinite ``h``, so it and the step after it are first order.
+
+``sample(..., guide=g, guide_strength=1.0, guide_t_min=0)`` (default None: unchanged): the low-resolution guide as in ``DDIMSampler``
+-- every N x N block of the clamped x0 shifted by ``guide_strength * (g - block mean)`` on the steps with ``ts[i] >= guide_t_min`` --
+and the x0 history holds the shifted x0.
 """
 from __future__ import annotations
 
@@ -79,13 +83,15 @@ class DPMSolverSampler:
 
     @torch.no_grad()
     def sample(self, model, z_clip: torch.Tensor, shape: tuple, steps: int = 20, cfg_scale: float = 1.0,
-               x_T: Optional[torch.Tensor] = None, slot: int = 0, seeds=None) -> torch.Tensor:
+               x_T: Optional[torch.Tensor] = None, slot: int = 0, seeds=None, guide: Optional[torch.Tensor] = None,
+               guide_strength: float = 1.0, guide_t_min: int = 0) -> torch.Tensor:
         ts, coef = self.tables(steps)
         w, null_z = guidance.resolve(self.guided, self.null_z, z_clip, cfg_scale)
         device = z_clip.device
         if device.type != "cuda":
             raise RuntimeError(f"z_clip is on {device}: DPMSolverSampler (MI355X build) needs a HIP device; no CPU fallback")
         seeds, x = sampling.start_state(shape, device, x_T, seeds)
+        guide = sampling.guide_options(guide, shape, guide_strength, guide_t_min, device)
         if hasattr(model, "sample_ddim"):
-            return model.sample_ddim(z_clip, x, ts, coef[:, :4], c4=coef[:, 4], **sampling.fused_kwargs(self, w, null_z, slot))
-        return sampling.stepwise(self, model, x, z_clip, ts, coef, w, null_z, multistep=True)
+            return model.sample_ddim(z_clip, x, ts, coef[:, :4], c4=coef[:, 4], **sampling.fused_kwargs(self, w, null_z, slot, guide))
+        return sampling.stepwise(self, model, x, z_clip, ts, coef, w, null_z, multistep=True, guide=guide)

@@ -1,5 +1,6 @@
 """What ``DDIMSampler`` and ``DPMSolverSampler`` share: the constructor's checks of the parameterisation, the dynamic threshold, the
-guidance rescale and the schedule's terminal SNR, the start state, the keyword arguments of the fused route and the stepwise loop.
+guidance rescale and the schedule's terminal SNR, the start state, the low-resolution guide's arguments, the keyword arguments of the
+fused route and the stepwise loop.
 What differs stays in the two classes: the tables."""
 from __future__ import annotations
 
@@ -40,9 +41,24 @@ def start_state(shape: tuple, device, x_T: Optional[torch.Tensor], seeds):
     return None, (torch.randn(shape, device=device) if x_T is None else x_T.to(device))
 
 
-def fused_kwargs(sampler, w: Optional[float], null_z: Optional[torch.Tensor], slot: int) -> dict:
-    """The keyword arguments of ``model.sample_ddim`` that do not depend on the tables."""
+def guide_options(guide, shape: tuple, guide_strength: float, guide_t_min: int, device) -> Optional[dict]:
+    """The low-resolution guide of one ``sample`` call, checked: None without a guide, else ``dict(guide=, guide_strength=,
+    guide_t_min=)`` with the guide as a contiguous fp32 tensor on ``device``.  ``guide`` is ``(B, C, H/N, W/N)`` against ``shape`` =
+    ``(B, C, H, W)``: N is inferred, and must be a power of two in 2..64 that divides H and W; ``guide_strength`` in (0, 1];
+    ``guide_t_min >= 0``; anything else is a ``ValueError``."""
+    if guide is None:
+        return None
+    if not isinstance(guide, torch.Tensor):
+        guide = torch.as_tensor(guide)
+    _, lam, t_min = _native.guide_args(guide, tuple(shape), guide_strength, guide_t_min)
+    return dict(guide=guide.to(device=device, dtype=torch.float32).contiguous(), guide_strength=lam, guide_t_min=t_min)
+
+
+def fused_kwargs(sampler, w: Optional[float], null_z: Optional[torch.Tensor], slot: int, guide: Optional[dict] = None) -> dict:
+    """The keyword arguments of ``model.sample_ddim`` that do not depend on the tables (``guide``: ``guide_options``' result)."""
     kw = dict(use_graph=sampler.use_graph, slot=slot)
+    if guide is not None:
+        kw.update(guide)
     if w is not None:
         kw.update(guidance=w, null_z=null_z)
         if sampler.guidance_rescale is not None:
@@ -55,9 +71,10 @@ def fused_kwargs(sampler, w: Optional[float], null_z: Optional[torch.Tensor], sl
 
 
 def stepwise(sampler, model, x: torch.Tensor, z_clip: torch.Tensor, ts, coef, w: Optional[float], null_z: Optional[torch.Tensor],
-             sigma=None, seeds: Optional[torch.Tensor] = None, multistep: bool = False) -> torch.Tensor:
+             sigma=None, seeds: Optional[torch.Tensor] = None, multistep: bool = False, guide: Optional[dict] = None) -> torch.Tensor:
     """The loop for any callable ``model(x, z, t)``.  Per step: the model call (two when guided), the guidance-rescale factors if the
-    sampler has a rescale and the step is guided, the dynamic threshold if the sampler has one, then one ``sampler_step`` on
+    sampler has a rescale and the step is guided, the dynamic threshold if the sampler has one, the low-resolution guide's
+    ``lowres_delta`` if ``guide`` (``guide_options``' result) is given and ``ts[i] >= guide_t_min``, then one ``sampler_step`` on
     ``coef[i]`` -- with ``sigma[i] > 0`` it adds draw ``1 + i`` of the seeds or, unseeded,
     one ``torch.randn_like`` (drawn on those steps only); ``multistep``: with the x0 history."""
     x = _native.require_dev(x, "x_T").clone()
@@ -77,9 +94,14 @@ def stepwise(sampler, model, x: torch.Tensor, z_clip: torch.Tensor, ts, coef, w:
         if sampler.dynamic_threshold is not None:
             thr = _native.x0_threshold(x, out, coef[i, :2], sampler.prediction, sampler.dynamic_threshold, sampler.threshold_max, out_u=out_u,
                                        w=w or 0.0, gscale=gscale)
+        delta = None
+        if guide is not None and int(ts[i]) >= guide["guide_t_min"]:
+            delta = _native.lowres_delta(x, out, coef[i, :2], guide["guide"], guide["guide_strength"], sampler.prediction, out_u=out_u,
+                                         w=w or 0.0, thr=thr, gscale=gscale)
         if s > 0 and seeds is not None:
             noise = dict(seeds=seeds, draw=1 + i)
         else:
             noise = dict(noise=torch.randn_like(x) if s > 0 else None)
-        _native.sampler_step(x, out, coef[i], sampler.prediction, out_u=out_u, w=w or 0.0, hist=hist, sigma=s, thr=thr, gscale=gscale, **noise)
+        _native.sampler_step(x, out, coef[i], sampler.prediction, out_u=out_u, w=w or 0.0, hist=hist, sigma=s, thr=thr, gscale=gscale, delta=delta,
+                             **noise)
     return x

@@ -166,7 +166,8 @@ class CLIPCondUNet(nn.Module):
                     use_graph: bool = True, slot: int = 0, sigma=None, noise: Optional[torch.Tensor] = None,
                     guidance: Optional[float] = None, null_z: Optional[torch.Tensor] = None, c4=None,
                     prediction: str = "eps", seeds: Optional[torch.Tensor] = None, dynamic_threshold: Optional[float] = None,
-                    threshold_max: Optional[float] = None, guidance_rescale: Optional[float] = None) -> torch.Tensor:
+                    threshold_max: Optional[float] = None, guidance_rescale: Optional[float] = None,
+                    guide: Optional[torch.Tensor] = None, guide_strength: float = 1.0, guide_t_min: int = 0) -> torch.Tensor:
         """All sampler steps inside the library (``NativeUNet.sample``; the ``ccn_sample*`` entries in include/ccn_hip.h).  ``slot``
         selects an independent workspace / captured graph, so that consecutive batches can be in flight on different streams.
         ``sigma`` / ``noise``: the eta > 0 loop.  ``guidance``: a classifier-free guidance scale; the loop then runs at batch 2B, the
@@ -178,13 +179,17 @@ class CLIPCondUNet(nn.Module):
         ``threshold_max`` (None: unbounded): x0 is clamped to the record's own threshold on every step of whichever loop runs
         (``ccn_set_dynamic_threshold``; DESIGN.md section 1, Thresholding).  ``guidance_rescale`` (phi in (0, 1]; None: off): with
         ``guidance``, every step matches the per-image std of the combined output to the conditional one's
-        (``ccn_set_guidance_rescale``; DESIGN.md section 1, Guidance rescale)."""
+        (``ccn_set_guidance_rescale``; DESIGN.md section 1, Guidance rescale).  ``guide`` (a thumbnail per image, ``(B, C, H/N, W/N)``
+        in [-1, 1]; None: off), ``guide_strength`` (in (0, 1]) and ``guide_t_min``: on the steps with ``ts[i] >= guide_t_min`` every
+        N x N block mean of x0 is moved towards the guide (``ccn_set_lowres_guide``; DESIGN.md section 1, Low-resolution guide); a
+        guide buffer and a scratch are kept per slot and the guide is copied into the buffer, so other thumbnails replay the graph."""
         nat = self.native(x_T.device)
         nat.set_prediction(prediction)
         if c4 is not None:
             coef = np.concatenate([np.asarray(coef, np.float32).reshape(-1, 4), np.asarray(c4, np.float32).reshape(-1, 1)], axis=1)
         return nat.sample(z_clip, x_T, ts, coef, use_graph=use_graph, slot=slot, sigma=sigma, noise=noise, w=guidance, z_null=null_z,
-                          seeds=seeds, dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale)
+                          seeds=seeds, dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale,
+                          guide=guide, guide_strength=guide_strength, guide_t_min=guide_t_min)
 
     def read_activation(self, name: str, shape) -> torch.Tensor:
         return self.native().read_activation(name, tuple(shape))

@@ -191,6 +191,15 @@ struct SamplerRun {
     double rs_phi = 0.0;
     float* gscale = nullptr;
     void* rs_part = nullptr;
+    // The low-resolution guide (the handle's ccn_set_lowres_guide when the run was built; lr_N == 0: off, and the fields below are
+    // zero).  A step with ts[i] >= lr_tmin takes the split route: after the rescale and threshold launches one delta launch leaves
+    // the correction of every block in `lr_delta`, which the sampler-step launch adds to the clamped x0.  `lr_guide` (the caller's
+    // thumbnails, contents read at run time) and `lr_delta` (part of the handle's guide scratch) are captured by address.
+    const float* lr_guide = nullptr;
+    int lr_N = 0;
+    float lr_strength = 0.f;
+    int lr_tmin = 0;
+    float* lr_delta = nullptr;
 
     // Does a graph captured for `o` replay this run?  Every member a captured launch holds by value or by address, that is all but
     // z_null, the tables bit for bit.  No feature decides which members count: the ones a run does not use are normalised above.
@@ -202,7 +211,8 @@ struct SamplerRun {
         return steps == o.steps && ts == o.ts && same(coef, o.coef) && same(sigma, o.sigma) && noise == o.noise && seeds == o.seeds &&
                guided == o.guided && w == o.w && out_scratch == o.out_scratch && same(c4, o.c4) && hist == o.hist && pred == o.pred &&
                thr_p == o.thr_p && thr_max == o.thr_max && thr == o.thr && thr_sel == o.thr_sel && rs_phi == o.rs_phi &&
-               gscale == o.gscale && rs_part == o.rs_part;
+               gscale == o.gscale && rs_part == o.rs_part && lr_guide == o.lr_guide && lr_N == o.lr_N && lr_strength == o.lr_strength &&
+               lr_tmin == o.lr_tmin && lr_delta == o.lr_delta;
     }
 };
 
@@ -252,6 +262,12 @@ struct ccn_handle_s {
     double rs_phi = 0.0;                                // guidance rescale in the guided ccn_sample* loops (ccn_set_guidance_rescale); 0: off
     char* rs_scratch = nullptr;                         // caller-owned: [B factors | the partial sums]
     size_t rs_scratch_bytes = 0;
+    const float* lr_guide = nullptr;                    // the low-resolution guide in the ccn_sample* loops (ccn_set_lowres_guide); lr_N == 0: off
+    int lr_N = 0;
+    float lr_strength = 0.f;
+    int lr_tmin = 0;
+    char* lr_scratch = nullptr;                         // caller-owned: [delta table | raw output of one state]
+    size_t lr_scratch_bytes = 0;
     std::vector<std::unique_ptr<ShapePlan>> shape_plans;   // of the committed model, one per (B, H, W, steps)
     std::vector<std::unique_ptr<Binding>> bindings;         // plan x workspace address, least recently used first
     hipStream_t cap_stream = nullptr;
@@ -916,7 +932,8 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, const SamplerRun
         const float sigma = noisy ? r.sigma[i] : 0.f;
         const uint64_t* seeds = noisy ? r.seeds : nullptr;          // this step's update generates draw 1 + i
         const bool thresholded = r.thr_p > 0.0;
-        const bool split = r.guided || seeds || thresholded;        // the head writes the raw output, a sampler-step launch updates
+        const bool lowres = r.lr_N > 0 && r.ts[i] >= r.lr_tmin;     // this step holds x0 to the guide
+        const bool split = r.guided || seeds || thresholded || lowres;   // the head writes the raw output, a sampler-step launch updates
         StepCtx c;
         c.step = i; c.x_in = xstate; c.pred = r.pred;
         if (split) { c.x_state = nullptr; c.eps_out = r.out_scratch; c.do_ddim = 0; }
@@ -932,7 +949,7 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, const SamplerRun
         // (unguided with seeds, a noisy step: the same launch without the second half -- 3 passes over one state)
         // (thresholded: the same launch with the record's threshold; the noise tensor and the history enter as in the head's epilogue)
         const double passes = r.guided ? 5 + (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0)
-                                       : 3 + (thresholded ? (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0) : 0);
+                                       : 3 + (thresholded || lowres ? (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0) : 0);
         SamplerStep u;
         u.x = xstate; u.hist = r.hist; u.out_c = r.out_scratch; u.noise = nz; u.pred = r.pred; u.w = r.w;
         if (r.guided) { u.x_dup = xstate + img; u.out_u = r.out_scratch + img; }
@@ -949,6 +966,13 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, const SamplerRun
             if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * 3 * (r.guided ? 3 : 2), s, [&] {
                     return launch_x0_threshold(u.x, u.out_c, u.out_u, u.pred, u.w, cf[0], cf[1], (int)(u.n / u.per_record), u.per_record, r.thr_p,
                                                r.thr_max, r.thr, r.thr_sel, s, r.gscale); })) return rc;
+        // the low-resolution guide: the correction of every block, one read of the state and the output(s)
+        if (lowres) {
+            u.delta = r.lr_delta; u.lr_W = p.W; u.lr_N = r.lr_N;
+            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * (r.guided ? 3 : 2), s, [&] {
+                    return launch_lowres_delta(u.x, u.out_c, u.out_u, u.pred, u.w, cf[0], cf[1], (int)(u.n / u.per_record), h->cfg.img_ch, p.H, p.W,
+                                               r.lr_N, r.lr_guide, r.lr_strength, u.thr, u.gscale, r.lr_delta, s); })) return rc;
+        }
         if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * passes, s, [&] { return launch_sampler_step(u, s); })) return rc;
     }
     return CCN_OK;
@@ -1186,6 +1210,51 @@ int ccn_set_guidance_rescale(ccn_handle_t h, double phi, void* scratch_dev, size
     return CCN_OK;
 }
 
+// The low-resolution guide is handle state likewise.  The scratch of ccn_set_lowres_guide is cut into [delta table | raw output of one
+// state], each part 16-byte aligned (lowres_scratch_layout).
+struct LrLayout { size_t raw, total; };
+static int lowres_scratch_layout(const ccn_handle_s* h, int32_t B, int32_t H, int32_t W, int32_t N, LrLayout& l)
+{
+    if (B <= 0) return fail(CCN_EINVAL, "B, H, W must be positive");
+    if (B > 65535) return fail(CCN_EINVAL, "the low-resolution guide takes at most 65535 records: one grid row each");
+    if (int rc = guide_check(H, W, N)) return rc;
+    const int64_t per = (int64_t)h->cfg.img_ch * H * W;
+    if (per >= kThrMaxPerRecord) return fail(CCN_EINVAL, "a record of 2^34 elements or more cannot be guided");
+    l.raw = ((size_t)B * (size_t)(per / N / N) * 4 + 15) / 16 * 16;
+    l.total = l.raw + ((size_t)B * (size_t)per * 4 + 15) / 16 * 16;
+    return CCN_OK;
+}
+
+int ccn_set_lowres_guide(ccn_handle_t h, const float* guide_dev, int32_t N, float strength, int32_t t_min, void* scratch_dev, size_t scratch_bytes)
+{
+    // the arguments first (they can be judged without a handle), then the handle
+    if (N != 0) {
+        if (N < 2 || N > 64 || (N & (N - 1))) return fail(CCN_EINVAL, "N must be a power of two in 2..64 (0: off)");
+        if (!guide_dev) return fail(CCN_EINVAL, "the guide is NULL");
+        if (!(strength > 0.0f && strength <= 1.0f)) return fail(CCN_EINVAL, "the guide strength must be in (0, 1]");
+        if (t_min < 0) return fail(CCN_EINVAL, "t_min must not be negative");
+        if (!scratch_dev || ((uintptr_t)scratch_dev & 15)) return fail(CCN_EINVAL, "the low-resolution-guide scratch must be non-null and 16-byte aligned");
+        // the smallest shape there is (one record of one block of one channel): a scratch below that fits no call
+        if (scratch_bytes < 16 + (size_t)N * N * 4)
+            return fail(CCN_EINVAL, "the low-resolution-guide scratch is too small (ccn_lowres_guide_scratch_bytes)");
+    }
+    if (!h) return fail(CCN_EINVAL, "null handle");
+    if (N == 0) { h->lr_guide = nullptr; h->lr_N = 0; h->lr_strength = 0.f; h->lr_tmin = 0; h->lr_scratch = nullptr; h->lr_scratch_bytes = 0; return CCN_OK; }
+    h->lr_guide = guide_dev; h->lr_N = N; h->lr_strength = strength; h->lr_tmin = t_min;
+    h->lr_scratch = (char*)scratch_dev; h->lr_scratch_bytes = scratch_bytes;
+    return CCN_OK;
+}
+
+int ccn_lowres_guide_scratch_bytes(ccn_handle_t h, int32_t B, int32_t H, int32_t W, int32_t N, size_t* bytes)
+{
+    if (!h) return fail(CCN_EINVAL, "null handle");
+    if (!bytes) return fail(CCN_EINVAL, "null argument");
+    LrLayout l;
+    if (int rc = lowres_scratch_layout(h, B, H, W, N, l)) return rc;
+    *bytes = l.total;
+    return CCN_OK;
+}
+
 int ccn_commit_params(ccn_handle_t h)
 {
     if (!h) return fail(CCN_EINVAL, "null handle");
@@ -1285,7 +1354,8 @@ int ccn_forward(ccn_handle_t h, const float* x_dev, const float* z_dev, const in
 }
 
 // (handle, descriptor, shape) -> the run: every check of the descriptor, the host tables copied, the handle's prediction, dynamic
-// threshold and guidance rescale read -- here and nowhere else -- and every unused field at its fixed value (SamplerRun)
+// threshold, guidance rescale and low-resolution guide read -- here and nowhere else -- and every unused field at its fixed value
+// (SamplerRun)
 static int build_run(ccn_handle_t h, const ccn_sampler_run_t* d, int32_t B, int32_t H, int32_t W, SamplerRun& r)
 {
     if (!d) return fail(CCN_EINVAL, "null sampler run descriptor");
@@ -1341,6 +1411,15 @@ static int build_run(ccn_handle_t h, const ccn_sampler_run_t* d, int32_t B, int3
         if (h->rs_scratch_bytes < need)
             return fail(CCN_EINVAL, "the guidance-rescale scratch is too small for this shape: need " + std::to_string(need) + " bytes");
         r.rs_phi = h->rs_phi; r.gscale = (float*)h->rs_scratch; r.rs_part = guidance_rescale_partials(h->rs_scratch, B);
+    }
+    if (h->lr_N > 0) {
+        LrLayout l;
+        if (int rc = lowres_scratch_layout(h, B, H, W, h->lr_N, l)) return rc;
+        if (h->lr_scratch_bytes < l.total)
+            return fail(CCN_EINVAL, "the low-resolution-guide scratch is too small for this shape: need " + std::to_string(l.total) + " bytes");
+        r.lr_guide = h->lr_guide; r.lr_N = h->lr_N; r.lr_strength = h->lr_strength; r.lr_tmin = h->lr_tmin;
+        r.lr_delta = (float*)h->lr_scratch;
+        if (!r.out_scratch) r.out_scratch = (float*)(h->lr_scratch + l.raw);   // no guided, seeded or threshold scratch owns the raw output
     }
     return CCN_OK;
 }
@@ -1602,12 +1681,27 @@ int ccn_sampler_step_rs(float* x_dev, float* x_dup_dev, float* x0_hist_dev, cons
                         const float* noise_dev, const uint64_t* seeds_dev, uint32_t draw, int64_t per_record, int32_t pred, float w,
                         const float* coef_host, float sigma, int64_t n, const float* thr_dev, const float* gscale_dev, void* stream)
 {
+    return ccn_sampler_step_lr(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, noise_dev, seeds_dev, draw, per_record, pred, w, coef_host,
+                               sigma, n, thr_dev, gscale_dev, 0, 0, 0, 0, nullptr, stream);
+}
+
+int ccn_sampler_step_lr(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,
+                        const float* noise_dev, const uint64_t* seeds_dev, uint32_t draw, int64_t per_record, int32_t pred, float w,
+                        const float* coef_host, float sigma, int64_t n, const float* thr_dev, const float* gscale_dev, int32_t C, int32_t H,
+                        int32_t W, int32_t N, const float* delta_dev, void* stream)
+{
     SamplerStep a;
     if (int rc = general_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, pred, w, coef_host, sigma, n, a)) return rc;
     if (noise_dev && seeds_dev) return fail(CCN_EINVAL, "noise_dev and seeds_dev exclude each other");
     if (seeds_dev && ((uintptr_t)seeds_dev & 7)) return fail(CCN_EINVAL, "the seeds must be 8-byte aligned");
     if (int rc = check_records(per_record, n)) return rc;
     a.noise = noise_dev; a.seeds = seeds_dev; a.draw = draw; a.per_record = per_record; a.thr = thr_dev; a.gscale = gscale_dev;
+    if (delta_dev) {
+        if (int rc = guide_check(H, W, N)) return rc;
+        if (C <= 0 || (int64_t)C * H * W != per_record) return fail(CCN_EINVAL, "per_record must equal C*H*W");
+        if (n / per_record > 65535) return fail(CCN_EINVAL, "at most 65535 records: one grid row each");
+        a.delta = delta_dev; a.lr_W = W; a.lr_N = N;
+    }
     return enqueue_step(a, stream);
 }
 

@@ -79,6 +79,28 @@ __device__ __forceinline__ float sampler_update_thr(int pred, float s, float x, 
     const float e = pred == PRED_V ? __fadd_rn(__fmul_rn(c0, x), __fmul_rn(c1, y)) : y;
     return sampler_tail(x0, e, c2, c3, c4, hist, x0_out);
 }
+// The low-resolution guide (Low-resolution guide) needs the clamped x0 on its own: clamped_x0_p is the x0 of
+// sampler_update_p (thr false: the static clamp) or of sampler_update_thr (thr true: the record's threshold s), the same operations on
+// the same operands, and pred_e is their e.  ccn_guide.hip takes the block mean of clamped_x0_p and the LR form of the step kernel adds
+// the block's correction to the value of the same call, so the mean is taken over the very bits the step corrects.
+__device__ __forceinline__ float clamped_x0_p(int pred, bool thr, float s, float x, float y, float c0, float c1)
+{
+    const float r = raw_x0_p(pred, x, y, c0, c1);
+    return thr ? __fdiv_rn(fminf(fmaxf(r, -s), s), s) : fminf(fmaxf(r, -1.0f), 1.0f);
+}
+__device__ __forceinline__ float pred_e(int pred, float x, float y, float c0, float c1)
+{
+    return pred == PRED_V ? __fadd_rn(__fmul_rn(c0, x), __fmul_rn(c1, y)) : y;
+}
+__device__ __forceinline__ float sampler_update_lr(int pred, bool thr, float s, float d, float x, float y, float c0, float c1, float c2, float c3,
+                                                   float c4, float hist, float& x0_out)
+{
+    const float x0 = __fadd_rn(clamped_x0_p(pred, thr, s, x, y, c0, c1), d);     // no re-clamp: |x0'| <= 1 + |d|
+    return sampler_tail(x0, pred_e(pred, x, y, c0, c1), c2, c3, c4, hist, x0_out);
+}
+// The fixed-point form of a value in [-1, 1] that the guide's block sums add: v * 2^30 is exact in fp32 and the conversion rounds to
+// nearest even, so a sum of N^2 <= 4096 of them fits int64 with room and is the same in any order.
+__device__ __forceinline__ long long guide_fixed(float v) { return __float2ll_rn(__fmul_rn(v, 1073741824.0f)); }
 
 // ---- record-keyed normals (Noise) ----------------------------------------------------------------------------
 // Element j of draw d of the record with seed s: the Philox words of quad q = j >> 2 (ccn_philox.h), pair p = (j & 3) >> 1 of them

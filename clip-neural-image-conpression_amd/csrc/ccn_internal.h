@@ -289,8 +289,22 @@ struct SamplerStep {
     int64_t per_record = 0;
     const float* thr = nullptr;
     const float* gscale = nullptr;
+    // the low-resolution guide (nullable): launch_lowres_delta's table of this state, (records, C, H / lr_N, lr_W / lr_N); element j
+    // of a record adds the d of its block to the clamped x0.  lr_W, lr_N: the image's width and the block size (per_record = C H lr_W)
+    const float* delta = nullptr;
+    int lr_W = 0, lr_N = 0;
 };
 hipError_t launch_sampler_step(const SamplerStep& a, hipStream_t s);
+// the low-resolution guide (ccn_guide.hip; ccn_lowres_delta and ccn_block_mean in ccn_hip.h).  guide_block_ok: N a power of two in
+// 2..64 that divides H and W, N rows below 2^31 elements; guide_check: the same as a CCN_* code with the message set.
+// launch_lowres_delta: delta[b][c][i][j] = (float)(strength (guide - block mean of the clamped x0)) with x0 formed as the launch above
+// forms it (same combine, gscale, thr); one launch, nothing else.  The caller has checked the arguments.
+bool guide_block_ok(int N, int H, int W);
+int guide_check(int32_t H, int32_t W, int32_t N);
+hipError_t launch_lowres_delta(const float* x, const float* out_c, const float* out_u, int pred, float w, float c0, float c1, int B, int C, int H,
+                               int W, int N, const float* guide, float strength, const float* thr, const float* gscale, float* delta,
+                               hipStream_t s);
+hipError_t launch_block_mean(const float* x, int64_t planes, int H, int W, int N, float* out, hipStream_t s);
 // the dynamic threshold of every record (ccn_threshold.hip; ccn_x0_threshold in ccn_hip.h): thr[b] = min(max(Q_p(|x0_b|), 1), max_value)
 // of the raw x0 the launch above would form.  `scratch`: x0_threshold_scratch_bytes(B) bytes, 16-byte aligned, any contents.  The
 // caller has checked the arguments (0 <= p <= 1, 1 <= B <= 65535, 0 < per < 2^34).  Five launches, nothing else.

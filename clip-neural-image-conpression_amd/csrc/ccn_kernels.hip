@@ -825,16 +825,21 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
 // section 1, Thresholding); a noise tensor is then walked by record too.  Without THR nothing of it is compiled in.
 // RS: the same grid rows, and record b's guidance-rescale factor gscale[b] multiplies y right after the combine (DESIGN.md section 1,
 // Guidance rescale): everything downstream -- the raw x0, e, the history -- is formed from k y.  Without RS nothing of it is compiled in.
-template <bool VEC, bool SEEDED, bool THR, bool RS>
+// LR: the same grid rows, and element j of record b adds delta[b][block(j)] to its x0 right after the clamp (sampler_update_lr; DESIGN.md
+// section 1, Low-resolution guide): with W the image's width, N = 2^lgN the block size and WB = W / N, row R = j / W of the record's
+// C H rows lies in strip R >> lgN (H % N == 0: no strip crosses a plane) and block(j) = (R >> lgN) WB + ((j - R W) >> lgN).  A quad
+// may straddle two blocks or two rows, so the row and the column are carried per element.  Without LR nothing of it is compiled in.
+template <bool VEC, bool SEEDED, bool THR, bool RS, bool LR>
 __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x_dup, float* __restrict__ hist, const float* __restrict__ out_c,
                                     const float* __restrict__ out_u, const float* __restrict__ noise, int pred, float w, float c0, float c1,
                                     float c2, float c3, float c4, float sigma, int64_t n, const uint64_t* __restrict__ seeds, uint32_t draw,
-                                    int64_t per, const float* __restrict__ thr, const float* __restrict__ gscale)
+                                    int64_t per, const float* __restrict__ thr, const float* __restrict__ gscale,
+                                    const float* __restrict__ delta, int lrW, int lgN, int lrWB)
 {
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     uint64_t seed = 0;
     float s = 1.0f, k = 1.0f;
-    if constexpr (SEEDED || THR || RS) {                            // this record's slice of every tensor
+    if constexpr (SEEDED || THR || RS || LR) {                      // this record's slice of every tensor
         const int64_t off = (int64_t)blockIdx.y * per;
         if constexpr (SEEDED) seed = seeds[blockIdx.y];
         if constexpr (THR) s = thr[blockIdx.y];
@@ -843,14 +848,25 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         if (x_dup) x_dup += off;
         if (hist) hist += off;
         if (out_u) out_u += off;
-        if constexpr (THR || RS) { if (noise) noise += off; }
+        if constexpr (THR || RS || LR) { if (noise) noise += off; }
+        if constexpr (LR) delta += (int64_t)blockIdx.y * ((per >> lgN) >> lgN);
     }
     const int64_t n4 = VEC ? n / 4 : 0;
     if (!hist) c4 = 0.f;
     // one element's update: the threshold form only where it was asked for
-    auto update = [&](float xv, float yv, float hv, float& p) {
-        if constexpr (THR) return sampler_update_thr(pred, s, xv, yv, c0, c1, c2, c3, c4, hv, p);
+    auto update = [&](float xv, float yv, float hv, float& p, float dv) {
+        if constexpr (LR) return sampler_update_lr(pred, THR, s, dv, xv, yv, c0, c1, c2, c3, c4, hv, p);
+        else if constexpr (THR) return sampler_update_thr(pred, s, xv, yv, c0, c1, c2, c3, c4, hv, p);
         else return sampler_update_p(pred, xv, yv, c0, c1, c2, c3, c4, hv, p);
+    };
+    // LR: the d of element j and of the three after it (row R, column col of the record's rows; one division per call)
+    auto block_d = [&](int64_t j, float* d4, int count) {
+        int64_t R = per <= 0x7fffffff ? (int64_t)((uint32_t)j / (uint32_t)lrW) : j / lrW;
+        int col = (int)(j - R * lrW);
+        for (int e = 0; e < count; ++e) {
+            d4[e] = delta[(R >> lgN) * lrWB + (col >> lgN)];
+            if (++col == lrW) { col = 0; ++R; }
+        }
     };
     for (int64_t q = tid; q < n4; q += nthr) {
         const float4 xv = ((const float4*)x)[q];
@@ -863,10 +879,12 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         if constexpr (RS) { yv.x = __fmul_rn(k, yv.x); yv.y = __fmul_rn(k, yv.y); yv.z = __fmul_rn(k, yv.z); yv.w = __fmul_rn(k, yv.w); }
         float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), o, p;
         if (c4 != 0.f) hv = ((const float4*)hist)[q];
-        o.x = update(xv.x, yv.x, hv.x, p.x);
-        o.y = update(xv.y, yv.y, hv.y, p.y);
-        o.z = update(xv.z, yv.z, hv.z, p.z);
-        o.w = update(xv.w, yv.w, hv.w, p.w);
+        float dv[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (LR) block_d(q * 4, dv, 4);
+        o.x = update(xv.x, yv.x, hv.x, p.x, dv[0]);
+        o.y = update(xv.y, yv.y, hv.y, p.y, dv[1]);
+        o.z = update(xv.z, yv.z, hv.z, p.z, dv[2]);
+        o.w = update(xv.w, yv.w, hv.w, p.w, dv[3]);
         if (SEEDED || noise) {
             float4 nv;
             if constexpr (SEEDED) nv = draw_quad(seed, draw, (uint32_t)q);
@@ -883,8 +901,9 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         if (out_u) { const float u = out_u[i]; y = __fadd_rn(u, __fmul_rn(w, __fsub_rn(y, u))); }
         if constexpr (RS) y = __fmul_rn(k, y);
         const float hv = c4 != 0.f ? hist[i] : 0.f;
-        float p;
-        float xn = update(x[i], y, hv, p);
+        float p, dv = 0.f;
+        if constexpr (LR) block_d(i, &dv, 1);
+        float xn = update(x[i], y, hv, p, dv);
         if constexpr (SEEDED) xn = __fadd_rn(xn, __fmul_rn(sigma, draw_element(seed, draw, i)));
         else if (noise) xn = __fadd_rn(xn, __fmul_rn(sigma, noise[i]));
         if (hist) hist[i] = p;
@@ -892,15 +911,22 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         if (x_dup) x_dup[i] = xn;
     }
 }
-// seeds given and sigma > 0: the seeded form; thr given: the threshold form; gscale given: the rescaled form; each walks the state
-// record by record, one grid row each (the caller has checked per > 0 and n % per == 0).  With seeds `noise` is not read.
+// seeds given and sigma > 0: the seeded form; thr given: the threshold form; gscale given: the rescaled form; delta given: the
+// low-resolution-guide form; each walks the state record by record, one grid row each (the caller has checked per > 0 and
+// n % per == 0, and with delta that lr_N is a power of two and per a multiple of lr_W lr_N).  With seeds `noise` is not read.
 hipError_t launch_sampler_step(const SamplerStep& a, hipStream_t s)
 {
     const int64_t n = a.n, per = a.per_record;
-    const float *thr = a.thr, *gscale = a.gscale;
+    const float *thr = a.thr, *gscale = a.gscale, *delta = a.delta;
     const bool seeded = a.seeds && a.sigma > 0.f;
     const float* noise = seeded ? nullptr : a.noise;
-    const bool rowed = seeded || thr || gscale;
+    const bool rowed = seeded || thr || gscale || delta;
+    int lgN = 0;
+    if (delta) {
+        if (a.lr_N < 2 || (a.lr_N & (a.lr_N - 1)) || a.lr_W <= 0 || a.lr_W % a.lr_N || per <= 0 || per % ((int64_t)a.lr_W * a.lr_N)) return hipErrorInvalidValue;
+        while ((1 << lgN) < a.lr_N) ++lgN;
+    }
+    const int lrWB = delta ? a.lr_W / a.lr_N : 0;
     if (rowed && (per <= 0 || n % per || n / per > 65535)) return hipErrorInvalidValue;      // one grid row per record
     const bool vec = !(((uintptr_t)a.x | (uintptr_t)a.x_dup | (uintptr_t)a.hist | (uintptr_t)a.out_c | (uintptr_t)a.out_u | (uintptr_t)noise) & 15) &&
                      !(rowed && (per & 3));
@@ -908,15 +934,20 @@ hipError_t launch_sampler_step(const SamplerStep& a, hipStream_t s)
     const int64_t work = vec ? (row + 3) / 4 : row, blocks = (work + 255) / 256;
     const int gx = (int)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);        // 256 CUs x 8 blocks, grid-stride beyond
     const dim3 grid(gx, (unsigned)rows);
-#define CCN_STEP_ARGS a.x, a.x_dup, a.hist, a.out_c, a.out_u, noise, a.pred, a.w, a.c[0], a.c[1], a.c[2], a.c[3], a.c[4], a.sigma, n, a.seeds, a.draw, per, thr, gscale
+#define CCN_STEP_ARGS a.x, a.x_dup, a.hist, a.out_c, a.out_u, noise, a.pred, a.w, a.c[0], a.c[1], a.c[2], a.c[3], a.c[4], a.sigma, n, a.seeds, a.draw, per, thr, gscale, delta, a.lr_W, lgN, lrWB
+#define CCN_STEP_GO4(SEEDED, THR, RS, LR)                                                                                    \
+    do {                                                                                                                     \
+        if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, SEEDED, THR, RS, LR>), grid, dim3(256), 0, s, CCN_STEP_ARGS);  \
+        else hipLaunchKernelGGL((sampler_step_kernel<false, SEEDED, THR, RS, LR>), grid, dim3(256), 0, s, CCN_STEP_ARGS);     \
+    } while (0)
 #define CCN_STEP_GO(SEEDED, THR)                                                                                             \
     do {                                                                                                                     \
         if (gscale) {                                                                                                        \
-            if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, SEEDED, THR, true>), grid, dim3(256), 0, s, CCN_STEP_ARGS);   \
-            else hipLaunchKernelGGL((sampler_step_kernel<false, SEEDED, THR, true>), grid, dim3(256), 0, s, CCN_STEP_ARGS);      \
+            if (delta) CCN_STEP_GO4(SEEDED, THR, true, true);                                                                \
+            else CCN_STEP_GO4(SEEDED, THR, true, false);                                                                     \
         } else {                                                                                                             \
-            if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, SEEDED, THR, false>), grid, dim3(256), 0, s, CCN_STEP_ARGS);  \
-            else hipLaunchKernelGGL((sampler_step_kernel<false, SEEDED, THR, false>), grid, dim3(256), 0, s, CCN_STEP_ARGS);     \
+            if (delta) CCN_STEP_GO4(SEEDED, THR, false, true);                                                               \
+            else CCN_STEP_GO4(SEEDED, THR, false, false);                                                                    \
         }                                                                                                                    \
     } while (0)
     if (seeded && thr) CCN_STEP_GO(true, true);
@@ -924,6 +955,7 @@ hipError_t launch_sampler_step(const SamplerStep& a, hipStream_t s)
     else if (thr) CCN_STEP_GO(false, true);
     else CCN_STEP_GO(false, false);
 #undef CCN_STEP_GO
+#undef CCN_STEP_GO4
 #undef CCN_STEP_ARGS
     return hipGetLastError();
 }

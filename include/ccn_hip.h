@@ -398,6 +398,67 @@ int ccn_sampler_step_rs(float* x_dev, float* x_dup_dev, float* x0_hist_dev,
  * later guided ccn_sample* call is that call's CCN_EINVAL, as are more than 65535 images or C*H*W outside [2, 2^34)). */
 int ccn_set_guidance_rescale(ccn_handle_t h, double phi, void* scratch_dev, size_t scratch_bytes);
 
+/* ---- low-resolution guide ---------------------------------------------------------------------------------------------------------- *
+ * (No reference counterpart.  ILVR, Choi et al. 2021; in x0 space the super-resolution case of DDNM, Wang et al. 2022:
+ * x0' = x0 - A+(A x0 - g) with A the N x N block mean and A+ the replication of a block's value over its pixels.)  The decoder holds a
+ * thumbnail g of the image, (B, C, H/N, W/N) fp32 with values expected in [-1, 1], and keeps every step's x0 prediction consistent
+ * with it.  N: a power of two in 2..64 that divides H and W.  lambda = strength in (0, 1].  Per record, channel and N x N block:
+ *   1. x0 is the prediction exactly as ccn_sampler_step_rs forms it: the guidance combine, the multiplication by gscale[b], the raw x0
+ *      of either parameterisation, then the static clamp or clamp(., -thr[b], thr[b]) / thr[b].  |x0| <= 1 in every case.
+ *   2. q(v) = the int64 nearest to v * 2^30, ties to even (the product is exact in fp32).  S = the int64 sum of q(x0) over the block;
+ *      |S| <= 2^42 and integer addition is exact in any order, so S -- and with it everything below -- is reproducible bit for bit and
+ *      independent of B, of the record's position, of pointer alignment and of the load width.
+ *   3. m = (double)S / (N^2 2^30);  d = (float)((double)lambda * ((double)g - m)), rounded to fp32 once.
+ *   4. x0' = x0 + d (one fp32 addition) for every pixel of the block, NOT clamped again; x0' replaces x0 in the update and in the
+ *      multistep history; e is untouched, as with the clamp and the threshold.
+ * Non-finite values are not looked for: the static clamp maps a NaN to -1 and +-inf to +-1; under a NaN threshold the record's x0 is
+ * NaN, its d is unspecified and its update is NaN, as without a guide.
+ *
+ * ccn_block_mean: out_dev[p][i][j] = (float)m of clamp(x, -1, 1) for each of `planes` planes of H x W: the guide of an original, or the
+ * thumbnail of a result.  ccn_lowres_delta: delta_dev, (B, C, H/N, W/N), = d above; out_u_dev (with w), thr_dev and gscale_dev are
+ * nullable and mean what they mean to ccn_sampler_step_rs.  One launch each on `stream`: 64-bit integer LDS atomics only, no memset,
+ * no scratch, never synchronises, allocates nothing, capturable; 16-byte loads when every tensor is 16-byte aligned, else 4-byte
+ * loads, the same bits.
+ * CCN_EINVAL: a NULL tensor, N not a power of two in 2..64, H or W not a multiple of N, strength outside (0, 1] or NaN, B outside
+ * [1, 65535], C*H*W >= 2^34, an unknown pred. */
+int ccn_block_mean(const float* x_dev, int64_t planes, int32_t H, int32_t W, int32_t N, float* out_dev, void* stream);
+int ccn_lowres_delta(const float* x_dev, const float* out_c_dev, const float* out_u_dev,
+                     int32_t pred, float w, float c0, float c1,
+                     int32_t B, int32_t C, int32_t H, int32_t W, int32_t N,
+                     const float* guide_dev, float strength,
+                     const float* thr_dev, const float* gscale_dev,
+                     float* delta_dev, void* stream);
+
+/* ccn_sampler_step_rs plus the image's geometry and delta_dev (ccn_lowres_delta's table of the same state): element j of record b adds
+ * the d of its block right after the clamp, and the state is walked record by record.  per_record must equal C*H*W.  delta_dev NULL:
+ * ccn_sampler_step_rs, bit for bit (C, H, W, N are then not read).  CCN_EINVAL: as for that entry, and with delta_dev the N, H, W
+ * rules above. */
+int ccn_sampler_step_lr(float* x_dev, float* x_dup_dev, float* x0_hist_dev,
+                        const float* out_c_dev, const float* out_u_dev,
+                        const float* noise_dev, const uint64_t* seeds_dev, uint32_t draw,
+                        int64_t per_record, int32_t pred, float w,
+                        const float* coef_host /* [5] */, float sigma, int64_t n,
+                        const float* thr_dev, const float* gscale_dev,
+                        int32_t C, int32_t H, int32_t W, int32_t N, const float* delta_dev, void* stream);
+
+/* Handle state, exactly like ccn_set_dynamic_threshold: read by every ccn_sample* entry when it enqueues or captures, and part of
+ * every captured graph's cache key (the guide's address, N, strength, t_min and the scratch address; the guide's CONTENTS are read when
+ * the kernels run, like seeds, so new contents at the same address replay the same graph).  N == 0: off (the default; the other
+ * arguments are not read).  Otherwise guide_dev is (B, C, H/N, W/N) fp32 for the B images of the call, and every step i with
+ * ts[i] >= t_min takes the split route: after the network the rescale launches (if set), the threshold launches (if set), one
+ * ccn_lowres_delta launch, then one ccn_sampler_step_lr launch.  Guided, one d per image is formed from the combined output and both
+ * halves of the state get the same update.  A step with ts[i] < t_min is exactly the step the run takes without a guide.
+ * scratch_dev: ccn_lowres_guide_scratch_bytes(h, B, H, W, N) bytes for the largest shape sampled with it -- the delta table, then room
+ * for the raw output of one state, which is used only by a run in which no guided, seeded or threshold scratch already holds it --
+ * 16-byte aligned, owned by the caller and kept at its address while a graph captured with it is cached.  ccn_workspace_bytes is
+ * unchanged.
+ * CCN_EINVAL: N not 0 and not a power of two in 2..64; a NULL guide; strength outside (0, 1] or NaN; t_min < 0; a NULL, misaligned or
+ * short scratch (a scratch too small for the shape of a later ccn_sample* call is that call's CCN_EINVAL, as are H or W not a
+ * multiple of N and more than 65535 images). */
+int ccn_set_lowres_guide(ccn_handle_t h, const float* guide_dev, int32_t N, float strength, int32_t t_min,
+                         void* scratch_dev, size_t scratch_bytes);
+int ccn_lowres_guide_scratch_bytes(ccn_handle_t h, int32_t B, int32_t H, int32_t W, int32_t N, size_t* bytes);
+
 /* ---- the sampler loop, described by one record ------------------------------------------------------------------------------------ *
  * Everything a run of the loop is a function of besides the handle (its prediction and dynamic threshold are read like by every
  * other ccn_sample* entry), the tensors and the shape.  ccn_sample, ccn_sample_eta, ccn_sample_guided, ccn_sample_seeded,
