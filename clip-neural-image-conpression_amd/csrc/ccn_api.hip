@@ -27,8 +27,7 @@ using namespace ccn;
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
+thread_local std::string g_err;             // behind ccn_last_error(); written by ccn::fail (ccn_internal.h) from every file
 #define HIPCHK(expr)                                                                                     \
     do {                                                                                                 \
         hipError_t e_ = (expr);                                                                          \
@@ -37,8 +36,19 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
     } while (0)
 
 }  // namespace
-// ccn_train.hip reports its failures through the same thread-local message
 extern "C" void ccn_internal_set_error(const char* msg) { g_err = msg ? msg : ""; }
+
+// the one argument check of the launches that take an X0Operands record (ccn_internal.h)
+int ccn::check_x0_operands(const X0Operands& o, bool for_rescale, bool pointers)
+{
+    if (pointers && (!o.out_c || (for_rescale ? !o.out_u : !o.x))) return fail(CCN_EINVAL, "a tensor pointer is NULL");
+    if (o.pred != CCN_PRED_EPS && o.pred != CCN_PRED_V) return fail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
+    if (o.records <= 0 || o.records > 65535) return fail(CCN_EINVAL, "the number of records must be in [1, 65535]: one grid row per record");
+    if (for_rescale && (o.per_record < 2 || o.per_record >= kThrMaxPerRecord))
+        return fail(CCN_EINVAL, "per_record must be in [2, 2^34): an unbiased std needs two elements");
+    if (o.per_record <= 0 || o.per_record >= kThrMaxPerRecord) return fail(CCN_EINVAL, "per_record must be in [1, 2^34)");
+    return CCN_OK;
+}
 namespace {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -950,28 +960,28 @@ int run_steps(ccn_handle_s* h, const Binding* b, hipStream_t s, const SamplerRun
         // (thresholded: the same launch with the record's threshold; the noise tensor and the history enter as in the head's epilogue)
         const double passes = r.guided ? 5 + (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0)
                                        : 3 + (thresholded || lowres ? (nz ? 1 : 0) + (ms ? (c4 != 0.f ? 2 : 1) : 0) : 0);
+        // the operands of this step's x0, named once for the (up to) four launches that form it
         SamplerStep u;
-        u.x = xstate; u.hist = r.hist; u.out_c = r.out_scratch; u.noise = nz; u.pred = r.pred; u.w = r.w;
-        if (r.guided) { u.x_dup = xstate + img; u.out_u = r.out_scratch + img; }
-        for (int k = 0; k < 4; ++k) u.c[k] = cf[k];
-        u.c[4] = c4; u.sigma = sigma; u.n = (int64_t)img;
-        u.seeds = seeds; u.draw = 1u + (uint32_t)i; u.per_record = (int64_t)h->cfg.img_ch * p.H * p.W; u.thr = r.thr; u.gscale = r.gscale;
+        X0Operands& o = u.o;
+        o.x = xstate; o.out_c = r.out_scratch; o.gscale = r.gscale; o.thr = r.thr; o.pred = r.pred; o.w = r.w; o.c0 = cf[0]; o.c1 = cf[1];
+        o.per_record = (int64_t)h->cfg.img_ch * p.H * p.W; o.records = (int64_t)img / o.per_record;
+        u.hist = r.hist; u.noise = nz;
+        if (r.guided) { u.x_dup = xstate + img; o.out_u = r.out_scratch + img; }
+        u.c2 = cf[2]; u.c3 = cf[3]; u.c4 = c4; u.sigma = sigma;
+        u.seeds = seeds; u.draw = 1u + (uint32_t)i;
         // guidance rescale: the factor of every record, one read of both halves of the output scratch
         if (r.rs_phi > 0.0)
-            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * 2, s, [&] {
-                    return launch_guidance_rescale(u.out_c, u.out_u, u.w, r.rs_phi, (int)(u.n / u.per_record), u.per_record, r.gscale, r.rs_part, s); }))
+            if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * 2, s, [&] { return launch_guidance_rescale(o, r.rs_phi, r.gscale, r.rs_part, s); }))
                 return rc;
         // the quantile of |x0| per record, on the combined output when guided: three select passes over the state and the output(s)
         if (thresholded)
             if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * 3 * (r.guided ? 3 : 2), s, [&] {
-                    return launch_x0_threshold(u.x, u.out_c, u.out_u, u.pred, u.w, cf[0], cf[1], (int)(u.n / u.per_record), u.per_record, r.thr_p,
-                                               r.thr_max, r.thr, r.thr_sel, s, r.gscale); })) return rc;
+                    return launch_x0_threshold(o, r.thr_p, r.thr_max, r.thr, r.thr_sel, s); })) return rc;
         // the low-resolution guide: the correction of every block, one read of the state and the output(s)
         if (lowres) {
             u.delta = r.lr_delta; u.lr_W = p.W; u.lr_N = r.lr_N;
             if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * (r.guided ? 3 : 2), s, [&] {
-                    return launch_lowres_delta(u.x, u.out_c, u.out_u, u.pred, u.w, cf[0], cf[1], (int)(u.n / u.per_record), h->cfg.img_ch, p.H, p.W,
-                                               r.lr_N, r.lr_guide, r.lr_strength, u.thr, u.gscale, r.lr_delta, s); })) return rc;
+                    return launch_lowres_delta(o, h->cfg.img_ch, p.H, p.W, r.lr_N, r.lr_guide, r.lr_strength, r.lr_delta, s); })) return rc;
         }
         if (int rc = timed(h, F_HEAD, 0, (double)img * 4 * passes, s, [&] { return launch_sampler_step(u, s); })) return rc;
     }
@@ -1150,15 +1160,22 @@ int ccn_set_prediction(ccn_handle_t h, int32_t pred)
     return CCN_OK;
 }
 
+// what the three handle features below need of a run's state, B records of img_ch x H x W: check_x0_operands without the pointers
+static int check_state_shape(const ccn_handle_s* h, int32_t B, int32_t H, int32_t W, bool for_rescale, int64_t& per)
+{
+    if (H <= 0 || W <= 0) return fail(CCN_EINVAL, "B, H, W must be positive");
+    X0Operands o;
+    o.records = B; o.per_record = per = (int64_t)h->cfg.img_ch * H * W;
+    return check_x0_operands(o, for_rescale, false);
+}
+
 // Dynamic thresholding is handle state: every ccn_sample* entry picks it up here.  The scratch of ccn_set_dynamic_threshold is cut
 // into [raw output of one state | B thresholds | select state], each part 16-byte aligned (threshold_scratch_layout).
 struct ThrLayout { size_t thr, sel, total; };
 static int threshold_scratch_layout(const ccn_handle_s* h, int32_t B, int32_t H, int32_t W, ThrLayout& l)
 {
-    if (B <= 0 || H <= 0 || W <= 0) return fail(CCN_EINVAL, "B, H, W must be positive");
-    if (B > 65535) return fail(CCN_EINVAL, "dynamic thresholding takes at most 65535 records: one grid row each");
-    const int64_t per = (int64_t)h->cfg.img_ch * H * W;
-    if (per >= kThrMaxPerRecord) return fail(CCN_EINVAL, "a record of 2^34 elements or more cannot be thresholded");
+    int64_t per;
+    if (int rc = check_state_shape(h, B, H, W, false, per)) return rc;
     l.thr = ((size_t)B * (size_t)per * 4 + 15) / 16 * 16;
     l.sel = l.thr + ((size_t)B * 4 + 15) / 16 * 16;
     l.total = l.sel + x0_threshold_scratch_bytes(B);
@@ -1215,11 +1232,9 @@ int ccn_set_guidance_rescale(ccn_handle_t h, double phi, void* scratch_dev, size
 struct LrLayout { size_t raw, total; };
 static int lowres_scratch_layout(const ccn_handle_s* h, int32_t B, int32_t H, int32_t W, int32_t N, LrLayout& l)
 {
-    if (B <= 0) return fail(CCN_EINVAL, "B, H, W must be positive");
-    if (B > 65535) return fail(CCN_EINVAL, "the low-resolution guide takes at most 65535 records: one grid row each");
     if (int rc = guide_check(H, W, N)) return rc;
-    const int64_t per = (int64_t)h->cfg.img_ch * H * W;
-    if (per >= kThrMaxPerRecord) return fail(CCN_EINVAL, "a record of 2^34 elements or more cannot be guided");
+    int64_t per;
+    if (int rc = check_state_shape(h, B, H, W, false, per)) return rc;
     l.raw = ((size_t)B * (size_t)(per / N / N) * 4 + 15) / 16 * 16;
     l.total = l.raw + ((size_t)B * (size_t)per * 4 + 15) / 16 * 16;
     return CCN_OK;
@@ -1403,10 +1418,8 @@ static int build_run(ccn_handle_t h, const ccn_sampler_run_t* d, int32_t B, int3
         if (!r.out_scratch) r.out_scratch = (float*)h->thr_scratch;   // a run without a scratch of its own: the head of the handle's
     }
     if (h->rs_phi > 0.0 && guided) {                                // (an unguided run ignores it: there is nothing to match)
-        if (H <= 0 || W <= 0) return fail(CCN_EINVAL, "B, H, W must be positive");
-        if (B > 65535) return fail(CCN_EINVAL, "guidance rescale takes at most 65535 records: one grid row each");
-        const int64_t per = (int64_t)h->cfg.img_ch * H * W;
-        if (per < 2 || per >= kThrMaxPerRecord) return fail(CCN_EINVAL, "guidance rescale needs records of 2 to 2^34 - 1 elements");
+        int64_t per;
+        if (int rc = check_state_shape(h, B, H, W, true, per)) return rc;
         const size_t need = guidance_rescale_scratch_bytes(B, per);
         if (h->rs_scratch_bytes < need)
             return fail(CCN_EINVAL, "the guidance-rescale scratch is too small for this shape: need " + std::to_string(need) + " bytes");
@@ -1581,7 +1594,7 @@ int ccn_sample_guided_ms(ccn_handle_t h, const float* z_dev, const float* z_null
 // ---- the stand-alone updates: their own argument checks, then the one kernel ----------------------------------------------------
 static int enqueue_step(const SamplerStep& a, void* stream)
 {
-    if (a.n == 0) return CCN_OK;
+    if (a.o.records * a.o.per_record == 0) return CCN_OK;
     HIPCHK(launch_sampler_step(a, (hipStream_t)stream));
     return CCN_OK;
 }
@@ -1589,7 +1602,8 @@ static int enqueue_step(const SamplerStep& a, void* stream)
 static SamplerStep eps_step(float* x, const float* eps_c, float c0, float c1, float c2, float c3, int64_t n)
 {
     SamplerStep a;
-    a.x = x; a.out_c = eps_c; a.c[0] = c0; a.c[1] = c1; a.c[2] = c2; a.c[3] = c3; a.n = n;
+    a.o.x = x; a.o.out_c = eps_c; a.o.c0 = c0; a.o.c1 = c1; a.c2 = c2; a.c3 = c3;
+    a.o.records = 1; a.o.per_record = n;                           // one run of n elements
     return a;
 }
 
@@ -1597,7 +1611,7 @@ int ccn_ms_step(float* x_dev, float* x0_hist_dev, const float* eps_dev, float c0
 {
     if (!x_dev || !x0_hist_dev || !eps_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
     SamplerStep a = eps_step(x_dev, eps_dev, c0, c1, c2, c3, n);
-    a.hist = x0_hist_dev; a.c[4] = c4;
+    a.hist = x0_hist_dev; a.c4 = c4;
     return enqueue_step(a, stream);
 }
 
@@ -1606,7 +1620,7 @@ int ccn_cfg_ms_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const fl
 {
     if (!x_dev || !x0_hist_dev || !eps_c_dev || !eps_u_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
     SamplerStep a = eps_step(x_dev, eps_c_dev, c0, c1, c2, c3, n);
-    a.x_dup = x_dup_dev; a.out_u = eps_u_dev; a.w = w; a.hist = x0_hist_dev; a.c[4] = c4;
+    a.x_dup = x_dup_dev; a.o.out_u = eps_u_dev; a.o.w = w; a.hist = x0_hist_dev; a.c4 = c4;
     return enqueue_step(a, stream);
 }
 
@@ -1615,7 +1629,7 @@ int ccn_cfg_ddim_step(float* x_dev, float* x_dup_dev, const float* eps_c_dev, co
 {
     if (!x_dev || !eps_c_dev || !eps_u_dev || n < 0) return fail(CCN_EINVAL, "bad argument");
     SamplerStep a = eps_step(x_dev, eps_c_dev, c0, c1, c2, c3, n);
-    a.x_dup = x_dup_dev; a.out_u = eps_u_dev; a.w = w; a.noise = noise_dev; a.sigma = sigma;
+    a.x_dup = x_dup_dev; a.o.out_u = eps_u_dev; a.o.w = w; a.noise = noise_dev; a.sigma = sigma;
     return enqueue_step(a, stream);
 }
 
@@ -1635,17 +1649,17 @@ static int general_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, cons
     if (!x_dev || !out_c_dev || !coef_host || n < 0) return fail(CCN_EINVAL, "bad argument");
     if (pred != CCN_PRED_EPS && pred != CCN_PRED_V) return fail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
     a = eps_step(x_dev, out_c_dev, coef_host[0], coef_host[1], coef_host[2], coef_host[3], n);
-    a.x_dup = x_dup_dev; a.hist = x0_hist_dev; a.out_u = out_u_dev; a.pred = pred; a.w = w; a.sigma = sigma;
-    if (x0_hist_dev) a.c[4] = coef_host[4];
+    a.x_dup = x_dup_dev; a.hist = x0_hist_dev; a.o.out_u = out_u_dev; a.o.pred = pred; a.o.w = w; a.sigma = sigma;
+    if (x0_hist_dev) a.c4 = coef_host[4];
     return CCN_OK;
 }
-// ... and of the two that walk the state record by record
+// ... and of the two that walk the state record by record: n elements as records of per_record, into `a`, checked
 static_assert(kDrawMaxPerRecord == kThrMaxPerRecord, "one per_record limit for the draws and the select");
-static int check_records(int64_t per_record, int64_t n)
+static int set_records(SamplerStep& a, int64_t per_record, int64_t n)
 {
     if (per_record <= 0 || per_record >= kDrawMaxPerRecord || n % per_record) return fail(CCN_EINVAL, "per_record must be in [1, 2^34) and divide n");
-    if (n / per_record > 65535) return fail(CCN_EINVAL, "at most 65535 records per launch");
-    return CCN_OK;
+    a.o.per_record = per_record; a.o.records = n / per_record;
+    return n == 0 ? CCN_OK : check_x0_operands(a.o, false);         // (n == 0: nothing is launched)
 }
 
 int ccn_sampler_step(float* x_dev, float* x_dup_dev, float* x0_hist_dev, const float* out_c_dev, const float* out_u_dev,
@@ -1664,8 +1678,8 @@ int ccn_sampler_step_seeded(float* x_dev, float* x_dup_dev, float* x0_hist_dev, 
     SamplerStep a;
     if (int rc = general_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, pred, w, coef_host, sigma, n, a)) return rc;
     if (!seeds_dev || ((uintptr_t)seeds_dev & 7)) return fail(CCN_EINVAL, "the seeds must be non-null and 8-byte aligned");
-    if (int rc = check_records(per_record, n)) return rc;
-    a.seeds = seeds_dev; a.draw = draw; a.per_record = per_record;
+    if (int rc = set_records(a, per_record, n)) return rc;
+    a.seeds = seeds_dev; a.draw = draw;
     return enqueue_step(a, stream);
 }
 
@@ -1694,12 +1708,11 @@ int ccn_sampler_step_lr(float* x_dev, float* x_dup_dev, float* x0_hist_dev, cons
     if (int rc = general_step(x_dev, x_dup_dev, x0_hist_dev, out_c_dev, out_u_dev, pred, w, coef_host, sigma, n, a)) return rc;
     if (noise_dev && seeds_dev) return fail(CCN_EINVAL, "noise_dev and seeds_dev exclude each other");
     if (seeds_dev && ((uintptr_t)seeds_dev & 7)) return fail(CCN_EINVAL, "the seeds must be 8-byte aligned");
-    if (int rc = check_records(per_record, n)) return rc;
-    a.noise = noise_dev; a.seeds = seeds_dev; a.draw = draw; a.per_record = per_record; a.thr = thr_dev; a.gscale = gscale_dev;
+    if (int rc = set_records(a, per_record, n)) return rc;
+    a.noise = noise_dev; a.seeds = seeds_dev; a.draw = draw; a.o.thr = thr_dev; a.o.gscale = gscale_dev;
     if (delta_dev) {
         if (int rc = guide_check(H, W, N)) return rc;
         if (C <= 0 || (int64_t)C * H * W != per_record) return fail(CCN_EINVAL, "per_record must equal C*H*W");
-        if (n / per_record > 65535) return fail(CCN_EINVAL, "at most 65535 records: one grid row each");
         a.delta = delta_dev; a.lr_W = W; a.lr_N = N;
     }
     return enqueue_step(a, stream);

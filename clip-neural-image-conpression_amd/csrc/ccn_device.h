@@ -36,53 +36,22 @@ __device__ __forceinline__ float sampler_tail(float x0, float e, float c2, float
     x0_out = x0;
     return xn;
 }
-// The x0 prediction before any clamp, either parameterisation: the ONE formation, shared by the updates below and by the dynamic
-// threshold's quantile (ccn_threshold.hip), so that the order statistic is taken on the very bits the update clamps.
-__device__ __forceinline__ float raw_x0_eps(float x, float e, float c0, float c1) { return __fdiv_rn(__fsub_rn(x, __fmul_rn(c0, e)), c1); }
-__device__ __forceinline__ float raw_x0_v(float x, float y, float c0, float c1) { return __fsub_rn(__fmul_rn(c1, x), __fmul_rn(c0, y)); }
-__device__ __forceinline__ float sampler_update(float x, float e, float c0, float c1, float c2, float c3, float c4, float hist, float& x0_out)
-{
-    float x0 = raw_x0_eps(x, e, c0, c1);
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    return sampler_tail(x0, e, c2, c3, c4, hist, x0_out);
-}
-// The v-parameterisation (CCN_PRED_V): the network output is y = v = a*noise - s*x0, and with the SAME table (c0 = s_t, c1 = a_t)
+// The x0 prediction before any clamp, either parameterisation.  `pred` is wave-uniform (a kernel argument): PRED_EPS / PRED_V have the
+// values of CCN_PRED_EPS / CCN_PRED_V.
+// The v-parameterisation: the network output is y = v = a*noise - s*x0, and with the SAME table (c0 = s_t, c1 = a_t)
 //     x0 = clamp(c1*x - c0*y, -1, 1);  e = c0*x + c1*y;  then the tail above.
 // x0 is formed directly, not as the eps form applied to e: at the noisy end of the cosine table 1/c1 = 6.4e4 and s rounds to 1.0f,
 // so (x - c0*e)/c1 cancels to nothing, while c1*x - c0*y has no division and no cancellation (Parameterisation).
-__device__ __forceinline__ float sampler_update_v(float x, float y, float c0, float c1, float c2, float c3, float c4, float hist, float& x0_out)
-{
-    float x0 = raw_x0_v(x, y, c0, c1);
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    const float e = __fadd_rn(__fmul_rn(c0, x), __fmul_rn(c1, y));
-    return sampler_tail(x0, e, c2, c3, c4, hist, x0_out);
-}
-// `pred` is wave-uniform (a kernel argument): PRED_EPS / PRED_V have the values of CCN_PRED_EPS / CCN_PRED_V
 enum { PRED_EPS = 0, PRED_V = 1 };
-__device__ __forceinline__ float sampler_update_p(int pred, float x, float y, float c0, float c1, float c2, float c3, float c4, float hist,
-                                                  float& x0_out)
-{
-    return pred == PRED_V ? sampler_update_v(x, y, c0, c1, c2, c3, c4, hist, x0_out) : sampler_update(x, y, c0, c1, c2, c3, c4, hist, x0_out);
-}
-// Dynamic thresholding (Thresholding): the record's threshold s >= 1 replaces the static clamp,
-//     x0 = clamp(raw, -s, s) / s
-// and everything after it is the update above.  s == 1 is the static clamp bit for bit (a division by 1.0f is exact).  A NaN
-// threshold (a record whose quantile fell on a NaN) passes fmaxf / fminf through and makes every x0 of that record NaN.
+__device__ __forceinline__ float raw_x0_eps(float x, float e, float c0, float c1) { return __fdiv_rn(__fsub_rn(x, __fmul_rn(c0, e)), c1); }
+__device__ __forceinline__ float raw_x0_v(float x, float y, float c0, float c1) { return __fsub_rn(__fmul_rn(c1, x), __fmul_rn(c0, y)); }
 __device__ __forceinline__ float raw_x0_p(int pred, float x, float y, float c0, float c1)
 {
     return pred == PRED_V ? raw_x0_v(x, y, c0, c1) : raw_x0_eps(x, y, c0, c1);
 }
-__device__ __forceinline__ float sampler_update_thr(int pred, float s, float x, float y, float c0, float c1, float c2, float c3, float c4,
-                                                    float hist, float& x0_out)
-{
-    const float x0 = __fdiv_rn(fminf(fmaxf(raw_x0_p(pred, x, y, c0, c1), -s), s), s);
-    const float e = pred == PRED_V ? __fadd_rn(__fmul_rn(c0, x), __fmul_rn(c1, y)) : y;
-    return sampler_tail(x0, e, c2, c3, c4, hist, x0_out);
-}
-// The low-resolution guide (Low-resolution guide) needs the clamped x0 on its own: clamped_x0_p is the x0 of
-// sampler_update_p (thr false: the static clamp) or of sampler_update_thr (thr true: the record's threshold s), the same operations on
-// the same operands, and pred_e is their e.  ccn_guide.hip takes the block mean of clamped_x0_p and the LR form of the step kernel adds
-// the block's correction to the value of the same call, so the mean is taken over the very bits the step corrects.
+// The clamp.  thr false: the static one.  thr true, dynamic thresholding (Thresholding): the record's threshold
+// s >= 1 replaces it,  x0 = clamp(raw, -s, s) / s;  s == 1 is the static clamp bit for bit (a division by 1.0f is exact).  A NaN
+// threshold (a record whose quantile fell on a NaN) passes fmaxf / fminf through and makes every x0 of that record NaN.
 __device__ __forceinline__ float clamped_x0_p(int pred, bool thr, float s, float x, float y, float c0, float c1)
 {
     const float r = raw_x0_p(pred, x, y, c0, c1);
@@ -92,12 +61,36 @@ __device__ __forceinline__ float pred_e(int pred, float x, float y, float c0, fl
 {
     return pred == PRED_V ? __fadd_rn(__fmul_rn(c0, x), __fmul_rn(c1, y)) : y;
 }
-__device__ __forceinline__ float sampler_update_lr(int pred, bool thr, float s, float d, float x, float y, float c0, float c1, float c2, float c3,
-                                                   float c4, float hist, float& x0_out)
-{
-    const float x0 = __fadd_rn(clamped_x0_p(pred, thr, s, x, y, c0, c1), d);     // no re-clamp: |x0'| <= 1 + |d|
-    return sampler_tail(x0, pred_e(pred, x, y, c0, c1), c2, c3, c4, hist, x0_out);
-}
+// The ONE formation of y, x0 and e ("The same x0"): both head epilogues, every form of sampler_step_kernel, the
+// dynamic threshold's quantile (raw), the low-resolution guide's block mean (x0) and the guidance rescale's statistics (combine) go
+// through it, so the order statistic and the block mean are taken over the very bits the step clamps and corrects.  A kernel sets the
+// parts it has.  Where a flag is the kernel's template argument it is a compile-time constant here too (the struct is a local of an
+// inlined caller): a part that is off leaves no instruction behind -- no multiply by k = 1, no division by s = 1, no + 0.
+struct X0Form {
+    int pred = PRED_EPS;
+    float c0 = 0.f, c1 = 1.f;
+    bool guided = false, rescaled = false, thr = false, lr = false;
+    float w = 0.f, k = 1.f, s = 1.f;       // guided: the guidance scale; rescaled: the record's factor; thr: the record's threshold
+    // u + w (c - u) of the two network outputs, three separately rounded ops
+    __device__ __forceinline__ float combine(float c, float u) const { return __fadd_rn(u, __fmul_rn(w, __fsub_rn(c, u))); }
+    // "the network output" of everything below: the combine when guided (u is not looked at otherwise), times k when rescaled
+    __device__ __forceinline__ float y(float c, float u) const
+    {
+        if (guided) c = combine(c, u);
+        return rescaled ? __fmul_rn(k, c) : c;
+    }
+    __device__ __forceinline__ float raw(float x, float y) const { return raw_x0_p(pred, x, y, c0, c1); }
+    __device__ __forceinline__ float x0(float x, float y) const { return clamped_x0_p(pred, thr, s, x, y, c0, c1); }
+    __device__ __forceinline__ float e(float x, float y) const { return pred_e(pred, x, y, c0, c1); }
+    // the update of one element; lr: the low-resolution guide's correction d of the element's block is added to the clamped x0 first
+    // (no re-clamp: |x0'| <= 1 + |d|), and only then -- x0 + 0.0f would turn a -0.0f into +0.0f on its way to the history
+    __device__ __forceinline__ float step(float x, float y, float d, float c2, float c3, float c4, float hist, float& x0_out) const
+    {
+        float v = x0(x, y);
+        if (lr) v = __fadd_rn(v, d);
+        return sampler_tail(v, e(x, y), c2, c3, c4, hist, x0_out);
+    }
+};
 // The fixed-point form of a value in [-1, 1] that the guide's block sums add: v * 2^30 is exact in fp32 and the conversion rounds to
 // nearest even, so a sum of N^2 <= 4096 of them fits int64 with room and is the same in any order.
 __device__ __forceinline__ long long guide_fixed(float v) { return __float2ll_rn(__fmul_rn(v, 1073741824.0f)); }

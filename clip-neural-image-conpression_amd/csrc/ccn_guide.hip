@@ -9,9 +9,9 @@
 // guide_strip_kernel: a strip -- the N rows of one plane that hold one row of blocks -- is N W contiguous floats, and the strips of a
 // (B, C, H, W) tensor follow each other without a gap.  A workgroup of 256 owns whole strips (grid-stride over them): it zeroes one
 // int64 per block of the strip in LDS, every lane walks the strip's quads (VEC: every pointer 16-byte aligned, 16-byte loads; N W is
-// always a multiple of 4, so every strip then starts aligned) or its elements (4-byte loads), forms x0 by clamped_x0_p -- the function
-// the LR form of sampler_step_kernel calls, after the same combine and the same guidance-rescale multiply -- keeps a running sum while
-// it stays inside one block (a quad may straddle two blocks, N = 2, or two rows, W % 4 != 0: the column is tracked per element) and adds
+// always a multiple of 4, so every strip then starts aligned) or its elements (4-byte loads), forms x0 by X0Form::x0 of X0Form::y
+// (ccn_device.h) -- what the LR form of sampler_step_kernel goes through: the same combine, rescale multiply and clamp -- keeps a running sum
+// while it stays inside one block (a quad may straddle two blocks, N = 2, or two rows, W % 4 != 0: the column is tracked per element) and adds
 // it to the block's LDS word with one 64-bit integer atomic when it leaves the block.  After a barrier, lane t forms d of block t and
 // stores it.  No global partial sums, no zeroed scratch, no floating-point atomics, one launch.  A strip of more than kSlots blocks
 // (W / N > 1024) is walked once per kSlots blocks.
@@ -27,22 +27,16 @@
 #include <cstdint>
 #include <string>
 
-extern "C" void ccn_internal_set_error(const char* msg);   // ccn_api.hip: thread-local message behind ccn_last_error()
-
 namespace ccn {
 namespace {
-
-int gfail(int code, const std::string& msg) { ccn_internal_set_error(msg.c_str()); return code; }
 
 constexpr int kThreads = 256, kSlots = 1024;
 
 struct GuideArgs {
-    const float *x, *yc, *yu;          // PLAIN: x alone
-    const float *thr, *gscale;         // nullable, one float per record
+    X0Operands o;                      // PLAIN: x alone
     const float* guide;                // (strips, W / N)
     float* out;                        // (strips, W / N): d, or the block means (PLAIN)
-    int pred;
-    float w, c0, c1, strength;
+    float strength;
     int W, lgN, WB;                    // WB = W / N blocks per strip
     long long strips;                  // B C (H / N)
     int strips_per_record;             // C (H / N)
@@ -56,23 +50,21 @@ __global__ __launch_bounds__(kThreads) void guide_strip_kernel(GuideArgs a)
     const double scale = (double)(1u << (2 * a.lgN)) * 1073741824.0;
     for (long long sid = blockIdx.x; sid < a.strips; sid += gridDim.x) {
         const long long base = sid * (long long)SW;
-        const float* x = a.x + base;
-        float s = 1.0f, k = 1.0f;
+        const float* x = a.o.x + base;
+        X0Form f;
         const float *yc = nullptr, *yu = nullptr;
         if constexpr (!PLAIN) {
             const long long b = sid / a.strips_per_record;
-            yc = a.yc + base;
-            if (a.yu) yu = a.yu + base;
-            if (a.thr) s = a.thr[b];
-            if (a.gscale) k = a.gscale[b];
+            yc = a.o.out_c + base;
+            if (a.o.out_u) yu = a.o.out_u + base;
+            f.pred = a.o.pred; f.c0 = a.o.c0; f.c1 = a.o.c1; f.w = a.o.w;
+            f.guided = yu != nullptr; f.rescaled = a.o.gscale != nullptr; f.thr = a.o.thr != nullptr;
+            if (f.thr) f.s = a.o.thr[b];
+            if (f.rescaled) f.k = a.o.gscale[b];
         }
         auto value = [&](float xv, float yv, float uv) {
             if constexpr (PLAIN) return fminf(fmaxf(xv, -1.0f), 1.0f);
-            else {
-                if (yu) yv = __fadd_rn(uv, __fmul_rn(a.w, __fsub_rn(yv, uv)));
-                if (a.gscale) yv = __fmul_rn(k, yv);
-                return clamped_x0_p(a.pred, a.thr != nullptr, s, xv, yv, a.c0, a.c1);
-            }
+            else return f.x0(xv, f.y(yv, uv));
         };
         for (int blk0 = 0; blk0 < a.WB; blk0 += kSlots) {
             const int nb = a.WB - blk0 < kSlots ? a.WB - blk0 : kSlots;
@@ -147,23 +139,20 @@ bool guide_block_ok(int N, int H, int W)
     return N >= 2 && N <= 64 && !(N & (N - 1)) && H > 0 && W > 0 && H % N == 0 && W % N == 0 && (int64_t)W * N <= INT32_MAX;
 }
 
-hipError_t launch_lowres_delta(const float* x, const float* out_c, const float* out_u, int pred, float w, float c0, float c1, int B, int C, int H,
-                               int W, int N, const float* guide, float strength, const float* thr, const float* gscale, float* delta,
-                               hipStream_t s)
+hipError_t launch_lowres_delta(const X0Operands& o, int C, int H, int W, int N, const float* guide, float strength, float* delta, hipStream_t s)
 {
-    if (B <= 0 || B > 65535 || !x || !out_c || !guide || !delta) return hipErrorInvalidValue;
+    if (o.records <= 0 || o.records > 65535 || !o.x || !o.out_c || !guide || !delta) return hipErrorInvalidValue;
     GuideArgs a{};
-    a.x = x; a.yc = out_c; a.yu = out_u; a.thr = thr; a.gscale = gscale; a.guide = guide; a.out = delta;
-    a.pred = pred; a.w = w; a.c0 = c0; a.c1 = c1; a.strength = strength;
-    const bool vec = !(((uintptr_t)x | (uintptr_t)out_c | (uintptr_t)out_u) & 15);
-    return launch_strips<false>(a, (int64_t)B * C, C, H, W, N, vec, s);
+    a.o = o; a.guide = guide; a.out = delta; a.strength = strength;
+    const bool vec = !(((uintptr_t)o.x | (uintptr_t)o.out_c | (uintptr_t)o.out_u) & 15);
+    return launch_strips<false>(a, o.records * C, C, H, W, N, vec, s);
 }
 
 hipError_t launch_block_mean(const float* x, int64_t planes, int H, int W, int N, float* out, hipStream_t s)
 {
     if (!x || !out) return hipErrorInvalidValue;
     GuideArgs a{};
-    a.x = x; a.out = out;
+    a.o.x = const_cast<float*>(x); a.out = out;
     return launch_strips<true>(a, planes, 1, H, W, N, !((uintptr_t)x & 15), s);
 }
 
@@ -174,19 +163,19 @@ using namespace ccn;
 // the block geometry every guide entry takes (ccn_api.hip's checks call it too)
 int ccn::guide_check(int32_t H, int32_t W, int32_t N)
 {
-    if (N < 2 || N > 64 || (N & (N - 1))) return gfail(CCN_EINVAL, "N must be a power of two in 2..64");
-    if (H <= 0 || W <= 0) return gfail(CCN_EINVAL, "H and W must be positive");
-    if (H % N || W % N) return gfail(CCN_EINVAL, "H and W must be multiples of N: whole blocks only");
-    if ((int64_t)W * N > INT32_MAX) return gfail(CCN_EINVAL, "N rows of the image must hold fewer than 2^31 elements");
+    if (N < 2 || N > 64 || (N & (N - 1))) return fail(CCN_EINVAL, "N must be a power of two in 2..64");
+    if (H <= 0 || W <= 0) return fail(CCN_EINVAL, "H and W must be positive");
+    if (H % N || W % N) return fail(CCN_EINVAL, "H and W must be multiples of N: whole blocks only");
+    if ((int64_t)W * N > INT32_MAX) return fail(CCN_EINVAL, "N rows of the image must hold fewer than 2^31 elements");
     return CCN_OK;
 }
 
 int ccn_block_mean(const float* x_dev, int64_t planes, int32_t H, int32_t W, int32_t N, float* out_dev, void* stream)
 {
-    if (!x_dev || !out_dev) return gfail(CCN_EINVAL, "a tensor pointer is NULL");
-    if (planes <= 0) return gfail(CCN_EINVAL, "planes must be positive");
+    if (!x_dev || !out_dev) return fail(CCN_EINVAL, "a tensor pointer is NULL");
+    if (planes <= 0) return fail(CCN_EINVAL, "planes must be positive");
     if (int rc = guide_check(H, W, N)) return rc;
-    if (launch_block_mean(x_dev, planes, H, W, N, out_dev, (hipStream_t)stream) != hipSuccess) return gfail(CCN_EHIP, "block_mean launch failed");
+    if (launch_block_mean(x_dev, planes, H, W, N, out_dev, (hipStream_t)stream) != hipSuccess) return fail(CCN_EHIP, "block_mean launch failed");
     return CCN_OK;
 }
 
@@ -194,15 +183,16 @@ int ccn_lowres_delta(const float* x_dev, const float* out_c_dev, const float* ou
                      int32_t C, int32_t H, int32_t W, int32_t N, const float* guide_dev, float strength, const float* thr_dev,
                      const float* gscale_dev, float* delta_dev, void* stream)
 {
-    if (!x_dev || !out_c_dev || !guide_dev || !delta_dev) return gfail(CCN_EINVAL, "a tensor pointer is NULL");
-    if (pred != CCN_PRED_EPS && pred != CCN_PRED_V) return gfail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
-    if (B <= 0 || B > 65535) return gfail(CCN_EINVAL, "B must be in [1, 65535]: one grid row per record in the step that follows");
-    if (C <= 0) return gfail(CCN_EINVAL, "C must be positive");
+    X0Operands o;
+    o.x = const_cast<float*>(x_dev); o.out_c = out_c_dev; o.out_u = out_u_dev; o.gscale = gscale_dev; o.thr = thr_dev;
+    o.pred = pred; o.w = w; o.c0 = c0; o.c1 = c1; o.records = B;
+    if (!guide_dev || !delta_dev) return fail(CCN_EINVAL, "a tensor pointer is NULL");
+    if (C <= 0) return fail(CCN_EINVAL, "C must be positive");
     if (int rc = guide_check(H, W, N)) return rc;
-    if ((int64_t)C * H * W >= kThrMaxPerRecord) return gfail(CCN_EINVAL, "a record must hold fewer than 2^34 elements");
-    if (!(strength > 0.0f && strength <= 1.0f)) return gfail(CCN_EINVAL, "the guide strength must be in (0, 1]");
-    if (launch_lowres_delta(x_dev, out_c_dev, out_u_dev, pred, w, c0, c1, B, C, H, W, N, guide_dev, strength, thr_dev, gscale_dev, delta_dev,
-                            (hipStream_t)stream) != hipSuccess)
-        return gfail(CCN_EHIP, "lowres_delta launch failed");
+    o.per_record = (int64_t)C * H * W;
+    if (int rc = check_x0_operands(o, false)) return rc;
+    if (!(strength > 0.0f && strength <= 1.0f)) return fail(CCN_EINVAL, "the guide strength must be in (0, 1]");
+    if (launch_lowres_delta(o, C, H, W, N, guide_dev, strength, delta_dev, (hipStream_t)stream) != hipSuccess)
+        return fail(CCN_EHIP, "lowres_delta launch failed");
     return CCN_OK;
 }

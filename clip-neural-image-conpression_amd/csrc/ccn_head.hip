@@ -183,7 +183,9 @@ __global__ __launch_bounds__(256, 4) void head_kernel(const ConvArgs a, const un
             const float c4 = a.x0_hist ? a.c4 : 0.f;
             const float hv = c4 != 0.f ? a.x0_hist[idx] : 0.f;
             float x0v;
-            float xn = sampler_update_p(a.pred, xs, e, a.c0, a.c1, a.c2, a.c3, c4, hv, x0v);
+            X0Form f;
+            f.pred = a.pred; f.c0 = a.c0; f.c1 = a.c1;
+            float xn = f.step(xs, e, 0.f, a.c2, a.c3, c4, hv, x0v);
             if (a.noise) xn = __fadd_rn(xn, __fmul_rn(a.sigma, a.noise[idx]));      // eta > 0 (diffusion/ddim.py:44-45)
             if (a.x0_hist) a.x0_hist[idx] = x0v;
             a.x_state[idx] = xn;

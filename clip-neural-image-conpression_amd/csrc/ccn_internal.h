@@ -6,6 +6,14 @@
 
 #include <stdlib.h>
 
+#include <string>
+
+// ---- failures ------------------------------------------------------------------------------------
+// Every entry of include/ccn_hip.h, whichever file defines it, reports through the thread-local message behind ccn_last_error()
+// (ccn_api.hip owns it): `return fail(CCN_EINVAL, "...")`.
+extern "C" void ccn_internal_set_error(const char* msg);
+namespace ccn { inline int fail(int code, const std::string& msg) { ccn_internal_set_error(msg.c_str()); return code; } }
+
 // ---- diagnostics ---------------------------------------------------------------------------------
 // The product library (plain `make`) reads NO environment variable and contains no ablation code: every A/B switch
 // (kernel choice, split-K policy, pre-pass placement ...) is fixed at its measured default, the CCN_DBG / CCN_WG_DBG
@@ -151,8 +159,8 @@ struct ConvArgs {
     float wscale_inv;       // f16x3: 1 / (power-of-two scale of the packed weights), applied to the accumulator before the bias
     float* x0_hist;         // head, multistep sampler: the previous step's clamped x0, NCHW fp32 like x_state; read when c4 != 0, then
                             // overwritten with this step's; null = the plain DDIM update
-    float c4;               // head: coefficient of (x0 - x0_hist) in the update (sampler_update in ccn_device.h)
-    int pred;               // head: what the network output is, 0 = eps, 1 = v (CCN_PRED_*): selects sampler_update / sampler_update_v
+    float c4;               // head: coefficient of (x0 - x0_hist) in the update (sampler_tail in ccn_device.h)
+    int pred;               // head: what the network output is, 0 = eps, 1 = v (CCN_PRED_*): X0Form::pred in ccn_device.h
     __host__ __device__ int tapinfo_dy(int i) const { return (tapinfo[i] & 3) - 1; }
     __host__ __device__ int tapinfo_dx(int i) const { return ((tapinfo[i] >> 2) & 3) - 1; }
     __host__ __device__ int tapinfo_w(int i) const { return tapinfo[i] >> 4; }
@@ -266,60 +274,62 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
                          float* y, int R, int K, int N, int act_silu, hipStream_t s);
 
 // ---- elementwise ---------------------------------------------------------------------------------
-// the stand-alone sampler update, either parameterisation (pred = CCN_PRED_*): x_dup, hist, out_u and noise are nullable -- no out_u:
-// out_c is the prediction itself; no hist: c4 is not applied and no history is written (hist is read only when c4 != 0).  `seeds`
-// (nullable; one uint64 per record of per_record elements, n a multiple of it) with sigma > 0: the noise is draw `draw` of each record,
-// generated in the kernel, and `noise` is not read.  `thr` (nullable; one float per record, per_record as above): the record's dynamic
-// threshold replaces the +-1 clamp of x0.  `gscale` (nullable; one float per record likewise): the record's guidance-rescale factor
-// multiplies the (combined) output before anything else reads it.  A caller fills the fields it uses; the rest stay absent.
+// What the post-network launches of one step form x0 from, named once: the step, the dynamic threshold, the low-resolution guide and
+// the guidance rescale take this record, so that they read the same operands ("The same x0").  `records` records
+// of `per_record` elements.  out_u (nullable): guided, y = out_u + w (out_c - out_u), else y = out_c.  gscale, thr (nullable; one float
+// per record): the guidance-rescale factor multiplies y before anything else reads it; the dynamic threshold replaces the +-1 clamp.
+struct X0Operands {
+    float* x = nullptr;                    // (the step updates it in place; the other launches only read it)
+    const float *out_c = nullptr, *out_u = nullptr, *gscale = nullptr, *thr = nullptr;
+    int pred = 0;                          // CCN_PRED_EPS
+    float w = 0.f, c0 = 0.f, c1 = 0.f;
+    int64_t per_record = 0, records = 0;
+};
+// what every launch below needs of the record, as a CCN_* code with the message set: the pointers it reads (`pointers`; a planner that
+// has none yet passes false), a known prediction, 1..65535 records (one grid row each) of fewer than 2^34 elements.  for_rescale: the
+// guidance rescale's statistics -- an unbiased std needs two elements, and both outputs instead of the state.
+constexpr int64_t kThrMaxPerRecord = (int64_t)1 << 34;
+int check_x0_operands(const X0Operands& o, bool for_rescale, bool pointers = true);
+
+// the stand-alone sampler update, either parameterisation: x_dup, hist and noise are nullable -- no hist: c4 is not applied and no
+// history is written (hist is read only when c4 != 0).  `seeds` (nullable; one uint64 per record) with sigma > 0: the noise is draw
+// `draw` of each record, generated in the kernel, and `noise` is not read.  Without seeds, thr, gscale and delta the state is one run
+// of records * per_record elements (the older entries: one record of n).
 struct SamplerStep {
-    float* x = nullptr;
+    X0Operands o;
     float* x_dup = nullptr;
     float* hist = nullptr;
-    const float* out_c = nullptr;
-    const float* out_u = nullptr;
     const float* noise = nullptr;
-    int pred = 0;                          // CCN_PRED_EPS
-    float w = 0.f;
-    float c[5] = {0.f, 0.f, 0.f, 0.f, 0.f};   // c0..c4
-    float sigma = 0.f;
-    int64_t n = 0;
+    float c2 = 0.f, c3 = 0.f, c4 = 0.f, sigma = 0.f;
     const uint64_t* seeds = nullptr;
     uint32_t draw = 0;
-    int64_t per_record = 0;
-    const float* thr = nullptr;
-    const float* gscale = nullptr;
     // the low-resolution guide (nullable): launch_lowres_delta's table of this state, (records, C, H / lr_N, lr_W / lr_N); element j
     // of a record adds the d of its block to the clamped x0.  lr_W, lr_N: the image's width and the block size (per_record = C H lr_W)
     const float* delta = nullptr;
     int lr_W = 0, lr_N = 0;
+    int lr_lgN = 0, lr_WB = 0;             // (set by launch_sampler_step: log2 lr_N, lr_W / lr_N)
 };
 hipError_t launch_sampler_step(const SamplerStep& a, hipStream_t s);
 // the low-resolution guide (ccn_guide.hip; ccn_lowres_delta and ccn_block_mean in ccn_hip.h).  guide_block_ok: N a power of two in
 // 2..64 that divides H and W, N rows below 2^31 elements; guide_check: the same as a CCN_* code with the message set.
 // launch_lowres_delta: delta[b][c][i][j] = (float)(strength (guide - block mean of the clamped x0)) with x0 formed as the launch above
-// forms it (same combine, gscale, thr); one launch, nothing else.  The caller has checked the arguments.
+// forms it (same combine, gscale, thr; per_record = C H W); one launch, nothing else.  The caller has checked the arguments.
 bool guide_block_ok(int N, int H, int W);
 int guide_check(int32_t H, int32_t W, int32_t N);
-hipError_t launch_lowres_delta(const float* x, const float* out_c, const float* out_u, int pred, float w, float c0, float c1, int B, int C, int H,
-                               int W, int N, const float* guide, float strength, const float* thr, const float* gscale, float* delta,
-                               hipStream_t s);
+hipError_t launch_lowres_delta(const X0Operands& o, int C, int H, int W, int N, const float* guide, float strength, float* delta, hipStream_t s);
 hipError_t launch_block_mean(const float* x, int64_t planes, int H, int W, int N, float* out, hipStream_t s);
 // the dynamic threshold of every record (ccn_threshold.hip; ccn_x0_threshold in ccn_hip.h): thr[b] = min(max(Q_p(|x0_b|), 1), max_value)
-// of the raw x0 the launch above would form.  `scratch`: x0_threshold_scratch_bytes(B) bytes, 16-byte aligned, any contents.  The
-// caller has checked the arguments (0 <= p <= 1, 1 <= B <= 65535, 0 < per < 2^34).  Five launches, nothing else.
-constexpr int64_t kThrMaxPerRecord = (int64_t)1 << 34;
+// of the raw x0 the launch above would form (o.thr is not read).  `scratch`: x0_threshold_scratch_bytes(records) bytes, 16-byte
+// aligned, any contents.  The caller has checked the arguments (check_x0_operands, 0 <= p <= 1).  Five launches, nothing else.
 size_t x0_threshold_scratch_bytes(int B);
-hipError_t launch_x0_threshold(const float* x, const float* out_c, const float* out_u, int pred, float w, float c0, float c1, int B, int64_t per,
-                               double p, float max_value, float* thr, void* scratch, hipStream_t s, const float* gscale = nullptr);
+hipError_t launch_x0_threshold(const X0Operands& o, double p, float max_value, float* thr_out, void* scratch, hipStream_t s);
 // the guidance-rescale factor of every record (ccn_rescale.hip; ccn_guidance_rescale in ccn_hip.h): k[b] = phi std(out_c[b]) / std(y[b])
 // + 1 - phi, y the combined output.  `partials`: guidance_rescale_partials(scratch, B) of a scratch of guidance_rescale_scratch_bytes
 // bytes (its head holds B floats: the factors of a caller that keeps them there), 16-byte aligned, any contents.  The caller has
-// checked the arguments (1 <= B <= 65535, 2 <= per < 2^34).  Two launches, nothing else.
+// checked the arguments (check_x0_operands with for_rescale).  Two launches, nothing else.
 size_t guidance_rescale_scratch_bytes(int B, int64_t per);
 void* guidance_rescale_partials(void* scratch, int B);
-hipError_t launch_guidance_rescale(const float* out_c, const float* out_u, float w, double phi, int B, int64_t per, float* k, void* partials,
-                                   hipStream_t s);
+hipError_t launch_guidance_rescale(const X0Operands& o, double phi, float* k_out, void* partials, hipStream_t s);
 hipError_t launch_q_sample(float* out, const float* x0, const float* noise, const float* a, const float* sg,
                            int B, int64_t per, hipStream_t s);
 hipError_t launch_predict_x0(float* out, const float* xt, const float* eps, const float* a, const float* sg,

@@ -19,6 +19,9 @@
 // 32 consecutive rows read at one chunk index hit 16 distinct 16-B slots per ds_read_b128 lane group.
 #include "ccn_conv_tile.h"
 
+#include <array>
+#include <utility>
+
 namespace ccn {
 
 __host__ __device__ constexpr int cmax(int a, int b) { return a > b ? a : b; }
@@ -232,7 +235,9 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a)
                         const float c4 = a.x0_hist ? a.c4 : 0.f;
                         const float hv = c4 != 0.f ? a.x0_hist[idx] : 0.f;
                         float x0;
-                        float xn = sampler_update_p(a.pred, x, e, a.c0, a.c1, a.c2, a.c3, c4, hv, x0);
+                        X0Form f;
+                        f.pred = a.pred; f.c0 = a.c0; f.c1 = a.c1;
+                        float xn = f.step(x, e, 0.f, a.c2, a.c3, c4, hv, x0);
                         if (a.noise) xn = __fadd_rn(xn, __fmul_rn(a.sigma, a.noise[idx]));      // eta > 0 (diffusion/ddim.py:44-45)
                         if (a.x0_hist) a.x0_hist[idx] = x0;
                         a.x_state[idx] = xn;
@@ -812,7 +817,7 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
 }
 
 // ---- elementwise ----------------------------------------------------------------------------------------------
-// The stand-alone sampler update, for either parameterisation (`pred`, wave-uniform: sampler_update_p in ccn_device.h), every op rounded
+// The stand-alone sampler update, for either parameterisation (`pred`, wave-uniform: X0Form in ccn_device.h), every op rounded
 // to fp32 on its own.  y = out_c, or out_u + w*(out_c - out_u) when out_u is given (classifier-free guidance); hist (nullable) is read
 // when c4 != 0 and receives the clamped x0; noise (nullable) adds sigma*noise; x is updated in place and x_dup (nullable) receives the
 // same values: the unconditional half of the guided loop's state.  VEC: every pointer is 16-byte aligned, four elements per lane and
@@ -821,29 +826,38 @@ hipError_t launch_linear(const float* xa, const float* xb, int a_div, int b_mod,
 // elements, the blocks of row blockIdx.y work on record b = blockIdx.y alone (one seed load per lane, no division), and element j
 // of it is draw_quad / draw_element(seeds[b], draw, j).  VEC then also means per % 4 == 0, so that every record starts 16-byte
 // aligned and a lane's four elements are one quad of it.  The unseeded instantiations (gridDim.y == 1) are the kernel as it was.
-// THR: the same grid rows, and record b's dynamic threshold thr[b] replaces the +-1 clamp of x0 (sampler_update_thr; DESIGN.md
+// THR: the same grid rows, and record b's dynamic threshold thr[b] replaces the +-1 clamp of x0 (X0Form::thr; DESIGN.md
 // section 1, Thresholding); a noise tensor is then walked by record too.  Without THR nothing of it is compiled in.
 // RS: the same grid rows, and record b's guidance-rescale factor gscale[b] multiplies y right after the combine (DESIGN.md section 1,
 // Guidance rescale): everything downstream -- the raw x0, e, the history -- is formed from k y.  Without RS nothing of it is compiled in.
-// LR: the same grid rows, and element j of record b adds delta[b][block(j)] to its x0 right after the clamp (sampler_update_lr; DESIGN.md
+// LR: the same grid rows, and element j of record b adds delta[b][block(j)] to its x0 right after the clamp (X0Form::lr; DESIGN.md
 // section 1, Low-resolution guide): with W the image's width, N = 2^lgN the block size and WB = W / N, row R = j / W of the record's
 // C H rows lies in strip R >> lgN (H % N == 0: no strip crosses a plane) and block(j) = (R >> lgN) WB + ((j - R W) >> lgN).  A quad
 // may straddle two blocks or two rows, so the row and the column are carried per element.  Without LR nothing of it is compiled in.
+// The argument record comes by value.  No two of its tensors overlap (the caller's contract); the __restrict__ on the local copies
+// records that, but the compiler makes little of it on locals -- nothing here needs it: an iteration loads everything it reads before
+// its first store.
 template <bool VEC, bool SEEDED, bool THR, bool RS, bool LR>
-__global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x_dup, float* __restrict__ hist, const float* __restrict__ out_c,
-                                    const float* __restrict__ out_u, const float* __restrict__ noise, int pred, float w, float c0, float c1,
-                                    float c2, float c3, float c4, float sigma, int64_t n, const uint64_t* __restrict__ seeds, uint32_t draw,
-                                    int64_t per, const float* __restrict__ thr, const float* __restrict__ gscale,
-                                    const float* __restrict__ delta, int lrW, int lgN, int lrWB)
+__global__ void sampler_step_kernel(const SamplerStep a)
 {
+    float *__restrict__ x = a.o.x, *__restrict__ x_dup = a.x_dup, *__restrict__ hist = a.hist;
+    const float *__restrict__ out_c = a.o.out_c, *__restrict__ out_u = a.o.out_u, *__restrict__ noise = a.noise, *__restrict__ delta = a.delta;
+    const int64_t per = a.o.per_record;
+    const int lrW = a.lr_W, lgN = a.lr_lgN, lrWB = a.lr_WB;
+    const uint32_t draw = a.draw;
+    const float c2 = a.c2, c3 = a.c3, sigma = a.sigma;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+    int64_t n = a.o.records * per;
     uint64_t seed = 0;
-    float s = 1.0f, k = 1.0f;
+    // one element's y, x0, e and update: the rescale, the threshold and the guide only where they were asked for
+    X0Form f;
+    f.pred = a.o.pred; f.c0 = a.o.c0; f.c1 = a.o.c1; f.w = a.o.w;
+    f.rescaled = RS; f.thr = THR; f.lr = LR;
     if constexpr (SEEDED || THR || RS || LR) {                      // this record's slice of every tensor
         const int64_t off = (int64_t)blockIdx.y * per;
-        if constexpr (SEEDED) seed = seeds[blockIdx.y];
-        if constexpr (THR) s = thr[blockIdx.y];
-        if constexpr (RS) k = gscale[blockIdx.y];
+        if constexpr (SEEDED) seed = a.seeds[blockIdx.y];
+        if constexpr (THR) f.s = a.o.thr[blockIdx.y];
+        if constexpr (RS) f.k = a.o.gscale[blockIdx.y];
         x += off; out_c += off; n = per;
         if (x_dup) x_dup += off;
         if (hist) hist += off;
@@ -851,14 +865,9 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         if constexpr (THR || RS || LR) { if (noise) noise += off; }
         if constexpr (LR) delta += (int64_t)blockIdx.y * ((per >> lgN) >> lgN);
     }
+    f.guided = out_u != nullptr;
     const int64_t n4 = VEC ? n / 4 : 0;
-    if (!hist) c4 = 0.f;
-    // one element's update: the threshold form only where it was asked for
-    auto update = [&](float xv, float yv, float hv, float& p, float dv) {
-        if constexpr (LR) return sampler_update_lr(pred, THR, s, dv, xv, yv, c0, c1, c2, c3, c4, hv, p);
-        else if constexpr (THR) return sampler_update_thr(pred, s, xv, yv, c0, c1, c2, c3, c4, hv, p);
-        else return sampler_update_p(pred, xv, yv, c0, c1, c2, c3, c4, hv, p);
-    };
+    const float c4 = hist ? a.c4 : 0.f;
     // LR: the d of element j and of the three after it (row R, column col of the record's rows; one division per call)
     auto block_d = [&](int64_t j, float* d4, int count) {
         int64_t R = per <= 0x7fffffff ? (int64_t)((uint32_t)j / (uint32_t)lrW) : j / lrW;
@@ -868,23 +877,20 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
             if (++col == lrW) { col = 0; ++R; }
         }
     };
+    // (u is loaded, and the guided test made, once per quad / element: the guided arm is the combine, the other leaves it out)
+    auto y4 = [&](float4 c, float4 u) { return make_float4(f.y(c.x, u.x), f.y(c.y, u.y), f.y(c.z, u.z), f.y(c.w, u.w)); };
     for (int64_t q = tid; q < n4; q += nthr) {
         const float4 xv = ((const float4*)x)[q];
         float4 yv = ((const float4*)out_c)[q];
-        if (out_u) {
-            const float4 uv = ((const float4*)out_u)[q];
-            yv.x = __fadd_rn(uv.x, __fmul_rn(w, __fsub_rn(yv.x, uv.x))); yv.y = __fadd_rn(uv.y, __fmul_rn(w, __fsub_rn(yv.y, uv.y)));
-            yv.z = __fadd_rn(uv.z, __fmul_rn(w, __fsub_rn(yv.z, uv.z))); yv.w = __fadd_rn(uv.w, __fmul_rn(w, __fsub_rn(yv.w, uv.w)));
-        }
-        if constexpr (RS) { yv.x = __fmul_rn(k, yv.x); yv.y = __fmul_rn(k, yv.y); yv.z = __fmul_rn(k, yv.z); yv.w = __fmul_rn(k, yv.w); }
+        yv = f.guided ? y4(yv, ((const float4*)out_u)[q]) : y4(yv, make_float4(0.f, 0.f, 0.f, 0.f));
         float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), o, p;
         if (c4 != 0.f) hv = ((const float4*)hist)[q];
         float dv[4] = {0.f, 0.f, 0.f, 0.f};
         if constexpr (LR) block_d(q * 4, dv, 4);
-        o.x = update(xv.x, yv.x, hv.x, p.x, dv[0]);
-        o.y = update(xv.y, yv.y, hv.y, p.y, dv[1]);
-        o.z = update(xv.z, yv.z, hv.z, p.z, dv[2]);
-        o.w = update(xv.w, yv.w, hv.w, p.w, dv[3]);
+        o.x = f.step(xv.x, yv.x, dv[0], c2, c3, c4, hv.x, p.x);
+        o.y = f.step(xv.y, yv.y, dv[1], c2, c3, c4, hv.y, p.y);
+        o.z = f.step(xv.z, yv.z, dv[2], c2, c3, c4, hv.z, p.z);
+        o.w = f.step(xv.w, yv.w, dv[3], c2, c3, c4, hv.w, p.w);
         if (SEEDED || noise) {
             float4 nv;
             if constexpr (SEEDED) nv = draw_quad(seed, draw, (uint32_t)q);
@@ -897,13 +903,11 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         if (x_dup) ((float4*)x_dup)[q] = o;
     }
     for (int64_t i = n4 * 4 + tid; i < n; i += nthr) {
-        float y = out_c[i];
-        if (out_u) { const float u = out_u[i]; y = __fadd_rn(u, __fmul_rn(w, __fsub_rn(y, u))); }
-        if constexpr (RS) y = __fmul_rn(k, y);
+        const float y = f.guided ? f.y(out_c[i], out_u[i]) : f.y(out_c[i], 0.f);
         const float hv = c4 != 0.f ? hist[i] : 0.f;
         float p, dv = 0.f;
         if constexpr (LR) block_d(i, &dv, 1);
-        float xn = update(x[i], y, hv, p, dv);
+        float xn = f.step(x[i], y, dv, c2, c3, c4, hv, p);
         if constexpr (SEEDED) xn = __fadd_rn(xn, __fmul_rn(sigma, draw_element(seed, draw, i)));
         else if (noise) xn = __fadd_rn(xn, __fmul_rn(sigma, noise[i]));
         if (hist) hist[i] = p;
@@ -911,52 +915,39 @@ __global__ void sampler_step_kernel(float* __restrict__ x, float* __restrict__ x
         if (x_dup) x_dup[i] = xn;
     }
 }
-// seeds given and sigma > 0: the seeded form; thr given: the threshold form; gscale given: the rescaled form; delta given: the
-// low-resolution-guide form; each walks the state record by record, one grid row each (the caller has checked per > 0 and
-// n % per == 0, and with delta that lr_N is a power of two and per a multiple of lr_W lr_N).  With seeds `noise` is not read.
-hipError_t launch_sampler_step(const SamplerStep& a, hipStream_t s)
+// the 32 instantiations, indexed by the five bits VEC SEEDED THR RS LR (most significant first)
+using StepLaunch = void (*)(const SamplerStep&, dim3, hipStream_t);
+template <bool... F>
+void step_launch(const SamplerStep& a, dim3 grid, hipStream_t s) { hipLaunchKernelGGL((sampler_step_kernel<F...>), grid, dim3(256), 0, s, a); }
+template <size_t... I>
+constexpr std::array<StepLaunch, sizeof...(I)> step_table(std::index_sequence<I...>)
 {
-    const int64_t n = a.n, per = a.per_record;
-    const float *thr = a.thr, *gscale = a.gscale, *delta = a.delta;
+    return {{&step_launch<(I >> 4 & 1) != 0, (I >> 3 & 1) != 0, (I >> 2 & 1) != 0, (I >> 1 & 1) != 0, (I & 1) != 0>...}};
+}
+// seeds given and sigma > 0: the seeded form; thr given: the threshold form; gscale given: the rescaled form; delta given: the
+// low-resolution-guide form; each walks the state record by record, one grid row each (the caller has checked the record, and with
+// delta that lr_N is a power of two and per_record a multiple of lr_W lr_N).  With seeds `noise` is not read.
+hipError_t launch_sampler_step(const SamplerStep& step, hipStream_t s)
+{
+    SamplerStep a = step;
+    const int64_t per = a.o.per_record, n = a.o.records * per;
     const bool seeded = a.seeds && a.sigma > 0.f;
-    const float* noise = seeded ? nullptr : a.noise;
-    const bool rowed = seeded || thr || gscale || delta;
-    int lgN = 0;
-    if (delta) {
+    if (seeded) a.noise = nullptr;
+    const bool rowed = seeded || a.o.thr || a.o.gscale || a.delta;
+    if (a.delta) {
         if (a.lr_N < 2 || (a.lr_N & (a.lr_N - 1)) || a.lr_W <= 0 || a.lr_W % a.lr_N || per <= 0 || per % ((int64_t)a.lr_W * a.lr_N)) return hipErrorInvalidValue;
-        while ((1 << lgN) < a.lr_N) ++lgN;
+        a.lr_lgN = 0;
+        while ((1 << a.lr_lgN) < a.lr_N) ++a.lr_lgN;
+        a.lr_WB = a.lr_W / a.lr_N;
     }
-    const int lrWB = delta ? a.lr_W / a.lr_N : 0;
-    if (rowed && (per <= 0 || n % per || n / per > 65535)) return hipErrorInvalidValue;      // one grid row per record
-    const bool vec = !(((uintptr_t)a.x | (uintptr_t)a.x_dup | (uintptr_t)a.hist | (uintptr_t)a.out_c | (uintptr_t)a.out_u | (uintptr_t)noise) & 15) &&
+    if (rowed && (per <= 0 || a.o.records <= 0 || a.o.records > 65535)) return hipErrorInvalidValue;      // one grid row per record
+    const bool vec = !(((uintptr_t)a.o.x | (uintptr_t)a.x_dup | (uintptr_t)a.hist | (uintptr_t)a.o.out_c | (uintptr_t)a.o.out_u | (uintptr_t)a.noise) & 15) &&
                      !(rowed && (per & 3));
-    const int64_t rows = rowed ? n / per : 1, row = rowed ? per : n;
+    const int64_t rows = rowed ? a.o.records : 1, row = rowed ? per : n;
     const int64_t work = vec ? (row + 3) / 4 : row, blocks = (work + 255) / 256;
     const int gx = (int)(blocks < 2048 ? (blocks > 0 ? blocks : 1) : 2048);        // 256 CUs x 8 blocks, grid-stride beyond
-    const dim3 grid(gx, (unsigned)rows);
-#define CCN_STEP_ARGS a.x, a.x_dup, a.hist, a.out_c, a.out_u, noise, a.pred, a.w, a.c[0], a.c[1], a.c[2], a.c[3], a.c[4], a.sigma, n, a.seeds, a.draw, per, thr, gscale, delta, a.lr_W, lgN, lrWB
-#define CCN_STEP_GO4(SEEDED, THR, RS, LR)                                                                                    \
-    do {                                                                                                                     \
-        if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, SEEDED, THR, RS, LR>), grid, dim3(256), 0, s, CCN_STEP_ARGS);  \
-        else hipLaunchKernelGGL((sampler_step_kernel<false, SEEDED, THR, RS, LR>), grid, dim3(256), 0, s, CCN_STEP_ARGS);     \
-    } while (0)
-#define CCN_STEP_GO(SEEDED, THR)                                                                                             \
-    do {                                                                                                                     \
-        if (gscale) {                                                                                                        \
-            if (delta) CCN_STEP_GO4(SEEDED, THR, true, true);                                                                \
-            else CCN_STEP_GO4(SEEDED, THR, true, false);                                                                     \
-        } else {                                                                                                             \
-            if (delta) CCN_STEP_GO4(SEEDED, THR, false, true);                                                               \
-            else CCN_STEP_GO4(SEEDED, THR, false, false);                                                                    \
-        }                                                                                                                    \
-    } while (0)
-    if (seeded && thr) CCN_STEP_GO(true, true);
-    else if (seeded) CCN_STEP_GO(true, false);
-    else if (thr) CCN_STEP_GO(false, true);
-    else CCN_STEP_GO(false, false);
-#undef CCN_STEP_GO
-#undef CCN_STEP_GO4
-#undef CCN_STEP_ARGS
+    static constexpr auto table = step_table(std::make_index_sequence<32>());
+    table[vec << 4 | seeded << 3 | (a.o.thr != nullptr) << 2 | (a.o.gscale != nullptr) << 1 | (a.delta != nullptr)](a, dim3(gx, (unsigned)rows), s);
     return hipGetLastError();
 }
 

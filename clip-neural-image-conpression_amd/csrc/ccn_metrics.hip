@@ -28,12 +28,8 @@
 #include <cstdint>
 #include <string>
 
-extern "C" void ccn_internal_set_error(const char* msg);   // ccn_api.hip: thread-local message behind ccn_last_error()
-
 namespace ccn {
 namespace {
-
-int mfail(int code, const std::string& msg) { ccn_internal_set_error(msg.c_str()); return code; }
 
 constexpr int SC_WIN = 7;
 constexpr int SC_TX = 64, SC_TY = 16;                                // window positions per workgroup
@@ -227,13 +223,13 @@ ScoreGeom score_geom(int B, int C, int H, int W)
 int score(const void* recon, bool f32, const uint8_t* orig, uint8_t* recon_u8_out, double* out, int B, int C, int H, int W, void* scratch,
           size_t scratch_bytes, hipStream_t s)
 {
-    if (!recon || !orig || !out || !scratch) return mfail(CCN_EINVAL, "a buffer is NULL");
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return mfail(CCN_EINVAL, "B, C, H and W must be positive");
+    if (!recon || !orig || !out || !scratch) return fail(CCN_EINVAL, "a buffer is NULL");
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(CCN_EINVAL, "B, C, H and W must be positive");
     const ScoreGeom g = score_geom(B, C, H, W);
-    if (g.per_rec > INT32_MAX || g.total > INT32_MAX) return mfail(CCN_EINVAL, "too many tiles");
-    if (((uintptr_t)scratch & 7) != 0 || ((uintptr_t)out & 7) != 0) return mfail(CCN_EINVAL, "scratch_dev and out_dev must be 8-byte aligned");
-    if (scratch_bytes < (size_t)g.total * 16) return mfail(CCN_EINVAL, "scratch is smaller than ccn_score_scratch_bytes asks for");
-    if (f32 && ((uintptr_t)recon & 3) != 0) return mfail(CCN_EINVAL, "recon_dev must be 4-byte aligned");
+    if (g.per_rec > INT32_MAX || g.total > INT32_MAX) return fail(CCN_EINVAL, "too many tiles");
+    if (((uintptr_t)scratch & 7) != 0 || ((uintptr_t)out & 7) != 0) return fail(CCN_EINVAL, "scratch_dev and out_dev must be 8-byte aligned");
+    if (scratch_bytes < (size_t)g.total * 16) return fail(CCN_EINVAL, "scratch is smaller than ccn_score_scratch_bytes asks for");
+    if (f32 && ((uintptr_t)recon & 3) != 0) return fail(CCN_EINVAL, "recon_dev must be 4-byte aligned");
     const uintptr_t bits = (uintptr_t)recon | (uintptr_t)orig | (uintptr_t)recon_u8_out;
     const bool vec = W % 16 == 0 && (bits & 15) == 0;
     const dim3 grid((unsigned)g.total), block(256);
@@ -244,7 +240,7 @@ int score(const void* recon, bool f32, const uint8_t* orig, uint8_t* recon_u8_ou
     const int py = H - (SC_WIN - 1), px = W - (SC_WIN - 1);
     const double cnt = py > 0 && px > 0 ? (double)C * (double)py * (double)px : 0.0;
     hipLaunchKernelGGL(score_final_kernel, dim3((unsigned)B), dim3(64), 0, s, (const double*)scratch, (int)g.per_rec, cnt, out);
-    if (hipGetLastError() != hipSuccess) return mfail(CCN_EHIP, "score launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(CCN_EHIP, "score launch failed");
     return CCN_OK;
 }
 
@@ -257,9 +253,9 @@ extern "C" {
 
 int ccn_score_scratch_bytes(int32_t B, int32_t C, int32_t H, int32_t W, size_t* bytes)
 {
-    if (!bytes || B <= 0 || C <= 0 || H <= 0 || W <= 0) return mfail(CCN_EINVAL, "bad argument");
+    if (!bytes || B <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(CCN_EINVAL, "bad argument");
     const ScoreGeom g = score_geom(B, C, H, W);
-    if (g.per_rec > INT32_MAX || g.total > INT32_MAX) return mfail(CCN_EINVAL, "too many tiles");
+    if (g.per_rec > INT32_MAX || g.total > INT32_MAX) return fail(CCN_EINVAL, "too many tiles");
     *bytes = (size_t)g.total * 16;
     return CCN_OK;
 }

@@ -14,12 +14,8 @@
 #include <cstdint>
 #include <string>
 
-extern "C" void ccn_internal_set_error(const char* msg);   // ccn_api.hip: thread-local message behind ccn_last_error()
-
 namespace ccn {
 namespace {
-
-int tfail(int code, const std::string& msg) { ccn_internal_set_error(msg.c_str()); return code; }
 
 // ---- loss ----------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mse_partial_kernel(const float* __restrict__ eps, const float* __restrict__ target, int64_t n, float inv_n,
@@ -547,14 +543,14 @@ static int objective_entry(const float* eps_dev, const float* noise_dev, const f
 {
     const bool need_xt = !VP || recon_w != 0.f || tv_w != 0.f;
     if (!eps_dev || !noise_dev || (need_xt && !x_t_dev) || !x0_dev || !a_dev || !s_dev || !loss_dev || !scratch_dev || B <= 0 || C <= 0)
-        return tfail(CCN_EINVAL, "bad argument");
-    if (H < 2 || W < 2) return tfail(CCN_EINVAL, "H and W must be at least 2 (the total variation of a one-pixel-wide image is a mean over nothing)");
-    if (!(recon_w >= 0.f) || !(tv_w >= 0.f)) return tfail(CCN_EINVAL, "recon_w and tv_w must be non-negative");
-    if (((uintptr_t)scratch_dev & 7) != 0) return tfail(CCN_EINVAL, "scratch_dev must be 8-byte aligned");
-    if ((int64_t)B * C * H * W > (int64_t)1 << 40) return tfail(CCN_EINVAL, "tensor too large");
+        return fail(CCN_EINVAL, "bad argument");
+    if (H < 2 || W < 2) return fail(CCN_EINVAL, "H and W must be at least 2 (the total variation of a one-pixel-wide image is a mean over nothing)");
+    if (!(recon_w >= 0.f) || !(tv_w >= 0.f)) return fail(CCN_EINVAL, "recon_w and tv_w must be non-negative");
+    if (((uintptr_t)scratch_dev & 7) != 0) return fail(CCN_EINVAL, "scratch_dev must be 8-byte aligned");
+    if ((int64_t)B * C * H * W > (int64_t)1 << 40) return fail(CCN_EINVAL, "tensor too large");
     if (launch_objective<VP>(eps_dev, noise_dev, x_t_dev, x0_dev, a_dev, s_dev, B, C, H, W, recon_w, tv_w, loss_dev, d_eps_dev, scratch_dev,
                              (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "objective launch failed");
+        return fail(CCN_EHIP, "objective launch failed");
     return CCN_OK;
 }
 
@@ -562,8 +558,8 @@ extern "C" {
 
 int ccn_mse_loss_grad(const float* eps_dev, const float* target_dev, int64_t n, float* loss_dev, float* d_eps_dev, float* scratch_dev, void* stream)
 {
-    if (!eps_dev || !target_dev || !loss_dev || !scratch_dev || n <= 0) return tfail(CCN_EINVAL, "bad argument");
-    if (launch_mse_loss_grad(eps_dev, target_dev, n, loss_dev, d_eps_dev, scratch_dev, (hipStream_t)stream) != hipSuccess) return tfail(CCN_EHIP, "mse launch failed");
+    if (!eps_dev || !target_dev || !loss_dev || !scratch_dev || n <= 0) return fail(CCN_EINVAL, "bad argument");
+    if (launch_mse_loss_grad(eps_dev, target_dev, n, loss_dev, d_eps_dev, scratch_dev, (hipStream_t)stream) != hipSuccess) return fail(CCN_EHIP, "mse launch failed");
     return CCN_OK;
 }
 
@@ -584,69 +580,69 @@ int ccn_diffusion_loss_grad_v(const float* v_dev, const float* noise_dev, const 
 int ccn_adamw_step(float* params_dev, const float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n, float lr, float beta1, float beta2,
                    float eps, float weight_decay, int32_t step, void* stream)
 {
-    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || n <= 0 || step <= 0) return tfail(CCN_EINVAL, "bad argument");
+    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || n <= 0 || step <= 0) return fail(CCN_EINVAL, "bad argument");
     if (launch_adamw(params_dev, (float*)grads_dev, exp_avg_dev, exp_avg_sq_dev, nullptr, n, lr, beta1, beta2, eps, weight_decay, step, false, nullptr,
                      nullptr, (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "adamw launch failed");
+        return fail(CCN_EHIP, "adamw launch failed");
     return CCN_OK;
 }
 
 int ccn_adamw_step_zero_grad(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n, float lr, float beta1, float beta2,
                    float eps, float weight_decay, int32_t step, void* stream)
 {
-    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || n <= 0 || step <= 0) return tfail(CCN_EINVAL, "bad argument");
+    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || n <= 0 || step <= 0) return fail(CCN_EINVAL, "bad argument");
     if (launch_adamw(params_dev, grads_dev, exp_avg_dev, exp_avg_sq_dev, nullptr, n, lr, beta1, beta2, eps, weight_decay, step, true, nullptr, nullptr,
                      (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "adamw launch failed");
+        return fail(CCN_EHIP, "adamw launch failed");
     return CCN_OK;
 }
 
 int ccn_step_guard_init(void* guard_dev, float init_scale, int32_t growth_tracker0, int32_t good_steps0, int32_t skipped_steps0, void* stream)
 {
-    if (!guard_dev || ((uintptr_t)guard_dev & 3) != 0) return tfail(CCN_EINVAL, "guard_dev must be a 4-byte aligned device pointer");
-    if (!(init_scale > 0.f) || init_scale - init_scale != 0.f) return tfail(CCN_EINVAL, "init_scale must be positive and finite");
-    if (growth_tracker0 < 0 || good_steps0 < 0 || skipped_steps0 < 0) return tfail(CCN_EINVAL, "counters must be non-negative");
+    if (!guard_dev || ((uintptr_t)guard_dev & 3) != 0) return fail(CCN_EINVAL, "guard_dev must be a 4-byte aligned device pointer");
+    if (!(init_scale > 0.f) || init_scale - init_scale != 0.f) return fail(CCN_EINVAL, "init_scale must be positive and finite");
+    if (growth_tracker0 < 0 || good_steps0 < 0 || skipped_steps0 < 0) return fail(CCN_EINVAL, "counters must be non-negative");
     hipLaunchKernelGGL(step_guard_init_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (ccn_step_guard_t*)guard_dev, init_scale, growth_tracker0,
                        good_steps0, skipped_steps0);
     if (hipGetLastError() != hipSuccess)
-        return tfail(CCN_EHIP, "step guard init launch failed");
+        return fail(CCN_EHIP, "step guard init launch failed");
     return CCN_OK;
 }
 
 int ccn_grad_guard(const float* grads_dev, int64_t n, void* guard_dev, float max_grad_norm, float beta1, float beta2, float growth_factor,
                    float backoff_factor, int32_t growth_interval, float* scratch_dev, void* stream)
 {
-    if (!grads_dev || !guard_dev || !scratch_dev || n <= 0) return tfail(CCN_EINVAL, "bad argument");
-    if (((uintptr_t)grads_dev & 3) != 0 || ((uintptr_t)guard_dev & 3) != 0) return tfail(CCN_EINVAL, "grads_dev and guard_dev must be 4-byte aligned");
-    if (((uintptr_t)scratch_dev & 7) != 0) return tfail(CCN_EINVAL, "scratch_dev must be 8-byte aligned");
-    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return tfail(CCN_EINVAL, "betas must be in [0, 1)");
+    if (!grads_dev || !guard_dev || !scratch_dev || n <= 0) return fail(CCN_EINVAL, "bad argument");
+    if (((uintptr_t)grads_dev & 3) != 0 || ((uintptr_t)guard_dev & 3) != 0) return fail(CCN_EINVAL, "grads_dev and guard_dev must be 4-byte aligned");
+    if (((uintptr_t)scratch_dev & 7) != 0) return fail(CCN_EINVAL, "scratch_dev must be 8-byte aligned");
+    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(CCN_EINVAL, "betas must be in [0, 1)");
     if (!(growth_factor > 0.f) || !(backoff_factor > 0.f) || growth_interval <= 0)
-        return tfail(CCN_EINVAL, "growth_factor, backoff_factor and growth_interval must be positive");
-    if (max_grad_norm != max_grad_norm) return tfail(CCN_EINVAL, "max_grad_norm is NaN");
+        return fail(CCN_EINVAL, "growth_factor, backoff_factor and growth_interval must be positive");
+    if (max_grad_norm != max_grad_norm) return fail(CCN_EINVAL, "max_grad_norm is NaN");
     if (launch_grad_guard(grads_dev, n, guard_dev, max_grad_norm, beta1, beta2, growth_factor, backoff_factor, growth_interval,
                           (double*)scratch_dev, (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "grad guard launch failed");
+        return fail(CCN_EHIP, "grad guard launch failed");
     return CCN_OK;
 }
 
 int ccn_adamw_step_guarded(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n, float lr, float beta1,
                            float beta2, float eps, float weight_decay, const void* guard_dev, void* stream)
 {
-    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || !guard_dev || n <= 0) return tfail(CCN_EINVAL, "bad argument");
+    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || !guard_dev || n <= 0) return fail(CCN_EINVAL, "bad argument");
     if ((((uintptr_t)params_dev | (uintptr_t)grads_dev | (uintptr_t)exp_avg_dev | (uintptr_t)exp_avg_sq_dev | (uintptr_t)guard_dev) & 3) != 0)
-        return tfail(CCN_EINVAL, "buffers must be 4-byte aligned");
+        return fail(CCN_EINVAL, "buffers must be 4-byte aligned");
     if (launch_adamw(params_dev, grads_dev, exp_avg_dev, exp_avg_sq_dev, nullptr, n, lr, beta1, beta2, eps, weight_decay, 0, true,
                      (const ccn_step_guard_t*)guard_dev, nullptr, (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "guarded adamw launch failed");
+        return fail(CCN_EHIP, "guarded adamw launch failed");
     return CCN_OK;
 }
 
 int ccn_ema_init(void* ema_state_dev, int32_t updates0, void* stream)
 {
-    if (!ema_state_dev || ((uintptr_t)ema_state_dev & 3) != 0) return tfail(CCN_EINVAL, "ema_state_dev must be a 4-byte aligned device pointer");
-    if (updates0 < 0) return tfail(CCN_EINVAL, "updates0 must be non-negative");
+    if (!ema_state_dev || ((uintptr_t)ema_state_dev & 3) != 0) return fail(CCN_EINVAL, "ema_state_dev must be a 4-byte aligned device pointer");
+    if (updates0 < 0) return fail(CCN_EINVAL, "updates0 must be non-negative");
     hipLaunchKernelGGL(ema_init_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (ccn_ema_state_t*)ema_state_dev, updates0);
-    if (hipGetLastError() != hipSuccess) return tfail(CCN_EHIP, "ema init launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(CCN_EHIP, "ema init launch failed");
     return CCN_OK;
 }
 
@@ -655,14 +651,14 @@ int ccn_adamw_step_ema(float* params_dev, float* grads_dev, float* exp_avg_dev, 
                        int32_t ema_warmup, const void* guard_dev, void* ema_state_dev, void* stream)
 {
     if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || !ema_dev || !ema_state_dev)
-        return tfail(CCN_EINVAL, "a buffer or the EMA state block is NULL");
-    if (n < 0) return tfail(CCN_EINVAL, "n is negative");
-    if (!(ema_decay >= 0.0 && ema_decay < 1.0)) return tfail(CCN_EINVAL, "ema_decay must be in [0, 1)");
-    if (guard_dev && !zero_grad) return tfail(CCN_EINVAL, "a guarded step consumes the gradients: zero_grad must be non-zero with guard_dev");
-    if (!guard_dev && step <= 0) return tfail(CCN_EINVAL, "step must be at least 1 without guard_dev");
+        return fail(CCN_EINVAL, "a buffer or the EMA state block is NULL");
+    if (n < 0) return fail(CCN_EINVAL, "n is negative");
+    if (!(ema_decay >= 0.0 && ema_decay < 1.0)) return fail(CCN_EINVAL, "ema_decay must be in [0, 1)");
+    if (guard_dev && !zero_grad) return fail(CCN_EINVAL, "a guarded step consumes the gradients: zero_grad must be non-zero with guard_dev");
+    if (!guard_dev && step <= 0) return fail(CCN_EINVAL, "step must be at least 1 without guard_dev");
     if ((((uintptr_t)params_dev | (uintptr_t)grads_dev | (uintptr_t)exp_avg_dev | (uintptr_t)exp_avg_sq_dev | (uintptr_t)ema_dev |
           (uintptr_t)guard_dev | (uintptr_t)ema_state_dev) & 3) != 0)
-        return tfail(CCN_EINVAL, "buffers must be 4-byte aligned");
+        return fail(CCN_EINVAL, "buffers must be 4-byte aligned");
     if (n == 0) return CCN_OK;                       // nothing to average: no launch, the count of updates stays
     const float w = (float)(1.0 - ema_decay);        // the weight get_ema_multi_avg_fn(decay) hands to lerp_, rounded once to fp32
     // two launches: the one-wave tick that writes the state block, then the fused pass that reads it
@@ -670,7 +666,7 @@ int ccn_adamw_step_ema(float* params_dev, float* grads_dev, float* exp_avg_dev, 
                        ema_warmup ? 1 : 0);
     if (launch_adamw(params_dev, grads_dev, exp_avg_dev, exp_avg_sq_dev, ema_dev, n, lr, beta1, beta2, eps, weight_decay, step, zero_grad != 0,
                      (const ccn_step_guard_t*)guard_dev, (const ccn_ema_state_t*)ema_state_dev, (hipStream_t)stream) != hipSuccess)
-        return tfail(CCN_EHIP, "adamw + ema launch failed");
+        return fail(CCN_EHIP, "adamw + ema launch failed");
     return CCN_OK;
 }
 

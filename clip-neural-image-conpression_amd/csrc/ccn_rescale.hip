@@ -22,12 +22,8 @@
 #include <cstdint>
 #include <string>
 
-extern "C" void ccn_internal_set_error(const char* msg);   // ccn_api.hip: thread-local message behind ccn_last_error()
-
 namespace ccn {
 namespace {
-
-int rfail(int code, const std::string& msg) { ccn_internal_set_error(msg.c_str()); return code; }
 
 constexpr int kRsThreads = 256, kRsMaxGx = 64;
 constexpr int64_t kRsPerBlock = 4096;
@@ -41,9 +37,9 @@ size_t rs_factor_bytes(int B) { return ((size_t)B * 4 + 15) / 16 * 16; }
 
 struct Sums { double c, cc, y, yy; };
 
-__device__ __forceinline__ void rs_add(Sums& a, float c, float u, float w)
+__device__ __forceinline__ void rs_add(Sums& a, float c, float u, const X0Form& f)
 {
-    const float y = __fadd_rn(u, __fmul_rn(w, __fsub_rn(c, u)));
+    const float y = f.combine(c, u);            // (no k yet: this is what computes it)
     const double dc = (double)c, dy = (double)y;
     a.c += dc; a.cc += dc * dc; a.y += dy; a.yy += dy * dy;
 }
@@ -58,6 +54,7 @@ __global__ __launch_bounds__(kRsThreads) void rs_partial_kernel(const float* __r
     const float* u = out_u + (long long)b * per;
     const long long nq = (per + 3) / 4, nthr = (long long)gridDim.x * kRsThreads;
     Sums a = {0.0, 0.0, 0.0, 0.0};
+    X0Form f; f.w = w;
     // four quads of a lane in flight: the loads first, then the adds in increasing q
     for (long long q0 = (long long)blockIdx.x * kRsThreads + tid; q0 < nq; q0 += 4 * nthr) {
         float4 cv[4], uv[4];
@@ -79,10 +76,10 @@ __global__ __launch_bounds__(kRsThreads) void rs_partial_kernel(const float* __r
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const long long j = (q0 + i * nthr) * 4;
-            if (j < per) rs_add(a, cv[i].x, uv[i].x, w);
-            if (j + 1 < per) rs_add(a, cv[i].y, uv[i].y, w);
-            if (j + 2 < per) rs_add(a, cv[i].z, uv[i].z, w);
-            if (j + 3 < per) rs_add(a, cv[i].w, uv[i].w, w);
+            if (j < per) rs_add(a, cv[i].x, uv[i].x, f);
+            if (j + 1 < per) rs_add(a, cv[i].y, uv[i].y, f);
+            if (j + 2 < per) rs_add(a, cv[i].z, uv[i].z, f);
+            if (j + 3 < per) rs_add(a, cv[i].w, uv[i].w, f);
         }
     }
 #pragma unroll
@@ -121,16 +118,17 @@ __global__ __launch_bounds__(64) void rs_final_kernel(const double* __restrict__
 size_t guidance_rescale_scratch_bytes(int B, int64_t per) { return rs_factor_bytes(B) + (size_t)B * rs_gx(per) * 4 * sizeof(double); }
 void* guidance_rescale_partials(void* scratch, int B) { return (char*)scratch + rs_factor_bytes(B); }
 
-hipError_t launch_guidance_rescale(const float* out_c, const float* out_u, float w, double phi, int B, int64_t per, float* k, void* partials,
-                                   hipStream_t s)
+hipError_t launch_guidance_rescale(const X0Operands& o, double phi, float* k, void* partials, hipStream_t s)
 {
+    const float *out_c = o.out_c, *out_u = o.out_u, w = o.w;
+    const int64_t per = o.per_record, B = o.records;
     if (B <= 0 || B > 65535 || per < 2 || per >= kThrMaxPerRecord || !out_c || !out_u || !k || !partials) return hipErrorInvalidValue;
     const int gx = rs_gx(per);
     const bool vec = !(((uintptr_t)out_c | (uintptr_t)out_u) & 15) && !(per & 3);
     const dim3 grid(gx, (unsigned)B);
     if (vec) hipLaunchKernelGGL((rs_partial_kernel<true>), grid, dim3(kRsThreads), 0, s, out_c, out_u, w, (long long)per, (double*)partials);
     else hipLaunchKernelGGL((rs_partial_kernel<false>), grid, dim3(kRsThreads), 0, s, out_c, out_u, w, (long long)per, (double*)partials);
-    hipLaunchKernelGGL(rs_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const double*)partials, gx, B, (double)per, phi, k);
+    hipLaunchKernelGGL(rs_final_kernel, dim3((unsigned)(B + 63) / 64), dim3(64), 0, s, (const double*)partials, gx, (int)B, (double)per, phi, k);
     return hipGetLastError();
 }
 
@@ -138,17 +136,12 @@ hipError_t launch_guidance_rescale(const float* out_c, const float* out_u, float
 
 using namespace ccn;
 
-static int rs_check_shape(int32_t B, int64_t per_record)
-{
-    if (B <= 0 || B > 65535) return rfail(CCN_EINVAL, "B must be in [1, 65535]: one grid row per record");
-    if (per_record < 2 || per_record >= kThrMaxPerRecord) return rfail(CCN_EINVAL, "per_record must be in [2, 2^34): an unbiased std needs two elements");
-    return CCN_OK;
-}
-
 int ccn_guidance_rescale_scratch_bytes(int32_t B, int64_t per_record, size_t* bytes)
 {
-    if (!bytes) return rfail(CCN_EINVAL, "null argument");
-    if (int rc = rs_check_shape(B, per_record)) return rc;
+    if (!bytes) return fail(CCN_EINVAL, "null argument");
+    X0Operands o;
+    o.records = B; o.per_record = per_record;
+    if (int rc = check_x0_operands(o, true, false)) return rc;
     *bytes = guidance_rescale_scratch_bytes(B, per_record);
     return CCN_OK;
 }
@@ -156,15 +149,16 @@ int ccn_guidance_rescale_scratch_bytes(int32_t B, int64_t per_record, size_t* by
 int ccn_guidance_rescale(const float* out_c_dev, const float* out_u_dev, float w, double phi, int32_t B, int64_t per_record, float* k_dev,
                          void* scratch_dev, size_t scratch_bytes, void* stream)
 {
-    if (!out_c_dev || !out_u_dev || !k_dev) return rfail(CCN_EINVAL, "a tensor pointer is NULL (guidance rescale needs both outputs)");
-    if (!std::isfinite(w)) return rfail(CCN_EINVAL, "the guidance scale must be finite");
-    if (!(phi >= 0.0 && phi <= 1.0)) return rfail(CCN_EINVAL, "the rescale factor phi must be in [0, 1]");
-    if (int rc = rs_check_shape(B, per_record)) return rc;
-    if (!scratch_dev || ((uintptr_t)scratch_dev & 15)) return rfail(CCN_EINVAL, "the scratch must be non-null and 16-byte aligned");
+    X0Operands o;
+    o.out_c = out_c_dev; o.out_u = out_u_dev; o.w = w; o.per_record = per_record; o.records = B;
+    if (!k_dev) return fail(CCN_EINVAL, "a tensor pointer is NULL");
+    if (int rc = check_x0_operands(o, true)) return rc;
+    if (!std::isfinite(w)) return fail(CCN_EINVAL, "the guidance scale must be finite");
+    if (!(phi >= 0.0 && phi <= 1.0)) return fail(CCN_EINVAL, "the rescale factor phi must be in [0, 1]");
+    if (!scratch_dev || ((uintptr_t)scratch_dev & 15)) return fail(CCN_EINVAL, "the scratch must be non-null and 16-byte aligned");
     const size_t need = guidance_rescale_scratch_bytes(B, per_record);
-    if (scratch_bytes < need) return rfail(CCN_EINVAL, "the scratch is too small: need " + std::to_string(need) + " bytes");
-    if (launch_guidance_rescale(out_c_dev, out_u_dev, w, phi, B, per_record, k_dev, guidance_rescale_partials(scratch_dev, B),
-                                (hipStream_t)stream) != hipSuccess)
-        return rfail(CCN_EHIP, "guidance_rescale launch failed");
+    if (scratch_bytes < need) return fail(CCN_EINVAL, "the scratch is too small: need " + std::to_string(need) + " bytes");
+    if (launch_guidance_rescale(o, phi, k_dev, guidance_rescale_partials(scratch_dev, B), (hipStream_t)stream) != hipSuccess)
+        return fail(CCN_EHIP, "guidance_rescale launch failed");
     return CCN_OK;
 }

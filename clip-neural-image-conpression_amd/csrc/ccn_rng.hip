@@ -7,12 +7,8 @@
 #include <cstdint>
 #include <string>
 
-extern "C" void ccn_internal_set_error(const char* msg);   // ccn_api.hip: thread-local message behind ccn_last_error()
-
 namespace ccn {
 namespace {
-
-int rfail(int code, const std::string& msg) { ccn_internal_set_error(msg.c_str()); return code; }
 
 // grid (x, B): row blockIdx.y.  A row that starts 16-byte aligned goes a quad per lane with one 16-byte store each, its per % 4 tail
 // an element per lane; a row that does not goes an element per lane throughout (4-byte stores, coalesced across the wave).
@@ -34,14 +30,14 @@ using namespace ccn;
 
 int ccn_normal_fill(float* out_dev, const uint64_t* seeds_dev, int32_t B, int64_t per_record, uint32_t draw, void* stream)
 {
-    if (!out_dev || !seeds_dev) return rfail(CCN_EINVAL, "a buffer is NULL");
-    if (((uintptr_t)out_dev & 3) || ((uintptr_t)seeds_dev & 7)) return rfail(CCN_EINVAL, "out_dev must be 4-byte and seeds_dev 8-byte aligned");
-    if (B <= 0 || B > 65535 || per_record <= 0) return rfail(CCN_EINVAL, "B must be in [1, 65535] and per_record positive");
-    if (per_record >= kDrawMaxPerRecord) return rfail(CCN_EINVAL, "per_record must be below 2^34: the quad index is one 32-bit counter word");
+    if (!out_dev || !seeds_dev) return fail(CCN_EINVAL, "a buffer is NULL");
+    if (((uintptr_t)out_dev & 3) || ((uintptr_t)seeds_dev & 7)) return fail(CCN_EINVAL, "out_dev must be 4-byte and seeds_dev 8-byte aligned");
+    if (B <= 0 || B > 65535 || per_record <= 0) return fail(CCN_EINVAL, "B must be in [1, 65535] and per_record positive");
+    if (per_record >= kDrawMaxPerRecord) return fail(CCN_EINVAL, "per_record must be below 2^34: the quad index is one 32-bit counter word");
     // sized for the quad path (the common one); an unaligned row strides the same grid four times as often
     const int64_t blocks = ((per_record + 3) / 4 + 255) / 256;
     const int gx = (int)(blocks < 1024 ? blocks : 1024);
     hipLaunchKernelGGL(normal_fill_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, out_dev, seeds_dev, per_record, draw);
-    if (hipGetLastError() != hipSuccess) return rfail(CCN_EHIP, "normal_fill launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(CCN_EHIP, "normal_fill launch failed");
     return CCN_OK;
 }

@@ -8,8 +8,8 @@
 // that order, so NaNs sort last: a rank that lands on one makes q, the threshold and with it the record's update NaN (nothing here
 // looks for them), +inf is an ordinary largest value, -0 and +0 are one key, denormals keep their order.
 //
-// The raw x0 of an element is formed by raw_x0_p (ccn_device.h), the function the sampler update itself calls, after the same
-// guidance combine -- and, with `gscale`, after the multiplication by the record's guidance-rescale factor (ccn_rescale.hip): the
+// The raw x0 of an element is X0Form::raw of X0Form::y (ccn_device.h), the formation the sampler update itself goes through: the same
+// guidance combine and, with `gscale`, the same multiplication by the record's guidance-rescale factor (ccn_rescale.hip): the
 // quantile is taken on the bits the update clamps.
 //
 // Launches (all on the caller's stream, nothing synchronises, nothing is allocated):
@@ -29,12 +29,8 @@
 #include <cstdint>
 #include <string>
 
-extern "C" void ccn_internal_set_error(const char* msg);   // ccn_api.hip: thread-local message behind ccn_last_error()
-
 namespace ccn {
 namespace {
-
-int tfail(int code, const std::string& msg) { ccn_internal_set_error(msg.c_str()); return code; }
 
 // One record's select state: H0 (2048 bins), H1 and H2 (two ranks x 1024 bins) as 64-bit counts -- a record has up to 2^34
 // elements -- then the picks handed from one pass kernel to the next (written by workgroup 0 of a record, read by the NEXT launch).
@@ -45,14 +41,11 @@ constexpr size_t kRecBytes = kHistBytes + 2 * sizeof(Sel);
 static_assert(sizeof(Sel) == 32 && kRecBytes % 16 == 0, "the records of the scratch stay 16-byte aligned");
 
 struct ThrArgs {
-    const float *x, *yc, *yu;          // the state, the network output, the unconditional output (nullable)
-    int pred; float w, c0, c1;
-    long long per;
+    X0Operands o;                      // (o.thr is not read: this is what computes it)
     unsigned long long k0, k1;         // the two ranks: k and min(k + 1, per - 1)
     float frac, max_value;
     float* thr;
     char* scratch;
-    const float* gscale;               // nullable: the record's guidance-rescale factor multiplies the (combined) output first
 };
 
 __global__ __launch_bounds__(256) void thr_zero_kernel(uint4* __restrict__ p, long long n16)
@@ -142,17 +135,17 @@ __global__ __launch_bounds__(256) void thr_pass_kernel(ThrArgs a)
     for (int i = tid; i < kBins0; i += 256) lh[i] = 0u;
     __syncthreads();
 
-    const long long off = (long long)b * a.per;
-    const float* x = a.x + off;
-    const float* yc = a.yc + off;
-    const float* yu = a.yu ? a.yu + off : nullptr;
+    const long long per = a.o.per_record, off = (long long)b * per;
+    const float* x = a.o.x + off;
+    const float* yc = a.o.out_c + off;
+    const float* yu = a.o.out_u ? a.o.out_u + off : nullptr;
     const uint32_t pre0 = pre[0], pre1 = pre[1];
-    const bool rs = a.gscale != nullptr;
-    const float gk = rs ? a.gscale[b] : 1.0f;
+    X0Form f;
+    f.pred = a.o.pred; f.c0 = a.o.c0; f.c1 = a.o.c1; f.w = a.o.w;
+    f.guided = yu != nullptr; f.rescaled = a.o.gscale != nullptr;
+    if (f.rescaled) f.k = a.o.gscale[b];
     auto count = [&](float xv, float yv, float uv) {
-        if (yu) yv = __fadd_rn(uv, __fmul_rn(a.w, __fsub_rn(yv, uv)));
-        if (rs) yv = __fmul_rn(gk, yv);
-        const uint32_t key = __float_as_uint(raw_x0_p(a.pred, xv, yv, a.c0, a.c1)) & 0x7fffffffu;
+        const uint32_t key = __float_as_uint(f.raw(xv, f.y(yv, uv))) & 0x7fffffffu;
         if (PASS == 0) atomicAdd(&lh[key >> SH], 1u);
         else {
             const uint32_t hi = key >> (SH + 10), d = (key >> SH) & (uint32_t)(kBins - 1);
@@ -161,14 +154,14 @@ __global__ __launch_bounds__(256) void thr_pass_kernel(ThrArgs a)
         }
     };
     const long long t0 = (long long)blockIdx.x * blockDim.x + tid, nthr = (long long)gridDim.x * blockDim.x;
-    const long long n4 = VEC ? a.per / 4 : 0;
+    const long long n4 = VEC ? per / 4 : 0;
     for (long long q = t0; q < n4; q += nthr) {
         const float4 xv = ((const float4*)x)[q], yv = ((const float4*)yc)[q];
         float4 uv = make_float4(0.f, 0.f, 0.f, 0.f);
         if (yu) uv = ((const float4*)yu)[q];
         count(xv.x, yv.x, uv.x); count(xv.y, yv.y, uv.y); count(xv.z, yv.z, uv.z); count(xv.w, yv.w, uv.w);
     }
-    for (long long i = n4 * 4 + t0; i < a.per; i += nthr) count(x[i], yc[i], yu ? yu[i] : 0.f);
+    for (long long i = n4 * 4 + t0; i < per; i += nthr) count(x[i], yc[i], yu ? yu[i] : 0.f);
     __syncthreads();
 
     unsigned long long* H = (unsigned long long*)rec + (PASS == 0 ? 0 : kBins0 + (PASS - 1) * 2 * kBins);
@@ -199,21 +192,21 @@ __global__ __launch_bounds__(256) void thr_final_kernel(ThrArgs a)
 
 size_t x0_threshold_scratch_bytes(int B) { return (size_t)(B > 0 ? B : 0) * kRecBytes; }
 
-hipError_t launch_x0_threshold(const float* x, const float* out_c, const float* out_u, int pred, float w, float c0, float c1, int B, int64_t per,
-                               double p, float max_value, float* thr, void* scratch, hipStream_t s, const float* gscale)
+hipError_t launch_x0_threshold(const X0Operands& o, double p, float max_value, float* thr, void* scratch, hipStream_t s)
 {
+    const int64_t per = o.per_record, B = o.records;
     if (B <= 0 || B > 65535 || per <= 0 || per >= kThrMaxPerRecord || !(p >= 0.0 && p <= 1.0)) return hipErrorInvalidValue;
     ThrArgs a;
-    a.x = x; a.yc = out_c; a.yu = out_u; a.pred = pred; a.w = w; a.c0 = c0; a.c1 = c1; a.per = per;
+    a.o = o;
     const double pos = p * (double)(per - 1);
     double kf = std::floor(pos);
     if (kf > (double)(per - 1)) kf = (double)(per - 1);
     a.k0 = (unsigned long long)kf;
     a.k1 = a.k0 + 1 < (unsigned long long)per ? a.k0 + 1 : (unsigned long long)per - 1;
     a.frac = (float)(pos - kf);
-    a.max_value = max_value; a.thr = thr; a.scratch = (char*)scratch; a.gscale = gscale;
+    a.max_value = max_value; a.thr = thr; a.scratch = (char*)scratch;
 
-    const bool vec = !(((uintptr_t)x | (uintptr_t)out_c | (uintptr_t)out_u) & 15) && !(per & 3);
+    const bool vec = !(((uintptr_t)o.x | (uintptr_t)o.out_c | (uintptr_t)o.out_u) & 15) && !(per & 3);
     // about four workgroups per CU over the batch, never more than the record has work for; a workgroup's LDS counts are 32-bit,
     // so it takes at most 2^30 elements
     const int64_t work = vec ? per / 4 : per, blocks = (work + 255) / 256, want = 1024 / B > 0 ? 1024 / B : 1, least = (per >> 30) + 1;
@@ -242,9 +235,10 @@ using namespace ccn;
 
 int ccn_x0_threshold_scratch_bytes(int32_t B, int64_t per_record, size_t* bytes)
 {
-    if (!bytes) return tfail(CCN_EINVAL, "null argument");
-    if (B <= 0 || B > 65535) return tfail(CCN_EINVAL, "B must be in [1, 65535]: one grid row per record");
-    if (per_record <= 0 || per_record >= kThrMaxPerRecord) return tfail(CCN_EINVAL, "per_record must be in [1, 2^34)");
+    if (!bytes) return fail(CCN_EINVAL, "null argument");
+    X0Operands o;
+    o.records = B; o.per_record = per_record;
+    if (int rc = check_x0_operands(o, false, false)) return rc;
     *bytes = x0_threshold_scratch_bytes(B);
     return CCN_OK;
 }
@@ -261,17 +255,17 @@ int ccn_x0_threshold_rs(const float* x_dev, const float* out_c_dev, const float*
                         int32_t B, int64_t per_record, double p, float max_value, float* thr_dev, void* scratch_dev, size_t scratch_bytes,
                         const float* gscale_dev, void* stream)
 {
-    if (!x_dev || !out_c_dev || !thr_dev) return tfail(CCN_EINVAL, "a tensor pointer is NULL");
-    if (pred != CCN_PRED_EPS && pred != CCN_PRED_V) return tfail(CCN_EINVAL, "unknown prediction (CCN_PRED_EPS or CCN_PRED_V)");
-    if (B <= 0 || B > 65535) return tfail(CCN_EINVAL, "B must be in [1, 65535]: one grid row per record");
-    if (per_record <= 0 || per_record >= kThrMaxPerRecord) return tfail(CCN_EINVAL, "per_record must be in [1, 2^34)");
-    if (!(p >= 0.0 && p <= 1.0)) return tfail(CCN_EINVAL, "the quantile p must be in [0, 1]");
-    if (!(max_value >= 1.0f)) return tfail(CCN_EINVAL, "max_value must be at least 1 (+inf: no upper bound)");
-    if (!scratch_dev || ((uintptr_t)scratch_dev & 15)) return tfail(CCN_EINVAL, "the scratch must be non-null and 16-byte aligned");
+    X0Operands o;
+    o.x = const_cast<float*>(x_dev); o.out_c = out_c_dev; o.out_u = out_u_dev; o.gscale = gscale_dev;
+    o.pred = pred; o.w = w; o.c0 = c0; o.c1 = c1; o.per_record = per_record; o.records = B;
+    if (!thr_dev) return fail(CCN_EINVAL, "a tensor pointer is NULL");
+    if (int rc = check_x0_operands(o, false)) return rc;
+    if (!(p >= 0.0 && p <= 1.0)) return fail(CCN_EINVAL, "the quantile p must be in [0, 1]");
+    if (!(max_value >= 1.0f)) return fail(CCN_EINVAL, "max_value must be at least 1 (+inf: no upper bound)");
+    if (!scratch_dev || ((uintptr_t)scratch_dev & 15)) return fail(CCN_EINVAL, "the scratch must be non-null and 16-byte aligned");
     if (scratch_bytes < x0_threshold_scratch_bytes(B))
-        return tfail(CCN_EINVAL, "the scratch is too small: need " + std::to_string(x0_threshold_scratch_bytes(B)) + " bytes");
-    if (launch_x0_threshold(x_dev, out_c_dev, out_u_dev, pred, w, c0, c1, B, per_record, p, max_value, thr_dev, scratch_dev,
-                            (hipStream_t)stream, gscale_dev) != hipSuccess)
-        return tfail(CCN_EHIP, "x0_threshold launch failed");
+        return fail(CCN_EINVAL, "the scratch is too small: need " + std::to_string(x0_threshold_scratch_bytes(B)) + " bytes");
+    if (launch_x0_threshold(o, p, max_value, thr_dev, scratch_dev, (hipStream_t)stream) != hipSuccess)
+        return fail(CCN_EHIP, "x0_threshold launch failed");
     return CCN_OK;
 }

@@ -31,11 +31,8 @@
 
 using namespace ccn;
 
-extern "C" void ccn_internal_set_error(const char* msg);   // ccn_api.hip: thread-local message behind ccn_last_error()
-
 namespace {
 
-int tfail(int code, const std::string& msg) { ccn_internal_set_error(msg.c_str()); return code; }
 #define THIP(expr)                                                                                       \
     do {                                                                                                 \
         hipError_t e_ = (expr);                                                                          \
@@ -906,9 +903,9 @@ std::string shape_key(int B, int H, int W)
 // the cached plan of a shape, built (and its repack list uploaded) on first use
 int step_plan(ccn_trainer_s* tr, int B, int H, int W, const StepPlan** out)
 {
-    if (B <= 0 || H <= 0 || W <= 0) return tfail(CCN_EINVAL, "B, H, W must be positive");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(CCN_EINVAL, "B, H, W must be positive");
     const int div = 1 << tr->cfg.n_mult;
-    if (H % div || W % div) return tfail(CCN_EINVAL, "H and W must be divisible by 2^len(ch_mult)");
+    if (H % div || W % div) return fail(CCN_EINVAL, "H and W must be divisible by 2^len(ch_mult)");
     const std::string key = shape_key(B, H, W);
     auto it = tr->shapes.find(key);
     if (it == tr->shapes.end()) {
@@ -917,8 +914,8 @@ int step_plan(ccn_trainer_s* tr, int B, int H, int W, const StepPlan** out)
         Planner(tr, pl).run();
         std::string err;
         void* dev = nullptr;
-        if (!alloc_dev(tr, pl.pack_list.size() * sizeof(PackDesc), &dev, err)) return tfail(CCN_EHIP, err);
-        if (hipMemcpy(dev, pl.pack_list.data(), pl.pack_list.size() * sizeof(PackDesc), hipMemcpyHostToDevice) != hipSuccess) return tfail(CCN_EHIP, "descriptor upload failed");
+        if (!alloc_dev(tr, pl.pack_list.size() * sizeof(PackDesc), &dev, err)) return fail(CCN_EHIP, err);
+        if (hipMemcpy(dev, pl.pack_list.data(), pl.pack_list.size() * sizeof(PackDesc), hipMemcpyHostToDevice) != hipSuccess) return fail(CCN_EHIP, "descriptor upload failed");
         pl.packs = (PackDesc*)dev; pl.n_packs = (int)pl.pack_list.size();
         it = tr->shapes.emplace(key, std::move(pl)).first;
     }
@@ -943,25 +940,25 @@ int run_graphed(ccn_trainer_s* tr, const std::vector<const void*>& key, hipStrea
 {
     for (auto& g : tr->graphs)
         if (g.key == key) {
-            if (hipGraphLaunch(g.exec, user) != hipSuccess) return tfail(CCN_EHIP, "hipGraphLaunch failed");
+            if (hipGraphLaunch(g.exec, user) != hipSuccess) return fail(CCN_EHIP, "hipGraphLaunch failed");
             return CCN_OK;
         }
-    if (!tr->cap_stream && hipStreamCreateWithFlags(&tr->cap_stream, hipStreamNonBlocking) != hipSuccess) return tfail(CCN_EHIP, "capture stream");
-    if (hipStreamBeginCapture(tr->cap_stream, hipStreamCaptureModeRelaxed) != hipSuccess) return tfail(CCN_EHIP, "hipStreamBeginCapture failed");
+    if (!tr->cap_stream && hipStreamCreateWithFlags(&tr->cap_stream, hipStreamNonBlocking) != hipSuccess) return fail(CCN_EHIP, "capture stream");
+    if (hipStreamBeginCapture(tr->cap_stream, hipStreamCaptureModeRelaxed) != hipSuccess) return fail(CCN_EHIP, "hipStreamBeginCapture failed");
     std::string err;
     const bool good = body(tr->cap_stream, err);
     hipGraph_t graph = nullptr;
     const hipError_t ce = hipStreamEndCapture(tr->cap_stream, &graph);
-    if (!good) { if (graph) (void)hipGraphDestroy(graph); return tfail(CCN_EHIP, err); }
-    if (ce != hipSuccess) return tfail(CCN_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+    if (!good) { if (graph) (void)hipGraphDestroy(graph); return fail(CCN_EHIP, err); }
+    if (ce != hipSuccess) return fail(CCN_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
     ccn_trainer_s::TGraph g; g.key = key; g.graph = graph;
-    if (hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(graph); return tfail(CCN_EHIP, "hipGraphInstantiate failed"); }
+    if (hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(graph); return fail(CCN_EHIP, "hipGraphInstantiate failed"); }
     if (tr->graphs.size() >= 8) {
         (void)hipGraphExecDestroy(tr->graphs.front().exec); (void)hipGraphDestroy(tr->graphs.front().graph);
         tr->graphs.erase(tr->graphs.begin());
     }
     tr->graphs.push_back(g);
-    if (hipGraphLaunch(g.exec, user) != hipSuccess) return tfail(CCN_EHIP, "hipGraphLaunch failed");
+    if (hipGraphLaunch(g.exec, user) != hipSuccess) return fail(CCN_EHIP, "hipGraphLaunch failed");
     return CCN_OK;
 }
 
@@ -971,21 +968,21 @@ extern "C" {
 
 int ccn_train_set_graph(ccn_trainer_t tr, int32_t on)
 {
-    if (!tr) return tfail(CCN_EINVAL, "null handle");
+    if (!tr) return fail(CCN_EINVAL, "null handle");
     tr->use_graph = on != 0;
     return CCN_OK;
 }
 
 int ccn_train_create(const ccn_config_t* cfg, ccn_trainer_t* out)
 {
-    if (!cfg || !out) return tfail(CCN_EINVAL, "null argument");
+    if (!cfg || !out) return fail(CCN_EINVAL, "null argument");
     if (cfg->n_mult <= 0 || cfg->n_mult > CCN_MAX_MULT || cfg->base <= 0 || cfg->time_dim <= 0 || cfg->z_dim <= 0 || cfg->img_ch <= 0 || cfg->img_ch > 3)
-        return tfail(CCN_EINVAL, "bad config");
-    if (cfg->dtype == CCN_DTYPE_F16X3) return tfail(CCN_EINVAL, "training supports CCN_DTYPE_F32 (fp32) and CCN_DTYPE_BF16 (bf16); f16x3 is an inference mode");
-    if (cfg->dtype != CCN_DTYPE_F32 && cfg->dtype != CCN_DTYPE_BF16) return tfail(CCN_EINVAL, "bad dtype");
-    if (cfg->base % 8) return tfail(CCN_EINVAL, "training path needs base % 8 == 0");
+        return fail(CCN_EINVAL, "bad config");
+    if (cfg->dtype == CCN_DTYPE_F16X3) return fail(CCN_EINVAL, "training supports CCN_DTYPE_F32 (fp32) and CCN_DTYPE_BF16 (bf16); f16x3 is an inference mode");
+    if (cfg->dtype != CCN_DTYPE_F32 && cfg->dtype != CCN_DTYPE_BF16) return fail(CCN_EINVAL, "bad dtype");
+    if (cfg->base % 8) return fail(CCN_EINVAL, "training path needs base % 8 == 0");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tfail(CCN_EHIP, "no HIP device: libccn_hip.so has no CPU fallback");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(CCN_EHIP, "no HIP device: libccn_hip.so has no CPU fallback");
     ccn_trainer_s* tr = new ccn_trainer_s();
     tr->cfg = *cfg;
     tr->elem = cfg->dtype == CCN_DTYPE_BF16 ? 2 : 4;
@@ -1016,7 +1013,7 @@ int ccn_train_create(const ccn_config_t* cfg, ccn_trainer_t* out)
         if (good && hipMemcpy(ldd, ld.data(), ld.size() * sizeof(LinDesc), hipMemcpyHostToDevice) != hipSuccess) { good = false; err = "descriptor upload failed"; }
         tr->lin_descs = (LinDesc*)ldd; tr->n_lin = (int)ld.size();
     }
-    if (!good) { ccn_train_destroy(tr); return tfail(CCN_EHIP, err); }
+    if (!good) { ccn_train_destroy(tr); return fail(CCN_EHIP, err); }
     tr->zero_bias = (float*)zb;
     *out = tr;
     return CCN_OK;
@@ -1039,7 +1036,7 @@ int ccn_train_destroy(ccn_trainer_t tr)
 
 int ccn_train_num_params(ccn_trainer_t tr, int32_t* n, int64_t* total_floats)
 {
-    if (!tr || !n) return tfail(CCN_EINVAL, "null argument");
+    if (!tr || !n) return fail(CCN_EINVAL, "null argument");
     *n = (int32_t)tr->arch.params.size();
     if (total_floats) *total_floats = (int64_t)tr->arch.total;
     return CCN_OK;
@@ -1047,7 +1044,7 @@ int ccn_train_num_params(ccn_trainer_t tr, int32_t* n, int64_t* total_floats)
 
 int ccn_train_param_info(ccn_trainer_t tr, int32_t i, const char** name, int64_t shape[4], int32_t* ndim, int64_t* offset)
 {
-    if (!tr || i < 0 || i >= (int32_t)tr->arch.params.size()) return tfail(CCN_EINVAL, "parameter index out of range");
+    if (!tr || i < 0 || i >= (int32_t)tr->arch.params.size()) return fail(CCN_EINVAL, "parameter index out of range");
     const ArchParam& p = tr->arch.params[i];
     if (name) *name = p.name.c_str();
     if (ndim) *ndim = (int32_t)p.shape.size();
@@ -1056,10 +1053,9 @@ int ccn_train_param_info(ccn_trainer_t tr, int32_t i, const char** name, int64_t
     return CCN_OK;
 }
 
-
 int ccn_train_workspace_bytes(ccn_trainer_t tr, int32_t B, int32_t H, int32_t W, size_t* bytes)
 {
-    if (!tr || !bytes) return tfail(CCN_EINVAL, "null argument");
+    if (!tr || !bytes) return fail(CCN_EINVAL, "null argument");
     const StepPlan* pl;
     const int rc = step_plan(tr, B, H, W, &pl);
     if (rc) return rc;
@@ -1070,12 +1066,12 @@ int ccn_train_workspace_bytes(ccn_trainer_t tr, int32_t B, int32_t H, int32_t W,
 int ccn_train_forward(ccn_trainer_t tr, const float* params_dev, const float* x_t_dev, const float* z_dev, const int64_t* t_dev, float* eps_dev,
                       int32_t B, int32_t H, int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream)
 {
-    if (!tr || !params_dev || !x_t_dev || !z_dev || !t_dev || !eps_dev) return tfail(CCN_EINVAL, "null argument");
+    if (!tr || !params_dev || !x_t_dev || !z_dev || !t_dev || !eps_dev) return fail(CCN_EINVAL, "null argument");
     const StepPlan* pl;
     int rc = step_plan(tr, B, H, W, &pl);
     if (rc) return rc;
-    if (!workspace_dev || ((uintptr_t)workspace_dev & 255)) return tfail(CCN_EWORKSPACE, "workspace must be non-null and 256-byte aligned");
-    if (workspace_bytes < pl->total) return tfail(CCN_EWORKSPACE, "workspace too small: need " + std::to_string(pl->total));
+    if (!workspace_dev || ((uintptr_t)workspace_dev & 255)) return fail(CCN_EWORKSPACE, "workspace must be non-null and 256-byte aligned");
+    if (workspace_bytes < pl->total) return fail(CCN_EWORKSPACE, "workspace too small: need " + std::to_string(pl->total));
     auto body = [&](hipStream_t st, std::string& err) {
         Step s(tr, *pl, workspace_dev, st, params_dev, nullptr);
         if (!s.forward(x_t_dev, z_dev, t_dev, eps_dev)) { err = s.err; return false; }
@@ -1089,7 +1085,7 @@ int ccn_train_forward(ccn_trainer_t tr, const float* params_dev, const float* x_
         if (rc) return rc;
     } else {
         std::string err;
-        if (!body((hipStream_t)stream, err)) return tfail(CCN_EHIP, err);
+        if (!body((hipStream_t)stream, err)) return fail(CCN_EHIP, err);
     }
     tr->fB = B; tr->fH = H; tr->fW = W; tr->fws = workspace_dev;
     return CCN_OK;
@@ -1104,11 +1100,11 @@ int train_backward(const char* who, ccn_trainer_t tr, const float* params_dev, f
                    int32_t B, int32_t H, int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream, int64_t bucket_floats, ccn_grad_ready_cb cb, void* user)
 {
     if (tr->fB != B || tr->fH != H || tr->fW != W || tr->fws != workspace_dev)
-        return tfail(CCN_ESTATE, std::string(who) + " must follow ccn_train_forward with the same shape and workspace");
+        return fail(CCN_ESTATE, std::string(who) + " must follow ccn_train_forward with the same shape and workspace");
     const StepPlan* pl;
     const int rc = step_plan(tr, B, H, W, &pl);
     if (rc) return rc;
-    if (workspace_bytes < pl->total) return tfail(CCN_EWORKSPACE, "workspace too small");
+    if (workspace_bytes < pl->total) return fail(CCN_EWORKSPACE, "workspace too small");
     auto body = [&](hipStream_t st, std::string& err) {
         Step s(tr, *pl, workspace_dev, st, params_dev, grads_dev);
         s.bucket_cb = cb; s.bucket_user = user; s.bucket_floats = bucket_floats > 0 ? bucket_floats : 1;
@@ -1122,7 +1118,7 @@ int train_backward(const char* who, ccn_trainer_t tr, const float* params_dev, f
         return run_graphed(tr, key, (hipStream_t)stream, body);
     }
     std::string err;
-    if (!body((hipStream_t)stream, err)) return tfail(CCN_EHIP, err);
+    if (!body((hipStream_t)stream, err)) return fail(CCN_EHIP, err);
     return CCN_OK;
 }
 
@@ -1149,7 +1145,7 @@ extern "C" {
 int ccn_train_backward(ccn_trainer_t tr, const float* params_dev, float* grads_dev, const float* x_t_dev, const float* z_dev, const float* d_eps_dev,
                        int32_t B, int32_t H, int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream)
 {
-    if (!tr || !params_dev || !grads_dev || !x_t_dev || !z_dev || !d_eps_dev) return tfail(CCN_EINVAL, "null argument");
+    if (!tr || !params_dev || !grads_dev || !x_t_dev || !z_dev || !d_eps_dev) return fail(CCN_EINVAL, "null argument");
     return train_backward("ccn_train_backward", tr, params_dev, grads_dev, x_t_dev, z_dev, d_eps_dev, B, H, W, workspace_dev, workspace_bytes, stream, 0, nullptr, nullptr);
 }
 
@@ -1157,7 +1153,7 @@ int ccn_train_backward_bucketed(ccn_trainer_t tr, const float* params_dev, float
                                 int32_t B, int32_t H, int32_t W, void* workspace_dev, size_t workspace_bytes, void* stream, int64_t bucket_floats,
                                 ccn_grad_ready_cb cb, void* user)
 {
-    if (!tr || !params_dev || !grads_dev || !x_t_dev || !z_dev || !d_eps_dev || !cb) return tfail(CCN_EINVAL, "null argument");
+    if (!tr || !params_dev || !grads_dev || !x_t_dev || !z_dev || !d_eps_dev || !cb) return fail(CCN_EINVAL, "null argument");
     return train_backward("ccn_train_backward_bucketed", tr, params_dev, grads_dev, x_t_dev, z_dev, d_eps_dev, B, H, W, workspace_dev, workspace_bytes, stream, bucket_floats,
                           cb, user);
 }
@@ -1205,31 +1201,31 @@ int ccn_internal_wgrad(int32_t dtype, int32_t kind, const void* x, const void* g
                        int32_t Cin, int32_t Civ, int32_t Cout, int32_t Cov, int32_t split, void* scratch, size_t scratch_bytes, float* grad, void* stream,
                        int32_t* nsplit_out, int32_t* tiles_out, size_t* need)
 {
-    if (dtype != CCN_DTYPE_F32 && dtype != CCN_DTYPE_BF16) return tfail(CCN_EINVAL, "ccn_internal_wgrad: dtype must be fp32 or bf16");
-    if (kind != KIND_C3S1 && kind != KIND_C3S2 && kind != KIND_CT4 && kind != KIND_STEM) return tfail(CCN_EINVAL, "ccn_internal_wgrad: bad kind");
-    if (B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0) return tfail(CCN_EINVAL, "ccn_internal_wgrad: sizes must be positive");
+    if (dtype != CCN_DTYPE_F32 && dtype != CCN_DTYPE_BF16) return fail(CCN_EINVAL, "ccn_internal_wgrad: dtype must be fp32 or bf16");
+    if (kind != KIND_C3S1 && kind != KIND_C3S2 && kind != KIND_CT4 && kind != KIND_STEM) return fail(CCN_EINVAL, "ccn_internal_wgrad: bad kind");
+    if (B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0) return fail(CCN_EINVAL, "ccn_internal_wgrad: sizes must be positive");
     const int epc = dtype == CCN_DTYPE_F32 ? 4 : 8;
-    if (Cin % epc || Cout % epc) return tfail(CCN_EINVAL, "ccn_internal_wgrad: Cin and Cout must be multiples of " + std::to_string(epc));
-    if (Civ <= 0 || Civ > Cin || Cov <= 0 || Cov > Cout) return tfail(CCN_EINVAL, "ccn_internal_wgrad: Civ / Cov must lie in 1..Cin / 1..Cout");
-    if (kind == KIND_C3S2 && (Hin % 2 || Win % 2)) return tfail(CCN_EINVAL, "ccn_internal_wgrad: the stride-2 conv needs even Hin and Win");
-    if (gn_ab && !silu && kind != KIND_C3S1) return tfail(CCN_EINVAL, "ccn_internal_wgrad: GroupNorm without SiLU only exists in front of a 3x3 s1 conv");
-    if (split < -1) return tfail(CCN_EINVAL, "ccn_internal_wgrad: split must be -1, 0 or a count");
+    if (Cin % epc || Cout % epc) return fail(CCN_EINVAL, "ccn_internal_wgrad: Cin and Cout must be multiples of " + std::to_string(epc));
+    if (Civ <= 0 || Civ > Cin || Cov <= 0 || Cov > Cout) return fail(CCN_EINVAL, "ccn_internal_wgrad: Civ / Cov must lie in 1..Cin / 1..Cout");
+    if (kind == KIND_C3S2 && (Hin % 2 || Win % 2)) return fail(CCN_EINVAL, "ccn_internal_wgrad: the stride-2 conv needs even Hin and Win");
+    if (gn_ab && !silu && kind != KIND_C3S1) return fail(CCN_EINVAL, "ccn_internal_wgrad: GroupNorm without SiLU only exists in front of a 3x3 s1 conv");
+    if (split < -1) return fail(CCN_EINVAL, "ccn_internal_wgrad: split must be -1, 0 or a count");
     const WgPlan w = wgrad_plan(dtype, kind, B, Hin, Win, Cin, Civ, silu ? 1 : 0, Cout, Cov);
     const int nsplit = split == 0 ? w.nsplit[0] : (split < 0 ? w.nsplit[1] : (split > w.tiles ? w.tiles : split));
     const size_t bytes = (size_t)nsplit * w.a.taps_w * Cout * Cin * 4;
     if (nsplit_out) *nsplit_out = nsplit;
     if (tiles_out) *tiles_out = w.tiles;
     if (need) *need = bytes;
-    if (!scratch) return need ? CCN_OK : tfail(CCN_EINVAL, "ccn_internal_wgrad: null scratch and nowhere to report its size");
-    if (!x || !dy || !grad) return tfail(CCN_EINVAL, "ccn_internal_wgrad: null argument");
-    if (scratch_bytes < bytes) return tfail(CCN_EINVAL, "ccn_internal_wgrad: scratch too small: need " + std::to_string(bytes));
-    if (wgrad_prepare() != hipSuccess) return tfail(CCN_EHIP, "kernel attribute setup failed");
+    if (!scratch) return need ? CCN_OK : fail(CCN_EINVAL, "ccn_internal_wgrad: null scratch and nowhere to report its size");
+    if (!x || !dy || !grad) return fail(CCN_EINVAL, "ccn_internal_wgrad: null argument");
+    if (scratch_bytes < bytes) return fail(CCN_EINVAL, "ccn_internal_wgrad: scratch too small: need " + std::to_string(bytes));
+    if (wgrad_prepare() != hipSuccess) return fail(CCN_EHIP, "kernel attribute setup failed");
     WgArgs a = w.a;
     a.x = x; a.gn_ab = (const float2*)gn_ab; a.dy = dy; a.part = (float*)scratch; a.nsplit = nsplit;
     hipError_t e = launch_wgrad(dtype, kind, a, (hipStream_t)stream);
-    if (e != hipSuccess) return tfail(CCN_EHIP, std::string("wgrad: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(CCN_EHIP, std::string("wgrad: ") + hipGetErrorString(e));
     e = launch_wgrad_reduce(a.part, nsplit, a.taps_w, Cout, Cin, Cov, Civ, kind == KIND_CT4 ? 1 : 0, grad, (hipStream_t)stream);
-    if (e != hipSuccess) return tfail(CCN_EHIP, std::string("wgrad_reduce: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(CCN_EHIP, std::string("wgrad_reduce: ") + hipGetErrorString(e));
     return CCN_OK;
 }
 
@@ -1242,33 +1238,33 @@ int ccn_internal_gn_bwd(int32_t dtype, const void* x, const void* dA, const void
                         float* dgamma, float* dbeta, float* dfilm, float* dbias, void* scratch, size_t scratch_bytes, void* stream, int32_t* geom,
                         size_t* need)
 {
-    if (dtype != CCN_DTYPE_F32 && dtype != CCN_DTYPE_BF16) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: dtype must be fp32 or bf16");
-    if (B <= 0 || HW <= 0 || C <= 0 || G <= 0) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: sizes must be positive");
-    if (C % 8) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: C must be a multiple of 8");
-    if (C % G) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: C must be a multiple of G");
-    if (film && film_bstride < 2 * C) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: a FiLM row holds C scales and C shifts");
-    if (film && !dfilm) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: FiLM needs dfilm");
+    if (dtype != CCN_DTYPE_F32 && dtype != CCN_DTYPE_BF16) return fail(CCN_EINVAL, "ccn_internal_gn_bwd: dtype must be fp32 or bf16");
+    if (B <= 0 || HW <= 0 || C <= 0 || G <= 0) return fail(CCN_EINVAL, "ccn_internal_gn_bwd: sizes must be positive");
+    if (C % 8) return fail(CCN_EINVAL, "ccn_internal_gn_bwd: C must be a multiple of 8");
+    if (C % G) return fail(CCN_EINVAL, "ccn_internal_gn_bwd: C must be a multiple of G");
+    if (film && film_bstride < 2 * C) return fail(CCN_EINVAL, "ccn_internal_gn_bwd: a FiLM row holds C scales and C shifts");
+    if (film && !dfilm) return fail(CCN_EINVAL, "ccn_internal_gn_bwd: FiLM needs dfilm");
     const GnBwdGeom gg = gn_bwd_geom(dtype, B, HW, C);
     const size_t half = align_up((size_t)B * gg.nblk * C * sizeof(float2), 256), bytes = 2 * half;
     if (geom) { geom[0] = gg.nslb; geom[1] = gg.pstep; geom[2] = gg.ppb; geom[3] = gg.nblk; geom[4] = gg.zblocks; }
     if (need) *need = bytes;
-    if (!scratch) return need ? CCN_OK : tfail(CCN_EINVAL, "ccn_internal_gn_bwd: null scratch and nowhere to report its size");
-    if (!x || !dA || !ab || !stats || !gamma || !out || !gstat || !dgamma || !dbeta) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: null argument");
-    if (scratch_bytes < bytes) return tfail(CCN_EINVAL, "ccn_internal_gn_bwd: scratch too small: need " + std::to_string(bytes));
+    if (!scratch) return need ? CCN_OK : fail(CCN_EINVAL, "ccn_internal_gn_bwd: null scratch and nowhere to report its size");
+    if (!x || !dA || !ab || !stats || !gamma || !out || !gstat || !dgamma || !dbeta) return fail(CCN_EINVAL, "ccn_internal_gn_bwd: null argument");
+    if (scratch_bytes < bytes) return fail(CCN_EINVAL, "ccn_internal_gn_bwd: scratch too small: need " + std::to_string(bytes));
     hipStream_t st = (hipStream_t)stream;
     float2 *scr_gn = (float2*)scratch, *scr_film = (float2*)((char*)scratch + half);
     const int cpg = C / G;
     const double count = (double)cpg * HW;
     const float2 *abt = (const float2*)ab, *stt = (const float2*)stats;
     hipError_t e = launch_gn_bwd_reduce(dtype, x, dA, abt, stt, scr_gn, B, HW, C, cpg, G, silu ? 1 : 0, st);
-    if (e != hipSuccess) return tfail(CCN_EHIP, std::string("gn_bwd_reduce: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(CCN_EHIP, std::string("gn_bwd_reduce: ") + hipGetErrorString(e));
     e = launch_gn_bwd_finalize(scr_gn, gg.nblk, B, C, cpg, G, count, gamma, (float2*)gstat, dgamma, dbeta, st);
-    if (e != hipSuccess) return tfail(CCN_EHIP, std::string("gn_bwd_finalize: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(CCN_EHIP, std::string("gn_bwd_finalize: ") + hipGetErrorString(e));
     e = launch_gn_bwd_apply(dtype, x, dA, abt, stt, (const float2*)gstat, addend, out, film, film_bstride, scr_film, B, HW, C, cpg, G, silu ? 1 : 0, st);
-    if (e != hipSuccess) return tfail(CCN_EHIP, std::string("gn_bwd_apply: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(CCN_EHIP, std::string("gn_bwd_apply: ") + hipGetErrorString(e));
     if (film) e = launch_film_bwd_finalize(scr_film, gg.nblk, film, film_bstride, dfilm, dbias, B, C, st);
     else if (dbias) e = launch_colsum_from_pairs(scr_film, B * gg.nblk, C, dbias, st);
-    if (e != hipSuccess) return tfail(CCN_EHIP, std::string(film ? "film_bwd: " : "colsum_from_pairs: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(CCN_EHIP, std::string(film ? "film_bwd: " : "colsum_from_pairs: ") + hipGetErrorString(e));
     return CCN_OK;
 }
 
@@ -1276,16 +1272,16 @@ int ccn_internal_gn_bwd(int32_t dtype, const void* x, const void* dA, const void
 int ccn_internal_colsum(int32_t dtype, const void* dy, int32_t B, int32_t HW, int32_t C, void* scratch, size_t scratch_bytes, float* db, void* stream,
                         size_t* need)
 {
-    if (dtype != CCN_DTYPE_F32 && dtype != CCN_DTYPE_BF16) return tfail(CCN_EINVAL, "ccn_internal_colsum: dtype must be fp32 or bf16");
-    if (B <= 0 || HW <= 0 || C <= 0) return tfail(CCN_EINVAL, "ccn_internal_colsum: sizes must be positive");
-    if (C % 8) return tfail(CCN_EINVAL, "ccn_internal_colsum: C must be a multiple of 8");
+    if (dtype != CCN_DTYPE_F32 && dtype != CCN_DTYPE_BF16) return fail(CCN_EINVAL, "ccn_internal_colsum: dtype must be fp32 or bf16");
+    if (B <= 0 || HW <= 0 || C <= 0) return fail(CCN_EINVAL, "ccn_internal_colsum: sizes must be positive");
+    if (C % 8) return fail(CCN_EINVAL, "ccn_internal_colsum: C must be a multiple of 8");
     const size_t bytes = (size_t)B * gn_bwd_geom(dtype, B, HW, C).nblk * C * 4;
     if (need) *need = bytes;
-    if (!scratch) return need ? CCN_OK : tfail(CCN_EINVAL, "ccn_internal_colsum: null scratch and nowhere to report its size");
-    if (!dy || !db) return tfail(CCN_EINVAL, "ccn_internal_colsum: null argument");
-    if (scratch_bytes < bytes) return tfail(CCN_EINVAL, "ccn_internal_colsum: scratch too small: need " + std::to_string(bytes));
+    if (!scratch) return need ? CCN_OK : fail(CCN_EINVAL, "ccn_internal_colsum: null scratch and nowhere to report its size");
+    if (!dy || !db) return fail(CCN_EINVAL, "ccn_internal_colsum: null argument");
+    if (scratch_bytes < bytes) return fail(CCN_EINVAL, "ccn_internal_colsum: scratch too small: need " + std::to_string(bytes));
     const hipError_t e = launch_colsum(dtype, dy, (float*)scratch, db, B, HW, C, (hipStream_t)stream);
-    if (e != hipSuccess) return tfail(CCN_EHIP, std::string("colsum: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(CCN_EHIP, std::string("colsum: ") + hipGetErrorString(e));
     return CCN_OK;
 }
 
@@ -1302,21 +1298,21 @@ int ccn_internal_colsum(int32_t dtype, const void* dy, int32_t B, int32_t HW, in
 int ccn_internal_conv_dgrad(ccn_trainer_t tr, const char* weight_name, const float* params_dev, const void* dy, const void* res, void* dx, int32_t B,
                             int32_t Hdy, int32_t Wdy, void* stream, char* route, size_t route_cap)
 {
-    if (!tr || !weight_name || !params_dev || !dy || !dx) return tfail(CCN_EINVAL, "ccn_internal_conv_dgrad: null argument");
-    if (B <= 0 || Hdy <= 0 || Wdy <= 0) return tfail(CCN_EINVAL, "ccn_internal_conv_dgrad: sizes must be positive");
+    if (!tr || !weight_name || !params_dev || !dy || !dx) return fail(CCN_EINVAL, "ccn_internal_conv_dgrad: null argument");
+    if (B <= 0 || Hdy <= 0 || Wdy <= 0) return fail(CCN_EINVAL, "ccn_internal_conv_dgrad: sizes must be positive");
     const TConvW* w = nullptr;
     for (const TConvW& c : tr->convs)
         if (tr->arch.params[c.pw].name == weight_name) w = &c;
-    if (!w) return tfail(CCN_EINVAL, std::string("ccn_internal_conv_dgrad: no conv weight named ") + weight_name);
-    if (w->kind == KIND_STEM) return tfail(CCN_EINVAL, "ccn_internal_conv_dgrad: the stem has no data gradient");
-    if (w->kind == KIND_CT4 && (Hdy % 2 || Wdy % 2)) return tfail(CCN_EINVAL, "ccn_internal_conv_dgrad: the ConvTranspose's gradient needs even Hdy and Wdy");
-    if (res && w->kind != KIND_C3S2) return tfail(CCN_EINVAL, "ccn_internal_conv_dgrad: only the stride-2 conv's gradient adds a residual in the step");
+    if (!w) return fail(CCN_EINVAL, std::string("ccn_internal_conv_dgrad: no conv weight named ") + weight_name);
+    if (w->kind == KIND_STEM) return fail(CCN_EINVAL, "ccn_internal_conv_dgrad: the stem has no data gradient");
+    if (w->kind == KIND_CT4 && (Hdy % 2 || Wdy % 2)) return fail(CCN_EINVAL, "ccn_internal_conv_dgrad: the ConvTranspose's gradient needs even Hdy and Wdy");
+    if (res && w->kind != KIND_C3S2) return fail(CCN_EINVAL, "ccn_internal_conv_dgrad: only the stride-2 conv's gradient adds a residual in the step");
     StepPlan pl;
     pl.B = B; pl.H = Hdy; pl.W = Wdy;
     const ConvPlan c = Planner(tr, pl).conv_dgrad(*w, Hdy, Wdy, res != nullptr);   // (leaves the operand's descriptor on pl.pack_list)
     hipStream_t st = (hipStream_t)stream;
     PackDesc* desc = nullptr;
-    if (hipMalloc((void**)&desc, sizeof(PackDesc)) != hipSuccess) return tfail(CCN_EHIP, "ccn_internal_conv_dgrad: hipMalloc failed");
+    if (hipMalloc((void**)&desc, sizeof(PackDesc)) != hipSuccess) return fail(CCN_EHIP, "ccn_internal_conv_dgrad: hipMalloc failed");
     std::string err;
     if (hipMemcpy(desc, &pl.pack_list.back(), sizeof(PackDesc), hipMemcpyHostToDevice) != hipSuccess) err = "descriptor upload failed";
     if (err.empty()) {
@@ -1336,14 +1332,14 @@ int ccn_internal_conv_dgrad(ccn_trainer_t tr, const char* weight_name, const flo
     }
     const hipError_t se = hipStreamSynchronize(st);                       // the descriptor is read by the pack kernel
     (void)hipFree(desc);
-    if (!err.empty()) return tfail(CCN_EHIP, "ccn_internal_conv_dgrad: " + err);
-    if (se != hipSuccess) return tfail(CCN_EHIP, std::string("ccn_internal_conv_dgrad: ") + hipGetErrorString(se));
+    if (!err.empty()) return fail(CCN_EHIP, "ccn_internal_conv_dgrad: " + err);
+    if (se != hipSuccess) return fail(CCN_EHIP, std::string("ccn_internal_conv_dgrad: ") + hipGetErrorString(se));
     return CCN_OK;
 }
 
 int ccn_train_profile_enable(ccn_trainer_t tr, int32_t on)
 {
-    if (!tr) return tfail(CCN_EINVAL, "null handle");
+    if (!tr) return fail(CCN_EINVAL, "null handle");
     tr->profiling = on != 0;
     tr->marks.clear(); tr->ev_used = 0;
     return CCN_OK;
@@ -1351,15 +1347,15 @@ int ccn_train_profile_enable(ccn_trainer_t tr, int32_t on)
 
 int ccn_train_profile_read(ccn_trainer_t tr, const char** names, float* ms, int32_t* calls, double* flops, double* bytes, int32_t cap, int32_t* n)
 {
-    if (!tr || !names || !ms || !calls || !flops || !bytes || !n) return tfail(CCN_EINVAL, "null argument");
-    if (cap < TF_COUNT) return tfail(CCN_EINVAL, "cap too small");
-    if (hipDeviceSynchronize() != hipSuccess) return tfail(CCN_EHIP, "hipDeviceSynchronize failed");
+    if (!tr || !names || !ms || !calls || !flops || !bytes || !n) return fail(CCN_EINVAL, "null argument");
+    if (cap < TF_COUNT) return fail(CCN_EINVAL, "cap too small");
+    if (hipDeviceSynchronize() != hipSuccess) return fail(CCN_EHIP, "hipDeviceSynchronize failed");
     for (int f = 0; f < TF_COUNT; ++f) { names[f] = kTrainFamilies[f]; ms[f] = 0.f; calls[f] = 0; flops[f] = 0.0; bytes[f] = 0.0; }
     for (size_t i = 0; i + 1 < tr->marks.size(); ++i) {
         const Mark& m = tr->marks[i];
         if (m.fam < 0) continue;
         float t = 0.f;
-        if (hipEventElapsedTime(&t, m.ev, tr->marks[i + 1].ev) != hipSuccess) return tfail(CCN_EHIP, "hipEventElapsedTime failed");
+        if (hipEventElapsedTime(&t, m.ev, tr->marks[i + 1].ev) != hipSuccess) return fail(CCN_EHIP, "hipEventElapsedTime failed");
         ms[m.fam] += t; calls[m.fam] += 1; flops[m.fam] += m.flops; bytes[m.fam] += m.bytes;
     }
     *n = TF_COUNT;
