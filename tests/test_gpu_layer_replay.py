@@ -21,6 +21,13 @@ launches it), and the coverage test checks that the shape matrix reaches every r
 Each replayed layer also checks three deliberately wrong references computed on the host (a zeroed weight tap of one output channel,
 the input shifted by one pixel inside the last column tile, GroupNorm statistics that count the padding of partial tiles): each must
 violate the bound on a clear majority of the outputs it changes, i.e. the bound tells those bug classes apart from rounding.
+
+The fp32 and f16x3 modes (fp32 storage) run through the same harness.  Their GroupNorm term is not a constant: gn_chain_depth
+states the longest chain of fp32 additions behind one partial sum from the kernel that wrote the input, and gn_coef_err turns it
+into the error of scale and shift per group, from the data (the cancellation in E[x^2] - mean^2 included).  A layer on split
+operands (``ops=f16x3`` in the route report) has the bound's split terms and, as its sharp criterion, the RMS comparison with
+references that omit one term of the three-term product (split_terms, omissions, check_rows); tests/test_gpu_split_replay.py holds
+that mode's shape matrix.
 """
 import ctypes
 import sys
@@ -40,8 +47,9 @@ from infer_plan_cases import plan_routes  # noqa: E402
 
 DEV = "cuda:0"
 U32 = 2.0 ** -24          # fp32 unit roundoff
-ETA = 2.0 ** -12          # relative error of the kernels' GroupNorm scale / shift: fp32 partial sums of up to 4096 terms per slot
-                          # (worst case 4096 u), then a float64 / fp32 reduction over slots
+ETA = 2.0 ** -12          # bf16 mode: relative error of the kernels' GroupNorm scale / shift (fp32 partial sums of rounded bf16 values;
+                          # an operand within it of a bf16 rounding boundary may round the other way).  The fp32 and f16x3 modes do
+                          # not use it: their coefficient error is derived from the summation chain (gn_chain_depth, gn_coef_err)
 ETA_COND = 2.0 ** -11     # FiLM scale / shift against float64, relative to sum|W||h| + |b|: the device's timestep embedding is within
                           # 2e-4 of the CPU's on O(1) values (test_gpu_parity.test_timestep_embedding) and the linears are fp32
 SILU_REL = 2.0 ** -18     # bf16 mode's SiLU (v_exp / v_rcp approximations) relative to its value
@@ -196,15 +204,86 @@ def gn_affine(x, gamma, beta, G, pad_hw=None):
     return a[:, :, None, None], c[:, :, None, None]
 
 
-def operand(x, a, c, silu, bf16_mode):
+def mode_name(m):
+    """the storage / arithmetic mode of a run: "bf16", "fp32" or "f16x3" (True / False: the former bf16_mode flag)"""
+    if isinstance(m, str):
+        assert m in ("bf16", "fp32", "f16x3"), m
+        return m
+    return "bf16" if m else "fp32"
+
+
+def gn_chain_depth(route, C, G=8):
+    """Longest chain of fp32 additions between one stored value and the partial sum that holds it, for a tensor of C channels written
+    by the launch `route` in fp32 storage (fp32 and f16x3 modes).  From the kernels:
+
+      tile/epilogue.inc (ws / fr, 512 threads) and the epilogue of conv_igemm_kernel (ccn_kernels.hip, 256 threads): thread (o, ps)
+          owns 8 channels of the pixels ps, ps + PSL, ... of each 128-pixel pass, PSL = threads / (BN / 8): it adds 128 / PSL values
+          per pass, th / 4 passes (the 4-wave kernel: one), into s1 (and fmaf(v, v, s2): one rounding per term as well)
+      tile/gn_part_tail.inc: xor-shuffle levels NOCT, 2 NOCT, .. 32 with NOCT = BN / 8: log2(512 / BN) additions
+          the waves in index order:                                                     NWAVES additions (8; 4-wave kernel: 4)
+          the channels of one group inside the N tile in index order:                   min(cpg, BN) additions
+      gn_group_stats (gn_act_fused_kernel, in-kernel finalize) / gn_finalize_kernel: the slots in double (2^-53 each: nothing next
+          to the above), mean, var and rstd in double; one more step is charged for them.
+
+    A value passes through at most that many roundings, each relative 2^-24 to a partial sum that is bounded by the sum of the
+    absolute values: |sum_kernel - sum| <= gamma_D sum|x|, gamma_D = D u / (1 - D u) (Higham, Accuracy and Stability, section 4.2).
+    D is 20 .. 51 for the layers of the test matrices (a few dozen: 2^-19 .. 2^-18), against the 4096 u that ETA charged."""
+    bn = 128 if C >= 128 else (64 if C >= 64 else 32)        # conv_bn_for
+    kern = route["kernel"]
+    if kern in ("ws", "fr"):
+        threads, nwaves, passes = 512, 8, route["th"] // 4
+    elif kern == "igemm":
+        threads, nwaves, passes = 256, 4, 1
+    else:
+        raise AssertionError(f"no GroupNorm summation model for a tensor written by {kern!r} in fp32 storage")
+    noct = bn // 8
+    per_pass = 128 // (threads // noct)
+    levels = int(np.log2(64 // noct))
+    cpg = C // min(G, C)
+    return passes * per_pass + levels + nwaves + min(cpg, bn) + 1
+
+
+def gn_coef_err(x, a, c, G, D):
+    """Error of the kernels' fp32 GroupNorm coefficients against the float64 (a, c) of gn_affine, from the data: (relative error of
+    a, absolute error of c), per (sample, channel).  With gamma = gamma_D of gn_chain_depth and E.. the means over a group:
+
+        |d mean|  <= gamma E|x|                              (sum of the stored values, the same fp32 values the tap returns)
+        |d E[x^2]| <= gamma E[x^2]                            (all terms positive)
+        |d var|   <= gamma (E[x^2] + 2 |mean| E|x|) + (d mean)^2          var = E[x^2] - mean^2 in double
+        rstd      =  (var + eps)^-1/2:  relative error (1 - |d var| / (var + eps))^-1/2 - 1
+                     -- this is where the cancellation factor E[x^2] / var enters
+        a = fp32(gamma_c rstd):         relative error of rstd, then 2^-24
+        c = fp32(beta_c - mean a):      |a| (|d mean| + |mean| rel(rstd)) (1 + rel(rstd)), then 2^-24 |c|"""
+    N, C, H, W = x.shape
+    g = min(G, C)
+    xs = x.reshape(N, g, -1)
+    gam = D * U32 / (1 - D * U32)
+    m1, m2, mean = xs.abs().mean(2), (xs * xs).mean(2), xs.mean(2)
+    var = m2 - mean * mean
+    dmean = gam * m1
+    dvar = gam * (m2 + 2 * mean.abs() * m1) + dmean * dmean
+    rel = (1 - dvar / (var + 1e-5)).clamp_min(1e-30) ** -0.5 - 1
+    rep = lambda v: v.repeat_interleave(C // g, 1)[:, :, None, None]
+    eta_a = (1 + rep(rel)) * (1 + U32) - 1
+    dc = a.abs() * (rep(dmean) + rep(mean.abs()) * rep(rel)) * (1 + rep(rel)) + U32 * c.abs()
+    return eta_a, dc
+
+
+def operand(x, a, c, silu, mode, coef_err=None):
     """MFMA operand of a GroupNorm input and the width of its uncertainty: bf16 mode -> (bf16(y), hi - lo) where [lo, hi] holds every
-    rounding the kernel may produce from its fp32 statistics; fp32 mode -> (y, bound on the kernel's operand error)"""
+    rounding the kernel may produce from its fp32 statistics; fp32 / f16x3 mode -> (y, bound on the kernel's operand error) with the
+    coefficient error of gn_coef_err: z = fmaf(x, a, c) rounds once, SiLU (slope at most 1.1) is y / (1 + expf(-y)) with a
+    full-precision expf and a true division, 4 roundings' worth"""
+    mode = mode_name(mode)
     z = x * a + c
     y = z * torch.sigmoid(z) if silu else z
-    d = (1.1 if silu else 1.0) * ETA * ((x * a).abs() + c.abs()) + (SILU_REL if (silu and bf16_mode) else 4 * U32) * y.abs()
-    if not bf16_mode:
-        return y, d
-    return bf16(y), bf16(y + d) - bf16(y - d)
+    if mode == "bf16":
+        d = (1.1 if silu else 1.0) * ETA * ((x * a).abs() + c.abs()) + (SILU_REL if silu else 4 * U32) * y.abs()
+        return bf16(y), bf16(y + d) - bf16(y - d)
+    eta_a, dc = coef_err
+    dz = (x * a).abs() * eta_a + dc
+    dz = dz + U32 * (z.abs() + dz)
+    return y, (1.1 if silu else 1.0) * dz + 4 * U32 * y.abs()
 
 
 def bands(Hout, T, even, rng):
@@ -233,7 +312,9 @@ class Source:
 
     def __init__(self, sd, ch_mult, x_in, eps, h, tap_fn, samples, version, bf16_mode, routes):
         self.sd, self.ch_mult, self.x_in, self.eps, self.h = sd, ch_mult, x_in, eps, h
-        self.tap_fn, self.samples, self.version, self.bf16_mode, self.routes = tap_fn, samples, version, bf16_mode, routes
+        self.tap_fn, self.samples, self.version, self.routes = tap_fn, samples, version, routes
+        self.mode = mode_name(bf16_mode)              # "bf16", "fp32" or "f16x3" (a bool: bf16 or fp32)
+        self.bf16_mode = self.mode == "bf16"
         self._taps, self._w = {}, {}
 
     def tap(self, name):
@@ -254,11 +335,52 @@ class Source:
         return self._w[key]
 
 
-def replay_layer(src, layer, G=8, rng=None, check_wrong=True):
+# ---- f16x3: the split operands and the omission references of criterion (a) ---------------------------------------------------------
+SLICE_K_MAX = 1152        # the single-slice omission is asserted on layers with K <= 1152 (64- and 128-channel 3x3 convs, ConvTransposes
+                          # with Cin <= 256); on wider layers its share is too small to tell from fp32 accumulation: printed only
+OMIT_FACTOR = 10          # RMS(omission reference - full) >= 10 RMS(got - full): test_gpu_split.test_conv_transpose_exact_operand_replay
+
+
+def split_terms(kind, a32, w, Cin):
+    """The halves the kernel multiplies (split_emulation.split = split_pack and the commit-time weight split, test_split_host.py),
+    as float64: a_hi, a_lo of the fp32 operand; w_hi / s, w_lo / s of the weights scaled by their power of two s; and the channels
+    [c0, Cin) of the last K = 16 slice that holds real channels (a partial 32-channel chunk ends in a slice of padding)."""
+    import split_emulation
+    w32 = w.float()
+    sc = split_emulation.weight_scale(w32)
+    wh, wl = split_emulation.split(w32 * sc)
+    ah, al = split_emulation.split(a32.float())
+    return dict(scale=sc, wh=wh.double() / sc, wl=wl.double() / sc, ah=ah.double(), al=al.double(), c0=16 * ((Cin - 1) // 16))
+
+
+def omissions(kind, sp, r0, r1):
+    """{name: omission reference - full product, before the epilogue's gain} on output rows [r0, r1), float64:
+      alwh   a_lo w_hi omitted everywhere: a_hi (w_hi + w_lo) in place of the full product
+      ahwl   a_hi w_lo omitted everywhere: (a_hi + a_lo) w_hi
+      slice  a_lo w_hi omitted in one K = 16 slice, the last step of the K loop (tile/split_steps.inc: last slice of the last tap of
+             the last Cin chunk, where the fetch one term ahead ends): tap (2, 2) of a 3x3 conv; of a ConvTranspose the fourth tap of
+             each output parity (fill_taps: kernel rows / columns 3 for even outputs, 2 for odd ones)"""
+    ah, al, wh, wl, c0 = sp["ah"], sp["al"], sp["wh"], sp["wl"], sp["c0"]
+    ws = torch.zeros_like(wh[:, c0:] if kind != "up" else wh[c0:])
+    if kind == "up":
+        ws[:, :, 2:4, 2:4] = wh[c0:, :, 2:4, 2:4]
+    else:
+        ws[:, :, 2, 2] = wh[:, c0:, 2, 2]
+    # (the convolution is linear and float64 here: a_hi (w_hi + w_lo) - (a_hi + a_lo)(w_hi + w_lo) = -a_lo (w_hi + w_lo), and so on)
+    return {"alwh": -conv_rows(kind, al, wh + wl, r0, r1), "ahwl": -conv_rows(kind, ah + al, wl, r0, r1),
+            "slice": -conv_rows(kind, al[:, c0:], ws, r0, r1)}
+
+
+def replay_layer(src, layer, G=8, rng=None, check_wrong=True, band_px=96 * 96):
     """max bound ratio, RMS error in output ulps and the wrong references' violated shares of one layer"""
     name, kind, inp, resn, wkey, nkey, fkey = layer
     route = src.routes[name]
     bfm = src.bf16_mode
+    mode = src.mode
+    split = route.get("ops") == "f16x3"
+    assert (mode == "f16x3") == ("ops" in route) and route.get("ops", "f32") in ("f32", "f16x3"), (mode, route)
+    if split:       # the only launches with a model for split operands: tile/split_steps.inc in ccn_conv_ws.hip / ccn_conv_fr.hip
+        assert route["kernel"] in ("ws", "fr") and route["kind"] in ("C3S1", "CT4") and route["ksplit"] == 1, route
     sd = src.sd
     ks = route["ksplit"]
     kern = route["kernel"]
@@ -276,13 +398,20 @@ def replay_layer(src, layer, G=8, rng=None, check_wrong=True):
         if nkey:
             gam = torch.from_numpy(np.asarray(sd[nkey + ".weight"], np.float64)); bet = torch.from_numpy(np.asarray(sd[nkey + ".bias"], np.float64))
             ga, gc = gn_affine(x, gam, bet, G)
+            # fp32 storage: the coefficient error from the summation chain of the launch that wrote the input and its partial sums
+            cerr = None if bfm else gn_coef_err(x, ga, gc, G, gn_chain_depth(src.routes[inp], x.shape[1], G))
             if head2:
                 op, dop = x, torch.zeros_like(x)
             else:
-                op, dop = operand(x, ga, gc, kind != "head", bfm)
+                op, dop = operand(x, ga, gc, kind != "head", mode, cerr)
         else:
             op, dop = x, torch.zeros_like(x)
     N, Cin, Hin, Win = x.shape
+    if split:
+        # the kernel's operand is an fp32 value (the tap, or fp32 GroupNorm + SiLU of it: GnCoef<float>), split by split_pack
+        dop = dop + U32 * op.abs()
+        op = op.float().double()
+        sp = split_terms(kind, op, w, Cin)
     K = 27 if kind == "stem" else Cin * (4 if kind == "up" else 9)
     if kern == "stem2":
         K += 1
@@ -294,7 +423,7 @@ def replay_layer(src, layer, G=8, rng=None, check_wrong=True):
     else:
         Cout, Hout, Wout = w.shape[0], Hin, Win
     T = route["th"] * (2 if kind == "up" else 1)
-    bl = bands(Hout, T, kind == "up", rng) if Hout * Wout > 96 * 96 else [(0, Hout)]
+    bl = bands(Hout, T, kind == "up", rng) if Hout * Wout > band_px else [(0, Hout)]
     got = src.eps if kind == "head" else src.tap(name)
     film = None
     if fkey:
@@ -307,6 +436,7 @@ def replay_layer(src, layer, G=8, rng=None, check_wrong=True):
         film = (s, t, ds, dt)
     bb = b[None, :, None, None]
     ratios, sq, sr, nel = [], 0.0, 0.0, 0
+    om_sq = {}                                           # f16x3: sum of squares of (omission reference - full), per omission
     viol = {"tap": [0, 0], "shift": [0, 0], "gnpad": [0, 0]}
     # wrong references: zeroed centre tap of one output channel, shifted last column tile, padded GroupNorm statistics
     o_bad = (Cout * 2) // 3
@@ -322,7 +452,7 @@ def replay_layer(src, layer, G=8, rng=None, check_wrong=True):
     if nkey and not head2 and (Win % 32 or Hin % route["th"]):
         th = route["th"]
         ga2, gc2 = gn_affine(x, gam, bet, G, pad_hw=(-(-Hin // th) * th, -(-Win // 32) * 32))
-        gp = operand(x, ga2, gc2, kind != "head", bfm)[0]
+        gp = operand(x, ga2, gc2, kind != "head", mode, cerr)[0]
     if head2:
         aw = [ga[i, :, 0, 0][None, :, None, None] * w for i in range(N)]         # per-sample W' (out, in, 3, 3), float64
         cmask = [gc[i:i + 1] * torch.ones_like(x[i:i + 1]) for i in range(N)]
@@ -339,8 +469,15 @@ def replay_layer(src, layer, G=8, rng=None, check_wrong=True):
                 dref["tap"] = torch.cat([conv_rows(kind, x[i:i + 1], ga[i, :, 0, 0][None, :, None, None] * wz, r0, r1) for i in range(N)])
         else:
             acc = conv_rows(kind, op, w, r0, r1)
-            A = conv_rows(kind, torch.cat([op.abs(), dop]), wa, r0, r1)
-            e_acc = K * U32 * A[:N] + A[N:]
+            if split:
+                # three fp32 accumulations per product; residuals of the two splits (2^-22 each: hi to 11 bits, lo to 11 more) and the
+                # dropped a_lo w_lo (2^-12 2^-12); halves in fp16's subnormal range round to 2^-25 absolute: every activation (x sum|w|),
+                # and the scaled weights (split_emulation.weight_scale: 2^-25 / scale each, x sum|a|)
+                e_acc = (conv_rows(kind, op.abs(), (3 * K * U32 + 2.0 ** -21 + 2.0 ** -24) * wa + 2.0 ** -25 / sp["scale"], r0, r1)
+                         + conv_rows(kind, dop + 2.0 ** -25, wa, r0, r1))
+            else:
+                A = conv_rows(kind, torch.cat([op.abs(), dop]), wa, r0, r1)
+                e_acc = K * U32 * A[:N] + A[N:]
             dref = {"tap": conv_rows(kind, op, wz, r0, r1), "shift": conv_rows(kind, sh - op, w, r0, r1)} if check_wrong else {}
             if gp is not None and check_wrong:
                 dref["gnpad"] = conv_rows(kind, gp - op, w, r0, r1)
@@ -355,6 +492,9 @@ def replay_layer(src, layer, G=8, rng=None, check_wrong=True):
                 ref = acc + bb + res
                 ecd = 0.0
             epi = 4 * U32 * ((acc + bb).abs() * gain + (ref - acc).abs() + ref.abs())
+            if split:
+                for kk, d in omissions(kind, sp, r0, r1).items():
+                    om_sq[kk] = om_sq.get(kk, 0.0) + float(((d * gain) ** 2).sum())
             pts = ROUNDING[(kern, ks)] if (bfm and kind != "head") else ()
             e = gain * e_acc
             if "acc" in pts:
@@ -380,11 +520,18 @@ def replay_layer(src, layer, G=8, rng=None, check_wrong=True):
         sq += float((err * err).sum()); sr += float((ref * ref).sum()); nel += err.numel()
     # RMS error in ulps of the layer's RMS output (an ulp of each element's own value would be dominated by outputs that cancel to ~0)
     ulp = 2 * float((hu16 if bfm else (lambda m: half_ulp(m, 24)))(torch.tensor((sr / nel) ** 0.5)))
-    return dict(name=name, route=f"{route['kind']}/{kern}/th{route['th']}/k{ks}/{route['gn']}", ratio=max(ratios),
-                rms_ulp=(sq / nel) ** 0.5 / ulp, viol={k: (v[0] / v[1] if v[1] else None) for k, v in viol.items()})
+    out = dict(name=name, route=f"{route['kind']}/{kern}/th{route['th']}/k{ks}/{route['gn']}", ratio=max(ratios),
+               rms_ulp=(sq / nel) ** 0.5 / ulp, viol={k: (v[0] / v[1] if v[1] else None) for k, v in viol.items()})
+    if split:
+        # criterion (a): RMS(got - full) against RMS(omission reference - full), over every replayed output
+        out["route"] += f"/bn{128 if Cout >= 128 else 64}"
+        out["K"] = K
+        out["rms_got"] = (sq / nel) ** 0.5
+        out["omit"] = {kk: (v / nel) ** 0.5 / max(out["rms_got"], 1e-300) for kk, v in om_sq.items()}
+    return out
 
 
-def replay_all(src, layers, label, skip=(), rng_seed=0, check_wrong=True):
+def replay_all(src, layers, label, skip=(), rng_seed=0, check_wrong=True, band_px=96 * 96):
     """replay every layer, print one row each, return the rows"""
     rng = np.random.default_rng(rng_seed)
     out = []
@@ -392,12 +539,18 @@ def replay_all(src, layers, label, skip=(), rng_seed=0, check_wrong=True):
     for L in layers:
         if L[0] in skip:
             continue
-        r = replay_layer(src, L, rng=rng, check_wrong=check_wrong)
+        r = replay_layer(src, L, rng=rng, check_wrong=check_wrong, band_px=band_px)
         v = r["viol"]
         print(f"  {r['name']:<14} {r['route']:<34} max ratio {r['ratio']:.3f}  rms {r['rms_ulp']:.3f} ulp   wrong refs violate: "
-              + " ".join(f"{k} {'-' if x is None else f'{x:.2f}'}" for k, x in v.items()))
+              + " ".join(f"{k} {'-' if x is None else f'{x:.2f}'}" for k, x in v.items())
+              + ("" if "omit" not in r else f"   K {r['K']} rms(got - full) {r['rms_got']:.3e}, omissions / that: "
+                 + " ".join(f"{k} {x:.1f}" + ("" if slice_asserted(r, k) else " (not asserted)") for k, x in r["omit"].items())))
         out.append(r)
     return out
+
+
+def slice_asserted(r, k):
+    return k != "slice" or r["K"] <= SLICE_K_MAX
 
 
 def check_rows(rows):
@@ -405,6 +558,9 @@ def check_rows(rows):
     assert not bad, f"layers outside their rounding bound: {bad}"
     weak = [(r["name"], k, x) for r in rows for k, x in r["viol"].items() if x is not None and x < MIN_VIOLATED]
     assert not weak, f"wrong references that the bound does not reject: {weak}"
+    # f16x3 split layers, criterion (a): the kernel is at least OMIT_FACTOR times closer (RMS) to the full product than each omission
+    blunt = [(r["name"], r["route"], k, x) for r in rows for k, x in r.get("omit", {}).items() if slice_asserted(r, k) and not x >= OMIT_FACTOR]
+    assert not blunt, f"split layers no closer to the full product than to one with an omitted term: {blunt}"
 
 
 def film_h(sd64, z, t):
@@ -518,7 +674,9 @@ def run_forward(synth, case, dtype):
     return dict(sd=sd, net=net, nat=nat, x=x, z=z, t=t, eps=eps, routes=routes, base=base, ch_mult=ch_mult, B=B, H=H, W=W)
 
 
-def make_source(run, samples, version, bf16_mode, t=None):
+def make_source(run, samples, version, bf16_mode, t=None, device_temb=False):
+    """bf16_mode: True / False or the mode's name.  device_temb: the conditioning vector in float64 from the timestep embedding the
+    device computed (oracle.ref_unet.cond_vector's `temb`), so that cos / sin at up to 999 rad are not counted against the FiLM layers"""
     nat, B = run["nat"], run["B"]
     shapes = tap_shapes(run["base"], run["ch_mult"], run["H"], run["W"])
     idx = torch.tensor(samples, device=DEV)
@@ -527,17 +685,34 @@ def make_source(run, samples, version, bf16_mode, t=None):
         return nat.read_activation(name, (B,) + shapes[name]).index_select(0, idx).double().cpu()
     sd64 = ref_unet.as_torch_sd(run["sd"], torch.float64)
     t = run["t"] if t is None else t
-    h = film_h(sd64, run["z"][samples], t[samples])
+    if device_temb:
+        from clip_feature_codec import _native
+        temb = _native.timestep_embedding(t[samples].to(DEV), int(sd64["time_proj.0.weight"].shape[1])).cpu().double()
+        with torch.no_grad():
+            h = ref_unet.cond_vector(sd64, run["z"][samples].double(), t[samples], temb=temb)
+    else:
+        h = film_h(sd64, run["z"][samples], t[samples])
     eps = run["eps"].index_select(0, idx).double().cpu() if run["eps"] is not None else None
     return Source(run["sd"], run["ch_mult"], run["x"][samples].double(), eps, h, tap_fn, samples, version, bf16_mode, run["routes"])
 
 
-def replay_case(synth, case, dtype):
+def replay_case(synth, case, dtype, only_split=False, one_per_class=False, band_px=96 * 96):
+    """only_split: the f16x3 layers on split operands only.  one_per_class: the first layer of every route class -- the whole route
+    line but the name (kernel, tile rows, N tiles, input form, FiLM / residual, operands) and the layer's widths"""
     run = run_forward(synth, case, dtype)
     B = run["B"]
-    src = make_source(run, sorted({0, B // 2, B - 1}), 0, dtype == "bf16")
-    rows = replay_all(src, layer_list(run["ch_mult"]), f"{case[0]} {dtype}: B={B} {run['H']}x{run['W']} (samples {src.samples})",
-                      rng_seed=B + run["H"])
+    src = make_source(run, sorted({0, B // 2, B - 1}), 0, dtype, device_temb=dtype == "f16x3")
+    layers = layer_list(run["ch_mult"])
+    if only_split:
+        layers = [L for L in layers if run["routes"][L[0]].get("ops") == "f16x3"]
+    if one_per_class:
+        first = {}
+        for L in layers:
+            r = run["routes"][L[0]]
+            first.setdefault(tuple(sorted((k, v) for k, v in r.items() if k != "name")) + tuple(run["sd"][L[4] + ".weight"].shape), L)
+        layers = list(first.values())
+    rows = replay_all(src, layers, f"{case[0]} {dtype}: B={B} {run['H']}x{run['W']} (samples {src.samples})", rng_seed=B + run["H"],
+                      band_px=band_px)
     return rows
 
 

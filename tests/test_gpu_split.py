@@ -2,7 +2,11 @@
 three v_mfma_f32_32x32x16_f16 per product).  It is held to the fp32 parity mode's own tolerances (tests/test_gpu_parity.py): the CPU
 emulation of the arithmetic (tests/split_emulation.py) meets each of them with >= 6x headroom -- C1 taps worst 2.9e-6, eps 1.6e-7 at C2,
 C2 50 steps 3.2e-5 -- and the GPU's own fp32 summation order is what those constants already carry for the fp32 mode.  The route and
-exact-operand tests at the end are what an alias of the fp32 mode, or a kernel that dropped a cross term, cannot pass."""
+exact-operand tests at the end are what an alias of the fp32 mode, or a kernel that dropped a cross term, cannot pass.
+
+These are end-to-end gates: the measured errors sit 10x to 60x below them (docs/EXPERIMENTS.md R6.4).  The pin of the arithmetic
+itself is tests/test_gpu_split_replay.py: every split conv, on all 16 compiled forms of the ws / fr kernels, against a float64
+product of its own operands (with tests/test_split_replay_host.py as its proof on the host)."""
 import sys
 from pathlib import Path
 
